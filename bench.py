@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the imaging hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps of the headline (below), writes what the last
+step computed if --dump-outputs is given, and prints its line.  Everything else described here
+(the `chunked` launches, the fp16 hi/lo block, the errors against float64, the CPU baseline, the
+secondary measurements and the major-cycle loop) runs only with --full, after the headline.
 
 Workload (BASELINE.json configs[1], "C2"): one spectral channel per GPU, 4096^2 image, 32
 W-planes, ~50 M synthetic visibilities (tools/synth.py: 64-antenna array, earth-rotation tracks,
@@ -57,19 +62,26 @@ def parse_args():
     p.add_argument('--kernel-width', type=int, default=28)
     p.add_argument('--polarizations', type=int, default=1)
     p.add_argument('--vis-block', type=int, default=1048576,
-                   help='chunk size of the `chunked` measurements (the reference\'s --vis-block)')
+                   help='(--full) chunk size of the `chunked` measurements (the reference\'s --vis-block)')
     p.add_argument('--variant', default='auto', choices=['auto', 'generic', 'mfma'])
+    p.add_argument('--full', action='store_true',
+                   help='after the headline, everything else the benchmark measures: the fp16 '
+                        'hi/lo form, the CPU baseline, the error against float64, the secondary '
+                        'measurements and the major-cycle loop (without it only the headline runs)')
+    p.add_argument('--dump-outputs', metavar='DIR',
+                   help='write what the last timed step computed (the gridded W-slice, float32 '
+                        're/im pairs) to DIR/<name>.npy')
     p.add_argument('--clean-cycles', type=int, default=1000)
     p.add_argument('--cpu-sample', type=int, default=3_200_000,
-                   help='visibilities per timed pass of the CPU baseline (0 disables it)')
+                   help='(--full) visibilities per timed pass of the CPU baseline (0 disables it)')
     p.add_argument('--cpu-passes', type=int, default=5)
     p.add_argument('--no-secondary', action='store_true',
-                   help='only the headline gridder measurement (and the CPU baseline)')
+                   help='(--full) only the gridder measurements (and the CPU baseline)')
     p.add_argument('--no-major-loop', action='store_true',
-                   help='skip the major-cycle loop (BASELINE config 5)')
+                   help='(--full) skip the major-cycle loop (BASELINE config 5)')
     p.add_argument('--extras', action='store_true',
-                   help='also: preprocessing + store-driven driver, several channels in flight, '
-                        'host-chunk (PCIe-inclusive) gridding')
+                   help='(--full) also: preprocessing + store-driven driver, several channels in '
+                        'flight, host-chunk (PCIe-inclusive) gridding')
     p.add_argument('--traffic-json',
                    default=os.path.join(os.path.dirname(os.path.abspath(__file__)), 'profiles',
                                         'gridder_traffic_fp32.json'),
@@ -78,7 +90,7 @@ def parse_args():
                         'kernel); included as roofline.traffic only if its recorded configuration '
                         'matches this run')
     p.add_argument('--roctx', action='store_true',
-                   help='named roctx ranges around the stages of the major-cycle loop '
+                   help='(--full) named roctx ranges around the stages of the major-cycle loop '
                         '(rocprofv3 --marker-trace)')
     p.add_argument('--force-dist', action='store_true',
                    help='take the distributed code path (RCCL process group, broadcast, '
@@ -258,9 +270,11 @@ def main():
     uv_all, wp_all, vis_all = padded(obs.uv), padded(obs.w_plane), padded(obs.vis)
     n_pad = n_chunks * vb
 
+    # (a plain run sets up only what the headline times; --full also the fp16 hi/lo form and the
+    # vis_block-sized launches)
     templates = {a: grid.GridderTemplate(ctx, ip.fixed, gp.fixed,
                                          {'variant': args.variant, 'arith': a})
-                 for a in ('fp32', 'split_fp16')}
+                 for a in (('fp32', 'split_fp16') if args.full else ('fp32',))}
     slice_ops = {a: t.instantiate(q, ap, ip, gp, n_pad) for a, t in templates.items()}
     fn = slice_ops['fp32']
     Gg = fn.slots['grid'].shape[1]
@@ -279,13 +293,13 @@ def main():
         # the resident store measures a slice's order once (VisibilityReaderDevice._locality) and
         # hands the answer to the gridder with every chunk: do the same here, outside the timing
         jump_fraction = op.measure_locality()
-    chunk_ops = {a: t.instantiate(q, ap, ip, gp, vb) for a, t in templates.items()}
+    chunk_ops = {a: t.instantiate(q, ap, ip, gp, vb) for a, t in templates.items()} if args.full else {}
     for op in chunk_ops.values():
         op.bind(grid=grid_buf, weights_grid=wg)
         op.ensure_all_bound()
         op.locality_hint = fn.locality_hint
     chunks = []
-    for i in range(n_chunks):
+    for i in range(n_chunks if args.full else 0):
         s = slice(i * vb, (i + 1) * vb)
         chunks.append((accel.DeviceArray(ctx, (vb, 4), np.int16, tensor=uv_all[s]),
                        accel.DeviceArray(ctx, (vb,), np.int16, tensor=wp_all[s]),
@@ -323,6 +337,9 @@ def main():
     timer = Timer(q, barrier, dev)
     # ---- the headline: float32 arithmetic, one launch per slice ---------------------------
     sec_per_step, kern_ms = timer.run(slice_step('fp32'), args.steps, args.warmup)
+    if rank == 0 and args.dump_outputs:
+        # before anything else writes to grid_buf: the grid the last timed step left
+        dump_outputs(args.dump_outputs, {'grid': grid_buf.tensor})
     mvis = world * n_vis / sec_per_step / 1e6
     roofline = grid_roofline('fp32', K, P, n_vis, 1, kern_ms, args.variant)
     # every rank's own numbers, so that the first multi-GPU run localises a slow rank
@@ -355,8 +372,8 @@ def main():
     }
     assert [p['device'] for p in result['per_rank']] == rank_devices
 
-    # ---- the opt-in fp16 hi/lo form, same step, scored against the pipe it uses -----------
-    if args.variant != 'generic' and K <= 64:
+    # ---- --full: the opt-in fp16 hi/lo form, same step, scored against the pipe it uses ----
+    if args.full and args.variant != 'generic' and K <= 64:
         s_split, k_split = timer.run(slice_step('split_fp16'), args.steps, args.warmup)
         result['split_fp16'] = {
             'value': round(world * n_vis / s_split / 1e6, 2), 'unit': 'Mvis/s',
@@ -365,10 +382,10 @@ def main():
             'roofline': grid_roofline('split_fp16', K, P, n_vis, 1, k_split, args.variant),
         }
 
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         result['cpu_baseline'] = cpu_baseline(args, obs, fn, wg, Gg)
 
-    if rank == 0 and not args.no_secondary:
+    if args.full and rank == 0 and not args.no_secondary:
         sec = {}
         # accuracy of both forms against float64 on one vis_block chunk of this workload
         mid = (n_chunks // 2) * vb
@@ -414,7 +431,7 @@ def main():
         if args.extras:
             result['extras'] = extras(args, ctx, q, obs, ip, gp, ap, templates['fp32'], grid_buf,
                                       wg, uv_all, wp_all, vis_all)
-    if rank == 0 and not args.no_major_loop and not args.no_secondary:
+    if args.full and rank == 0 and not args.no_major_loop and not args.no_secondary:
         del slice_ops, chunk_ops, chunks
         result['major_cycle_loop'] = major_cycle_loop(args, ctx, q, obs, extras=args.extras)
         if args.variant != 'generic' and K <= 64:
@@ -426,6 +443,30 @@ def main():
         print(json.dumps(result))
     if distributed:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 60_000_000     # of array data: --dump-outputs writes at most 64 MB in all
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every tensor of `arrays` as out_dir/<name>.npy in float32, a complex one as
+    trailing (re, im) pairs.  If they hold more than `limit` bytes in all, each keeps only a fixed
+    sample of its elements (flattened), at the sorted indices
+    np.unique(np.random.RandomState(0).randint(0, n, m)), the same for every run of one shape.
+    The caller has synchronised the device."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    real = {name: (torch.view_as_real(t) if t.is_complex() else t[..., None]).to(torch.float32)
+            for name, t in arrays.items()}
+    total = sum(r.numel() * 4 for r in real.values())
+    for name, r in real.items():
+        if total > limit:
+            flat = r.reshape(-1, r.shape[-1])
+            n = flat.shape[0]
+            idx = np.unique(np.random.RandomState(0).randint(0, n, n * limit // total))
+            r = flat[torch.from_numpy(idx).to(flat.device)]
+        out = r.cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), out if arrays[name].is_complex() else out[..., 0])
 
 
 def load_traffic(args, roofline):

@@ -62,7 +62,7 @@ def test_bench_force_dist_takes_the_rccl_branch():
         env.pop(k, None)
     out = subprocess.run(
         [sys.executable, os.path.join(ROOT, 'bench.py'), '--force-dist', '--vis', '4000000', '--steps',
-         '2', '--warmup', '1', '--cpu-sample', '0', '--no-secondary'],
+         '2', '--warmup', '1', '--full', '--cpu-sample', '0', '--no-secondary'],
         capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([x for x in out.stdout.splitlines() if x.startswith('{"metric"')][-1])

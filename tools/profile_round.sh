@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 R=${1:-r02}
 OUT=gpurun_out/prof_$R
 mkdir -p $OUT
-HEAD="python3 bench.py --steps 3 --warmup 1 --cpu-sample 0 --no-secondary"
+HEAD="python3 bench.py --steps 3 --warmup 1 --full --cpu-sample 0 --no-secondary"
 # 0. the same command unprofiled, on this lease (boxes differ by several per cent: the profiled
 #    steady state below is to be compared with THIS line, not with another box's)
 $HEAD > $OUT/unprofiled.log 2>&1
@@ -33,7 +33,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $HEAD --tr
 echo "stats rc=$?"
 grep -h "^{\"metric\"" $OUT/stats.log | tail -1 > $OUT/${R}_bench_profiled.json
 # everything else the bench exercises (secondary measurements + the major-cycle loop)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_full -- python3 bench.py --steps 3 --warmup 1 --cpu-sample 0 > $OUT/stats_full.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_full -- python3 bench.py --steps 3 --warmup 1 --full --cpu-sample 0 > $OUT/stats_full.log 2>&1
 echo "stats_full rc=$?"
 grep -h "^{\"metric\"" $OUT/stats_full.log | tail -1 > $OUT/${R}_bench_full_profiled.json
 python3 tools/summarize_profiles.py $OUT $R stats

@@ -39,7 +39,7 @@ def pmc(out, tag):
         path = os.path.join(out, '{}_gridder_pmc_{}.txt'.format(tag, form))
         with open(path, 'w') as f:
             f.write('# rocprofv3 --pmc, grid_mfma_kernel ({} form), average per launch of\n'
-                    '# `bench.py --no-secondary` (one launch = the whole 50 M-visibility W-slice)\n'
+                    '# `bench.py --full --no-secondary` (one launch = the whole 50 M-visibility W-slice)\n'
                     .format(form))
             for k in sorted(per_launch):
                 f.write('{:<28s} {:.6g}\n'.format(k, per_launch[k]))
