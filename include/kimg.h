@@ -39,14 +39,20 @@ extern "C" {
                                     * kimg_clean_cycles) */
 
 /* Arithmetic of the gridder / degridder matrix instructions (argument `arith`):
- *   KIMG_ARITH_FP32        v_mfma_f32_32x32x2_f32 -- every product and sum in float32, bit-identical
- *                          to the fmaf chain of the reference's kernels (grid.py:1049-1052).  Default.
+ *   KIMG_ARITH_FP32        every product and sum in float32, bit-identical to the fmaf chain of the
+ *                          reference's kernels (grid.py:1049-1052).  Default.  The gridder runs it
+ *                          on v_mfma_f32_16x16x4_f32, two visibilities per instruction; the
+ *                          degridder on v_mfma_f32_32x32x2_f32.
  *   KIMG_ARITH_SPLIT_FP16  operands carried as fp16 (hi, lo) pairs (22 significant bits, lo*lo
  *                          dropped), two visibilities per v_mfma_f32_32x32x16_f16, float32
  *                          accumulation.  Faster, narrower than the reference's arithmetic: opt-in.
+ *   KIMG_ARITH_FP32_32X32  the same sums as KIMG_ARITH_FP32, the gridder on v_mfma_f32_32x32x2_f32
+ *                          (one visibility per instruction; the earlier default form, kept for
+ *                          comparison).  Gridder only: the degridder rejects it (KIMG_EINVAL).
  * The generic (non-MFMA) kernels always compute in float32 and ignore it. */
 #define KIMG_ARITH_FP32 0
 #define KIMG_ARITH_SPLIT_FP16 1
+#define KIMG_ARITH_FP32_32X32 2
 
 /* Kernel choice of kimg_grid / kimg_degrid (argument `variant`) */
 #define KIMG_VARIANT_AUTO 0     /* MFMA window kernel when the parameters allow it */

@@ -32,6 +32,10 @@
 //  * Window slack 32-K lets consecutive visibilities whose footprints differ by a few
 //    cells share accumulators without any flush.
 //
+//  * The default float32 form runs the same sums on v_mfma_f32_16x16x4_f32, TWO visibilities per
+//    instruction (PAIR: window_acc16, pair32_ops): fewer address and LDS instructions per visibility,
+//    8 instructions of 32 cycles per pair instead of 2 x 2 of 64; the 32x32x2 form stays selectable
+//    (KIMG_ARITH_FP32_32X32).
 // Algorithmic work per visibility: 8*K*K*P flop (complex MAC per tap) + 6*K*P (a-vector);
 // executed: 2 MFMA x 2048 MAC per visibility per polarization (32x32 window).
 #include "kimg_common.h"
@@ -42,6 +46,7 @@
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int WIN = 32;
 
@@ -135,9 +140,73 @@ __device__ __attribute__((always_inline)) inline void flush_cells(
     }
 }
 
-template <int P, bool SCALED>
+// Accumulators of the pair form (float32, v_mfma_f32_16x16x4_f32, two visibilities per instruction):
+// the same 32x32 window as 2 x 4 tiles of 16 rows x 8 complex columns, tile 4 rb + cb covering
+// rows 16 rb .. 16 rb + 15 and complex columns 8 cb .. 8 cb + 7:
+// tile t, register k, lane l  <->  row 16 (t >> 2) + 4 (l >> 4) + k,
+//                                  complex column 8 (t & 3) + ((l & 15) >> 1), part l & 1.
+template <int P>
+struct window_acc16 {
+    f32x4 t[P][8];
+};
+
+// flush_cells for the pair form's layout.  One wave instruction covers four grid rows x 64
+// contiguous bytes; a register whose rows (a move along v) or whose columns (a move along u) are
+// all unaffected is skipped with a scalar test.
+template <int P, bool SCALED, bool ROWS, bool COLS, bool BOUNDS>
+__device__ __attribute__((always_inline)) inline void flush_cells(
+    window_acc16<P> &acc, float *__restrict__ grid, unsigned row_bytes, int64_t pol_stride, int Gg,
+    int Wu, int Wv, uint32_t row_mask, uint32_t col_mask, int lane, const float (&scale)[P])
+{
+    const int part = lane & 1;
+    const int cx0 = (lane & 15) >> 1;
+    const int c = (lane >> 4) * 4 - Wv;             // window row of register k of row block rb = (16 rb + k + c) & 31
+    const uint32_t lane_rows = row_mask >> ((lane >> 4) * 4);   // bit 16 rb + k <-> this lane's row
+    unsigned base[4];
+    bool col_sel[4];
+#pragma unroll
+    for (int cb = 0; cb < 4; cb++) {
+        const int cx = cx0 + 8 * cb;
+        const int xold = Wu + ((cx - Wu) & 31);
+        base[cb] = (unsigned) Wv * row_bytes + (unsigned) (2 * xold + part) * 4u;   // (wraps like the sum)
+        col_sel[cb] = COLS ? ((col_mask >> cx) & 1u) != 0 : false;
+        if (BOUNDS && (unsigned) xold >= (unsigned) Gg)
+            base[cb] = 0xffffffffu;                 // marks a column outside the grid
+    }
+#pragma unroll
+    for (int rb = 0; rb < 2; rb++)
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int rk = 16 * rb + k;                     // row of register k for lanes 0-15
+        if (ROWS && !COLS && (row_mask & (0x1111u << rk)) == 0)
+            continue;                                   // uniform: nothing of these registers moves
+        const unsigned rr = (unsigned) (rk + c) & 31u;
+        const bool row_sel = ROWS ? ((lane_rows >> rk) & 1u) != 0 : false;
+        const bool y_ok = BOUNDS ? (unsigned) (Wv + (int) rr) < (unsigned) Gg : true;
+#pragma unroll
+        for (int cb = 0; cb < 4; cb++) {
+            if (COLS && !ROWS && ((col_mask >> (8 * cb)) & 0xffu) == 0)
+                continue;                               // uniform: none of the tile's columns moves
+            const bool sel = (ROWS || COLS) ? (row_sel || col_sel[cb]) : true;
+            const unsigned off = rr * row_bytes + base[cb];
+            const bool inside = BOUNDS ? (y_ok && base[cb] != 0xffffffffu) : true;
+#pragma unroll
+            for (int p = 0; p < P; p++) {
+                const float v = acc.t[p][4 * rb + cb][k];
+                if (sel && inside && v != 0.0f) {
+                    float *cell = reinterpret_cast<float *>(
+                        reinterpret_cast<char *>(grid + 2 * p * pol_stride) + off);
+                    atomicAdd(cell, SCALED ? v * scale[p] : v);
+                }
+                acc.t[p][4 * rb + cb][k] = sel ? 0.0f : v;
+            }
+        }
+    }
+}
+
+template <int P, bool SCALED, class ACC>
 __device__ __attribute__((always_inline)) inline void flush_window(
-    window_acc<P> &acc, float *__restrict__ grid, int64_t row_stride, int64_t pol_stride,
+    ACC &acc, float *__restrict__ grid, int64_t row_stride, int64_t pol_stride,
     int Gg, int Wu, int Wv, int nWu, int nWv, bool full, int lane, const float (&scale)[P])
 {
     const uint32_t row_mask = full ? 0xffffffffu : changed_mask(Wv, nWv);
@@ -280,7 +349,20 @@ struct pair_ops {
 __device__ long long *g_timing = nullptr;
 #endif
 
-template <int P, int NW, int SUB, int ROW, bool TWO, bool TG = false, bool F16 = false>
+// Operands of SUBP staged pairs of visibilities in the pair form (float32, v_mfma_f32_16x16x4_f32):
+// lane l serves member l >> 5 of a pair and the MFMA k index (l >> 4) & 1 (Re / Im of a).
+// c = (Re s, Im s) for k even, (Im s, -Re s) for k odd; kv = the row taps of the two row blocks
+// (16 taps apart); b = the column tap components of the four column blocks (8 taps apart) as two
+// (adjacent-register) pairs for v_pk_mul_f32.
+template <int P, int SUBP>
+struct pair32_ops {
+    float2 c[P][SUBP];
+    v2f kv[SUBP][2];
+    v2f b[SUBP][2];
+};
+
+template <int P, int NW, int SUB, int ROW, bool TWO, bool TG = false, bool F16 = false,
+          bool PAIR = false>
 __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
     float *__restrict__ grid, int64_t row_stride, int64_t pol_stride, int Gg,
     const float *__restrict__ weights_grid, int64_t wg_row_stride, int64_t wg_pol_stride,
@@ -295,6 +377,7 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
 #endif
     static_assert(!TWO || ROW == 32 || TG, "two tables only fit LDS with single rows");
     static_assert(!F16 || SUB % 2 == 0, "fp16 form: visibilities go in pairs");
+    static_assert(!PAIR || (!F16 && SUB % 2 == 0), "pair form: float32, visibilities go in pairs");
     extern __shared__ __align__(16) unsigned char smem[];
     const int table_rows = W * OV;
     const int table_bytes = table_rows * ROW * (int) sizeof(float2);
@@ -548,6 +631,15 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
     // -im_lo, re_lo, -im_hi, re_hi); the row operand is (re_hi, im_hi, re_hi, im_hi, re_lo, im_lo)
     const int member = lane >> 5;
     const int lane_u16 = ((lane & 31) >> 1) * 8;
+    // pair form: the same per lane, with the MFMA k index (l >> 4) & 1 in place of h, row tap l & 15 of
+    // the first row block, column tap (l & 15) >> 1 of the first column block
+    const bool pk = ((lane >> 4) & 1) != 0;
+    const bool pb_take_im = (pk != (part != 0));
+    const float pb_sign = (part && !pk) ? -1.0f : 1.0f;
+    const int lane_pv = (lane & 15) * 8;
+    const int lane_pu = ((lane & 15) >> 1) * 8 + (pb_take_im ? 4 : 0);
+    const int lane_ps = pk ? 8 : 0;
+    const uint64_t lane_puv = ((uint64_t) (lds_base + (unsigned) lane_pv) << 32) | (lds_base + (unsigned) lane_pu);
     const unsigned sel = part ? 0x01000302u : 0x03020100u;      // odd columns swap (re, im)
     const unsigned flip = part ? 0x00008000u : 0u;              // ... and negate im
     // fp16 form: per-polarization sample scale T = 2^-E, kept as the integer E so that every decision
@@ -583,13 +675,21 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
         return E != E_NONE && e - E <= 0 && e - E >= low;
     };
 
-    window_acc<P> acc;
+    typename std::conditional<PAIR, window_acc16<P>, window_acc<P>>::type acc;
+    if constexpr (PAIR) {
+#pragma unroll
+        for (int p = 0; p < P; p++)
+            for (int t = 0; t < 8; t++)
+                for (int k = 0; k < 4; k++)
+                    acc.t[p][t][k] = 0.0f;
+    } else {
 #pragma unroll
     for (int p = 0; p < P; p++)
         for (int k = 0; k < 16; k++) {
             acc.t0[p][k] = 0.0f;
             acc.t1[p][k] = 0.0f;
         }
+    }
     bool have = false;
     int Wu = 0, Wv = 0;
 
@@ -628,11 +728,60 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
     auto addr_u16 = [&](int rx) __attribute__((always_inline)) {         // whole column tap
         return (unsigned) (ROW == 64 ? rx + lane_u16 : (rx & ~0xff) | ((rx + lane_u16) & 0xf8));
     };
+    // pair form: row tap of row block rb, column tap component of column block cb
+    auto addr_pv = [&](int ry, int rb) __attribute__((always_inline)) {
+        return (unsigned) (ROW == 64 ? ry + lane_pv + 128 * rb : (ry & ~0xff) | ((ry + lane_pv + 128 * rb) & 0xf8));
+    };
+    auto addr_pu = [&](int rx, int cb) __attribute__((always_inline)) {
+        return (unsigned) (ROW == 64 ? rx + lane_pu + 64 * cb : (rx & ~0xff) | ((rx + lane_pu + 64 * cb) & 0xfc));
+    };
+    // pair form: this lane's operands of one visibility (record r, samples at index idx)
+    auto pair_read = [&](const int2 &r, int idx, float2 (&c)[P], v2f (&kv)[2], v2f (&bb)[2])
+        __attribute__((always_inline)) {
+        if constexpr (ROW == 64 && !TG) {
+            // both LDS base addresses with ONE 64-bit add, as in stage_b; the two row taps are one
+            // ds_read2_b64, the four column components two ds_read2_b32
+            typedef const __attribute__((address_space(3))) v2f *lds_f2;
+            typedef const __attribute__((address_space(3))) float *lds_f;
+            const uint64_t sum = (((uint64_t) (unsigned) r.y << 32) | (unsigned) r.x) + lane_puv;
+            const unsigned au = (unsigned) sum, av = (unsigned) (sum >> 32);
+            kv[0] = *reinterpret_cast<lds_f2>((uintptr_t) av);
+            kv[1] = *reinterpret_cast<lds_f2>((uintptr_t) (av + 128));            // row + 16
+            bb[0].x = *reinterpret_cast<lds_f>((uintptr_t) au);
+            bb[0].y = *reinterpret_cast<lds_f>((uintptr_t) (au + 64));            // column + 8
+            bb[1].x = *reinterpret_cast<lds_f>((uintptr_t) (au + 128));
+            bb[1].y = *reinterpret_cast<lds_f>((uintptr_t) (au + 192));
+        } else {
+#pragma unroll
+            for (int rb = 0; rb < 2; rb++)
+                kv[rb] = *reinterpret_cast<const v2f *>(tbytes + addr_pv(r.y, rb));
+            bb[0].x = *reinterpret_cast<const float *>(tbytes + addr_pu(r.x, 0));
+            bb[0].y = *reinterpret_cast<const float *>(tbytes + addr_pu(r.x, 1));
+            bb[1].x = *reinterpret_cast<const float *>(tbytes + addr_pu(r.x, 2));
+            bb[1].y = *reinterpret_cast<const float *>(tbytes + addr_pu(r.x, 3));
+        }
+#pragma unroll
+        for (int p = 0; p < P; p++)
+            c[p] = *reinterpret_cast<const float2 *>(
+                reinterpret_cast<const unsigned char *>(samples + p * 64 + idx) + lane_ps);
+    };
+    // pair form: the 8 MFMAs of one pair (or of one visibility with a zero partner)
+    auto pair_mfma = [&](const float (&a)[P][2], const v2f (&bb)[2]) __attribute__((always_inline)) {
+        if constexpr (PAIR)
+#pragma unroll
+        for (int p = 0; p < P; p++)
+#pragma unroll
+            for (int rb = 0; rb < 2; rb++)
+#pragma unroll
+                for (int cb = 0; cb < 4; cb++)
+                    acc.t[p][4 * rb + cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                        a[p][rb], (cb & 1) ? bb[cb >> 1].y : bb[cb >> 1].x, acc.t[p][4 * rb + cb], 0, 0, 0);
+    };
 
     // ---- software-pipeline stages over sub-blocks of SUB staged visibilities ---------------
     int2 rec[SUB];
     auto stage_a = [&](int first) __attribute__((always_inline)) {         // record reads
-        if constexpr (F16) {
+        if constexpr (F16 || PAIR) {
 #pragma unroll
             for (int t = 0; t < SUB / 2; t++)
                 rec[t] = recs[first + 2 * t + member];      // this lane's member of pair t
@@ -643,7 +792,16 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
         }
     };
     auto stage_b = [&](auto &o, int first) __attribute__((always_inline)) {     // sample + kernel-table reads
-        if constexpr (F16) {
+        if constexpr (PAIR) {
+#pragma unroll
+            for (int t = 0; t < SUB / 2; t++) {
+                float2 c[P];
+                pair_read(rec[t], first + 2 * t + member, c, o.kv[t], o.b[t]);
+#pragma unroll
+                for (int p = 0; p < P; p++)
+                    o.c[p][t] = c[p];
+            }
+        } else if constexpr (F16) {
 #pragma unroll
             for (int t = 0; t < SUB / 2; t++) {
                 const unsigned au = addr_u16(rec[t].x);
@@ -717,7 +875,27 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
         return B;
     };
     auto stage_c = [&](const auto &o) __attribute__((always_inline)) {
-        if constexpr (F16) {
+        if constexpr (PAIR) {
+            // all operands first, then the MFMAs back to back
+            float a[SUB / 2][P][2];
+            v2f b[SUB / 2][2];
+#pragma unroll
+            for (int t = 0; t < SUB / 2; t++) {
+#pragma unroll
+                for (int j = 0; j < 2; j++)
+                    b[t][j] = o.b[t][j] * v2f{pb_sign, pb_sign};       // v_pk_mul_f32
+#pragma unroll
+                for (int p = 0; p < P; p++)
+#pragma unroll
+                    for (int rb = 0; rb < 2; rb++)
+                        a[t][p][rb] = fmaf(o.c[p][t].x, o.kv[t][rb].x, o.c[p][t].y * o.kv[t][rb].y);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int t = 0; t < SUB / 2; t++)
+                pair_mfma(a[t], b[t]);
+            return;
+        } else if constexpr (F16) {
             u32x4 A[P][SUB / 2], B0[SUB / 2], B1[SUB / 2];
 #pragma unroll
             for (int t = 0; t < SUB / 2; t++) {
@@ -798,6 +976,23 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
             fit_window(__builtin_amdgcn_readfirstlane(org.x), __builtin_amdgcn_readfirstlane(org.x),
                        __builtin_amdgcn_readfirstlane(org.y), __builtin_amdgcn_readfirstlane(org.y));
             const int2 r = recs[idx];
+            if constexpr (PAIR) {
+                // one visibility, carried by the first member of a pair; the second contributes 0
+                float2 cp[P];
+                v2f kv[2], bb[2];
+                pair_read(r, idx, cp, kv, bb);
+                float a[P][2];
+#pragma unroll
+                for (int j = 0; j < 2; j++)
+                    bb[j] = bb[j] * v2f{pb_sign, pb_sign};
+#pragma unroll
+                for (int p = 0; p < P; p++)
+#pragma unroll
+                    for (int rb = 0; rb < 2; rb++)
+                        a[p][rb] = member ? 0.0f : fmaf(cp[p].x, kv[rb].x, cp[p].y * kv[rb].y);
+                pair_mfma(a, bb);
+                continue;
+            }
             if constexpr (F16) {
                 int vis_shift[P];
 #pragma unroll
@@ -848,6 +1043,7 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
                 }
                 continue;
             }
+            if constexpr (!PAIR) {
             const unsigned au = addr_u(r.x);
             const float2 kv = *reinterpret_cast<const float2 *>(tbytes + addr_v(r.y));
             const float b0 = *reinterpret_cast<const float *>(tbytes + au) * b_sign;
@@ -858,6 +1054,7 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
                 const float a = fmaf(c[p].x, kv.x, c[p].y * kv.y);
                 acc.t0[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc.t0[p], 0, 0, 0);
                 acc.t1[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, acc.t1[p], 0, 0, 0);
+            }
             }
         }
     };
@@ -957,7 +1154,8 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
 
         const int count = b.e - b.b < 64 ? (int) (b.e - b.b) : 64;
         const int npairs = (count + 2 * SUB - 1) / (2 * SUB);
-        typename std::conditional<F16, pair_ops<P, SUB / 2>, sub_ops<P, SUB>>::type X, Y;
+        typename std::conditional<F16, pair_ops<P, SUB / 2>,
+                                  typename std::conditional<PAIR, pair32_ops<P, SUB / 2>, sub_ops<P, SUB>>::type>::type X, Y;
         stage_a(0);
         stage_b(X, 0);
         stage_a(SUB);
@@ -1126,7 +1324,7 @@ constexpr size_t LDS_LIMIT = 160 * 1024;
 constexpr int64_t INTERLEAVE_MIN_CHUNK = KIMG_INTERLEAVE_MIN_CHUNK;     // visibilities: bounds the extra window flushes
 constexpr int64_t INTERLEAVE_MAX_PARTS = KIMG_INTERLEAVE_MAX_PARTS;
 
-template <int P, int ROW, int NW, bool TWO, bool TG = false, bool F16 = false>
+template <int P, int ROW, int NW, bool TWO, bool TG = false, bool F16 = false, bool PAIR = false>
 int launch(float *grid, int64_t row_stride, int64_t pol_stride, int Gg, const float *wg,
            int64_t wg_row_stride, int64_t wg_pol_stride, const int16_t *uv,
            const int16_t *w_plane, const float2 *vis, int64_t num_vis, const float2 *kern,
@@ -1157,7 +1355,7 @@ int launch(float *grid, int64_t row_stride, int64_t pol_stride, int Gg, const fl
     }
     {
         const int rc = kimg_dynamic_lds(
-            reinterpret_cast<const void *>(&grid_mfma_kernel<P, NW, SUB, ROW, TWO, TG, F16>), LDS_LIMIT);
+            reinterpret_cast<const void *>(&grid_mfma_kernel<P, NW, SUB, ROW, TWO, TG, F16, PAIR>), LDS_LIMIT);
         if (rc)
             return rc;
     }
@@ -1200,7 +1398,7 @@ int launch(float *grid, int64_t row_stride, int64_t pol_stride, int Gg, const fl
     }
     if (chunk > 0 && queue != nullptr)
         KIMG_HIP(hipMemsetAsync(queue, 0, sizeof(unsigned long long), stream));
-    grid_mfma_kernel<P, NW, SUB, ROW, TWO, TG, F16><<<blocks, NW * 64, lds, stream>>>(
+    grid_mfma_kernel<P, NW, SUB, ROW, TWO, TG, F16, PAIR><<<blocks, NW * 64, lds, stream>>>(
         grid, row_stride, pol_stride, Gg, wg, wg_row_stride, wg_pol_stride, uv, w_plane, vis,
         num_vis, kern, W, OV, ts, vis_per_block, p_total, dbg, padded, tab_max, chunk, scramble,
         chunk > 0 ? queue : nullptr);
@@ -1254,6 +1452,7 @@ int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
                    void *workspace, size_t workspace_bytes, int arith, hipStream_t stream)
 {
     const bool f16 = arith == KIMG_ARITH_SPLIT_FP16;
+    const bool pair = arith == KIMG_ARITH_FP32;         // (KIMG_ARITH_FP32_32X32: one visibility per instruction)
     const bool in_lds = table_in_lds(P, w_planes, oversample, kernel_width);
     if (!in_lds && (workspace == nullptr
                     || workspace_bytes < kimg_grid_mfma_workspace_bytes(P, w_planes, oversample,
@@ -1287,6 +1486,9 @@ int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
         if (f16) rc = launch<PP, ROWV, NWV, TWOV, TGV, true>(g, grid_row_stride, grid_pol_stride, \
             grid_size, wg, wg_row_stride, wg_pol_stride, uv, w_plane, v, num_vis, kern, w_planes, \
             oversample, ts, P, stream, padded, tab_max_offset, queue); \
+        else if (pair) rc = launch<PP, ROWV, NWV, TWOV, TGV, false, true>(g, grid_row_stride, \
+            grid_pol_stride, grid_size, wg, wg_row_stride, wg_pol_stride, uv, w_plane, v, num_vis, \
+            kern, w_planes, oversample, ts, P, stream, padded, tab_max_offset, queue); \
         else rc = launch<PP, ROWV, NWV, TWOV, TGV, false>(g, grid_row_stride, grid_pol_stride, \
             grid_size, wg, wg_row_stride, wg_pol_stride, uv, w_plane, v, num_vis, kern, w_planes, \
             oversample, ts, P, stream, padded, tab_max_offset, queue); } while (0)

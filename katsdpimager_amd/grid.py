@@ -210,10 +210,12 @@ def shared_kernel_device(context, image_parameters, grid_parameters, pad=0):
 # Operators
 # --------------------------------------------------------------------------
 GRID_VARIANTS = {'auto': 0, 'generic': 1, 'mfma': 2, 'binned': 3}           # KIMG_VARIANT_*
-#: Arithmetic of the matrix instructions (KIMG_ARITH_*): ``fp32`` = v_mfma_f32_32x32x2_f32, every
-#: product and sum in float32 like the reference (grid.py:1049-1052), the default; ``split_fp16`` =
-#: operands as fp16 hi/lo pairs with float32 accumulation (faster, 22-bit operands; opt-in).
-GRID_ARITH = {'fp32': 0, 'split_fp16': 1}
+#: Arithmetic of the matrix instructions (KIMG_ARITH_*): ``fp32`` = every product and sum in float32
+#: like the reference (grid.py:1049-1052), the default (gridder: v_mfma_f32_16x16x4_f32, two
+#: visibilities per instruction); ``split_fp16`` = operands as fp16 hi/lo pairs with float32
+#: accumulation (faster, 22-bit operands; opt-in); ``fp32_32x32`` = the same sums as ``fp32``, the
+#: gridder on v_mfma_f32_32x32x2_f32 (one visibility per instruction; for comparison; gridder only).
+GRID_ARITH = {'fp32': 0, 'split_fp16': 1, 'fp32_32x32': 2}
 
 
 #: `auto` variant: calls smaller than this go straight to the window kernel ...
@@ -236,7 +238,7 @@ def _tuning(tuning):
 
 class GridderTemplate:
     """grid.py:549-653.  ``tuning`` may hold ``{'variant': 'auto'|'generic'|'mfma'|'binned',
-    'arith': 'fp32'|'split_fp16'}`` (the reference's tuning dict carries its autotuned work-group
+    'arith': 'fp32'|'split_fp16'|'fp32_32x32'}`` (the reference's tuning dict carries its autotuned work-group
     shape; there is no autotuner here -- the kernel geometry is fixed by the MFMA tile shape).
     Both are per template, passed to the C ABI on every call: nothing is read from the environment.
 
