@@ -17,7 +17,8 @@
  *  - return value: 0 on success, a negated hipError_t on a HIP failure, or a
  *    KIMG_E* code below for argument errors.  Kernels themselves never report
  *    errors (same as the reference).
- *  - complex numbers are interleaved float (re, im) = numpy complex64.
+ *  - complex numbers are interleaved float (re, im) = numpy complex64; the `_f64` entry points
+ *    take complex128 / float64 grids, layers and images (see "float64 path" below).
  */
 #ifndef KIMG_H
 #define KIMG_H
@@ -29,7 +30,7 @@
 extern "C" {
 #endif
 
-#define KIMG_VERSION 4
+#define KIMG_VERSION 5
 
 #define KIMG_EINVAL (-10001)      /* bad argument (null pointer, negative size ...) */
 #define KIMG_EUNSUPPORTED (-10002) /* parameter combination not supported by this build */
@@ -209,6 +210,45 @@ size_t kimg_degrid_workspace_bytes(int num_polarizations, int w_planes, int over
 size_t kimg_degrid_binned_workspace_bytes(int64_t max_vis, int num_polarizations, int w_planes,
                                           int oversample, int kernel_width);
 
+/* ---- float64 path (the reference's --precision double, frontend.py:300): complex128 grid,
+ * complex64 visibilities and kernel table, float32 weights_grid and statistical weights.  Arguments
+ * as kimg_grid / kimg_degrid without `arith`; `variant` may carry KIMG_WINDOW_CUS(n) (ignored).
+ *   grid  complex128 [P][grid_size][grid_size] (strides in complex elements)
+ * Arithmetic contract:
+ *   gridder    s_p = float32(vis_p * wgt_p), as in the float32 forms; then in double
+ *              a_j = s_p * conj(kv_j) (taps promoted exactly) and
+ *              grid[p][v0+j][u0+k] += a_j * conj(ku_k).
+ *              (The reference's GPU double path rounds kv_j * ku_k to float32 first,
+ *              grid.mako:21-35; this separable form differs from it by at most 2^-24 relative
+ *              per tap and is the more accurate.)
+ *   degridder  in double, pred = sum_k ku_k sum_j kv_j g[j][k] (a separable contraction, either
+ *              order), residual = complex64(vis - weight * pred) with one final rounding
+ *              (DegridderHost._degrid on complex128 values, grid.py:1139-1154).
+ *   The order of summation is free: with integer operands whose partial sums stay below 2^53
+ *   both results are exact.  Out-of-range coordinates contribute nothing, as in kimg_grid (the
+ *   whole record for a cell, sub-cell or plane outside the grid or table; single taps for a
+ *   footprint that crosses the grid's edge).
+ * Kernels (csrc/grid_f64.hip): widths up to 32 run a moving 32 x 32 complex128 window held in
+ * registers (v_fma_f64; flushes with global_atomic_add_f64 only where the window's mapping changes):
+ * KIMG_VARIANT_MFMA, and KIMG_VARIANT_BINNED over the tile-sorted copies of the float32 binned
+ * variant (same scratch: kimg_grid_binned_workspace_bytes / kimg_degrid_binned_workspace_bytes).
+ * Widths 33 and
+ * up run the generic one-wave-per-visibility kernels (no 2 x 2 tap-block split): MFMA and BINNED
+ * are KIMG_EUNSUPPORTED there.  AUTO = the window kernel up to 32, generic above; GENERIC = the
+ * generic kernels.  Only BINNED needs a workspace (NULL, 0 accepted otherwise). */
+int kimg_grid_f64(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride, int grid_size,
+                  int num_polarizations,
+                  const float *weights_grid, int64_t wg_row_stride, int64_t wg_pol_stride,
+                  const int16_t *uv, const int16_t *w_plane, const void *vis, int64_t num_vis,
+                  const void *convolve_kernel, int w_planes, int oversample, int kernel_width,
+                  void *workspace, size_t workspace_bytes, int variant, void *stream);
+int kimg_degrid_f64(const void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
+                    int grid_size, int num_polarizations,
+                    const int16_t *uv, const int16_t *w_plane, const float *weights, void *vis,
+                    int64_t num_vis,
+                    const void *convolve_kernel, int w_planes, int oversample, int kernel_width,
+                    void *workspace, size_t workspace_bytes, int variant, void *stream);
+
 /* ---- direct prediction: predict.py:386-416 Predict._run + predict.mako:10-87
  * vis[r][p] -= weights[r][p] * sum_s flux[s][p] * exp(-2 pi i (l u + m v + (n-1) w)),
  * u = (uv.x*oversample + uv.z + 0.5)*uv_scale, w = w_plane*w_scale + w_bias.
@@ -321,6 +361,19 @@ int kimg_layer_to_image(float *image, int64_t image_row_stride, const void *laye
 int kimg_image_to_layer(void *layer, const float *image, int64_t image_row_stride, int size,
                         const float *kernel1d, float lm_scale, float lm_bias, float w,
                         void *stream);
+/* The float64 forms of the four calls above: complex128 grid and layer, float64 image and kernel1d,
+ * double lm_scale / lm_bias / w; the phase from double sincospi.  Float64 takes this plain route
+ * (copy, kimg_fft_plan_create_f64 transform, layer -> image) for every w. */
+int kimg_grid_to_layer_f64(void *layer, int layer_size, const void *grid, int64_t grid_row_stride,
+                           int grid_size, void *stream);
+int kimg_layer_to_grid_f64(void *grid, int64_t grid_row_stride, int grid_size, const void *layer,
+                           int layer_size, void *stream);
+int kimg_layer_to_image_f64(double *image, int64_t image_row_stride, const void *layer, int size,
+                            const double *kernel1d, double lm_scale, double lm_bias, double w,
+                            void *stream);
+int kimg_image_to_layer_f64(void *layer, const double *image, int64_t image_row_stride, int size,
+                            const double *kernel1d, double lm_scale, double lm_bias, double w,
+                            void *stream);
 /* The same pair for a layer whose transform is only wanted for its real part, i.e. w = 0 (the
  * phase factor of layer_to_image is then exactly 1): the reference notes at image.py:561-566 that a
  * complex-to-real transform would do; here it does.
@@ -392,6 +445,8 @@ int kimg_convolve_beam(float *image, int64_t row_stride, int size, float amplitu
 /* 2-D complex-to-complex FFT plans (katsdpsigproc.fft.FftTemplate, image.py:585-600,629,698)
  * on rocFFT (called directly); unnormalised, in place.  direction: -1 forward, +1 inverse. */
 int kimg_fft_plan_create(void **plan, int size_y, int size_x);
+/* The same for complex128 layers (rocfft_precision_double); exec and destroy take either kind. */
+int kimg_fft_plan_create_f64(void **plan, int size_y, int size_x);
 int kimg_fft_exec(void *plan, void *layer, int direction, void *stream);
 int kimg_fft_plan_destroy(void *plan);
 
@@ -427,6 +482,17 @@ int kimg_apply_primary_beam(float *image, int64_t row_stride, int64_t pol_stride
                             const float *beam_power, int64_t beam_row_stride,
                             int width, int height, int num_polarizations,
                             float threshold, float replacement, void *stream);
+/* The float64 forms of kimg_scale, kimg_add_image and kimg_apply_primary_beam (float64 images and
+ * beam; scale_host: P doubles on the HOST). */
+int kimg_scale_f64(double *image, int64_t row_stride, int64_t pol_stride, int width, int height,
+                   int num_polarizations, const double *scale_host, void *stream);
+int kimg_add_image_f64(double *dest, int64_t dest_row_stride, int64_t dest_pol_stride,
+                       const double *src, int64_t src_row_stride, int64_t src_pol_stride,
+                       int width, int height, int num_polarizations, void *stream);
+int kimg_apply_primary_beam_f64(double *image, int64_t row_stride, int64_t pol_stride,
+                                const double *beam_power, int64_t beam_row_stride,
+                                int width, int height, int num_polarizations,
+                                double threshold, double replacement, void *stream);
 
 /* Output statistics of the restore step (frontend.py:171-209, host loops in the reference):
  *   kimg_image_peak:   find_peak -- max |image| over all polarizations and pixels with

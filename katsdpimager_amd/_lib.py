@@ -18,8 +18,9 @@ P = c_void_p
 I = c_int
 L = c_int64
 F = c_float
+D = c_double
 
-VERSION = 4     # KIMG_VERSION of include/kimg.h
+VERSION = 5     # KIMG_VERSION of include/kimg.h
 
 PROTOTYPES = {
     'kimg_version': (c_int, []),
@@ -91,6 +92,17 @@ PROTOTYPES = {
     'kimg_clean_major_cycles': (c_int, [P, P, L, L, I, I, I, P, L, L, I, I, I, I, I, I, F, c_double, c_double,
                                         P, P, I, I, I, I, P, P, P, P, P]),
     'kimg_clean_cycles_batch': (c_int, [P, I, L, L, I, I, I, L, L, I, I, I, I, F, I, I, P]),
+    # float64 path
+    'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
+    'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
+    'kimg_grid_to_layer_f64': (c_int, [P, I, P, L, I, P]),
+    'kimg_layer_to_grid_f64': (c_int, [P, L, I, P, I, P]),
+    'kimg_layer_to_image_f64': (c_int, [P, L, P, I, P, D, D, D, P]),
+    'kimg_image_to_layer_f64': (c_int, [P, P, L, I, P, D, D, D, P]),
+    'kimg_fft_plan_create_f64': (c_int, [ctypes.POINTER(c_void_p), I, I]),
+    'kimg_scale_f64': (c_int, [P, L, L, I, I, I, ctypes.POINTER(c_double), P]),
+    'kimg_add_image_f64': (c_int, [P, L, L, P, L, L, I, I, I, P]),
+    'kimg_apply_primary_beam_f64': (c_int, [P, L, L, P, L, I, I, I, D, D, P]),
 }
 
 

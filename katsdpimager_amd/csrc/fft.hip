@@ -5,7 +5,7 @@
 // routes on the library's plan.
 // Replaces katsdpsigproc.fft.FftTemplate as used by GridImageTemplate.make_fft_plan
 // (image.py:585-600) and the transforms at image.py:629 (inverse) and :698 (forward):
-// unnormalised, complex64 / float32, row-major size_y x size_x.
+// unnormalised, complex64 / float32 (complex128 for the float64 C2C plans), row-major size_y x size_x.
 #include "kimg_common.h"
 #include <rocfft/rocfft.h>
 #include <mutex>
@@ -35,7 +35,8 @@ struct roc_plan {
     // lengths: {fastest, slowest}.  Strides (in elements of the respective type) describe rows that
     // are longer than the data, as the in-place real transforms need; 0 = dense.
     int create(rocfft_result_placement placement, rocfft_transform_type type, size_t size_x, size_t size_y,
-               size_t in_row_stride, size_t out_row_stride)
+               size_t in_row_stride, size_t out_row_stride,
+               rocfft_precision precision = rocfft_precision_single)
     {
         library_setup();
         const size_t lengths[2] = {size_x, size_y};
@@ -52,7 +53,7 @@ struct roc_plan {
                     nullptr, 2, in_strides, in_row_stride * size_y, 2, out_strides, out_row_stride * size_y);
         }
         if (r == rocfft_status_success)
-            r = rocfft_plan_create(&plan, placement, type, rocfft_precision_single, 2, lengths, 1, desc);
+            r = rocfft_plan_create(&plan, placement, type, precision, 2, lengths, 1, desc);
         if (desc)
             (void) rocfft_plan_description_destroy(desc);
         if (r != rocfft_status_success)
@@ -110,15 +111,17 @@ struct rfft_plan {
 
 } // namespace
 
-extern "C" int kimg_fft_plan_create(void **plan, int size_y, int size_x)
+namespace {
+
+int fft_plan_create(void **plan, int size_y, int size_x, rocfft_precision precision)
 {
     KIMG_CHECK_ARG(plan && size_y > 0 && size_x > 0);
     fft_plan *p = new fft_plan;
     int rc = p->forward.create(rocfft_placement_inplace, rocfft_transform_type_complex_forward, size_x,
-                               size_y, 0, 0);
+                               size_y, 0, 0, precision);
     if (rc == 0)
         rc = p->inverse.create(rocfft_placement_inplace, rocfft_transform_type_complex_inverse, size_x,
-                               size_y, 0, 0);
+                               size_y, 0, 0, precision);
     if (rc) {
         p->forward.destroy();
         p->inverse.destroy();
@@ -127,6 +130,19 @@ extern "C" int kimg_fft_plan_create(void **plan, int size_y, int size_x)
     }
     *plan = p;
     return 0;
+}
+
+} // namespace
+
+extern "C" int kimg_fft_plan_create(void **plan, int size_y, int size_x)
+{
+    return fft_plan_create(plan, size_y, size_x, rocfft_precision_single);
+}
+
+// complex128 layers (the float64 path); run and destroyed by kimg_fft_exec / kimg_fft_plan_destroy
+extern "C" int kimg_fft_plan_create_f64(void **plan, int size_y, int size_x)
+{
+    return fft_plan_create(plan, size_y, size_x, rocfft_precision_double);
 }
 
 extern "C" int kimg_fft_exec(void *plan, void *layer, int direction, void *stream)

@@ -318,6 +318,121 @@ int kimg_grid_binned(void *grid, int64_t grid_row_stride, int64_t grid_pol_strid
                           base + ws.table, ws.keys[0], arith, stream);
 }
 
+// ---- float64 (kimg_grid_f64 / kimg_degrid_f64, KIMG_VARIANT_BINNED; widths <= 32): the same sort and
+// gather into the same scratch (kimg_grid_binned_workspace_bytes / kimg_degrid_binned_workspace_bytes,
+// of which the padded-table part goes unused), then the float64 window kernels of grid_f64.hip.
+int kimg_grid_window_f64(double *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
+                         int grid_size, int P, const float *weights_grid, int64_t wg_row_stride,
+                         int64_t wg_pol_stride, const int16_t *uv, const int16_t *w_plane,
+                         const float2 *vis, int64_t num_vis, const float2 *kern, int w_planes,
+                         int oversample, int K, hipStream_t s);
+int kimg_degrid_window_f64(const double2 *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
+                           int grid_size, int P, const int16_t *uv, const int16_t *w_plane,
+                           const float *weights, float2 *vis, int64_t num_vis, const float2 *kern,
+                           int w_planes, int oversample, int K, hipStream_t s);
+
+int kimg_grid_binned_f64(double *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
+                         int grid_size, int P, const float *weights_grid, int64_t wg_row_stride,
+                         int64_t wg_pol_stride, const int16_t *uv, const int16_t *w_plane,
+                         const void *vis, int64_t num_vis, const void *kern, int w_planes,
+                         int oversample, int K, void *workspace, size_t workspace_bytes,
+                         hipStream_t stream)
+{
+    if (num_vis >= ((int64_t) 1 << 31))
+        return KIMG_EUNSUPPORTED;
+    binned_ws ws;
+    hipError_t e = layout(num_vis, P, w_planes, oversample, K, ws);
+    if (e != hipSuccess)
+        return -(int) e;
+    if (workspace == nullptr || workspace_bytes < ws.total)
+        return KIMG_EWORKSPACE;
+    unsigned char *base = static_cast<unsigned char *>(workspace);
+    hipcub::DoubleBuffer<unsigned> keys(reinterpret_cast<unsigned *>(base + ws.keys[0]),
+                                        reinterpret_cast<unsigned *>(base + ws.keys[1]));
+    hipcub::DoubleBuffer<unsigned> index(reinterpret_cast<unsigned *>(base + ws.index[0]),
+                                         reinterpret_cast<unsigned *>(base + ws.index[1]));
+    int rc = sort_by_tile(uv, num_vis, grid_size, K, base, ws, keys, index, stream);
+    if (rc)
+        return rc;
+    const int blocks = kimg_divup(num_vis, 256);
+    int2 *uv_s = reinterpret_cast<int2 *>(base + ws.uv);
+    int16_t *wp_s = reinterpret_cast<int16_t *>(base + ws.wp);
+    float2 *vis_s = reinterpret_cast<float2 *>(base + ws.vis);
+#define GATHER(PP) gather_kernel<PP><<<blocks, 256, 0, stream>>>(index.Current(), num_vis, \
+        reinterpret_cast<const int2 *>(uv), w_plane, static_cast<const float2 *>(vis), uv_s, wp_s, vis_s)
+    switch (P) {
+    case 1: GATHER(1); break;
+    case 2: GATHER(2); break;
+    case 3: GATHER(3); break;
+    default: GATHER(4); break;
+    }
+#undef GATHER
+    rc = kimg_launch_status();
+    if (rc)
+        return rc;
+    return kimg_grid_window_f64(grid, grid_row_stride, grid_pol_stride, grid_size, P, weights_grid,
+                                wg_row_stride, wg_pol_stride, reinterpret_cast<const int16_t *>(uv_s),
+                                wp_s, vis_s, num_vis, static_cast<const float2 *>(kern), w_planes,
+                                oversample, K, stream);
+}
+
+int kimg_degrid_binned_f64(const double2 *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
+                           int grid_size, int P, const int16_t *uv, const int16_t *w_plane,
+                           const float *weights, void *vis, int64_t num_vis, const void *kern,
+                           int w_planes, int oversample, int K, void *workspace,
+                           size_t workspace_bytes, hipStream_t stream)
+{
+    if (num_vis >= ((int64_t) 1 << 31))
+        return KIMG_EUNSUPPORTED;
+    binned_ws ws;
+    hipError_t e = layout(num_vis, P, w_planes, oversample, K, ws, true);
+    if (e != hipSuccess)
+        return -(int) e;
+    if (workspace == nullptr || workspace_bytes < ws.total)
+        return KIMG_EWORKSPACE;
+    unsigned char *base = static_cast<unsigned char *>(workspace);
+    hipcub::DoubleBuffer<unsigned> keys(reinterpret_cast<unsigned *>(base + ws.keys[0]),
+                                        reinterpret_cast<unsigned *>(base + ws.keys[1]));
+    hipcub::DoubleBuffer<unsigned> index(reinterpret_cast<unsigned *>(base + ws.index[0]),
+                                         reinterpret_cast<unsigned *>(base + ws.index[1]));
+    int rc = sort_by_tile(uv, num_vis, grid_size, K, base, ws, keys, index, stream);
+    if (rc)
+        return rc;
+    const int blocks = kimg_divup(num_vis, 256);
+    int2 *uv_s = reinterpret_cast<int2 *>(base + ws.uv);
+    int16_t *wp_s = reinterpret_cast<int16_t *>(base + ws.wp);
+    float *w_s = reinterpret_cast<float *>(base + ws.weights);
+    float2 *vis_s = reinterpret_cast<float2 *>(base + ws.vis);
+#define GATHER(PP) gather_degrid_kernel<PP><<<blocks, 256, 0, stream>>>(index.Current(), num_vis, \
+        reinterpret_cast<const int2 *>(uv), w_plane, weights, static_cast<const float2 *>(vis), uv_s, wp_s, \
+        w_s, vis_s)
+    switch (P) {
+    case 1: GATHER(1); break;
+    case 2: GATHER(2); break;
+    case 3: GATHER(3); break;
+    default: GATHER(4); break;
+    }
+#undef GATHER
+    rc = kimg_launch_status();
+    if (rc)
+        return rc;
+    rc = kimg_degrid_window_f64(grid, grid_row_stride, grid_pol_stride, grid_size, P,
+                                reinterpret_cast<const int16_t *>(uv_s), wp_s, w_s, vis_s, num_vis,
+                                static_cast<const float2 *>(kern), w_planes, oversample, K, stream);
+    if (rc)
+        return rc;
+#define SCATTER(PP) scatter_vis_kernel<PP><<<blocks, 256, 0, stream>>>(index.Current(), num_vis, vis_s, \
+        static_cast<float2 *>(vis))
+    switch (P) {
+    case 1: SCATTER(1); break;
+    case 2: SCATTER(2); break;
+    case 3: SCATTER(3); break;
+    default: SCATTER(4); break;
+    }
+#undef SCATTER
+    return kimg_launch_status();
+}
+
 extern "C" size_t kimg_grid_binned_workspace_bytes(int64_t max_vis, int num_polarizations,
                                                   int w_planes, int oversample, int kernel_width)
 {

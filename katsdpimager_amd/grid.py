@@ -225,15 +225,22 @@ AUTO_MIN_VIS = 65536
 AUTO_JUMP_FRACTION = 0.05
 
 
-def _tuning(tuning):
+def _tuning(tuning, real_dtype=np.float32):
     tuning = tuning or {}
     unknown = set(tuning) - {'variant', 'arith'}
     if unknown:
         raise ValueError('unknown tuning keys: {}'.format(sorted(unknown)))
     try:
-        return GRID_VARIANTS[tuning.get('variant', 'auto')], GRID_ARITH[tuning.get('arith', 'fp32')]
+        variant, arith = (GRID_VARIANTS[tuning.get('variant', 'auto')],
+                          GRID_ARITH[tuning.get('arith', 'fp32')])
     except KeyError as e:
         raise ValueError('unknown tuning value {}'.format(e)) from None
+    if np.dtype(real_dtype) == np.float64:
+        # kimg_grid_f64 / kimg_degrid_f64: one arithmetic (include/kimg.h)
+        if arith != GRID_ARITH['fp32']:
+            raise ValueError('float64 gridding has one arithmetic; arith={!r} is float32 only'.format(
+                tuning['arith']))
+    return variant, arith
 
 
 class GridderTemplate:
@@ -247,15 +254,20 @@ class GridderTemplate:
     measures the stream (``kimg_grid_jumps``: records that would force a whole-window flush, one
     4-byte read-back per call of at least :data:`AUTO_MIN_VIS` visibilities) and takes ``binned``
     when more than :data:`AUTO_JUMP_FRACTION` of the records jump, unless the caller already knows
-    (``Gridder.locality_hint``)."""
+    (``Gridder.locality_hint``).
+
+    Float64 (``fixed_image_parameters.real_dtype``): complex128 grid, complex64 visibilities and
+    kernel table, float32 weights (``kimg_grid_f64``).  Every variant; ``mfma`` and ``binned`` (the
+    float64 window kernel) take kernel widths up to 32, ``auto`` runs the generic kernel above that.
+    Only the default ``arith``: anything else raises ValueError."""
 
     def __init__(self, context, fixed_image_parameters, fixed_grid_parameters, tuning=None):
-        types.require_float32(fixed_image_parameters.real_dtype, 'GridderTemplate')
+        types.require_float32_or_64(fixed_image_parameters.real_dtype, 'GridderTemplate')
         lib()
         self.context = context
         self.fixed_image_parameters = fixed_image_parameters
         self.fixed_grid_parameters = fixed_grid_parameters
-        self.variant, self.arith = _tuning(tuning)
+        self.variant, self.arith = _tuning(tuning, fixed_image_parameters.real_dtype)
         self.kernel_pad = 0
 
     def instantiate(self, *args, **kwargs):
@@ -313,6 +325,7 @@ class GridDegrid(VisOperation):
         self.grid_parameters = grid_parameters
         self.slots['grid'] = accel.IOSlot(
             (num_polarizations, grid_pixels, grid_pixels), image_parameters.fixed.complex_dtype)
+        self._f64 = image_parameters.fixed.real_dtype == np.float64
 
     def parameters(self):
         return {'grid_parameters': self.grid_parameters,
@@ -393,14 +406,15 @@ class Gridder(GridDegrid):
         self.slots['weights_grid'] = accel.IOSlot(self.slots['grid'].shape, np.float32)
         num_pols = self.slots['grid'].shape[0]
         table = self.convolve_kernel.padded_data
-        nbytes = lib().kimg_grid_workspace_bytes(self.max_vis, num_pols, table.shape[0],
-                                                 table.shape[1], table.shape[2])
+        nbytes = 0 if self._f64 else lib().kimg_grid_workspace_bytes(
+            self.max_vis, num_pols, table.shape[0], table.shape[1], table.shape[2])
         self._workspace = None
         self._workspace_bytes = nbytes
         if nbytes:
             self._workspace = accel.DeviceArray(self.command_queue.context, (nbytes,), np.uint8,
                                                 queue=self.command_queue)
-        binned = lib().kimg_grid_binned_workspace_bytes(
+        # (float64: no scratch except for the sort; window kernels for widths up to 32)
+        binned = 0 if self._f64 and table.shape[2] > 32 else lib().kimg_grid_binned_workspace_bytes(
             self.max_vis, num_pols, table.shape[0], table.shape[1], table.shape[2])
         # the window gridder packs first-tap coordinates into 16 bits and addresses a polarization
         # plane with 32-bit byte offsets (kimg_grid: grid_size <= 32000, grid_size * row_stride * 8
@@ -417,6 +431,20 @@ class Gridder(GridDegrid):
         P, G = grid.shape[0], grid.shape[1]
         table, W, OV, K = self._kernel_args()
         variant = self._choose_variant()
+        if self._f64:
+            if variant == GRID_VARIANTS['binned']:
+                self._binned_workspace()
+            rc = lib().kimg_grid_f64(
+                grid.ptr, G, G * G, G, P,
+                wg.ptr, G, G * G,
+                self.buffer('uv').ptr, self.buffer('w_plane').ptr, self.buffer('vis').ptr,
+                self.num_vis, table, W, OV, K,
+                self._workspace.ptr if self._workspace is not None else None,
+                self._workspace_bytes, variant | int(self.window_cus) << 8,
+                self.command_queue.handle)
+            check(rc, 'kimg_grid_f64')
+            self._note_variant(variant)
+            return
         if variant == GRID_VARIANTS['binned']:
             self._binned_workspace()        # 34 + 8 P bytes per visibility of max_vis
         rc = lib().kimg_grid(
@@ -436,12 +464,12 @@ class DegridderTemplate:
     the statistical weights and scatters the residual visibilities back into the caller's order)."""
 
     def __init__(self, context, fixed_image_parameters, fixed_grid_parameters, tuning=None):
-        types.require_float32(fixed_image_parameters.real_dtype, 'DegridderTemplate')
+        types.require_float32_or_64(fixed_image_parameters.real_dtype, 'DegridderTemplate')
         lib()
         self.context = context
         self.fixed_image_parameters = fixed_image_parameters
         self.fixed_grid_parameters = fixed_grid_parameters
-        self.variant, self.arith = _tuning(tuning)
+        self.variant, self.arith = _tuning(tuning, fixed_image_parameters.real_dtype)
         self.kernel_pad = 0
 
     def instantiate(self, *args, **kwargs):
@@ -461,21 +489,36 @@ class Degridder(GridDegrid):
         self.slots['weights'] = accel.IOSlot(
             (self.max_vis, accel.Dimension(num_pols, exact=True)), np.float32)
         table = self.convolve_kernel.padded_data
-        nbytes = lib().kimg_degrid_workspace_bytes(num_pols, table.shape[0], table.shape[1],
-                                                   table.shape[2])
+        nbytes = 0 if self._f64 else lib().kimg_degrid_workspace_bytes(
+            num_pols, table.shape[0], table.shape[1], table.shape[2])
         self._workspace = None
         self._workspace_bytes = nbytes
         if nbytes:
             self._workspace = accel.DeviceArray(self.command_queue.context, (nbytes,), np.uint8,
                                                 queue=self.command_queue)
-        self._init_locality(lib().kimg_degrid_binned_workspace_bytes(
-            self.max_vis, num_pols, table.shape[0], table.shape[1], table.shape[2]))
+        self._init_locality(0 if self._f64 and table.shape[2] > 32 else
+                            lib().kimg_degrid_binned_workspace_bytes(
+                                self.max_vis, num_pols, table.shape[0], table.shape[1],
+                                table.shape[2]))
 
     def _run(self):
         grid = self.buffer('grid')
         P, G = grid.shape[0], grid.shape[1]
         table, W, OV, K = self._kernel_args()
         variant = self._choose_variant()
+        if self._f64:
+            if variant == GRID_VARIANTS['binned']:
+                self._binned_workspace()
+            rc = lib().kimg_degrid_f64(
+                grid.ptr, G, G * G, G, P,
+                self.buffer('uv').ptr, self.buffer('w_plane').ptr, self.buffer('weights').ptr,
+                self.buffer('vis').ptr, self.num_vis, table, W, OV, K,
+                self._workspace.ptr if self._workspace is not None else None,
+                self._workspace_bytes, variant | int(self.window_cus) << 8,
+                self.command_queue.handle)
+            check(rc, 'kimg_degrid_f64')
+            self._note_variant(variant)
+            return
         if variant == GRID_VARIANTS['binned']:
             self._binned_workspace()        # 38 + 12 P bytes per visibility of max_vis
         rc = lib().kimg_degrid(

@@ -18,10 +18,14 @@ def _pol_ptr(array, pol):
     return array.ptr + pol * array.shape[1] * array.shape[2] * array.dtype.itemsize
 
 
+def _is_f64(dtype):
+    return np.dtype(dtype) == np.float64
+
+
 class _LayerImageTemplate:
-    """image.py:15-86."""
+    """image.py:15-86.  float32 or float64 (the ``kimg_*_f64`` calls)."""
     def __init__(self, context, real_dtype, tuning=None):
-        types.require_float32(real_dtype, type(self).__name__)
+        types.require_float32_or_64(real_dtype, type(self).__name__)
         lib()
         self.context = context
         self.real_dtype = np.dtype(real_dtype)
@@ -67,11 +71,12 @@ class LayerToImage(_LayerImage):
     def _run(self):
         image = self.buffer('image')
         size = image.shape[-1]
-        rc = lib().kimg_layer_to_image(
+        fn = 'kimg_layer_to_image_f64' if _is_f64(self.template.real_dtype) else 'kimg_layer_to_image'
+        rc = getattr(lib(), fn)(
             _pol_ptr(image, self.polarization), size, self.buffer('layer').ptr, size,
             self.buffer('kernel1d').ptr, self.lm_scale, self.lm_bias, self.w,
             self.command_queue.handle)
-        check(rc, 'kimg_layer_to_image')
+        check(rc, fn)
 
 
 class ImageToLayerTemplate(_LayerImageTemplate):
@@ -84,16 +89,18 @@ class ImageToLayer(_LayerImage):
     def _run(self):
         image = self.buffer('image')
         size = image.shape[-1]
-        rc = lib().kimg_image_to_layer(
+        fn = 'kimg_image_to_layer_f64' if _is_f64(self.template.real_dtype) else 'kimg_image_to_layer'
+        rc = getattr(lib(), fn)(
             self.buffer('layer').ptr, _pol_ptr(image, self.polarization), size, size,
             self.buffer('kernel1d').ptr, self.lm_scale, self.lm_bias, self.w,
             self.command_queue.handle)
-        check(rc, 'kimg_image_to_layer')
+        check(rc, fn)
 
 
 class _ImageTemplate:
+    """float32 or float64 (the ``kimg_*_f64`` calls)."""
     def __init__(self, context, dtype, num_polarizations, tuning=None):
-        types.require_float32(dtype, type(self).__name__)
+        types.require_float32_or_64(dtype, type(self).__name__)
         lib()
         self.context = context
         self.dtype = np.dtype(dtype)
@@ -128,6 +135,13 @@ class Scale(accel.Operation):
     def _run(self):
         data = self.buffer('data')
         P, H, W = data.shape
+        if _is_f64(self.template.dtype):
+            sf = np.ascontiguousarray(self.scale_factor, np.float64)
+            rc = lib().kimg_scale_f64(data.ptr, W, H * W, W, H, P,
+                                      sf.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                      self.command_queue.handle)
+            check(rc, 'kimg_scale_f64')
+            return
         sf = np.ascontiguousarray(self.scale_factor, np.float32)
         rc = lib().kimg_scale(data.ptr, W, H * W, W, H, P,
                               sf.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
@@ -153,9 +167,10 @@ class AddImage(accel.Operation):
     def _run(self):
         src, dest = self.buffer('src'), self.buffer('dest')
         P, H, W = src.shape
-        rc = lib().kimg_add_image(dest.ptr, W, H * W, src.ptr, W, H * W, W, H, P,
-                                  self.command_queue.handle)
-        check(rc, 'kimg_add_image')
+        fn = 'kimg_add_image_f64' if _is_f64(self.template.dtype) else 'kimg_add_image'
+        rc = getattr(lib(), fn)(dest.ptr, W, H * W, src.ptr, W, H * W, W, H, P,
+                                self.command_queue.handle)
+        check(rc, fn)
 
 
 class ApplyPrimaryBeamTemplate(_ImageTemplate):
@@ -178,10 +193,11 @@ class ApplyPrimaryBeam(accel.Operation):
     def _run(self):
         data = self.buffer('data')
         P, H, W = data.shape
-        rc = lib().kimg_apply_primary_beam(
+        fn = 'kimg_apply_primary_beam_f64' if _is_f64(self.template.dtype) else 'kimg_apply_primary_beam'
+        rc = getattr(lib(), fn)(
             data.ptr, W, H * W, self.buffer('beam_power').ptr, W, W, H, P,
             self.threshold, self.replacement, self.command_queue.handle)
-        check(rc, 'kimg_apply_primary_beam')
+        check(rc, fn)
 
 
 class _PlanPool:
@@ -213,15 +229,22 @@ _plan_pool = _PlanPool()
 
 
 class FftPlan:
-    """rocFFT 2-D C2C plan (stands in for katsdpsigproc.fft.FftTemplate, image.py:599)."""
-    def __init__(self, shape):
+    """rocFFT 2-D C2C plan (stands in for katsdpsigproc.fft.FftTemplate, image.py:599) on
+    complex64 or complex128 layers."""
+    def __init__(self, shape, dtype=np.complex64):
         self.shape = tuple(int(x) for x in shape)
-        self.dtype_src = self.dtype_dest = np.dtype(np.complex64)
-        handle = _plan_pool.take(self.shape)
+        self.dtype_src = self.dtype_dest = np.dtype(dtype)
+        if self.dtype_src == np.complex64:
+            self._key, create = self.shape, 'kimg_fft_plan_create'
+        elif self.dtype_src == np.complex128:
+            self._key, create = ('complex128',) + self.shape, 'kimg_fft_plan_create_f64'
+        else:
+            raise ValueError('FftPlan: complex64 or complex128, not {}'.format(self.dtype_src))
+        handle = _plan_pool.take(self._key)
         if handle is None:
             handle = ctypes.c_void_p()
-            check(lib().kimg_fft_plan_create(ctypes.byref(handle), self.shape[0], self.shape[1]),
-                  'kimg_fft_plan_create')
+            check(getattr(lib(), create)(ctypes.byref(handle), self.shape[0], self.shape[1]),
+                  create)
         self._handle = handle
         self._queue = None
         self._real = None
@@ -236,6 +259,8 @@ class FftPlan:
         ImageToGrid, made on first use and shared by the operators that share this plan (and its
         `layer` buffer)."""
         if self._real is None:
+            if self.dtype_src != np.complex64:
+                raise ValueError('the real-to-complex plans are float32 only')
             self._real = RealFftPlan(self.shape)
         return self._real
 
@@ -244,7 +269,7 @@ class FftPlan:
             handle, self._handle = self._handle, None
             if handle and self._queue is not None:
                 self._queue.finish()      # the next owner may run the plan on another stream
-            if handle and not _plan_pool.give(self.shape, handle):
+            if handle and not _plan_pool.give(self._key, handle):
                 lib().kimg_fft_plan_destroy(handle)
         except Exception:
             pass
@@ -289,10 +314,14 @@ class GridImageTemplate:
     takes for w = 0 (see :class:`GridToImage`); ``{'own_transform': False}`` keeps that route on
     the library's 2-D plans where it would otherwise run the two-launch transforms of
     ``kimg_grid_to_image_real`` / ``kimg_image_to_grid_real`` and their any-w counterparts (even
-    layer sizes up to 8192 without a prime factor above 7)."""
+    layer sizes up to 8192 without a prime factor above 7).
+
+    Float64 (complex128 grid and layer, float64 image): every w takes the plain route -- grid ->
+    layer copy, double-precision C2C transform, layer -> image -- and the two tuning keys are
+    accepted and have no effect (the real and own transforms are float32 only)."""
 
     def __init__(self, context, real_dtype, tuning=None):
-        types.require_float32(real_dtype, 'GridImageTemplate')
+        types.require_float32_or_64(real_dtype, 'GridImageTemplate')
         tuning = tuning or {}
         if set(tuning) - {'real_transform', 'own_transform'}:
             raise ValueError('bad GridImageTemplate tuning {}'.format(tuning))
@@ -304,8 +333,8 @@ class GridImageTemplate:
         self.image_to_layer = ImageToLayerTemplate(context, real_dtype)
 
     def make_fft_plan(self, shape_layer, padded_shape_layer=None):
-        plan = FftPlan(shape_layer)
-        if self.real_transform:
+        plan = FftPlan(shape_layer, types.real_to_complex(self.real_dtype))
+        if self.real_transform and not _is_f64(self.real_dtype):
             plan.real_plan()        # (plan creation costs milliseconds of host time: not in the loop)
         return plan
 
@@ -327,7 +356,9 @@ class _GridImage(accel.Operation):
             command_queue, shape_image, lm_scale, lm_bias, allocator)
         for name in ('layer', 'image', 'kernel1d'):
             self.slots[name] = self._layer_image.slots[name]
-        self.slots['grid'] = accel.IOSlot(shape_grid, np.complex64)
+        self.slots['grid'] = accel.IOSlot(shape_grid, types.real_to_complex(template.real_dtype))
+        #: float64: the plain route for every w (see GridImageTemplate)
+        self._plain = _is_f64(template.real_dtype)
         if shape_grid[1] != shape_grid[2] or shape_grid[1] % 2:
             raise ValueError('grid must be square with even size')     # image.py:655-656
 
@@ -338,7 +369,7 @@ class _GridImage(accel.Operation):
         """Whether the w = 0 route runs on the library's own transforms."""
         G = self.buffer('layer').shape[0]
         Gg = self.buffer('grid').shape[1]
-        return (self.template.real_transform and self.template.own_transform
+        return (not self._plain and self.template.real_transform and self.template.own_transform
                 and bool(lib().kimg_grid_image_real_supported(G, Gg)))
 
 
@@ -363,6 +394,14 @@ class GridToImage(_GridImage):
         P, Gg, _ = grid.shape
         G = layer.shape[0]
         q = self.command_queue
+        if self._plain:
+            for pol in range(P):
+                check(lib().kimg_grid_to_layer_f64(layer.ptr, G, _pol_ptr(grid, pol), Gg, Gg,
+                                                   q.handle), 'kimg_grid_to_layer_f64')
+                self._fft.execute(q, layer, inverse=True)
+                self._layer_image.set_polarization(pol)
+                self._layer_image()
+            return
         if self._layer_image.w == 0 and self.template.real_transform:
             # w = 0: the phase factor is 1 and only the real part of the transform is used, which
             # is the transform of the grid's Hermitian part: half the layer, a complex-to-real
@@ -421,6 +460,15 @@ class ImageToGrid(_GridImage):
         grid, layer = self.buffer('grid'), self.buffer('layer')
         P, Gg, _ = grid.shape
         G = layer.shape[0]
+        if self._plain:
+            for pol in range(P):
+                self._layer_image.set_polarization(pol)
+                self._layer_image()
+                self._fft.execute(self.command_queue, layer, inverse=False)
+                check(lib().kimg_layer_to_grid_f64(_pol_ptr(grid, pol), Gg, Gg, layer.ptr, G,
+                                                   self.command_queue.handle),
+                      'kimg_layer_to_grid_f64')
+            return
         if self._layer_image.w == 0 and self.template.real_transform:
             # w = 0: the layer is real; real-to-complex transform in place, the grid's other half
             # from F(-k) = conj F(k)

@@ -16,7 +16,7 @@ import functools
 
 import numpy as np
 
-from . import accel, clean, grid, image, predict, weight
+from . import accel, clean, grid, image, predict, types, weight
 
 
 class ImagingTemplate:
@@ -26,6 +26,9 @@ class ImagingTemplate:
 
     def __init__(self, context, array_parameters, fixed_image_parameters,
                  weight_parameters, fixed_grid_parameters, clean_parameters, tuning=None):
+        # The gridder, degridder and grid <-> image have float64 forms, CLEAN, the PSF patch, the
+        # noise estimate and prediction do not: refuse float64 here, whatever is built first.
+        types.require_float32(fixed_image_parameters.real_dtype, 'ImagingTemplate')
         self.context = context
         self.array_parameters = array_parameters
         self.fixed_image_parameters = fixed_image_parameters

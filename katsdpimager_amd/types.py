@@ -26,3 +26,11 @@ def require_float32(dtype, what):
     if np.dtype(dtype) != np.float32:
         raise ValueError('{}: only float32 is supported by the HIP path, not {}'.format(
             what, np.dtype(dtype)))
+
+
+def require_float32_or_64(dtype, what):
+    """For the operators that have a float64 form (the reference's --precision double): the
+    gridder, degridder, grid <-> image and the image-plane operators."""
+    if np.dtype(dtype) not in (np.float32, np.float64):
+        raise ValueError('{}: only float32 and float64 are supported by the HIP path, not {}'.format(
+            what, np.dtype(dtype)))
