@@ -253,6 +253,21 @@ int kimg_degrid_f64(const void *grid, int64_t grid_row_stride, int64_t grid_pol_
  * vis[r][p] -= weights[r][p] * sum_s flux[s][p] * exp(-2 pi i (l u + m v + (n-1) w)),
  * u = (uv.x*oversample + uv.z + 0.5)*uv_scale, w = w_plane*w_scale + w_bias.
  *   lmn float32 [S][3] (l, m, n-1);  flux float32 [S][P]
+ * Arithmetic (float32 throughout, fl() = one round to nearest, no contraction unless named):
+ *   u_f = fl(fl(uv.x*oversample + uv.z + 0.5) * uv_scale)   (the integer converts exactly below
+ *         2^24 and the + 0.5 is exact below 2^23: one rounding);  v_f likewise from uv.y, uv.w
+ *   w_f = fl(fl(w_plane*w_scale) + w_bias)
+ *   phi = fl(fl(fl(l*u_f) + fl(m*v_f)) + fl((n-1)*w_f))               in turns
+ *   t = v_fract_f32(phi) = phi - floor(phi)   (exact but for a tiny negative phi, where it lies
+ *         within 2^-24 of 1);  c = v_cos_f32(t), s = v_sin_f32(t)
+ *         (argument in turns: c ~ cos(2 pi t), s ~ sin(2 pi t))
+ *   acc[p] = fmaf(c, flux[j][p], acc[p]) (re), fmaf(-s, flux[j][p], acc[p]) (im), one rounding
+ *         per source, for j = 0 .. S-1 in order from acc = 0 (the LDS chunks of 256 are padded
+ *         with zero-flux sources, which add exact zeros)
+ *   vis[r][p] = fl(vis[r][p] - fl(acc[p]*weights[r][p]))      re and im separately
+ * Nothing at or beyond num_vis is read from weights or written to vis.  num_vis == 0 or
+ * num_sources == 0 returns 0 with no launch (lmn, flux may then be NULL).  P outside 1-4:
+ * KIMG_EUNSUPPORTED.  There is no float64 form.
  */
 int kimg_predict(void *vis, const int16_t *uv, const int16_t *w_plane, const float *weights,
                  const float *lmn, const float *flux, int64_t num_vis, int num_sources,

@@ -9,7 +9,7 @@ scope for the hot path).
 """
 import numpy as np
 
-from . import accel, grid
+from . import accel, grid, types
 from ._lib import lib, check
 
 
@@ -65,6 +65,9 @@ class PredictTemplate:
     """predict.py:152-287 (no autotuning: one thread per visibility, 256-wide groups)."""
 
     def __init__(self, context, real_dtype, num_polarizations, tuning=None):
+        # The kernel accumulates in float32 only; the reference takes real_dtype as the
+        # accumulation type, so float64 is refused rather than silently run in float32.
+        types.require_float32(real_dtype, 'PredictTemplate')
         lib()
         self.context = context
         self.real_dtype = np.dtype(real_dtype)
