@@ -423,7 +423,44 @@ int kimg_half_layer_to_grid(void *grid, int64_t grid_row_stride, int grid_size,
  * Results equal the route above up to the rounding of the transform.  accumulate = 0: the image
  * is written, not added to (what the reference gets by zeroing it first, imaging.py:258-261:
  * saves the fill and the read).
- *   kimg_grid_image_real_supported: 1 when the two functions take these sizes, else 0. */
+ *   kimg_grid_image_real_supported: 1 when the two functions take these sizes, else 0.
+ *
+ * Arithmetic the five functions below promise (tests/test_transform_truth.py restates it).  fl()
+ * is one float32 rounding; nothing is fused except where fma() is written (the library is built
+ * with -ffp-contract=off); sqrt and / are correctly rounded (hipcc's default for float32 when no
+ * fast-math flag is given; katsdpimager_amd/build.py FLAGS gives none and must not).  G = layer_size, Gg = grid_size, h = Gg / 2; image index y <-> layer index
+ * sy = (y + G/2) mod G; grid index gy <-> frequency cy = gy - h <-> layer index cy mod G.
+ *   l(x)   = fl(fl((float) x * lm_scale) + lm_bias), m(y) likewise;
+ *   n(y,x) = sqrt(fl(1 - fl(fl(m m) + fl(l l))))      (lm_scale = 0, lm_bias = 0 is taken: n = 1);
+ *   p(y,x) = fl(w * fl(n - 1)) turns, r = p - rint(p) (exact), c + i s = cospi(2 r) + i sinpi(2 r);
+ *            the image -> grid direction uses fl(-w * fl(n - 1)) = -p, so c - i s;
+ *   t(y,x) = fl(k[y] * k[x]) with k = kernel1d.
+ * The transforms F are unnormalised sums of G terms per axis, sign + grid -> image and - image ->
+ * grid, evaluated in float32 as decimation-in-time stages of radix 4 (as many as fit), 2 (at most
+ * one), 3, 5, 7 in that order; a complex product a b is (fma(a.x, b.x, -fl(a.y b.y)),
+ * fma(a.x, b.y, fl(a.y b.x))); the twiddles e^{2 pi i j / (r q)} of a stage are double values rounded to
+ * float32, their powers float32 products of those, the 3rd, 5th and 7th roots of unity float32
+ * constants.  The order of the sums inside F is not part of the contract; its accuracy is (the
+ * test module's bound).
+ *   grid -> image, w = 0: the layer is the grid's Hermitian part, fl(0.5 (g(c) + conj g(-c))) per
+ *     component, with g = 0 outside -h .. h - 1 (so row and column -h meet no partner unless
+ *     Gg = G, where -G/2 is its own mirror); v = Re F;
+ *     out = fl(fl(v n) / t); image = out (accumulate = 0) or fl(image + out).
+ *   grid -> image, any w: v = fl(fl(Re F c) - fl(Im F s)); out and image as above.  At w = 0 this
+ *     is the same quantity as the function above, by another sum.
+ *   image -> grid, w = 0: layer = fl(image / fl(t n)); grid cell (gy, gx) = F at (cy, cx).  Every
+ *     cell of the Gg x Gg grid is overwritten, nothing is added to it; cells of a row beyond
+ *     grid_size (grid_row_stride) are not touched.
+ *   image -> grid, any w: u = fl(image / fl(t n)), layer = (fl(u c), -fl(u s)); grid as above.
+ *   kimg_convolve_beam: per cell (v, u) of the half spectrum, v = ly - size if 2 ly >= size else
+ *     ly, u = 0 .. size/2: power = fl(fl(fl(fl(a v) + fl(b u)) v) + fl(fl(c u) u)), factor =
+ *     fl(amplitude * expf(power)), spectrum cell times factor per component; rows forward, columns
+ *     forward, factor, columns inverse, rows inverse.  Nothing is divided by size^2: the caller
+ *     folds it into `amplitude`.
+ * Every function writes `workspace` only below the byte count its _workspace_bytes function
+ * returns, refuses (KIMG_EINVAL, nothing written) a workspace that is smaller or not 16-byte
+ * aligned, a stride below the width and sizes kimg_grid_image_real_supported refuses, and leaves
+ * the cells of a row beyond the width alone. */
 int kimg_grid_image_real_supported(int layer_size, int grid_size);
 size_t kimg_grid_image_real_workspace_bytes(int layer_size, int grid_size);
 int kimg_grid_to_image_real(float *image, int64_t image_row_stride, int layer_size,

@@ -2187,7 +2187,8 @@ def test_dirty_image_vs_fp64_truth(golden, name):
 @pytest.mark.gpu
 @pytest.mark.parametrize('name', list(gi.IMAGE_CONFIGS))
 def test_grid_image_vs_fp64_truth(golden, name):
-    """G5 against a float64 truth: GridToImage (zero-pad + rocFFT + layer_to_image) and the
+    """G5 against a float64 truth: GridToImage (the library's own transform at size 64; zero-pad +
+    rocFFT + layer_to_image at 102 = 2 3 17, which the own transforms refuse) and the
     reference's float32 host result are both within 1e-5 (unweighted: the G5 kernel1d stays within
     [1, 2]) of the float64 evaluation at w = 0, and within 1e-5 + 4e-7 |w| at w != 0 (the float32
     evaluation of n - 1 that both share)."""
