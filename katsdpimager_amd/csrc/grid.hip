@@ -7,31 +7,6 @@
 // chip's atomic rate (~1.3 TB/s of added bytes), not at the FMA rate.
 #include "kimg_common.h"
 
-int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride, int grid_size,
-                   int P, const float *weights_grid, int64_t wg_row_stride, int64_t wg_pol_stride,
-                   const int16_t *uv, const int16_t *w_plane, const void *vis, int64_t num_vis,
-                   const void *convolve_kernel, int w_planes, int oversample, int kernel_width,
-                   void *workspace, size_t workspace_bytes, int arith, hipStream_t stream);
-int kimg_grid_binned(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride, int grid_size,
-                     int P, const float *weights_grid, int64_t wg_row_stride, int64_t wg_pol_stride,
-                     const int16_t *uv, const int16_t *w_plane, const void *vis, int64_t num_vis,
-                     const void *convolve_kernel, int w_planes, int oversample, int kernel_width,
-                     void *workspace, size_t workspace_bytes, int arith, hipStream_t stream);
-bool kimg_grid_mfma_supported(int P, int w_planes, int oversample, int kernel_width);
-size_t kimg_grid_mfma_workspace_bytes(int P, int w_planes, int oversample, int kernel_width);
-int kimg_degrid_mfma(const void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
-                     int grid_size, int P, const int16_t *uv, const int16_t *w_plane,
-                     const float *weights, void *vis, int64_t num_vis, const void *convolve_kernel,
-                     int w_planes, int oversample, int kernel_width, void *workspace,
-                     size_t workspace_bytes, int arith, hipStream_t stream);
-int kimg_degrid_binned(const void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
-                       int grid_size, int P, const int16_t *uv, const int16_t *w_plane,
-                       const float *weights, void *vis, int64_t num_vis, const void *convolve_kernel,
-                       int w_planes, int oversample, int kernel_width, void *workspace,
-                       size_t workspace_bytes, int arith, hipStream_t stream);
-size_t kimg_degrid_mfma_workspace_bytes(int P, int w_planes, int oversample, int kernel_width);
-bool kimg_degrid_mfma_supported(int P, int w_planes, int oversample, int kernel_width);
-
 namespace {
 
 __device__ inline float2 cmul(float2 a, float2 b)
@@ -43,21 +18,6 @@ __device__ inline float2 cmul(float2 a, float2 b)
 __device__ inline float2 cmul_conj(float2 a, float2 b)
 {
     return make_float2(fmaf(a.x, b.x, a.y * b.y), fmaf(a.y, b.x, -a.x * b.y));
-}
-
-struct vis_coord {
-    int u, v, sub_u, sub_v;
-};
-
-__device__ inline vis_coord load_uv(const int16_t *__restrict__ uv, int64_t i)
-{
-    const int2 packed = reinterpret_cast<const int2 *>(uv)[i];
-    vis_coord c;
-    c.u = (short) (packed.x & 0xffff);
-    c.v = (short) (packed.x >> 16);
-    c.sub_u = (short) (packed.y & 0xffff);
-    c.sub_v = (short) (packed.y >> 16);
-    return c;
 }
 
 // One wave per visibility; lanes sweep the K x K footprint (lane%32 along u).
@@ -299,11 +259,17 @@ extern "C" int kimg_grid(void *grid, int64_t grid_row_stride, int64_t grid_pol_s
                                                      kernel_width);
     if ((variant == KIMG_VARIANT_MFMA || variant == KIMG_VARIANT_BINNED) && !mfma_ok)
         return KIMG_EUNSUPPORTED;
-    if (variant == KIMG_VARIANT_BINNED)
-        return kimg_grid_binned(grid, grid_row_stride, grid_pol_stride, grid_size,
-                                num_polarizations, weights_grid, wg_row_stride, wg_pol_stride, uv,
-                                w_plane, vis, num_vis, convolve_kernel, w_planes, oversample,
-                                kernel_width, workspace, workspace_bytes, arith, s);
+    if (variant == KIMG_VARIANT_BINNED) {
+        kimg_binned_stream b;
+        rc = kimg_bin_stream(uv, w_plane, nullptr, vis, num_vis, grid_size, num_polarizations,
+                             w_planes, oversample, kernel_width, workspace, workspace_bytes, s, b);
+        if (rc)
+            return rc;
+        return kimg_grid_mfma(grid, grid_row_stride, grid_pol_stride, grid_size,
+                              num_polarizations, weights_grid, wg_row_stride, wg_pol_stride, b.uv,
+                              b.w_plane, b.vis, num_vis, convolve_kernel, w_planes, oversample,
+                              kernel_width, b.table, b.table_bytes, arith, s);
+    }
     if (variant == KIMG_VARIANT_MFMA || (variant == KIMG_VARIANT_AUTO && mfma_ok))
         return kimg_grid_mfma(grid, grid_row_stride, grid_pol_stride, grid_size,
                               num_polarizations, weights_grid, wg_row_stride, wg_pol_stride, uv,
@@ -312,17 +278,11 @@ extern "C" int kimg_grid(void *grid, int64_t grid_row_stride, int64_t grid_pol_s
     int blocks = kimg_divup(num_vis, 4);
     if (blocks > 8192)
         blocks = 8192;
-#define LAUNCH(P) grid_generic_kernel<P><<<blocks, 256, 0, s>>>( \
-        (float *) grid, grid_row_stride, grid_pol_stride, grid_size, weights_grid, wg_row_stride, \
-        wg_pol_stride, uv, w_plane, (const float2 *) vis, num_vis, \
-        (const float2 *) convolve_kernel, oversample, kernel_width)
-    switch (num_polarizations) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 3: LAUNCH(3); break;
-    case 4: LAUNCH(4); break;
-    }
-#undef LAUNCH
+    kimg_for_pols(num_polarizations, [&](auto p) {
+        grid_generic_kernel<decltype(p)::value><<<blocks, 256, 0, s>>>(
+            (float *) grid, grid_row_stride, grid_pol_stride, grid_size, weights_grid, wg_row_stride,
+            wg_pol_stride, uv, w_plane, (const float2 *) vis, num_vis,
+            (const float2 *) convolve_kernel, oversample, kernel_width); });
     return kimg_launch_status();
 }
 
@@ -357,11 +317,18 @@ extern "C" int kimg_degrid(const void *grid, int64_t grid_row_stride, int64_t gr
                                                     kernel_width);
     if ((variant == KIMG_VARIANT_MFMA || variant == KIMG_VARIANT_BINNED) && !mfma_ok)
         return KIMG_EUNSUPPORTED;
-    if (variant == KIMG_VARIANT_BINNED)
-        return kimg_degrid_binned(grid, grid_row_stride, grid_pol_stride, grid_size,
-                                  num_polarizations, uv, w_plane, weights, vis, num_vis,
-                                  convolve_kernel, w_planes, oversample, kernel_width, workspace,
-                                  workspace_bytes, arith, s);
+    if (variant == KIMG_VARIANT_BINNED) {
+        kimg_binned_stream b;
+        rc = kimg_bin_stream(uv, w_plane, weights, vis, num_vis, grid_size, num_polarizations,
+                             w_planes, oversample, kernel_width, workspace, workspace_bytes, s, b);
+        if (rc)
+            return rc;
+        rc = kimg_degrid_mfma(grid, grid_row_stride, grid_pol_stride, grid_size,
+                              num_polarizations, b.uv, b.w_plane, b.weights, b.vis, num_vis,
+                              convolve_kernel, w_planes, oversample, kernel_width, b.table,
+                              b.table_bytes, arith, s);
+        return rc ? rc : kimg_unbin_vis(b, vis, num_vis, num_polarizations, s);
+    }
     if (variant != KIMG_VARIANT_GENERIC && mfma_ok)
         return kimg_degrid_mfma(grid, grid_row_stride, grid_pol_stride, grid_size,
                                 num_polarizations, uv, w_plane, weights, vis, num_vis,
@@ -370,16 +337,10 @@ extern "C" int kimg_degrid(const void *grid, int64_t grid_row_stride, int64_t gr
     int blocks = kimg_divup(num_vis, 4);
     if (blocks > 16384)
         blocks = 16384;
-#define LAUNCH(P) degrid_generic_kernel<P><<<blocks, 256, 0, s>>>( \
-        (const float2 *) grid, grid_row_stride, grid_pol_stride, grid_size, uv, w_plane, weights, \
-        (float2 *) vis, num_vis, (const float2 *) convolve_kernel, oversample, kernel_width)
-    switch (num_polarizations) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 3: LAUNCH(3); break;
-    case 4: LAUNCH(4); break;
-    }
-#undef LAUNCH
+    kimg_for_pols(num_polarizations, [&](auto p) {
+        degrid_generic_kernel<decltype(p)::value><<<blocks, 256, 0, s>>>(
+            (const float2 *) grid, grid_row_stride, grid_pol_stride, grid_size, uv, w_plane, weights,
+            (float2 *) vis, num_vis, (const float2 *) convolve_kernel, oversample, kernel_width); });
     return kimg_launch_status();
 }
 
@@ -397,16 +358,10 @@ extern "C" int kimg_predict(void *vis, const int16_t *uv, const int16_t *w_plane
     KIMG_CHECK_ARG(lmn && flux);
     hipStream_t s = (hipStream_t) stream;
     const int blocks = kimg_divup(num_vis, 256);
-#define LAUNCH(P) predict_kernel<P><<<blocks, 256, 0, s>>>( \
-        (float2 *) vis, uv, w_plane, weights, lmn, flux, num_vis, num_sources, oversample, \
-        uv_scale, w_scale, w_bias)
-    switch (num_polarizations) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 3: LAUNCH(3); break;
-    case 4: LAUNCH(4); break;
-    }
-#undef LAUNCH
+    kimg_for_pols(num_polarizations, [&](auto p) {
+        predict_kernel<decltype(p)::value><<<blocks, 256, 0, s>>>(
+            (float2 *) vis, uv, w_plane, weights, lmn, flux, num_vis, num_sources, oversample,
+            uv_scale, w_scale, w_bias); });
     return kimg_launch_status();
 }
 

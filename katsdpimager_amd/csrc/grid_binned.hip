@@ -18,21 +18,6 @@
 #include "kimg_common.h"
 #include <hipcub/hipcub.hpp>
 
-int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride, int grid_size,
-                   int P, const float *weights_grid, int64_t wg_row_stride, int64_t wg_pol_stride,
-                   const int16_t *uv, const int16_t *w_plane, const void *vis, int64_t num_vis,
-                   const void *convolve_kernel, int w_planes, int oversample, int kernel_width,
-                   void *workspace, size_t workspace_bytes, int arith, hipStream_t stream);
-bool kimg_grid_mfma_supported(int P, int w_planes, int oversample, int kernel_width);
-size_t kimg_grid_mfma_workspace_bytes(int P, int w_planes, int oversample, int kernel_width);
-int kimg_degrid_mfma(const void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
-                     int grid_size, int P, const int16_t *uv, const int16_t *w_plane,
-                     const float *weights, void *vis, int64_t num_vis, const void *convolve_kernel,
-                     int w_planes, int oversample, int kernel_width, void *workspace,
-                     size_t workspace_bytes, int arith, hipStream_t stream);
-size_t kimg_degrid_mfma_workspace_bytes(int P, int w_planes, int oversample, int kernel_width);
-bool kimg_degrid_mfma_supported(int P, int w_planes, int oversample, int kernel_width);
-
 namespace {
 
 constexpr int WIN = 32;
@@ -53,14 +38,14 @@ struct bin_geometry {
 };
 
 __global__ __launch_bounds__(256) void bin_key_kernel(
-    const int2 *__restrict__ uv, int64_t n, bin_geometry g, int grid_size,
+    const int16_t *__restrict__ uv, int64_t n, bin_geometry g, int grid_size,
     unsigned *__restrict__ keys, unsigned *__restrict__ index)
 {
     const int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
     if (i >= n)
         return;
-    const int2 r = uv[i];
-    const int u = (short) (r.x & 0xffff) + g.half, v = (short) (r.x >> 16) + g.half;
+    const vis_coord c = load_uv(uv, i);
+    const int u = c.u + g.half, v = c.v + g.half;
     unsigned key = g.last_key;
     if ((unsigned) u < (unsigned) grid_size && (unsigned) v < (unsigned) grid_size) {
         const int bv = v / g.bin;
@@ -127,14 +112,13 @@ __global__ __launch_bounds__(256) void scatter_vis_kernel(
 }
 
 __global__ __launch_bounds__(256) void jump_count_kernel(
-    const int2 *__restrict__ uv, int64_t n, int slack, unsigned *__restrict__ count)
+    const int16_t *__restrict__ uv, int64_t n, int slack, unsigned *__restrict__ count)
 {
     unsigned local = 0;
     for (int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x + 1; i < n;
          i += (int64_t) gridDim.x * blockDim.x) {
-        const int2 a = uv[i - 1], b = uv[i];
-        const int du = (short) (b.x & 0xffff) - (short) (a.x & 0xffff);
-        const int dv = (short) (b.x >> 16) - (short) (a.x >> 16);
+        const vis_coord a = load_uv(uv, i - 1), b = load_uv(uv, i);
+        const int du = b.u - a.u, dv = b.v - a.v;
         local += (abs(du) > slack || abs(dv) > slack) ? 1u : 0u;
     }
 #pragma unroll
@@ -151,7 +135,7 @@ struct binned_ws {
 
 size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
-hipError_t layout(int64_t n, int P, int W, int OV, int K, binned_ws &ws, bool degrid = false)
+hipError_t layout(int64_t n, int P, int W, int OV, int K, bool degrid, binned_ws &ws)
 {
     size_t off = align256(degrid ? kimg_degrid_mfma_workspace_bytes(P, W, OV, K)
                                  : kimg_grid_mfma_workspace_bytes(P, W, OV, K));
@@ -181,24 +165,38 @@ hipError_t layout(int64_t n, int P, int W, int OV, int K, binned_ws &ws, bool de
     return e;
 }
 
-} // namespace
-
-size_t kimg_grid_binned_workspace_bytes_impl(int64_t n, int P, int W, int OV, int K)
+size_t binned_workspace_bytes(int64_t n, int P, int W, int OV, int K, bool degrid)
 {
-    if (n <= 0 || n >= ((int64_t) 1 << 31) || !kimg_grid_mfma_supported(P, W, OV, K))
+    if (n <= 0 || n >= ((int64_t) 1 << 31)
+        || !(degrid ? kimg_degrid_mfma_supported(P, W, OV, K) : kimg_grid_mfma_supported(P, W, OV, K)))
         return 0;
     binned_ws ws;
-    if (layout(n, P, W, OV, K, ws) != hipSuccess)
+    if (layout(n, P, W, OV, K, degrid, ws) != hipSuccess)
         return 0;
     return ws.total;
 }
 
-// keys of the footprint-origin bins, sorted; index.Current() = the caller's record of sorted place i
-static int sort_by_tile(const int16_t *uv, int64_t num_vis, int grid_size, int kernel_width,
-                        unsigned char *base, const binned_ws &ws,
-                        hipcub::DoubleBuffer<unsigned> &keys, hipcub::DoubleBuffer<unsigned> &index,
-                        hipStream_t stream)
+} // namespace
+
+int kimg_bin_stream(const int16_t *uv, const int16_t *w_plane, const float *weights, const void *vis,
+                    int64_t num_vis, int grid_size, int P, int w_planes, int oversample,
+                    int kernel_width, void *workspace, size_t workspace_bytes, hipStream_t stream,
+                    kimg_binned_stream &out)
 {
+    if (num_vis >= ((int64_t) 1 << 31))
+        return KIMG_EUNSUPPORTED;
+    binned_ws ws;
+    hipError_t e = layout(num_vis, P, w_planes, oversample, kernel_width, weights != nullptr, ws);
+    if (e != hipSuccess)
+        return -(int) e;
+    if (workspace == nullptr || workspace_bytes < ws.total)
+        return KIMG_EWORKSPACE;
+    unsigned char *base = static_cast<unsigned char *>(workspace);
+    hipcub::DoubleBuffer<unsigned> keys(reinterpret_cast<unsigned *>(base + ws.keys[0]),
+                                        reinterpret_cast<unsigned *>(base + ws.keys[1]));
+    hipcub::DoubleBuffer<unsigned> index(reinterpret_cast<unsigned *>(base + ws.index[0]),
+                                         reinterpret_cast<unsigned *>(base + ws.index[1]));
+    // keys of the footprint-origin bins, sorted; index.Current() = the caller's record of sorted place i
     bin_geometry g;
     g.half = grid_size / 2;
     g.bin = window_slack(kernel_width) + 1;
@@ -208,248 +206,56 @@ static int sort_by_tile(const int16_t *uv, int64_t num_vis, int grid_size, int k
     int bits = 1;
     while (bits < 32 && (g.last_key >> bits) != 0)
         bits++;
-    bin_key_kernel<<<kimg_divup(num_vis, 256), 256, 0, stream>>>(
-        reinterpret_cast<const int2 *>(uv), num_vis, g, grid_size, keys.Current(), index.Current());
+    const int blocks = kimg_divup(num_vis, 256);
+    bin_key_kernel<<<blocks, 256, 0, stream>>>(uv, num_vis, g, grid_size, keys.Current(),
+                                               index.Current());
     size_t cub_bytes = ws.cub_bytes;
     KIMG_HIP(hipcub::DeviceRadixSort::SortPairs(base + ws.cub, cub_bytes, keys, index, (int) num_vis,
                                                 0, bits, stream));
+    int rc = kimg_launch_status();
+    if (rc)
+        return rc;
+    int2 *uv_s = reinterpret_cast<int2 *>(base + ws.uv);
+    int16_t *wp_s = reinterpret_cast<int16_t *>(base + ws.wp);
+    out.uv = reinterpret_cast<const int16_t *>(uv_s);
+    out.w_plane = wp_s;
+    out.vis = reinterpret_cast<float2 *>(base + ws.vis);
+    out.weights = reinterpret_cast<float *>(base + ws.weights);
+    out.index = index.Current();
+    out.table = base + ws.table;
+    out.table_bytes = ws.keys[0];
+    const int2 *uv2 = reinterpret_cast<const int2 *>(uv);
+    const float2 *vis2 = static_cast<const float2 *>(vis);
+    kimg_for_pols(P, [&](auto p) {
+        if (weights)
+            gather_degrid_kernel<decltype(p)::value><<<blocks, 256, 0, stream>>>(
+                out.index, num_vis, uv2, w_plane, weights, vis2, uv_s, wp_s, out.weights, out.vis);
+        else
+            gather_kernel<decltype(p)::value><<<blocks, 256, 0, stream>>>(
+                out.index, num_vis, uv2, w_plane, vis2, uv_s, wp_s, out.vis); });
     return kimg_launch_status();
 }
 
-int kimg_degrid_binned(const void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
-                       int grid_size, int P, const int16_t *uv, const int16_t *w_plane,
-                       const float *weights, void *vis, int64_t num_vis, const void *convolve_kernel,
-                       int w_planes, int oversample, int kernel_width, void *workspace,
-                       size_t workspace_bytes, int arith, hipStream_t stream)
+int kimg_unbin_vis(const kimg_binned_stream &b, void *vis, int64_t num_vis, int P, hipStream_t stream)
 {
-    if (num_vis >= ((int64_t) 1 << 31))
-        return KIMG_EUNSUPPORTED;
-    binned_ws ws;
-    hipError_t e = layout(num_vis, P, w_planes, oversample, kernel_width, ws, true);
-    if (e != hipSuccess)
-        return -(int) e;
-    if (workspace == nullptr || workspace_bytes < ws.total)
-        return KIMG_EWORKSPACE;
-    unsigned char *base = static_cast<unsigned char *>(workspace);
-    hipcub::DoubleBuffer<unsigned> keys(reinterpret_cast<unsigned *>(base + ws.keys[0]),
-                                        reinterpret_cast<unsigned *>(base + ws.keys[1]));
-    hipcub::DoubleBuffer<unsigned> index(reinterpret_cast<unsigned *>(base + ws.index[0]),
-                                         reinterpret_cast<unsigned *>(base + ws.index[1]));
-    int rc = sort_by_tile(uv, num_vis, grid_size, kernel_width, base, ws, keys, index, stream);
-    if (rc)
-        return rc;
-    const int blocks = kimg_divup(num_vis, 256);
-    int2 *uv_s = reinterpret_cast<int2 *>(base + ws.uv);
-    int16_t *wp_s = reinterpret_cast<int16_t *>(base + ws.wp);
-    float *w_s = reinterpret_cast<float *>(base + ws.weights);
-    float2 *vis_s = reinterpret_cast<float2 *>(base + ws.vis);
-#define GATHER(PP) gather_degrid_kernel<PP><<<blocks, 256, 0, stream>>>(index.Current(), num_vis, \
-        reinterpret_cast<const int2 *>(uv), w_plane, weights, static_cast<const float2 *>(vis), uv_s, wp_s, \
-        w_s, vis_s)
-    switch (P) {
-    case 1: GATHER(1); break;
-    case 2: GATHER(2); break;
-    case 3: GATHER(3); break;
-    default: GATHER(4); break;
-    }
-#undef GATHER
-    rc = kimg_launch_status();
-    if (rc)
-        return rc;
-    rc = kimg_degrid_mfma(grid, grid_row_stride, grid_pol_stride, grid_size, P,
-                          reinterpret_cast<const int16_t *>(uv_s), wp_s, w_s, vis_s, num_vis,
-                          convolve_kernel, w_planes, oversample, kernel_width, base + ws.table,
-                          ws.keys[0], arith, stream);
-    if (rc)
-        return rc;
-#define SCATTER(PP) scatter_vis_kernel<PP><<<blocks, 256, 0, stream>>>(index.Current(), num_vis, vis_s, \
-        static_cast<float2 *>(vis))
-    switch (P) {
-    case 1: SCATTER(1); break;
-    case 2: SCATTER(2); break;
-    case 3: SCATTER(3); break;
-    default: SCATTER(4); break;
-    }
-#undef SCATTER
-    return kimg_launch_status();
-}
-
-int kimg_grid_binned(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride, int grid_size,
-                     int P, const float *weights_grid, int64_t wg_row_stride, int64_t wg_pol_stride,
-                     const int16_t *uv, const int16_t *w_plane, const void *vis, int64_t num_vis,
-                     const void *convolve_kernel, int w_planes, int oversample, int kernel_width,
-                     void *workspace, size_t workspace_bytes, int arith, hipStream_t stream)
-{
-    if (num_vis >= ((int64_t) 1 << 31))
-        return KIMG_EUNSUPPORTED;
-    binned_ws ws;
-    hipError_t e = layout(num_vis, P, w_planes, oversample, kernel_width, ws);
-    if (e != hipSuccess)
-        return -(int) e;
-    if (workspace == nullptr || workspace_bytes < ws.total)
-        return KIMG_EWORKSPACE;
-    unsigned char *base = static_cast<unsigned char *>(workspace);
-    hipcub::DoubleBuffer<unsigned> keys(reinterpret_cast<unsigned *>(base + ws.keys[0]),
-                                        reinterpret_cast<unsigned *>(base + ws.keys[1]));
-    hipcub::DoubleBuffer<unsigned> index(reinterpret_cast<unsigned *>(base + ws.index[0]),
-                                         reinterpret_cast<unsigned *>(base + ws.index[1]));
-    int rc = sort_by_tile(uv, num_vis, grid_size, kernel_width, base, ws, keys, index, stream);
-    if (rc)
-        return rc;
-    const int blocks = kimg_divup(num_vis, 256);
-    int2 *uv_s = reinterpret_cast<int2 *>(base + ws.uv);
-    int16_t *wp_s = reinterpret_cast<int16_t *>(base + ws.wp);
-    float2 *vis_s = reinterpret_cast<float2 *>(base + ws.vis);
-#define GATHER(PP) gather_kernel<PP><<<blocks, 256, 0, stream>>>(index.Current(), num_vis, \
-        reinterpret_cast<const int2 *>(uv), w_plane, static_cast<const float2 *>(vis), uv_s, wp_s, vis_s)
-    switch (P) {
-    case 1: GATHER(1); break;
-    case 2: GATHER(2); break;
-    case 3: GATHER(3); break;
-    default: GATHER(4); break;
-    }
-#undef GATHER
-    rc = kimg_launch_status();
-    if (rc)
-        return rc;
-    return kimg_grid_mfma(grid, grid_row_stride, grid_pol_stride, grid_size, P, weights_grid,
-                          wg_row_stride, wg_pol_stride, reinterpret_cast<const int16_t *>(uv_s), wp_s,
-                          vis_s, num_vis, convolve_kernel, w_planes, oversample, kernel_width,
-                          base + ws.table, ws.keys[0], arith, stream);
-}
-
-// ---- float64 (kimg_grid_f64 / kimg_degrid_f64, KIMG_VARIANT_BINNED; widths <= 32): the same sort and
-// gather into the same scratch (kimg_grid_binned_workspace_bytes / kimg_degrid_binned_workspace_bytes,
-// of which the padded-table part goes unused), then the float64 window kernels of grid_f64.hip.
-int kimg_grid_window_f64(double *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
-                         int grid_size, int P, const float *weights_grid, int64_t wg_row_stride,
-                         int64_t wg_pol_stride, const int16_t *uv, const int16_t *w_plane,
-                         const float2 *vis, int64_t num_vis, const float2 *kern, int w_planes,
-                         int oversample, int K, hipStream_t s);
-int kimg_degrid_window_f64(const double2 *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
-                           int grid_size, int P, const int16_t *uv, const int16_t *w_plane,
-                           const float *weights, float2 *vis, int64_t num_vis, const float2 *kern,
-                           int w_planes, int oversample, int K, hipStream_t s);
-
-int kimg_grid_binned_f64(double *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
-                         int grid_size, int P, const float *weights_grid, int64_t wg_row_stride,
-                         int64_t wg_pol_stride, const int16_t *uv, const int16_t *w_plane,
-                         const void *vis, int64_t num_vis, const void *kern, int w_planes,
-                         int oversample, int K, void *workspace, size_t workspace_bytes,
-                         hipStream_t stream)
-{
-    if (num_vis >= ((int64_t) 1 << 31))
-        return KIMG_EUNSUPPORTED;
-    binned_ws ws;
-    hipError_t e = layout(num_vis, P, w_planes, oversample, K, ws);
-    if (e != hipSuccess)
-        return -(int) e;
-    if (workspace == nullptr || workspace_bytes < ws.total)
-        return KIMG_EWORKSPACE;
-    unsigned char *base = static_cast<unsigned char *>(workspace);
-    hipcub::DoubleBuffer<unsigned> keys(reinterpret_cast<unsigned *>(base + ws.keys[0]),
-                                        reinterpret_cast<unsigned *>(base + ws.keys[1]));
-    hipcub::DoubleBuffer<unsigned> index(reinterpret_cast<unsigned *>(base + ws.index[0]),
-                                         reinterpret_cast<unsigned *>(base + ws.index[1]));
-    int rc = sort_by_tile(uv, num_vis, grid_size, K, base, ws, keys, index, stream);
-    if (rc)
-        return rc;
-    const int blocks = kimg_divup(num_vis, 256);
-    int2 *uv_s = reinterpret_cast<int2 *>(base + ws.uv);
-    int16_t *wp_s = reinterpret_cast<int16_t *>(base + ws.wp);
-    float2 *vis_s = reinterpret_cast<float2 *>(base + ws.vis);
-#define GATHER(PP) gather_kernel<PP><<<blocks, 256, 0, stream>>>(index.Current(), num_vis, \
-        reinterpret_cast<const int2 *>(uv), w_plane, static_cast<const float2 *>(vis), uv_s, wp_s, vis_s)
-    switch (P) {
-    case 1: GATHER(1); break;
-    case 2: GATHER(2); break;
-    case 3: GATHER(3); break;
-    default: GATHER(4); break;
-    }
-#undef GATHER
-    rc = kimg_launch_status();
-    if (rc)
-        return rc;
-    return kimg_grid_window_f64(grid, grid_row_stride, grid_pol_stride, grid_size, P, weights_grid,
-                                wg_row_stride, wg_pol_stride, reinterpret_cast<const int16_t *>(uv_s),
-                                wp_s, vis_s, num_vis, static_cast<const float2 *>(kern), w_planes,
-                                oversample, K, stream);
-}
-
-int kimg_degrid_binned_f64(const double2 *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
-                           int grid_size, int P, const int16_t *uv, const int16_t *w_plane,
-                           const float *weights, void *vis, int64_t num_vis, const void *kern,
-                           int w_planes, int oversample, int K, void *workspace,
-                           size_t workspace_bytes, hipStream_t stream)
-{
-    if (num_vis >= ((int64_t) 1 << 31))
-        return KIMG_EUNSUPPORTED;
-    binned_ws ws;
-    hipError_t e = layout(num_vis, P, w_planes, oversample, K, ws, true);
-    if (e != hipSuccess)
-        return -(int) e;
-    if (workspace == nullptr || workspace_bytes < ws.total)
-        return KIMG_EWORKSPACE;
-    unsigned char *base = static_cast<unsigned char *>(workspace);
-    hipcub::DoubleBuffer<unsigned> keys(reinterpret_cast<unsigned *>(base + ws.keys[0]),
-                                        reinterpret_cast<unsigned *>(base + ws.keys[1]));
-    hipcub::DoubleBuffer<unsigned> index(reinterpret_cast<unsigned *>(base + ws.index[0]),
-                                         reinterpret_cast<unsigned *>(base + ws.index[1]));
-    int rc = sort_by_tile(uv, num_vis, grid_size, K, base, ws, keys, index, stream);
-    if (rc)
-        return rc;
-    const int blocks = kimg_divup(num_vis, 256);
-    int2 *uv_s = reinterpret_cast<int2 *>(base + ws.uv);
-    int16_t *wp_s = reinterpret_cast<int16_t *>(base + ws.wp);
-    float *w_s = reinterpret_cast<float *>(base + ws.weights);
-    float2 *vis_s = reinterpret_cast<float2 *>(base + ws.vis);
-#define GATHER(PP) gather_degrid_kernel<PP><<<blocks, 256, 0, stream>>>(index.Current(), num_vis, \
-        reinterpret_cast<const int2 *>(uv), w_plane, weights, static_cast<const float2 *>(vis), uv_s, wp_s, \
-        w_s, vis_s)
-    switch (P) {
-    case 1: GATHER(1); break;
-    case 2: GATHER(2); break;
-    case 3: GATHER(3); break;
-    default: GATHER(4); break;
-    }
-#undef GATHER
-    rc = kimg_launch_status();
-    if (rc)
-        return rc;
-    rc = kimg_degrid_window_f64(grid, grid_row_stride, grid_pol_stride, grid_size, P,
-                                reinterpret_cast<const int16_t *>(uv_s), wp_s, w_s, vis_s, num_vis,
-                                static_cast<const float2 *>(kern), w_planes, oversample, K, stream);
-    if (rc)
-        return rc;
-#define SCATTER(PP) scatter_vis_kernel<PP><<<blocks, 256, 0, stream>>>(index.Current(), num_vis, vis_s, \
-        static_cast<float2 *>(vis))
-    switch (P) {
-    case 1: SCATTER(1); break;
-    case 2: SCATTER(2); break;
-    case 3: SCATTER(3); break;
-    default: SCATTER(4); break;
-    }
-#undef SCATTER
+    kimg_for_pols(P, [&](auto p) {
+        scatter_vis_kernel<decltype(p)::value><<<kimg_divup(num_vis, 256), 256, 0, stream>>>(
+            b.index, num_vis, b.vis, static_cast<float2 *>(vis)); });
     return kimg_launch_status();
 }
 
 extern "C" size_t kimg_grid_binned_workspace_bytes(int64_t max_vis, int num_polarizations,
                                                   int w_planes, int oversample, int kernel_width)
 {
-    return kimg_grid_binned_workspace_bytes_impl(max_vis, num_polarizations, w_planes, oversample,
-                                                 kernel_width);
+    return binned_workspace_bytes(max_vis, num_polarizations, w_planes, oversample, kernel_width,
+                                  false);
 }
 
 extern "C" size_t kimg_degrid_binned_workspace_bytes(int64_t max_vis, int num_polarizations,
                                                     int w_planes, int oversample, int kernel_width)
 {
-    if (max_vis <= 0 || max_vis >= ((int64_t) 1 << 31)
-        || !kimg_degrid_mfma_supported(num_polarizations, w_planes, oversample, kernel_width))
-        return 0;
-    binned_ws ws;
-    if (layout(max_vis, num_polarizations, w_planes, oversample, kernel_width, ws, true) != hipSuccess)
-        return 0;
-    return ws.total;
+    return binned_workspace_bytes(max_vis, num_polarizations, w_planes, oversample, kernel_width,
+                                  true);
 }
 
 extern "C" int kimg_grid_jumps(const int16_t *uv, int64_t num_vis, int kernel_width,
@@ -464,7 +270,7 @@ extern "C" int kimg_grid_jumps(const int16_t *uv, int64_t num_vis, int kernel_wi
     if (blocks > 2048)
         blocks = 2048;
     const int slack = kernel_width > 2 * WIN ? 0 : window_slack(kernel_width);
-    jump_count_kernel<<<blocks, 256, 0, s>>>(reinterpret_cast<const int2 *>(uv), num_vis, slack, count);
+    jump_count_kernel<<<blocks, 256, 0, s>>>(uv, num_vis, slack, count);
     return kimg_launch_status();
 }
 

@@ -12,32 +12,6 @@
 
 namespace {
 
-struct vis_coord_f64 {
-    int u, v, sub_u, sub_v;
-};
-
-__device__ inline vis_coord_f64 load_uv_f64(const int16_t *__restrict__ uv, int64_t i)
-{
-    const int2 packed = reinterpret_cast<const int2 *>(uv)[i];
-    vis_coord_f64 c;
-    c.u = (short) (packed.x & 0xffff);
-    c.v = (short) (packed.x >> 16);
-    c.sub_u = (short) (packed.y & 0xffff);
-    c.sub_v = (short) (packed.y >> 16);
-    return c;
-}
-
-// A record whose cell, sub-cell or plane lies outside the grid / table contributes nothing (the
-// window kernel's coords_ok, grid_mfma.hip).
-__device__ inline bool coords_ok_f64(const vis_coord_f64 &c, int wp, int Gg, int w_planes,
-                                     int oversample)
-{
-    const int half = Gg / 2;
-    return (unsigned) (c.u + half) < (unsigned) Gg && (unsigned) (c.v + half) < (unsigned) Gg
-           && (unsigned) c.sub_u < (unsigned) oversample && (unsigned) c.sub_v < (unsigned) oversample
-           && (unsigned) wp < (unsigned) w_planes;
-}
-
 // a * b in double, the two products of each part rounded separately (like numpy's complex128
 // multiply; the library is built with -ffp-contract=off)
 __device__ inline double2 zmul(double2 a, double2 b)
@@ -64,9 +38,9 @@ __global__ __launch_bounds__(256) void grid_f64_generic_kernel(
     const int half = Gg / 2;
     const int uv_bias = (K - 1) / 2 - half;                     // grid.py:1038
     for (int64_t i = wave; i < num_vis; i += nwaves) {
-        const vis_coord_f64 c = load_uv_f64(uv, i);
+        const vis_coord c = load_uv(uv, i);
         const int wp = w_plane[i];
-        if (!coords_ok_f64(c, wp, Gg, w_planes, oversample))
+        if (!coords_ok(c, wp, Gg, w_planes, oversample))
             continue;                                           // (uniform over the wave)
         const int u0 = c.u - uv_bias, v0 = c.v - uv_bias;
         const int64_t wa = (int64_t) (c.v + half) * wg_row_stride + (c.u + half);
@@ -114,9 +88,9 @@ __global__ __launch_bounds__(256) void degrid_f64_generic_kernel(
     const int64_t nwaves = (int64_t) gridDim.x * (blockDim.x >> 6);
     const int uv_bias = (K - 1) / 2 - Gg / 2;                   // grid.py:1141
     for (int64_t i = wave; i < num_vis; i += nwaves) {
-        const vis_coord_f64 c = load_uv_f64(uv, i);
+        const vis_coord c = load_uv(uv, i);
         const int wp = w_plane[i];
-        if (!coords_ok_f64(c, wp, Gg, w_planes, oversample))
+        if (!coords_ok(c, wp, Gg, w_planes, oversample))
             continue;                                           // predicts 0: vis unchanged
         const int u0 = c.u - uv_bias, v0 = c.v - uv_bias;
         const float2 *kv = kern + ((int64_t) wp * oversample + c.sub_v) * K;
@@ -250,9 +224,9 @@ __global__ __launch_bounds__(64) void grid_f64_window_kernel(
     };
 
     for (int64_t i = begin; i < end; i++) {
-        const vis_coord_f64 co = load_uv_f64(uv, i);
+        const vis_coord co = load_uv(uv, i);
         const int wp = w_plane[i];
-        if (!coords_ok_f64(co, wp, Gg, w_planes, oversample))
+        if (!coords_ok(co, wp, Gg, w_planes, oversample))
             continue;                                           // (uniform over the wave)
         const int x0 = co.u - uv_bias, y0 = co.v - uv_bias;
         if (!have || x0 < Wu || x0 + K > Wu + WINF || y0 < Wv || y0 + K > Wv + WINF) {
@@ -323,9 +297,9 @@ __global__ __launch_bounds__(64) void degrid_f64_window_kernel(
     };
 
     for (int64_t i = begin; i < end; i++) {
-        const vis_coord_f64 co = load_uv_f64(uv, i);
+        const vis_coord co = load_uv(uv, i);
         const int wp = w_plane[i];
-        if (!coords_ok_f64(co, wp, Gg, w_planes, oversample))
+        if (!coords_ok(co, wp, Gg, w_planes, oversample))
             continue;                                           // predicts 0: vis unchanged
         const int x0 = co.u - uv_bias, y0 = co.v - uv_bias;
         if (!have || x0 < Wu || x0 + K > Wu + WINF || y0 < Wv || y0 + K > Wv + WINF) {
@@ -386,7 +360,7 @@ int check_f64_args(int grid_size, int P, int64_t num_vis, int w_planes, int over
 
 } // namespace
 
-// the window kernels over a stream as given (kimg_grid_binned_f64 calls them on its sorted copies)
+// the window kernels over a stream as given
 int kimg_grid_window_f64(double *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
                          int grid_size, int P, const float *weights_grid, int64_t wg_row_stride,
                          int64_t wg_pol_stride, const int16_t *uv, const int16_t *w_plane,
@@ -395,16 +369,10 @@ int kimg_grid_window_f64(double *grid, int64_t grid_row_stride, int64_t grid_pol
 {
     const int64_t chunk = window_chunk(num_vis, P);
     const dim3 blocks(kimg_divup(num_vis, chunk), P);
-#define LAUNCH(PP) grid_f64_window_kernel<PP><<<blocks, 64, 0, s>>>( \
-        grid, grid_row_stride, grid_pol_stride, grid_size, weights_grid, wg_row_stride, \
-        wg_pol_stride, uv, w_plane, vis, num_vis, kern, w_planes, oversample, K, chunk)
-    switch (P) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 3: LAUNCH(3); break;
-    case 4: LAUNCH(4); break;
-    }
-#undef LAUNCH
+    kimg_for_pols(P, [&](auto p) {
+        grid_f64_window_kernel<decltype(p)::value><<<blocks, 64, 0, s>>>(
+            grid, grid_row_stride, grid_pol_stride, grid_size, weights_grid, wg_row_stride,
+            wg_pol_stride, uv, w_plane, vis, num_vis, kern, w_planes, oversample, K, chunk); });
     return kimg_launch_status();
 }
 
@@ -415,30 +383,12 @@ int kimg_degrid_window_f64(const double2 *grid, int64_t grid_row_stride, int64_t
 {
     const int64_t chunk = window_chunk(num_vis, P);
     const dim3 blocks(kimg_divup(num_vis, chunk), P);
-#define LAUNCH(PP) degrid_f64_window_kernel<PP><<<blocks, 64, 0, s>>>( \
-        grid, grid_row_stride, grid_pol_stride, grid_size, uv, w_plane, weights, vis, num_vis, \
-        kern, w_planes, oversample, K, chunk)
-    switch (P) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 3: LAUNCH(3); break;
-    case 4: LAUNCH(4); break;
-    }
-#undef LAUNCH
+    kimg_for_pols(P, [&](auto p) {
+        degrid_f64_window_kernel<decltype(p)::value><<<blocks, 64, 0, s>>>(
+            grid, grid_row_stride, grid_pol_stride, grid_size, uv, w_plane, weights, vis, num_vis,
+            kern, w_planes, oversample, K, chunk); });
     return kimg_launch_status();
 }
-
-int kimg_grid_binned_f64(double *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
-                         int grid_size, int P, const float *weights_grid, int64_t wg_row_stride,
-                         int64_t wg_pol_stride, const int16_t *uv, const int16_t *w_plane,
-                         const void *vis, int64_t num_vis, const void *kern, int w_planes,
-                         int oversample, int K, void *workspace, size_t workspace_bytes,
-                         hipStream_t stream);
-int kimg_degrid_binned_f64(const double2 *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
-                           int grid_size, int P, const int16_t *uv, const int16_t *w_plane,
-                           const float *weights, void *vis, int64_t num_vis, const void *kern,
-                           int w_planes, int oversample, int K, void *workspace,
-                           size_t workspace_bytes, hipStream_t stream);
 
 extern "C" int kimg_grid_f64(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
                              int grid_size, int num_polarizations, const float *weights_grid,
@@ -457,11 +407,20 @@ extern "C" int kimg_grid_f64(void *grid, int64_t grid_row_stride, int64_t grid_p
         return 0;
     variant &= 0xff;
     hipStream_t s = (hipStream_t) stream;
-    if (variant == KIMG_VARIANT_BINNED)
-        return kimg_grid_binned_f64((double *) grid, grid_row_stride, grid_pol_stride, grid_size,
+    if (variant == KIMG_VARIANT_BINNED) {
+        // the float32 path's sort and gather into the same scratch (of which the padded-table part
+        // goes unused), then the window kernel on the sorted copies
+        kimg_binned_stream b;
+        rc = kimg_bin_stream(uv, w_plane, nullptr, vis, num_vis, grid_size, num_polarizations,
+                             w_planes, oversample, kernel_width, workspace, workspace_bytes, s, b);
+        if (rc)
+            return rc;
+        return kimg_grid_window_f64((double *) grid, grid_row_stride, grid_pol_stride, grid_size,
                                     num_polarizations, weights_grid, wg_row_stride, wg_pol_stride,
-                                    uv, w_plane, vis, num_vis, convolve_kernel, w_planes,
-                                    oversample, kernel_width, workspace, workspace_bytes, s);
+                                    b.uv, b.w_plane, b.vis, num_vis,
+                                    (const float2 *) convolve_kernel, w_planes, oversample,
+                                    kernel_width, s);
+    }
     if (variant == KIMG_VARIANT_MFMA || (variant == KIMG_VARIANT_AUTO && kernel_width <= WINF))
         return kimg_grid_window_f64((double *) grid, grid_row_stride, grid_pol_stride, grid_size,
                                     num_polarizations, weights_grid, wg_row_stride, wg_pol_stride,
@@ -471,17 +430,11 @@ extern "C" int kimg_grid_f64(void *grid, int64_t grid_row_stride, int64_t grid_p
     int blocks = kimg_divup(num_vis, 4);
     if (blocks > 8192)
         blocks = 8192;
-#define LAUNCH(P) grid_f64_generic_kernel<P><<<blocks, 256, 0, s>>>( \
-        (double *) grid, grid_row_stride, grid_pol_stride, grid_size, weights_grid, wg_row_stride, \
-        wg_pol_stride, uv, w_plane, (const float2 *) vis, num_vis, \
-        (const float2 *) convolve_kernel, w_planes, oversample, kernel_width)
-    switch (num_polarizations) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 3: LAUNCH(3); break;
-    case 4: LAUNCH(4); break;
-    }
-#undef LAUNCH
+    kimg_for_pols(num_polarizations, [&](auto p) {
+        grid_f64_generic_kernel<decltype(p)::value><<<blocks, 256, 0, s>>>(
+            (double *) grid, grid_row_stride, grid_pol_stride, grid_size, weights_grid, wg_row_stride,
+            wg_pol_stride, uv, w_plane, (const float2 *) vis, num_vis,
+            (const float2 *) convolve_kernel, w_planes, oversample, kernel_width); });
     return kimg_launch_status();
 }
 
@@ -501,11 +454,18 @@ extern "C" int kimg_degrid_f64(const void *grid, int64_t grid_row_stride, int64_
         return 0;
     variant &= 0xff;
     hipStream_t s = (hipStream_t) stream;
-    if (variant == KIMG_VARIANT_BINNED)
-        return kimg_degrid_binned_f64((const double2 *) grid, grid_row_stride, grid_pol_stride,
-                                      grid_size, num_polarizations, uv, w_plane, weights, vis,
-                                      num_vis, convolve_kernel, w_planes, oversample, kernel_width,
-                                      workspace, workspace_bytes, s);
+    if (variant == KIMG_VARIANT_BINNED) {
+        kimg_binned_stream b;
+        rc = kimg_bin_stream(uv, w_plane, weights, vis, num_vis, grid_size, num_polarizations,
+                             w_planes, oversample, kernel_width, workspace, workspace_bytes, s, b);
+        if (rc)
+            return rc;
+        rc = kimg_degrid_window_f64((const double2 *) grid, grid_row_stride, grid_pol_stride,
+                                    grid_size, num_polarizations, b.uv, b.w_plane, b.weights, b.vis,
+                                    num_vis, (const float2 *) convolve_kernel, w_planes, oversample,
+                                    kernel_width, s);
+        return rc ? rc : kimg_unbin_vis(b, vis, num_vis, num_polarizations, s);
+    }
     if (variant == KIMG_VARIANT_MFMA || (variant == KIMG_VARIANT_AUTO && kernel_width <= WINF))
         return kimg_degrid_window_f64((const double2 *) grid, grid_row_stride, grid_pol_stride,
                                       grid_size, num_polarizations, uv, w_plane, weights,
@@ -514,17 +474,11 @@ extern "C" int kimg_degrid_f64(const void *grid, int64_t grid_row_stride, int64_
     int blocks = kimg_divup(num_vis, 4);
     if (blocks > 16384)
         blocks = 16384;
-#define LAUNCH(P) degrid_f64_generic_kernel<P><<<blocks, 256, 0, s>>>( \
-        (const double2 *) grid, grid_row_stride, grid_pol_stride, grid_size, uv, w_plane, weights, \
-        (float2 *) vis, num_vis, (const float2 *) convolve_kernel, w_planes, oversample, \
-        kernel_width)
-    switch (num_polarizations) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 3: LAUNCH(3); break;
-    case 4: LAUNCH(4); break;
-    }
-#undef LAUNCH
+    kimg_for_pols(num_polarizations, [&](auto p) {
+        degrid_f64_generic_kernel<decltype(p)::value><<<blocks, 256, 0, s>>>(
+            (const double2 *) grid, grid_row_stride, grid_pol_stride, grid_size, uv, w_plane, weights,
+            (float2 *) vis, num_vis, (const float2 *) convolve_kernel, w_planes, oversample,
+            kernel_width); });
     return kimg_launch_status();
 }
 

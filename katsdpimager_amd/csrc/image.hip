@@ -12,10 +12,26 @@ namespace {
 
 struct c64 { float re, im; };
 
+// The plain kernels below (grid <-> layer copies, layer <-> image, scale, add_image,
+// apply_primary_beam) are templates on the real type T: float for the float32 entry points,
+// double for the *_f64 ones.  cplx<T> is the complex cell that goes with it.
+template <typename T> struct cplx_of;
+template <> struct cplx_of<float> { using type = float2; };
+template <> struct cplx_of<double> { using type = double2; };
+template <typename T> using cplx = typename cplx_of<T>::type;
+
+__device__ inline float real_rint(float x) { return rintf(x); }
+__device__ inline double real_rint(double x) { return rint(x); }
+__device__ inline float real_sqrt(float x) { return sqrtf(x); }
+__device__ inline double real_sqrt(double x) { return sqrt(x); }
+__device__ inline void real_sincospi(float x, float *s, float *c) { sincospif(x, s, c); }
+__device__ inline void real_sincospi(double x, double *s, double *c) { sincospi(x, s, c); }
+
 // layer[ly][lx] = grid cell with the same (centred) frequency, or 0 outside the grid.
 // Fuses the reference's layer.zero() + 4 copy_region calls (image.py:660-671).
+template <typename T>
 __global__ __launch_bounds__(256) void grid_to_layer_kernel(
-    float2 *__restrict__ layer, int G, const float2 *__restrict__ grid, int64_t grid_row_stride,
+    cplx<T> *__restrict__ layer, int G, const cplx<T> *__restrict__ grid, int64_t grid_row_stride,
     int Gg)
 {
     const int lx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -26,7 +42,7 @@ __global__ __launch_bounds__(256) void grid_to_layer_kernel(
     // centred coordinates of this layer pixel: 0..G/2-1 positive, G/2.. negative
     const int cx = lx < G - half ? lx : lx - G;
     const int cy = ly < G - half ? ly : ly - G;
-    float2 v = make_float2(0.0f, 0.0f);
+    cplx<T> v(T(0), T(0));
     if (cx >= -half && cx < half && cy >= -half && cy < half)
         v = grid[(int64_t) (cy + half) * grid_row_stride + (cx + half)];
     layer[(int64_t) ly * G + lx] = v;
@@ -67,8 +83,9 @@ __global__ __launch_bounds__(256) void grid_to_half_layer_kernel(
     half_layer[(int64_t) ly * W + lx] = half_layer_value(grid, grid_row_stride, Gg, G, lx, ly);
 }
 
+template <typename T>
 __global__ __launch_bounds__(256) void layer_to_grid_kernel(
-    float2 *__restrict__ grid, int64_t grid_row_stride, int Gg, const float2 *__restrict__ layer,
+    cplx<T> *__restrict__ grid, int64_t grid_row_stride, int Gg, const cplx<T> *__restrict__ layer,
     int G)
 {
     const int gx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -83,23 +100,26 @@ __global__ __launch_bounds__(256) void layer_to_grid_kernel(
 }
 
 // e^{2 pi i x} with the reference's range reduction (fast_math.py:14-15).
-__device__ inline void expj2pi(float x, float &c, float &s)
+template <typename T>
+__device__ inline void expj2pi(T x, T &c, T &s)
 {
-    float r = x - rintf(x);
-    sincospif(2.0f * r, &s, &c);
+    T r = x - real_rint(x);
+    real_sincospi(T(2) * r, &s, &c);
 }
 
 // n(l, m) following GridToImageHost.__call__ (image.py:785-790) operation by operation.
-__device__ inline float lm_coord(int i, float lm_scale, float lm_bias)
+template <typename T>
+__device__ inline T lm_coord(int i, T lm_scale, T lm_bias)
 {
-    return (float) i * lm_scale + lm_bias;
+    return (T) i * lm_scale + lm_bias;
 }
 
 // One thread: one image pixel pair... kept simple: one pixel per thread, x fastest.
 // image[y][x] += Re(layer[(y+G/2)%G][(x+G/2)%G] * e^{2 pi i w (n-1)}) * n / (k[y] k[x])
+template <typename T>
 __global__ __launch_bounds__(256) void layer_to_image_kernel(
-    float *__restrict__ image, int64_t image_row_stride, const float2 *__restrict__ layer, int G,
-    const float *__restrict__ kernel1d, float lm_scale, float lm_bias, float w)
+    T *__restrict__ image, int64_t image_row_stride, const cplx<T> *__restrict__ layer, int G,
+    const T *__restrict__ kernel1d, T lm_scale, T lm_bias, T w)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y;
@@ -108,15 +128,14 @@ __global__ __launch_bounds__(256) void layer_to_image_kernel(
     const int half = G / 2;
     const int sx = x < half ? x + half : x - half;
     const int sy = y < half ? y + half : y - half;
-    const float2 v = layer[(int64_t) sy * G + sx];
-    const float l = lm_coord(x, lm_scale, lm_bias);
-    const float m = lm_coord(y, lm_scale, lm_bias);
-    const float l2 = l * l, m2 = m * m;
-    const float n = sqrtf(1.0f - (m2 + l2));
-    float c, s;
-    expj2pi(w * (n - 1.0f), c, s);
-    const float rotated = v.x * c - v.y * s;
-    const float taper = kernel1d[y] * kernel1d[x];
+    const cplx<T> v = layer[(int64_t) sy * G + sx];
+    const T l = lm_coord(x, lm_scale, lm_bias);
+    const T m = lm_coord(y, lm_scale, lm_bias);
+    const T n = real_sqrt(T(1) - (m * m + l * l));
+    T c, s;
+    expj2pi(w * (n - T(1)), c, s);
+    const T rotated = v.x * c - v.y * s;
+    const T taper = kernel1d[y] * kernel1d[x];
     image[(int64_t) y * image_row_stride + x] += (rotated * n) / taper;
 }
 
@@ -143,9 +162,10 @@ __global__ __launch_bounds__(256) void real_layer_to_image_kernel(
 }
 
 // layer[(y+G/2)%G][(x+G/2)%G] = image[y][x] / (k[y] k[x] n) * e^{-2 pi i w (n-1)}
+template <typename T>
 __global__ __launch_bounds__(256) void image_to_layer_kernel(
-    float2 *__restrict__ layer, const float *__restrict__ image, int64_t image_row_stride, int G,
-    const float *__restrict__ kernel1d, float lm_scale, float lm_bias, float w)
+    cplx<T> *__restrict__ layer, const T *__restrict__ image, int64_t image_row_stride, int G,
+    const T *__restrict__ kernel1d, T lm_scale, T lm_bias, T w)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y;
@@ -154,15 +174,14 @@ __global__ __launch_bounds__(256) void image_to_layer_kernel(
     const int half = G / 2;
     const int sx = x < half ? x + half : x - half;
     const int sy = y < half ? y + half : y - half;
-    const float l = lm_coord(x, lm_scale, lm_bias);
-    const float m = lm_coord(y, lm_scale, lm_bias);
-    const float l2 = l * l, m2 = m * m;
-    const float n = sqrtf(1.0f - (m2 + l2));
-    float c, s;
-    expj2pi(-w * (n - 1.0f), c, s);
-    const float taper = kernel1d[y] * kernel1d[x];
-    const float v = image[(int64_t) y * image_row_stride + x] / (taper * n);
-    layer[(int64_t) sy * G + sx] = make_float2(v * c, v * s);
+    const T l = lm_coord(x, lm_scale, lm_bias);
+    const T m = lm_coord(y, lm_scale, lm_bias);
+    const T n = real_sqrt(T(1) - (m * m + l * l));
+    T c, s;
+    expj2pi(-w * (n - T(1)), c, s);
+    const T taper = kernel1d[y] * kernel1d[x];
+    const T v = image[(int64_t) y * image_row_stride + x] / (taper * n);
+    layer[(int64_t) sy * G + sx] = cplx<T>(v * c, v * s);
 }
 
 // image_to_layer for w = 0: the layer is real (phase factor exactly (1, 0)); rows of
@@ -209,11 +228,12 @@ __global__ __launch_bounds__(256) void half_layer_to_grid_kernel(
     grid[(int64_t) gy * grid_row_stride + gx] = v;
 }
 
-struct scale_t { float v[4]; };
+template <typename T> struct scale_t { T v[4]; };
 
+template <typename T>
 __global__ __launch_bounds__(256) void scale_kernel(
-    float *__restrict__ image, int64_t row_stride, int64_t pol_stride, int width, int num_pols,
-    scale_t scale)
+    T *__restrict__ image, int64_t row_stride, int64_t pol_stride, int width, int num_pols,
+    scale_t<T> scale)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= width)
@@ -245,9 +265,10 @@ __global__ void pixel_reciprocal_kernel(const float *__restrict__ image, int64_t
         out[p] = 1.0f / image[p * pol_stride + offset];     // (np.reciprocal of a float32: one rounding)
 }
 
+template <typename T>
 __global__ __launch_bounds__(256) void add_image_kernel(
-    float *__restrict__ dest, int64_t dest_row_stride, int64_t dest_pol_stride,
-    const float *__restrict__ src, int64_t src_row_stride, int64_t src_pol_stride,
+    T *__restrict__ dest, int64_t dest_row_stride, int64_t dest_pol_stride,
+    const T *__restrict__ src, int64_t src_row_stride, int64_t src_pol_stride,
     int width, int num_pols)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
@@ -259,15 +280,16 @@ __global__ __launch_bounds__(256) void add_image_kernel(
         dest[d] += src[s];
 }
 
+template <typename T>
 __global__ __launch_bounds__(256) void apply_primary_beam_kernel(
-    float *__restrict__ image, int64_t row_stride, int64_t pol_stride,
-    const float *__restrict__ beam_power, int64_t beam_row_stride, int width, int num_pols,
-    float threshold, float replacement)
+    T *__restrict__ image, int64_t row_stride, int64_t pol_stride,
+    const T *__restrict__ beam_power, int64_t beam_row_stride, int width, int num_pols,
+    T threshold, T replacement)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= width)
         return;
-    const float beam = beam_power[(int64_t) blockIdx.y * beam_row_stride + x];
+    const T beam = beam_power[(int64_t) blockIdx.y * beam_row_stride + x];
     int64_t addr = (int64_t) blockIdx.y * row_stride + x;
     for (int p = 0; p < num_pols; p++, addr += pol_stride)
         image[addr] = beam < threshold ? replacement : image[addr] / beam;
@@ -982,7 +1004,7 @@ extern "C" int kimg_grid_to_layer(void *layer, int layer_size, const void *grid,
     KIMG_CHECK_ARG(layer && grid && layer_size > 0 && grid_size > 0 && grid_size <= layer_size);
     KIMG_CHECK_ARG(layer_size % 2 == 0 && grid_size % 2 == 0);      // image.py:655-656
     dim3 g(kimg_divup(layer_size, 256), layer_size);
-    grid_to_layer_kernel<<<g, 256, 0, (hipStream_t) stream>>>(
+    grid_to_layer_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
         (float2 *) layer, layer_size, (const float2 *) grid, grid_row_stride, grid_size);
     return kimg_launch_status();
 }
@@ -1041,7 +1063,7 @@ extern "C" int kimg_layer_to_grid(void *grid, int64_t grid_row_stride, int grid_
     KIMG_CHECK_ARG(layer && grid && layer_size > 0 && grid_size > 0 && grid_size <= layer_size);
     KIMG_CHECK_ARG(layer_size % 2 == 0 && grid_size % 2 == 0);
     dim3 g(kimg_divup(grid_size, 256), grid_size);
-    layer_to_grid_kernel<<<g, 256, 0, (hipStream_t) stream>>>(
+    layer_to_grid_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
         (float2 *) grid, grid_row_stride, grid_size, (const float2 *) layer, layer_size);
     return kimg_launch_status();
 }
@@ -1052,7 +1074,7 @@ extern "C" int kimg_layer_to_image(float *image, int64_t image_row_stride, const
 {
     KIMG_CHECK_ARG(image && layer && kernel1d && size > 0 && size % 2 == 0);   // image.py:127-128
     dim3 g(kimg_divup(size, 256), size);
-    layer_to_image_kernel<<<g, 256, 0, (hipStream_t) stream>>>(
+    layer_to_image_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
         image, image_row_stride, (const float2 *) layer, size, kernel1d, lm_scale, lm_bias, w);
     return kimg_launch_status();
 }
@@ -1063,7 +1085,7 @@ extern "C" int kimg_image_to_layer(void *layer, const float *image, int64_t imag
 {
     KIMG_CHECK_ARG(image && layer && kernel1d && size > 0 && size % 2 == 0);
     dim3 g(kimg_divup(size, 256), size);
-    image_to_layer_kernel<<<g, 256, 0, (hipStream_t) stream>>>(
+    image_to_layer_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
         (float2 *) layer, image, image_row_stride, size, kernel1d, lm_scale, lm_bias, w);
     return kimg_launch_status();
 }
@@ -1074,12 +1096,12 @@ extern "C" int kimg_scale(float *image, int64_t row_stride, int64_t pol_stride, 
     KIMG_CHECK_ARG(image && scale_host && width > 0 && height > 0);
     if (num_polarizations < 1 || num_polarizations > 4)
         return KIMG_EUNSUPPORTED;
-    scale_t sc = {};
+    scale_t<float> sc = {};
     for (int p = 0; p < num_polarizations; p++)
         sc.v[p] = scale_host[p];
     dim3 g(kimg_divup(width, 256), height);
-    scale_kernel<<<g, 256, 0, (hipStream_t) stream>>>(image, row_stride, pol_stride, width,
-                                                      num_polarizations, sc);
+    scale_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(image, row_stride, pol_stride, width,
+                                                             num_polarizations, sc);
     return kimg_launch_status();
 }
 
@@ -1113,7 +1135,7 @@ extern "C" int kimg_add_image(float *dest, int64_t dest_row_stride, int64_t dest
 {
     KIMG_CHECK_ARG(dest && src && width > 0 && height > 0 && num_polarizations > 0);
     dim3 g(kimg_divup(width, 256), height);
-    add_image_kernel<<<g, 256, 0, (hipStream_t) stream>>>(
+    add_image_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
         dest, dest_row_stride, dest_pol_stride, src, src_row_stride, src_pol_stride, width,
         num_polarizations);
     return kimg_launch_status();
@@ -1126,7 +1148,99 @@ extern "C" int kimg_apply_primary_beam(float *image, int64_t row_stride, int64_t
 {
     KIMG_CHECK_ARG(image && beam_power && width > 0 && height > 0 && num_polarizations > 0);
     dim3 g(kimg_divup(width, 256), height);
-    apply_primary_beam_kernel<<<g, 256, 0, (hipStream_t) stream>>>(
+    apply_primary_beam_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
+        image, row_stride, pol_stride, beam_power, beam_row_stride, width, num_polarizations,
+        threshold, replacement);
+    return kimg_launch_status();
+}
+
+// ---- float64 (the reference's --precision double): the same plain kernels on complex128 /
+// float64 arrays; the phase comes from double sincospi after the same range reduction.
+// Float64 always takes the plain route (copy, C2C transform, layer -> image): the library's own
+// transforms and the w = 0 real route of this file are float32 only.
+extern "C" int kimg_grid_to_layer_f64(void *layer, int layer_size, const void *grid,
+                                      int64_t grid_row_stride, int grid_size, void *stream)
+{
+    KIMG_CHECK_ARG(layer && grid && layer_size > 0 && grid_size > 0 && grid_size <= layer_size);
+    KIMG_CHECK_ARG(layer_size % 2 == 0 && grid_size % 2 == 0 && grid_row_stride >= grid_size);
+    const dim3 g(kimg_divup(layer_size, 256), layer_size);
+    grid_to_layer_kernel<double><<<g, 256, 0, (hipStream_t) stream>>>(
+        (double2 *) layer, layer_size, (const double2 *) grid, grid_row_stride, grid_size);
+    return kimg_launch_status();
+}
+
+extern "C" int kimg_layer_to_grid_f64(void *grid, int64_t grid_row_stride, int grid_size,
+                                      const void *layer, int layer_size, void *stream)
+{
+    KIMG_CHECK_ARG(layer && grid && layer_size > 0 && grid_size > 0 && grid_size <= layer_size);
+    KIMG_CHECK_ARG(layer_size % 2 == 0 && grid_size % 2 == 0 && grid_row_stride >= grid_size);
+    const dim3 g(kimg_divup(grid_size, 256), grid_size);
+    layer_to_grid_kernel<double><<<g, 256, 0, (hipStream_t) stream>>>(
+        (double2 *) grid, grid_row_stride, grid_size, (const double2 *) layer, layer_size);
+    return kimg_launch_status();
+}
+
+extern "C" int kimg_layer_to_image_f64(double *image, int64_t image_row_stride, const void *layer,
+                                       int size, const double *kernel1d, double lm_scale,
+                                       double lm_bias, double w, void *stream)
+{
+    KIMG_CHECK_ARG(image && layer && kernel1d && size > 0 && size % 2 == 0
+                   && image_row_stride >= size);
+    const dim3 g(kimg_divup(size, 256), size);
+    layer_to_image_kernel<double><<<g, 256, 0, (hipStream_t) stream>>>(
+        image, image_row_stride, (const double2 *) layer, size, kernel1d, lm_scale, lm_bias, w);
+    return kimg_launch_status();
+}
+
+extern "C" int kimg_image_to_layer_f64(void *layer, const double *image, int64_t image_row_stride,
+                                       int size, const double *kernel1d, double lm_scale,
+                                       double lm_bias, double w, void *stream)
+{
+    KIMG_CHECK_ARG(image && layer && kernel1d && size > 0 && size % 2 == 0
+                   && image_row_stride >= size);
+    const dim3 g(kimg_divup(size, 256), size);
+    image_to_layer_kernel<double><<<g, 256, 0, (hipStream_t) stream>>>(
+        (double2 *) layer, image, image_row_stride, size, kernel1d, lm_scale, lm_bias, w);
+    return kimg_launch_status();
+}
+
+extern "C" int kimg_scale_f64(double *image, int64_t row_stride, int64_t pol_stride, int width,
+                              int height, int num_polarizations, const double *scale_host,
+                              void *stream)
+{
+    KIMG_CHECK_ARG(image && scale_host && width > 0 && height > 0);
+    if (num_polarizations < 1 || num_polarizations > 4)
+        return KIMG_EUNSUPPORTED;
+    scale_t<double> sc = {};
+    for (int p = 0; p < num_polarizations; p++)
+        sc.v[p] = scale_host[p];
+    const dim3 g(kimg_divup(width, 256), height);
+    scale_kernel<double><<<g, 256, 0, (hipStream_t) stream>>>(image, row_stride, pol_stride, width,
+                                                              num_polarizations, sc);
+    return kimg_launch_status();
+}
+
+extern "C" int kimg_add_image_f64(double *dest, int64_t dest_row_stride, int64_t dest_pol_stride,
+                                  const double *src, int64_t src_row_stride,
+                                  int64_t src_pol_stride, int width, int height,
+                                  int num_polarizations, void *stream)
+{
+    KIMG_CHECK_ARG(dest && src && width > 0 && height > 0 && num_polarizations > 0);
+    const dim3 g(kimg_divup(width, 256), height);
+    add_image_kernel<double><<<g, 256, 0, (hipStream_t) stream>>>(
+        dest, dest_row_stride, dest_pol_stride, src, src_row_stride, src_pol_stride, width,
+        num_polarizations);
+    return kimg_launch_status();
+}
+
+extern "C" int kimg_apply_primary_beam_f64(double *image, int64_t row_stride, int64_t pol_stride,
+                                           const double *beam_power, int64_t beam_row_stride,
+                                           int width, int height, int num_polarizations,
+                                           double threshold, double replacement, void *stream)
+{
+    KIMG_CHECK_ARG(image && beam_power && width > 0 && height > 0 && num_polarizations > 0);
+    const dim3 g(kimg_divup(width, 256), height);
+    apply_primary_beam_kernel<double><<<g, 256, 0, (hipStream_t) stream>>>(
         image, row_stride, pol_stride, beam_power, beam_row_stride, width, num_polarizations,
         threshold, replacement);
     return kimg_launch_status();

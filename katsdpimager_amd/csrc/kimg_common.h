@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/kimg.h"
 
 #define KIMG_CHECK_ARG(cond) do { if (!(cond)) return KIMG_EINVAL; } while (0)
@@ -65,6 +66,62 @@ int kimg_clean_multi_run(float *dirty, float *model, int64_t row_stride, int64_t
                          void *state, float *log, hipStream_t s, int *cycles_done = nullptr,
                          float *first_peak = nullptr);
 
+// ---- the gridding family (grid.hip, grid_f64.hip, grid_mfma.hip, degrid_mfma.hip, grid_binned.hip) ----
+// The float32 window kernels over a stream as given (grid_mfma.hip, degrid_mfma.hip)
+int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride, int grid_size,
+                   int P, const float *weights_grid, int64_t wg_row_stride, int64_t wg_pol_stride,
+                   const int16_t *uv, const int16_t *w_plane, const void *vis, int64_t num_vis,
+                   const void *convolve_kernel, int w_planes, int oversample, int kernel_width,
+                   void *workspace, size_t workspace_bytes, int arith, hipStream_t stream);
+bool kimg_grid_mfma_supported(int P, int w_planes, int oversample, int kernel_width);
+size_t kimg_grid_mfma_workspace_bytes(int P, int w_planes, int oversample, int kernel_width);
+int kimg_degrid_mfma(const void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
+                     int grid_size, int P, const int16_t *uv, const int16_t *w_plane,
+                     const float *weights, void *vis, int64_t num_vis, const void *convolve_kernel,
+                     int w_planes, int oversample, int kernel_width, void *workspace,
+                     size_t workspace_bytes, int arith, hipStream_t stream);
+bool kimg_degrid_mfma_supported(int P, int w_planes, int oversample, int kernel_width);
+size_t kimg_degrid_mfma_workspace_bytes(int P, int w_planes, int oversample, int kernel_width);
+// ... and the float64 ones (grid_f64.hip)
+int kimg_grid_window_f64(double *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
+                         int grid_size, int P, const float *weights_grid, int64_t wg_row_stride,
+                         int64_t wg_pol_stride, const int16_t *uv, const int16_t *w_plane,
+                         const float2 *vis, int64_t num_vis, const float2 *kern, int w_planes,
+                         int oversample, int K, hipStream_t s);
+int kimg_degrid_window_f64(const double2 *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
+                           int grid_size, int P, const int16_t *uv, const int16_t *w_plane,
+                           const float *weights, float2 *vis, int64_t num_vis, const float2 *kern,
+                           int w_planes, int oversample, int K, hipStream_t s);
+
+// KIMG_VARIANT_BINNED (grid_binned.hip): the stream in tile order, inside the caller's workspace
+// (kimg_grid_binned_workspace_bytes / kimg_degrid_binned_workspace_bytes), for a window kernel to run on
+struct kimg_binned_stream {
+    const int16_t *uv, *w_plane;
+    float2 *vis;
+    float *weights;                 // degridders only
+    const unsigned *index;          // the caller's record of sorted place i
+    void *table;                    // the float32 window kernel's own scratch
+    size_t table_bytes;
+};
+// `weights` null: a gridder's stream (no weights gathered, the gridder's workspace layout)
+int kimg_bin_stream(const int16_t *uv, const int16_t *w_plane, const float *weights, const void *vis,
+                    int64_t num_vis, int grid_size, int P, int w_planes, int oversample,
+                    int kernel_width, void *workspace, size_t workspace_bytes, hipStream_t stream,
+                    kimg_binned_stream &out);
+// a degridder's results back in the caller's order
+int kimg_unbin_vis(const kimg_binned_stream &b, void *vis, int64_t num_vis, int P, hipStream_t stream);
+
+// f(std::integral_constant<int, P>{}) for the runtime P in 1..4 (callers have checked the range)
+template <class F> inline void kimg_for_pols(int P, F &&f)
+{
+    switch (P) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    }
+}
+
 constexpr int WAVE = 64;    // gfx950 wavefront
 
 // Wave-wide sum by DPP-backed shuffles; result valid in every lane.
@@ -82,4 +139,30 @@ __device__ inline double wave_sum(double v)
     for (int off = 32; off > 0; off >>= 1)
         v += __shfl_xor(v, off, WAVE);
     return v;
+}
+
+// One record of the uv stream: (u, v, sub_u, sub_v) as four int16
+struct vis_coord {
+    int u, v, sub_u, sub_v;
+};
+
+__device__ inline vis_coord load_uv(const int16_t *__restrict__ uv, int64_t i)
+{
+    const int2 packed = reinterpret_cast<const int2 *>(uv)[i];
+    vis_coord c;
+    c.u = (short) (packed.x & 0xffff);
+    c.v = (short) (packed.x >> 16);
+    c.sub_u = (short) (packed.y & 0xffff);
+    c.sub_v = (short) (packed.y >> 16);
+    return c;
+}
+
+// A record whose cell, sub-cell or plane lies outside the grid / table contributes nothing (the
+// window kernel's coords_ok, grid_mfma.hip).
+__device__ inline bool coords_ok(const vis_coord &c, int wp, int Gg, int w_planes, int oversample)
+{
+    const int half = Gg / 2;
+    return (unsigned) (c.u + half) < (unsigned) Gg && (unsigned) (c.v + half) < (unsigned) Gg
+           && (unsigned) c.sub_u < (unsigned) oversample && (unsigned) c.sub_v < (unsigned) oversample
+           && (unsigned) wp < (unsigned) w_planes;
 }

@@ -267,15 +267,10 @@ extern "C" int kimg_store_reorder(int num_polarizations, int64_t num_vis, int ke
     const float2 *vis2 = static_cast<const float2 *>(vis);
     float2 *vis_o = static_cast<float2 *>(out_vis);
     if (!merge) {
-#define GATHER(PP) store_gather_kernel<PP><<<blocks, 256, 0, s>>>(index.Current(), num_vis, uv2, w_plane, \
-        weights, vis2, uv_o, out_w_plane, out_weights, vis_o, reinterpret_cast<unsigned long long *>(out_count))
-        switch (num_polarizations) {
-        case 1: GATHER(1); break;
-        case 2: GATHER(2); break;
-        case 3: GATHER(3); break;
-        default: GATHER(4); break;
-        }
-#undef GATHER
+        kimg_for_pols(num_polarizations, [&](auto p) {
+            store_gather_kernel<decltype(p)::value><<<blocks, 256, 0, s>>>(
+                index.Current(), num_vis, uv2, w_plane, weights, vis2, uv_o, out_w_plane, out_weights,
+                vis_o, reinterpret_cast<unsigned long long *>(out_count)); });
         return kimg_launch_status();
     }
     unsigned *runs = reinterpret_cast<unsigned *>(base + ws.runs);
@@ -285,16 +280,10 @@ extern "C" int kimg_store_reorder(int num_polarizations, int64_t num_vis, int ke
         counting, hf);
     cub_bytes = ws.cub_bytes;
     KIMG_HIP(hipcub::DeviceScan::InclusiveSum(base + ws.cub, cub_bytes, heads, runs, (int) num_vis, s));
-#define MERGE(PP) store_merge_kernel<PP><<<blocks, 256, 0, s>>>(index.Current(), runs, num_vis, uv2, \
-        w_plane, weights, vis2, uv_o, out_w_plane, out_weights, vis_o, \
-        reinterpret_cast<unsigned long long *>(out_count))
-    switch (num_polarizations) {
-    case 1: MERGE(1); break;
-    case 2: MERGE(2); break;
-    case 3: MERGE(3); break;
-    default: MERGE(4); break;
-    }
-#undef MERGE
+    kimg_for_pols(num_polarizations, [&](auto p) {
+        store_merge_kernel<decltype(p)::value><<<blocks, 256, 0, s>>>(
+            index.Current(), runs, num_vis, uv2, w_plane, weights, vis2, uv_o, out_w_plane,
+            out_weights, vis_o, reinterpret_cast<unsigned long long *>(out_count)); });
     return kimg_launch_status();
 }
 

@@ -164,18 +164,13 @@ extern "C" int kimg_grid_weights(float *grid, int64_t row_stride, int64_t pol_st
     KIMG_CHECK_ARG(width % 2 == 0 && height % 2 == 0);     // weight.py:131-132
     if (num_vis == 0)
         return 0;
+    if (num_polarizations < 1 || num_polarizations > 4)
+        return KIMG_EUNSUPPORTED;
     hipStream_t s = (hipStream_t) stream;
     dim3 grid_dim(kimg_divup(num_vis, 256)), block(256);
-#define LAUNCH(P) grid_weights_kernel<P><<<grid_dim, block, 0, s>>>( \
-        grid, row_stride, pol_stride, width / 2, height / 2, uv, weights, num_vis)
-    switch (num_polarizations) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 3: LAUNCH(3); break;
-    case 4: LAUNCH(4); break;
-    default: return KIMG_EUNSUPPORTED;
-    }
-#undef LAUNCH
+    kimg_for_pols(num_polarizations, [&](auto p) {
+        grid_weights_kernel<decltype(p)::value><<<grid_dim, block, 0, s>>>(
+            grid, row_stride, pol_stride, width / 2, height / 2, uv, weights, num_vis); });
     return kimg_launch_status();
 }
 

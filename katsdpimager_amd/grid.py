@@ -335,6 +335,37 @@ class GridDegrid(VisOperation):
         table = self.convolve_kernel.padded_data
         return (table.ptr, table.shape[0], table.shape[1], table.shape[2])
 
+    def _init_workspace(self, window_bytes, binned_bytes):
+        """Allocate the window kernel's scratch and note the binned variant's size (0: no binned
+        variant).  `window_bytes(pols, planes, oversample, width)` and
+        `binned_bytes(max_vis, pols, planes, oversample, width)` are the library's size functions."""
+        dims = (self.slots['grid'].shape[0],) + self._kernel_args()[1:]
+        # (float64: no scratch except for the sort; window kernels for widths up to 32)
+        nbytes = 0 if self._f64 else window_bytes(*dims)
+        self._workspace = None
+        self._workspace_bytes = nbytes
+        if nbytes:
+            self._workspace = accel.DeviceArray(self.command_queue.context, (nbytes,), np.uint8,
+                                                queue=self.command_queue)
+        self._init_locality(0 if self._f64 and dims[3] > 32 else binned_bytes(self.max_vis, *dims))
+
+    def _launch(self, name, *head):
+        """Call ``name`` (float32) or ``name + '_f64'`` with `head`, then the arguments the four have
+        in common; the float32 functions also take the template's ``arith``."""
+        variant = self._choose_variant()
+        if variant == GRID_VARIANTS['binned']:
+            # gridder 34 + 8 P, degridder 38 + 12 P bytes per visibility of max_vis
+            self._binned_workspace()
+        args = head + (self.num_vis,) + self._kernel_args() + (
+            self._workspace.ptr if self._workspace is not None else None, self._workspace_bytes,
+            variant | int(self.window_cus) << 8)
+        if self._f64:
+            name += '_f64'
+        else:
+            args += (self.template.arith,)
+        check(getattr(lib(), name)(*args, self.command_queue.handle), name)
+        self._note_variant(variant)
+
     # ---- stream order: window kernel as is, or tile-binned first (see GridderTemplate) ----------
     def _init_locality(self, binned_bytes):
         self._binned_bytes = binned_bytes
@@ -404,59 +435,23 @@ class Gridder(GridDegrid):
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self.slots['weights_grid'] = accel.IOSlot(self.slots['grid'].shape, np.float32)
-        num_pols = self.slots['grid'].shape[0]
-        table = self.convolve_kernel.padded_data
-        nbytes = 0 if self._f64 else lib().kimg_grid_workspace_bytes(
-            self.max_vis, num_pols, table.shape[0], table.shape[1], table.shape[2])
-        self._workspace = None
-        self._workspace_bytes = nbytes
-        if nbytes:
-            self._workspace = accel.DeviceArray(self.command_queue.context, (nbytes,), np.uint8,
-                                                queue=self.command_queue)
-        # (float64: no scratch except for the sort; window kernels for widths up to 32)
-        binned = 0 if self._f64 and table.shape[2] > 32 else lib().kimg_grid_binned_workspace_bytes(
-            self.max_vis, num_pols, table.shape[0], table.shape[1], table.shape[2])
+        self._init_workspace(
+            lambda *dims: lib().kimg_grid_workspace_bytes(self.max_vis, *dims),
+            lib().kimg_grid_binned_workspace_bytes)
         # the window gridder packs first-tap coordinates into 16 bits and addresses a polarization
         # plane with 32-bit byte offsets (kimg_grid: grid_size <= 32000, grid_size * row_stride * 8
         # < 2^32); wider grids go to the generic kernel whatever the stream's order, so `auto`
         # must not ask for the binned variant there
         Gg = self.slots['grid'].shape[1]
         if Gg > 32000 or Gg * Gg * 8 >= 1 << 32:
-            binned = 0
-        self._init_locality(binned)
+            self._binned_bytes = 0
 
     def _run(self):
         grid = self.buffer('grid')
         wg = self.buffer('weights_grid')
         P, G = grid.shape[0], grid.shape[1]
-        table, W, OV, K = self._kernel_args()
-        variant = self._choose_variant()
-        if self._f64:
-            if variant == GRID_VARIANTS['binned']:
-                self._binned_workspace()
-            rc = lib().kimg_grid_f64(
-                grid.ptr, G, G * G, G, P,
-                wg.ptr, G, G * G,
-                self.buffer('uv').ptr, self.buffer('w_plane').ptr, self.buffer('vis').ptr,
-                self.num_vis, table, W, OV, K,
-                self._workspace.ptr if self._workspace is not None else None,
-                self._workspace_bytes, variant | int(self.window_cus) << 8,
-                self.command_queue.handle)
-            check(rc, 'kimg_grid_f64')
-            self._note_variant(variant)
-            return
-        if variant == GRID_VARIANTS['binned']:
-            self._binned_workspace()        # 34 + 8 P bytes per visibility of max_vis
-        rc = lib().kimg_grid(
-            grid.ptr, G, G * G, G, P,
-            wg.ptr, G, G * G,
-            self.buffer('uv').ptr, self.buffer('w_plane').ptr, self.buffer('vis').ptr,
-            self.num_vis, table, W, OV, K,
-            self._workspace.ptr if self._workspace is not None else None,
-            self._workspace_bytes, variant | int(self.window_cus) << 8, self.template.arith,
-            self.command_queue.handle)
-        check(rc, 'kimg_grid')
-        self._note_variant(variant)
+        self._launch('kimg_grid', grid.ptr, G, G * G, G, P, wg.ptr, G, G * G,
+                     self.buffer('uv').ptr, self.buffer('w_plane').ptr, self.buffer('vis').ptr)
 
 
 class DegridderTemplate:
@@ -488,44 +483,12 @@ class Degridder(GridDegrid):
         num_pols = self.slots['grid'].shape[0]
         self.slots['weights'] = accel.IOSlot(
             (self.max_vis, accel.Dimension(num_pols, exact=True)), np.float32)
-        table = self.convolve_kernel.padded_data
-        nbytes = 0 if self._f64 else lib().kimg_degrid_workspace_bytes(
-            num_pols, table.shape[0], table.shape[1], table.shape[2])
-        self._workspace = None
-        self._workspace_bytes = nbytes
-        if nbytes:
-            self._workspace = accel.DeviceArray(self.command_queue.context, (nbytes,), np.uint8,
-                                                queue=self.command_queue)
-        self._init_locality(0 if self._f64 and table.shape[2] > 32 else
-                            lib().kimg_degrid_binned_workspace_bytes(
-                                self.max_vis, num_pols, table.shape[0], table.shape[1],
-                                table.shape[2]))
+        self._init_workspace(lib().kimg_degrid_workspace_bytes,
+                             lib().kimg_degrid_binned_workspace_bytes)
 
     def _run(self):
         grid = self.buffer('grid')
         P, G = grid.shape[0], grid.shape[1]
-        table, W, OV, K = self._kernel_args()
-        variant = self._choose_variant()
-        if self._f64:
-            if variant == GRID_VARIANTS['binned']:
-                self._binned_workspace()
-            rc = lib().kimg_degrid_f64(
-                grid.ptr, G, G * G, G, P,
-                self.buffer('uv').ptr, self.buffer('w_plane').ptr, self.buffer('weights').ptr,
-                self.buffer('vis').ptr, self.num_vis, table, W, OV, K,
-                self._workspace.ptr if self._workspace is not None else None,
-                self._workspace_bytes, variant | int(self.window_cus) << 8,
-                self.command_queue.handle)
-            check(rc, 'kimg_degrid_f64')
-            self._note_variant(variant)
-            return
-        if variant == GRID_VARIANTS['binned']:
-            self._binned_workspace()        # 38 + 12 P bytes per visibility of max_vis
-        rc = lib().kimg_degrid(
-            grid.ptr, G, G * G, G, P,
-            self.buffer('uv').ptr, self.buffer('w_plane').ptr, self.buffer('weights').ptr,
-            self.buffer('vis').ptr, self.num_vis, table, W, OV, K,
-            self._workspace.ptr if self._workspace is not None else None, self._workspace_bytes,
-            variant | int(self.window_cus) << 8, self.template.arith, self.command_queue.handle)
-        check(rc, 'kimg_degrid')
-        self._note_variant(variant)
+        self._launch('kimg_degrid', grid.ptr, G, G * G, G, P,
+                     self.buffer('uv').ptr, self.buffer('w_plane').ptr, self.buffer('weights').ptr,
+                     self.buffer('vis').ptr)

@@ -373,6 +373,7 @@ TRUTH_CASES = [
     (60, 4, 32, 'jumps', 0, 200),
     (8, 2, 32, 'slow', 1, 160),
     (28, 1, 32, 'slow', 65, 168),
+    (28, 3, 32, 'random', 1501, 168),
 ]
 
 
