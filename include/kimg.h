@@ -50,10 +50,21 @@ extern "C" {
  *   KIMG_ARITH_FP32_32X32  the same sums as KIMG_ARITH_FP32, the gridder on v_mfma_f32_32x32x2_f32
  *                          (one visibility per instruction; the earlier default form, kept for
  *                          comparison).  Gridder only: the degridder rejects it (KIMG_EINVAL).
- * The generic (non-MFMA) kernels always compute in float32 and ignore it. */
+ * The generic (non-MFMA) kernels always compute in float32 and ignore it.
+ *
+ * One exception to "bit-identical", in every form of the window gridder (kimg_grid, MFMA and binned
+ * variants): consecutive records of one call with equal (u, v, sub_u, sub_v, w_plane) add the same
+ * rank-1 matrix to the grid, and the gridder may sum their weighted samples (vis * weights_grid) in
+ * float32, in unspecified order, and apply ONE update with the sum -- what the reference's
+ * preprocessor does to such runs before its gridder sees them.  How long a folded run is is not
+ * part of the contract (runs are cut wherever the kernel's batches end).  A stream without adjacent
+ * duplicates is gridded exactly as before.
+ *   KIMG_ARITH_NO_FOLD     a bit OR-ed into any of the above (kimg_grid only): every record gets its
+ *                          own update, as before the fold existed.  For comparison and tests. */
 #define KIMG_ARITH_FP32 0
 #define KIMG_ARITH_SPLIT_FP16 1
 #define KIMG_ARITH_FP32_32X32 2
+#define KIMG_ARITH_NO_FOLD 0x100
 
 /* Kernel choice of kimg_grid / kimg_degrid (argument `variant`) */
 #define KIMG_VARIANT_AUTO 0     /* MFMA window kernel when the parameters allow it */

@@ -36,6 +36,12 @@
 //    instruction (PAIR: window_acc16, pair32_ops): fewer address and LDS instructions per visibility,
 //    8 instructions of 32 cycles per pair instead of 2 x 2 of 64; the 32x32x2 form stays selectable
 //    (KIMG_ARITH_FP32_32X32).
+//  * Consecutive records with equal (u, v, sub_u, sub_v, w_plane) apply the same rank-1 matrix, so the
+//    staging step sums their weighted samples and stages ONE record per run (a ballot for the run
+//    heads, a segmented sum over lanes, a compaction through LDS; runs are cut at the ends of a
+//    batch of 64).  An uncompressed track stream repeats its predecessor's sub-cell in 6 of 7
+//    records; a stream that was merged before takes a scalar branch around the step.
+//    KIMG_ARITH_NO_FOLD switches it off.
 // Algorithmic work per visibility: 8*K*K*P flop (complex MAC per tap) + 6*K*P (a-vector);
 // executed: 2 MFMA x 2048 MAC per visibility per polarization (32x32 window).
 #include "kimg_common.h"
@@ -1066,23 +1072,90 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
         int gmax_bits[P];       // fp16 form: bits of the group's largest sample | (spread too wide)
         int Evec[P];            // fp16 form: the scale (exponent) this lane's group was staged with,
                                 // E_WIDE (staged unscaled) or E_NONE (no sample yet)
+        int count = b.e - b.b < 64 ? (int) (b.e - b.b) : 64;    // staged records (fewer once runs are folded)
         {
             const bool ok = coords_ok(b, r0);
             const int u = (short) (r0.uv.x & 0xffff), v = (short) (r0.uv.x >> 16);
             const int su = (short) (r0.uv.y & 0xffff), sv = (short) (r0.uv.y >> 16);
-            const int mu = u - uv_bias + ts.tu0, mv = v - uv_bias + ts.tv0;
+            int mu = u - uv_bias + ts.tu0, mv = v - uv_bias + ts.tv0;
             // row byte offset (a multiple of ROW * 8) + tap byte offset (< 256)
             int2 r;
             r.x = (ok ? (r0.wp * OV + su) * (ROW * 8) : 0) + ((-mu) & 31) * 8 + u_table;
             r.y = (ok ? (r0.wp * OV + sv) * (ROW * 8) : 0) + ((-mv) & 31) * 8;
-            recs[lane] = r;
-            origins[lane] = make_int2(mu, mv);
             bool live = false;
             float2 sp[P];
 #pragma unroll
             for (int p = 0; p < P; p++)
                 sp[p] = ok ? make_float2(r0.v[p].x * r0.w[p], r0.v[p].y * r0.w[p])
                            : make_float2(0.0f, 0.0f);                       // grid.py:1046
+            // ---- fold runs ---------------------------------------------------------------------
+            // Consecutive records with equal (u, v, sub_u, sub_v, w_plane) read the same weight cell
+            // and apply the same rank-1 matrix conj(kv) (x) conj(ku): their updates add up to ONE
+            // update with the sum of their weighted samples.  Lane i heads a run unless lane i - 1
+            // holds the same five integers (a record that fails coords_ok never joins a run; runs
+            // are cut at the batch's ends).  A batch of heads only -- every batch of a stream that was
+            // merged before -- takes the scalar branch around all of it.
+            // (FOLD: the float32 forms with one polarization and single table rows in LDS have no
+            // register to spare -- with this block they spill or lose a wave per SIMD -- and keep the
+            // plain staging)
+            constexpr bool FOLD = !(P == 1 && ROW == 32 && !TG && !F16);
+            uint64_t heads = ~0ull;
+            bool head = true;
+            if (FOLD && !(dbg & 4)) {
+                const int pux = __builtin_amdgcn_update_dpp(0, r0.uv.x, 0x138, 0xf, 0xf, false);   // wave_shr:1
+                const int puy = __builtin_amdgcn_update_dpp(0, r0.uv.y, 0x138, 0xf, 0xf, false);
+                const int pwp = __builtin_amdgcn_update_dpp(0, r0.wp, 0x138, 0xf, 0xf, false);
+                head = !(lane > 0 && ok && pux == r0.uv.x && puy == r0.uv.y && pwp == r0.wp);
+                heads = __ballot(head);
+            }
+            if (!FOLD || heads == ~0ull) {
+                recs[lane] = r;
+                origins[lane] = make_int2(mu, mv);
+            } else {
+                // compact: the heads move up to slots 0 .. count - 1 in order; the slots behind them
+                // are staged dead, as the tail of a short batch is (lanes >= count are heads: not ok)
+                const uint64_t hv = count == 64 ? heads : heads & ((1ull << count) - 1);
+                const int rank = (int) __builtin_amdgcn_mbcnt_hi((unsigned) (hv >> 32),
+                                                                 __builtin_amdgcn_mbcnt_lo((unsigned) hv, 0u));
+                const bool keep = head && lane < count;
+                count = __builtin_popcountll(hv);
+                // segmented sum towards the head: after the steps below d, a lane holds the sum of
+                // itself and the next d - 1 lanes of its run; `rem` = lanes of the run behind this one
+                const uint64_t above = (heads >> lane) >> 1;
+                const int rem = above ? __builtin_ctzll(above) : 63 - lane;
+#pragma unroll 1
+                for (int d = 1; d < 64; d *= 2) {
+                    const bool take = d <= rem;
+                    if (__ballot(take) == 0)
+                        break;                          // (uniform) no run of the batch is that long
+#pragma unroll
+                    for (int p = 0; p < P; p++) {
+                        const float x = __shfl_down(sp[p].x, d, WAVE), y = __shfl_down(sp[p].y, d, WAVE);
+                        sp[p].x += take ? x : 0.0f;
+                        sp[p].y += take ? y : 0.0f;
+                    }
+                }
+                if (keep) {
+                    recs[rank] = r;
+                    origins[rank] = make_int2(mu, mv);
+#pragma unroll
+                    for (int p = 0; p < P; p++)
+                        *reinterpret_cast<float2 *>(samples + p * 64 + rank) = sp[p];
+                }
+                __builtin_amdgcn_wave_barrier();
+                // lane j goes on with the record of slot j
+                const bool kept = lane < count;
+                const int2 org = origins[lane];
+                mu = kept ? org.x : mu;
+                mv = kept ? org.y : mv;
+#pragma unroll
+                for (int p = 0; p < P; p++) {
+                    const float2 t = *reinterpret_cast<const float2 *>(samples + p * 64 + lane);
+                    sp[p] = kept ? t : make_float2(0.0f, 0.0f);
+                }
+                if (!kept)
+                    recs[lane] = make_int2(u_table, 0);
+            }
             if constexpr (F16) {
                 // keep the samples in fp16 range: a scale T = 2^-E per group of 8 visibilities and
                 // polarization (see keeps_scale / T_SPREAD above), chosen group after group so that
@@ -1152,7 +1225,6 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
             load_raw(p2, r1);
         __builtin_amdgcn_wave_barrier();        // LDS is in-order per wave; just pin the order
 
-        const int count = b.e - b.b < 64 ? (int) (b.e - b.b) : 64;
         const int npairs = (count + 2 * SUB - 1) / (2 * SUB);
         typename std::conditional<F16, pair_ops<P, SUB / 2>,
                                   typename std::conditional<PAIR, pair32_ops<P, SUB / 2>, sub_ops<P, SUB>>::type>::type X, Y;
@@ -1330,7 +1402,7 @@ int launch(float *grid, int64_t row_stride, int64_t pol_stride, int Gg, const fl
            const int16_t *w_plane, const float2 *vis, int64_t num_vis, const float2 *kern,
            int W, int OV, const tap_split &ts, int p_total, hipStream_t stream,
            unsigned char *padded = nullptr, size_t tab_max_offset = 0,
-           unsigned long long *queue = nullptr)
+           unsigned long long *queue = nullptr, bool fold = true)
 {
     constexpr int SUB = (P == 1 && NW <= 12) ? 4 : 2;       // pipeline depth bounded by the VGPR budget
     const size_t lds = TG ? lds_bytes(P, NW, 0, 0, ROW) : lds_bytes(P, NW, W, OV, ROW, TWO ? 2 : 1);
@@ -1362,11 +1434,12 @@ int launch(float *grid, int64_t row_stride, int64_t pol_stride, int Gg, const fl
     // bits 8-15: span stagger of a SIMD's waves, percent.  Bits 0-1 (test builds with
     // -DKIMG_NO_ATOMICS, the counterpart of the reference's NO_ATOMICS switch,
     // imager_kernels/atomic.mako:29-40): no end flush / no window flushes -- wrong results, for
-    // measuring what the float atomics cost.
+    // measuring what the float atomics cost.  Bit 2: runs of records with one sub-cell are NOT folded
+    // (KIMG_ARITH_NO_FOLD).
 #ifdef KIMG_NO_ATOMICS
-    const int dbg = (12 << 8) | 3;
+    const int dbg = (12 << 8) | 3 | (fold ? 0 : 4);
 #else
-    const int dbg = 12 << 8;
+    const int dbg = (12 << 8) | (fold ? 0 : 4);
 #endif
     // as many blocks resident per CU as the LDS (kernel table + staging) allows;
     // every block streams a contiguous span (a multiple of 64).
@@ -1451,6 +1524,8 @@ int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
                    const void *convolve_kernel, int w_planes, int oversample, int kernel_width,
                    void *workspace, size_t workspace_bytes, int arith, hipStream_t stream)
 {
+    const bool fold = !(arith & KIMG_ARITH_NO_FOLD);
+    arith &= ~KIMG_ARITH_NO_FOLD;
     const bool f16 = arith == KIMG_ARITH_SPLIT_FP16;
     const bool pair = arith == KIMG_ARITH_FP32;         // (KIMG_ARITH_FP32_32X32: one visibility per instruction)
     const bool in_lds = table_in_lds(P, w_planes, oversample, kernel_width);
@@ -1485,13 +1560,13 @@ int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
 #define GO(PP, ROWV, NWV, TWOV, TGV) do { \
         if (f16) rc = launch<PP, ROWV, NWV, TWOV, TGV, true>(g, grid_row_stride, grid_pol_stride, \
             grid_size, wg, wg_row_stride, wg_pol_stride, uv, w_plane, v, num_vis, kern, w_planes, \
-            oversample, ts, P, stream, padded, tab_max_offset, queue); \
+            oversample, ts, P, stream, padded, tab_max_offset, queue, fold); \
         else if (pair) rc = launch<PP, ROWV, NWV, TWOV, TGV, false, true>(g, grid_row_stride, \
             grid_pol_stride, grid_size, wg, wg_row_stride, wg_pol_stride, uv, w_plane, v, num_vis, \
-            kern, w_planes, oversample, ts, P, stream, padded, tab_max_offset, queue); \
+            kern, w_planes, oversample, ts, P, stream, padded, tab_max_offset, queue, fold); \
         else rc = launch<PP, ROWV, NWV, TWOV, TGV, false>(g, grid_row_stride, grid_pol_stride, \
             grid_size, wg, wg_row_stride, wg_pol_stride, uv, w_plane, v, num_vis, kern, w_planes, \
-            oversample, ts, P, stream, padded, tab_max_offset, queue); } while (0)
+            oversample, ts, P, stream, padded, tab_max_offset, queue, fold); } while (0)
                 const size_t tab_max_offset = workspace_bytes >= 256 ? workspace_bytes - 256 : 0;
                 // Diagonal blocks of a wide kernel take row and column taps from the same half of
                 // the table: one table, which fits LDS whenever a narrow kernel's would.

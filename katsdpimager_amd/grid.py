@@ -216,6 +216,10 @@ GRID_VARIANTS = {'auto': 0, 'generic': 1, 'mfma': 2, 'binned': 3}           # KI
 #: accumulation (faster, 22-bit operands; opt-in); ``fp32_32x32`` = the same sums as ``fp32``, the
 #: gridder on v_mfma_f32_32x32x2_f32 (one visibility per instruction; for comparison; gridder only).
 GRID_ARITH = {'fp32': 0, 'split_fp16': 1, 'fp32_32x32': 2}
+#: OR-ed into ``arith`` for kimg_grid when ``tuning['fold_runs']`` is False (KIMG_ARITH_NO_FOLD): the
+#: window gridder then gives every record its own update instead of summing the samples of
+#: consecutive records with equal (u, v, sub_u, sub_v, w_plane) first.  For comparison and tests.
+GRID_ARITH_NO_FOLD = 0x100
 
 
 #: `auto` variant: calls smaller than this go straight to the window kernel ...
@@ -227,7 +231,7 @@ AUTO_JUMP_FRACTION = 0.05
 
 def _tuning(tuning, real_dtype=np.float32):
     tuning = tuning or {}
-    unknown = set(tuning) - {'variant', 'arith'}
+    unknown = set(tuning) - {'variant', 'arith', 'fold_runs'}
     if unknown:
         raise ValueError('unknown tuning keys: {}'.format(sorted(unknown)))
     try:
@@ -240,14 +244,20 @@ def _tuning(tuning, real_dtype=np.float32):
         if arith != GRID_ARITH['fp32']:
             raise ValueError('float64 gridding has one arithmetic; arith={!r} is float32 only'.format(
                 tuning['arith']))
-    return variant, arith
+    fold_runs = tuning.get('fold_runs', True)
+    if not isinstance(fold_runs, (bool, np.bool_)):
+        raise ValueError('unknown tuning value {!r} for fold_runs'.format(fold_runs))
+    return variant, arith, bool(fold_runs)
 
 
 class GridderTemplate:
     """grid.py:549-653.  ``tuning`` may hold ``{'variant': 'auto'|'generic'|'mfma'|'binned',
-    'arith': 'fp32'|'split_fp16'|'fp32_32x32'}`` (the reference's tuning dict carries its autotuned work-group
+    'arith': 'fp32'|'split_fp16'|'fp32_32x32', 'fold_runs': True|False}`` (the reference's tuning dict carries its autotuned work-group
     shape; there is no autotuner here -- the kernel geometry is fixed by the MFMA tile shape).
-    Both are per template, passed to the C ABI on every call: nothing is read from the environment.
+    All are per template, passed to the C ABI on every call: nothing is read from the environment.
+    ``fold_runs`` (default True): the window kernel sums the weighted samples of consecutive records
+    with equal (u, v, sub_u, sub_v, w_plane) and applies one update (include/kimg.h); the float64
+    gridder and the degridder have no such step and ignore the key.
 
     ``mfma`` is the window kernel on the stream as it comes; ``binned`` first sorts the visibilities
     by grid tile on the device (for streams without locality: time order, shuffled).  ``auto``
@@ -267,7 +277,7 @@ class GridderTemplate:
         self.context = context
         self.fixed_image_parameters = fixed_image_parameters
         self.fixed_grid_parameters = fixed_grid_parameters
-        self.variant, self.arith = _tuning(tuning, fixed_image_parameters.real_dtype)
+        self.variant, self.arith, self.fold_runs = _tuning(tuning, fixed_image_parameters.real_dtype)
         self.kernel_pad = 0
 
     def instantiate(self, *args, **kwargs):
@@ -349,7 +359,7 @@ class GridDegrid(VisOperation):
                                                 queue=self.command_queue)
         self._init_locality(0 if self._f64 and dims[3] > 32 else binned_bytes(self.max_vis, *dims))
 
-    def _launch(self, name, *head):
+    def _launch(self, name, *head, arith_flags=0):
         """Call ``name`` (float32) or ``name + '_f64'`` with `head`, then the arguments the four have
         in common; the float32 functions also take the template's ``arith``."""
         variant = self._choose_variant()
@@ -362,7 +372,7 @@ class GridDegrid(VisOperation):
         if self._f64:
             name += '_f64'
         else:
-            args += (self.template.arith,)
+            args += (self.template.arith | arith_flags,)
         check(getattr(lib(), name)(*args, self.command_queue.handle), name)
         self._note_variant(variant)
 
@@ -451,7 +461,8 @@ class Gridder(GridDegrid):
         wg = self.buffer('weights_grid')
         P, G = grid.shape[0], grid.shape[1]
         self._launch('kimg_grid', grid.ptr, G, G * G, G, P, wg.ptr, G, G * G,
-                     self.buffer('uv').ptr, self.buffer('w_plane').ptr, self.buffer('vis').ptr)
+                     self.buffer('uv').ptr, self.buffer('w_plane').ptr, self.buffer('vis').ptr,
+                     arith_flags=0 if self.template.fold_runs else GRID_ARITH_NO_FOLD)
 
 
 class DegridderTemplate:
@@ -464,7 +475,7 @@ class DegridderTemplate:
         self.context = context
         self.fixed_image_parameters = fixed_image_parameters
         self.fixed_grid_parameters = fixed_grid_parameters
-        self.variant, self.arith = _tuning(tuning, fixed_image_parameters.real_dtype)
+        self.variant, self.arith, self.fold_runs = _tuning(tuning, fixed_image_parameters.real_dtype)
         self.kernel_pad = 0
 
     def instantiate(self, *args, **kwargs):
