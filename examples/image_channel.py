@@ -32,6 +32,8 @@ def main(argv=None):
                     help='W planes per slice (more than 64: the kernel table is read from HBM)')
     ap.add_argument('--kernel-width', type=int, default=28)
     ap.add_argument('--output', help='write the restored image to this FITS file')
+    ap.add_argument('--mask-radius', type=int, default=0,
+                    help='CLEAN only within this many pixels of a source (a mask of disks); 0 = no mask')
     args = ap.parse_args(argv)
     import torch
     import scipy.optimize       # noqa: F401  (used by beam.fit_beam; imported here, outside the timings)
@@ -74,9 +76,16 @@ def main(argv=None):
     template = imaging.ImagingTemplate(ctx, array_p, image_p.fixed, weight_p, grid_p.fixed, clean_p)
     imager = template.instantiate(queue, image_p, grid_p, args.vis_block, 0, args.major, streams=2)
     imager.ensure_all_bound()
+    clean_mask = None
+    if args.mask_radius > 0:
+        yy, xx = np.mgrid[:args.pixels, :args.pixels]
+        clean_mask = np.zeros((args.pixels, args.pixels), bool)
+        for (lp, mp), _ in sources:
+            clean_mask |= ((yy - (args.pixels // 2 + mp)) ** 2 + (xx - (args.pixels // 2 + lp)) ** 2
+                           <= args.mask_radius ** 2)
     stats = frontend.process_channel(reader, 0, imager, image_p, grid_p, clean_p,
                                      weight_p.weight_type, args.vis_block, args.major, True,
-                                     fit_beam=True)
+                                     fit_beam=True, clean_mask=clean_mask)
     queue.finish()
     t2 = time.perf_counter()
     print('imaged in {:.1f} ms: {} major / {} minor cycles, PSF patch {}, noise {:.3g}'.format(

@@ -698,6 +698,48 @@ int kimg_clean_cycles_batch(const kimg_clean_channel *channels_host, int num_cha
                             int psf_width, int psf_height, int border, int mode, float loop_gain,
                             int tiles_x, int tiles_y, void *stream);
 
+/* ---- CLEAN masks (clean windows): a per-pixel allow map for the minor cycle.  The reference has
+ * none; the semantics are this library's.
+ *   mask   device uint8 [height][width] with mask_row_stride bytes between rows (>= width); ONE
+ *          plane serves all polarizations; nonzero = a component may be placed on this pixel.
+ *   Candidates.  A pixel is a candidate only if it is inside the border AND allowed; the metric of
+ *          every other pixel takes no part in any tile maximum.
+ *   Subtraction is unchanged: the whole PSF patch is subtracted around a component, masked pixels
+ *          included.  Only allowed pixels ever receive flux in the model.
+ *   Scan order and tie-breaks are those of the unmasked calls: first strict maximum in row-major
+ *          order within a tile, then the first maximal tile in row-major tile order.
+ *   Empty tiles.  A tile without a candidate (or whose candidates all have metric 0) records
+ *          tile_max = 0 and the tile_pos an all-zero tile records without a mask.
+ *   Stopping.  With a mask, a best metric of exactly 0 ends the search whatever the threshold, 0
+ *          included (otherwise an all-masked field would place a component on a masked pixel
+ *          through the start position an empty tile records): kimg_find_peak_masked then writes
+ *          peak_value 0, peak_pos (-1, -1) and a zero peak_pixel; kimg_clean_cycles_masked stops
+ *          and logs nothing for that cycle.  Unmasked calls keep their behaviour at metric 0.
+ * Each call takes the arguments of its unmasked namesake plus the mask.  A NULL mask means
+ * unmasked: the call then runs exactly what the namesake runs.
+ * kimg_clean_cycles_masked with a mask runs KIMG_CLEAN_FORM_TWO_LAUNCH or _ONE_LAUNCH (the latter
+ * with its fallback); _AUTO chooses between these two; _MULTI, _PERSISTENT and _ONE_WORKGROUP asked
+ * for with a mask return KIMG_EUNSUPPORTED before anything is enqueued.  kimg_clean_major_cycles and
+ * kimg_clean_cycles_batch have no masked form. */
+int kimg_update_tiles_masked(const float *dirty, int64_t row_stride, int64_t pol_stride,
+                             int width, int height, int num_polarizations, int border, int mode,
+                             float *tile_max, int32_t *tile_pos, int tiles_x, int tiles_y,
+                             int tile_x0, int tile_y0, int tile_x1, int tile_y1, void *stream,
+                             const uint8_t *mask, int64_t mask_row_stride);
+int kimg_find_peak_masked(const float *dirty, int64_t row_stride, int64_t pol_stride,
+                          int num_polarizations, const float *tile_max, const int32_t *tile_pos,
+                          int tiles_x, int tiles_y,
+                          float *peak_value, int32_t *peak_pos, float *peak_pixel, void *stream,
+                          const uint8_t *mask, int64_t mask_row_stride);
+int kimg_clean_cycles_masked(float *dirty, float *model, int64_t row_stride, int64_t pol_stride,
+                             int width, int height, int num_polarizations,
+                             const float *psf, int64_t psf_row_stride, int64_t psf_pol_stride,
+                             int psf_width, int psf_height, int patch_width, int patch_height,
+                             int border, int mode, float loop_gain, float threshold,
+                             float *tile_max, int32_t *tile_pos, int tiles_x, int tiles_y,
+                             int max_cycles, int form, void *state, float *log, void *stream,
+                             const uint8_t *mask, int64_t mask_row_stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,11 @@ PROTOTYPES = {
     'kimg_clean_major_cycles': (c_int, [P, P, L, L, I, I, I, P, L, L, I, I, I, I, I, I, F, c_double, c_double,
                                         P, P, I, I, I, I, P, P, P, P, P]),
     'kimg_clean_cycles_batch': (c_int, [P, I, L, L, I, I, I, L, L, I, I, I, I, F, I, I, P]),
+    # CLEAN masks: the unmasked argument lists plus (mask, mask_row_stride)
+    'kimg_update_tiles_masked': (c_int, [P, L, L, I, I, I, I, I, P, P, I, I, I, I, I, I, P, P, L]),
+    'kimg_find_peak_masked': (c_int, [P, L, L, I, P, P, I, I, P, P, P, P, P, L]),
+    'kimg_clean_cycles_masked': (c_int, [P, P, L, L, I, I, I, P, L, L, I, I, I, I, I, I, F, F,
+                                         P, P, I, I, I, I, P, P, P, P, L]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),

@@ -262,11 +262,15 @@ class IOSlotBase:
 
 
 class IOSlot(IOSlotBase):
-    def __init__(self, dimensions, dtype):
+    """``optional``: a slot that may stay unbound (``ensure_all_bound`` does not allocate it; the
+    operation then runs without what it would hold)."""
+
+    def __init__(self, dimensions, dtype, optional=False):
         self.dimensions = [d if isinstance(d, Dimension) else Dimension(d) for d in dimensions]
         self.shape = _dims(dimensions)
         self.dtype = np.dtype(dtype)
         self.buffer = None
+        self.optional = bool(optional)
 
     def required_padded_shape(self):
         return self.shape
@@ -301,6 +305,7 @@ class AliasIOSlot(IOSlotBase):
         self.shape = first.shape
         self.dtype = first.dtype
         self.dimensions = first.dimensions
+        self.optional = all(getattr(c, 'optional', False) for c in self.children)
 
     @property
     def buffer(self):
@@ -345,11 +350,13 @@ class Operation:
             slot.allocate(self.allocator).used_on(self.command_queue)
 
     def ensure_all_bound(self):
-        for name in self.slots:
-            self.ensure_bound(name)
+        for name, slot in self.slots.items():
+            if not getattr(slot, 'optional', False):
+                self.ensure_bound(name)
 
     def required_bytes(self):
-        return sum(int(np.prod(s.shape)) * s.dtype.itemsize for s in self.slots.values())
+        return sum(int(np.prod(s.shape)) * s.dtype.itemsize for s in self.slots.values()
+                   if s.is_bound() or not getattr(s, 'optional', False))
 
     def parameters(self):
         return {}

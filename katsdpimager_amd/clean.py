@@ -238,7 +238,8 @@ class _UpdateTilesTemplate(_CleanStepTemplate):
 
 class _UpdateTiles(accel.Operation):
     """Peak (value and position) of every 32x32 tile intersecting a window
-    (clean.py:398-480).  Slots **dirty**, **tile_max** [ty][tx], **tile_pos** [ty][tx][2]."""
+    (clean.py:398-480).  Slots **dirty**, **tile_max** [ty][tx], **tile_pos** [ty][tx][2], and the
+    optional **mask** uint8 [H][W] (see :class:`Clean`)."""
 
     def __init__(self, template, command_queue, image_shape, border, allocator=None):
         if image_shape[0] != template.num_polarizations:
@@ -252,6 +253,7 @@ class _UpdateTiles(accel.Operation):
         self.slots['dirty'] = accel.IOSlot(image_shape, template.dtype)
         self.slots['tile_max'] = accel.IOSlot((ty, tx), template.dtype)
         self.slots['tile_pos'] = accel.IOSlot((ty, tx, accel.Dimension(2, exact=True)), np.int32)
+        self.slots['mask'] = accel.IOSlot(image_shape[1:], np.uint8, optional=True)
 
     def _run(self):
         pass
@@ -266,7 +268,15 @@ class _UpdateTiles(accel.Operation):
         y0 = max((y0 - bp) // TILE, 0)
         x1 = min(accel.divup(x1 - bp, TILE), tile_max.shape[1])
         y1 = min(accel.divup(y1 - bp, TILE), tile_max.shape[0])
-        if x0 < x1 and y0 < y1:
+        mask = self.buffer('mask')
+        if x0 < x1 and y0 < y1 and mask is not None:
+            mask.used_on(self.command_queue)
+            rc = lib().kimg_update_tiles_masked(
+                *_image_args(self.buffer('dirty')), bp, self.template.mode,
+                tile_max.ptr, tile_pos.ptr, tile_max.shape[1], tile_max.shape[0],
+                x0, y0, x1, y1, self.command_queue.handle, mask.ptr, mask.shape[1])
+            check(rc, 'kimg_update_tiles_masked')
+        elif x0 < x1 and y0 < y1:
             rc = lib().kimg_update_tiles(
                 *_image_args(self.buffer('dirty')), bp, self.template.mode,
                 tile_max.ptr, tile_pos.ptr, tile_max.shape[1], tile_max.shape[0],
@@ -281,7 +291,8 @@ class _FindPeakTemplate(_CleanStepTemplate):
 
 
 class _FindPeak(accel.Operation):
-    """Global peak from the per-tile peaks (clean.py:516-587)."""
+    """Global peak from the per-tile peaks (clean.py:516-587).  With the optional **mask** slot
+    bound, a best metric of exactly 0 is reported as position (-1, -1): no allowed pixel is left."""
 
     def __init__(self, template, command_queue, image_shape, tile_shape, allocator=None):
         if image_shape[0] != template.num_polarizations:
@@ -295,11 +306,22 @@ class _FindPeak(accel.Operation):
         self.slots['peak_value'] = accel.IOSlot([1], template.dtype)
         self.slots['peak_pos'] = accel.IOSlot([2], np.int32)
         self.slots['peak_pixel'] = accel.IOSlot([template.num_polarizations], template.dtype)
+        self.slots['mask'] = accel.IOSlot(image_shape[1:], np.uint8, optional=True)
 
     def _run(self):
         dirty = self.buffer('dirty')
         tile_max = self.buffer('tile_max')
         P, H, W = dirty.shape
+        mask = self.buffer('mask')
+        if mask is not None:
+            mask.used_on(self.command_queue)
+            rc = lib().kimg_find_peak_masked(
+                dirty.ptr, W, H * W, P, tile_max.ptr, self.buffer('tile_pos').ptr,
+                tile_max.shape[1], tile_max.shape[0], self.buffer('peak_value').ptr,
+                self.buffer('peak_pos').ptr, self.buffer('peak_pixel').ptr,
+                self.command_queue.handle, mask.ptr, mask.shape[1])
+            check(rc, 'kimg_find_peak_masked')
+            return
         rc = lib().kimg_find_peak(
             dirty.ptr, W, H * W, P, tile_max.ptr, self.buffer('tile_pos').ptr,
             tile_max.shape[1], tile_max.shape[0], self.buffer('peak_value').ptr,
@@ -384,7 +406,14 @@ class CleanTemplate:
 
 class Clean(accel.OperationSequence):
     """CLEAN minor cycles (clean.py:756-891).  Slots: **dirty**, **model**, **psf**,
-    **tile_max**, **tile_pos**, **peak_value**, **peak_pos**, **peak_pixel**."""
+    **tile_max**, **tile_pos**, **peak_value**, **peak_pos**, **peak_pixel**, and the optional
+    **mask**: uint8 [height][width], one plane for all polarizations, nonzero = a component may be
+    placed on this pixel (include/kimg.h, "CLEAN masks").  ``ensure_all_bound`` leaves it unbound,
+    and unbound means unmasked; bind it (``bind(mask=...)``, ``bind(mask=None)`` to clear) before
+    :meth:`reset`.  With a mask, :meth:`__call__` and :meth:`run_cycles` only place components on
+    allowed pixels and stop at a best metric of exactly 0 whatever the threshold; the loop runs in
+    the two-launch or one-launch form, and :meth:`run_major_cycles` and the batch launch are not
+    available (they report so, and the callers take :meth:`run_cycles` per channel)."""
 
     def __init__(self, template, command_queue, image_parameters, allocator=None):
         if image_parameters.fixed.real_dtype != template.dtype:
@@ -411,6 +440,7 @@ class Clean(accel.OperationSequence):
             'peak_value': ['find_peak:peak_value'],
             'peak_pos': ['find_peak:peak_pos'],
             'peak_pixel': ['find_peak:peak_pixel', 'subtract_psf:peak_pixel'],
+            'mask': ['update_tiles:mask', 'find_peak:mask'],
         }
         super().__init__(command_queue, ops, compounds, allocator=allocator)
         self._state = accel.DeviceArray(
@@ -449,6 +479,8 @@ class Clean(accel.OperationSequence):
         if peak_value[0] < threshold:
             return None, None, None
         peak_pos = tuple(int(x) for x in both[1:3].view(np.int32))
+        if peak_pos[0] < 0:         # (only with a mask: metric 0, no allowed pixel left to take)
+            return None, None, None
         peak_pixel = both[3:].copy()
         model_pixel = np.float32(self.template.clean_parameters.loop_gain) * peak_pixel
         self._subtract_psf(peak_pos, psf_patch)
@@ -470,6 +502,18 @@ class Clean(accel.OperationSequence):
         cp = self.template.clean_parameters
         self._ensure_log(max_cycles)
         tile_max = self.buffer('tile_max')
+        mask = self.buffer('mask')
+        if mask is not None:
+            mask.used_on(self.command_queue)
+            rc = lib().kimg_clean_cycles_masked(
+                dirty.ptr, self.buffer('model').ptr, W, H * W, W, H, P,
+                psf.ptr, psf.shape[2], psf.shape[1] * psf.shape[2], psf.shape[2], psf.shape[1],
+                psf_patch[2], psf_patch[1], self._update_tiles.border_pixels, cp.mode,
+                cp.loop_gain, threshold, tile_max.ptr, self.buffer('tile_pos').ptr,
+                tile_max.shape[1], tile_max.shape[0], max_cycles, self.template.form,
+                self._state.ptr, self._log.ptr, self.command_queue.handle, mask.ptr, mask.shape[1])
+            check(rc, 'kimg_clean_cycles_masked')
+            return self._collect_cycles() if collect else None
         rc = lib().kimg_clean_cycles(
             dirty.ptr, self.buffer('model').ptr, W, H * W, W, H, P,
             psf.ptr, psf.shape[2], psf.shape[1] * psf.shape[2], psf.shape[2], psf.shape[1],
@@ -494,6 +538,8 @@ class Clean(accel.OperationSequence):
         import ctypes
         self.ensure_all_bound()
         if max_cycles <= 0 or (self.template.form & 0xff) not in (CLEAN_FORMS['auto'], CLEAN_FORMS['multi']):
+            return False
+        if self.buffer('mask') is not None:     # (the multi-component form has no masked kernels)
             return False
         dirty, psf = self.buffer('dirty'), self.buffer('psf')
         P, H, W = dirty.shape
@@ -618,12 +664,21 @@ class Clean(accel.OperationSequence):
                 str(self.command_queue.context.device))
 
 
+def _masked(clean):
+    """Does this :class:`Clean` have a mask bound?  (Its loop then runs on its own, in the
+    two-launch or one-launch form.)"""
+    slots = getattr(clean, 'slots', None)
+    return bool(slots) and 'mask' in slots and clean.buffer('mask') is not None
+
+
 def batch_supported(clean, psf_patch):
     """Can this patch take the one-launch-per-cycle form that :func:`run_cycles_batch` needs?
     (kimg_clean_cycles_batch: at most 32 x 32 lattice blocks, all of them plus one bookkeeping
     row resident at once.)"""
     bx = accel.divup(psf_patch[2], TILE) + 1
     by = accel.divup(psf_patch[1], TILE) + 1
+    if _masked(clean):
+        return False            # (the batch launch has no masked kernels)
     return bx <= 32 and by <= 32 and bx * (by + 1) <= 256
 
 
@@ -634,7 +689,7 @@ def multi_components(clean, psf_patch):
     bx = accel.divup(psf_patch[2], TILE) + 1
     by = accel.divup(psf_patch[1], TILE) + 1
     tiles = clean.buffer('tile_max').shape
-    if bx * by > 256 or max(tiles) > 2047 or tiles[0] * tiles[1] < 4:
+    if bx * by > 256 or max(tiles) > 2047 or tiles[0] * tiles[1] < 4 or _masked(clean):
         return 0
     seg = 16
     while seg < bx * by:

@@ -146,11 +146,15 @@ __device__ inline float clean_metric(const float *__restrict__ dirty, int64_t ad
 }
 
 // Scan tile (tx, ty): pixels [x0,x1) x [y0,y1); 256 threads, 4 pixels each in row-major order.
-template <int MODE>
+// MASKED: only pixels with a nonzero byte in `mask` (uint8 [height][width], one plane for all
+// polarizations, read with the row mapping of the dirty row) are candidates; a tile without any
+// records what an all-zero tile records.  Without MASKED the mask arguments are unused (null).
+template <int MODE, bool MASKED>
 __device__ inline void tile_peak(const float *__restrict__ dirty, int64_t row_stride,
                                  int64_t pol_stride, int width, int height, int P, int border,
                                  int tx, int ty, float *__restrict__ tile_max,
-                                 int32_t *__restrict__ tile_pos, int tiles_x)
+                                 int32_t *__restrict__ tile_pos, int tiles_x,
+                                 const uint8_t *__restrict__ mask, int64_t mask_row_stride)
 {
     const int x0 = tx * TILE + border, y0 = ty * TILE + border;
     best_t b = {0.0f, INT_MAX};
@@ -158,7 +162,8 @@ __device__ inline void tile_peak(const float *__restrict__ dirty, int64_t row_st
     for (int k = 0; k < 4; k++) {
         const int idx = threadIdx.x + k * 256;
         const int x = x0 + (idx & 31), y = y0 + (idx >> 5);
-        if (x < width - border && y < height - border) {
+        if (x < width - border && y < height - border
+            && (!MASKED || mask[(int64_t) y * mask_row_stride + x])) {
             float v = clean_metric<MODE>(dirty, (int64_t) y * row_stride + x, pol_stride, P);
             if (v > b.value) {
                 b.value = v;
@@ -186,8 +191,21 @@ __global__ __launch_bounds__(256) void update_tiles_kernel(
     int height, int P, int border, float *__restrict__ tile_max, int32_t *__restrict__ tile_pos,
     int tiles_x, int tile_x0, int tile_y0)
 {
-    tile_peak<MODE>(dirty, row_stride, pol_stride, width, height, P, border,
-                    tile_x0 + blockIdx.x, tile_y0 + blockIdx.y, tile_max, tile_pos, tiles_x);
+    tile_peak<MODE, false>(dirty, row_stride, pol_stride, width, height, P, border,
+                           tile_x0 + blockIdx.x, tile_y0 + blockIdx.y, tile_max, tile_pos, tiles_x,
+                           nullptr, 0);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void update_tiles_masked_kernel(
+    const float *__restrict__ dirty, int64_t row_stride, int64_t pol_stride, int width,
+    int height, int P, int border, float *__restrict__ tile_max, int32_t *__restrict__ tile_pos,
+    int tiles_x, int tile_x0, int tile_y0, const uint8_t *__restrict__ mask,
+    int64_t mask_row_stride)
+{
+    tile_peak<MODE, true>(dirty, row_stride, pol_stride, width, height, P, border,
+                          tile_x0 + blockIdx.x, tile_y0 + blockIdx.y, tile_max, tile_pos, tiles_x,
+                          mask, mask_row_stride);
 }
 
 // Global argmax over tiles, by a 1024-thread block; every thread returns the winning tile index
@@ -219,13 +237,25 @@ __device__ inline int peak_tile(const float *__restrict__ tile_max, int num_tile
     return best ? ~(int) (unsigned) best : -1;
 }
 
-__global__ __launch_bounds__(1024) void find_peak_kernel(
+// MASKED: a best metric of exactly 0 means that no allowed pixel is left to take (the winning
+// record would be the (x0, y0) start position of a tile without candidates, which may be a masked
+// pixel): the search ends, reported as position (-1, -1) with a zero pixel.
+template <bool MASKED>
+__device__ inline void find_peak(
     const float *__restrict__ dirty, int64_t row_stride, int64_t pol_stride, int P,
     const float *__restrict__ tile_max, const int32_t *__restrict__ tile_pos, int num_tiles,
     float *__restrict__ peak_value, int32_t *__restrict__ peak_pos, float *__restrict__ peak_pixel)
 {
     float value;
     int t = peak_tile(tile_max, num_tiles, value);
+    if (MASKED && threadIdx.x == 0 && t >= 0 && value == 0.0f) {
+        *peak_value = 0.0f;
+        peak_pos[0] = -1;
+        peak_pos[1] = -1;
+        for (int p = 0; p < P; p++)
+            peak_pixel[p] = 0.0f;
+        return;
+    }
     if (threadIdx.x == 0 && t >= 0) {
         const int y = tile_pos[2 * t], x = tile_pos[2 * t + 1];
         *peak_value = value;
@@ -234,6 +264,24 @@ __global__ __launch_bounds__(1024) void find_peak_kernel(
         for (int p = 0; p < P; p++)
             peak_pixel[p] = dirty[p * pol_stride + (int64_t) y * row_stride + x];
     }
+}
+
+__global__ __launch_bounds__(1024) void find_peak_kernel(
+    const float *__restrict__ dirty, int64_t row_stride, int64_t pol_stride, int P,
+    const float *__restrict__ tile_max, const int32_t *__restrict__ tile_pos, int num_tiles,
+    float *__restrict__ peak_value, int32_t *__restrict__ peak_pos, float *__restrict__ peak_pixel)
+{
+    find_peak<false>(dirty, row_stride, pol_stride, P, tile_max, tile_pos, num_tiles, peak_value,
+                     peak_pos, peak_pixel);
+}
+
+__global__ __launch_bounds__(1024) void find_peak_masked_kernel(
+    const float *__restrict__ dirty, int64_t row_stride, int64_t pol_stride, int P,
+    const float *__restrict__ tile_max, const int32_t *__restrict__ tile_pos, int num_tiles,
+    float *__restrict__ peak_value, int32_t *__restrict__ peak_pos, float *__restrict__ peak_pixel)
+{
+    find_peak<true>(dirty, row_stride, pol_stride, P, tile_max, tile_pos, num_tiles, peak_value,
+                    peak_pos, peak_pixel);
 }
 
 struct pixel_t { float v[4]; };
@@ -278,8 +326,9 @@ struct clean_state {
     float scale[4];     // loop_gain * pixel at the current peak
 };
 
-template <int MODE>
-__global__ __launch_bounds__(1024) void cycle_find_peak_kernel(
+// MASKED: a best metric of exactly 0 ends the loop whatever the threshold (see find_peak).
+template <bool MASKED>
+__device__ __attribute__((always_inline)) inline void cycle_find_peak(
     const float *__restrict__ dirty, float *__restrict__ model, int64_t row_stride,
     int64_t pol_stride, int P, const float *__restrict__ tile_max,
     const int32_t *__restrict__ tile_pos, int num_tiles, float loop_gain,
@@ -296,7 +345,7 @@ __global__ __launch_bounds__(1024) void cycle_find_peak_kernel(
     const int p = threadIdx.x;          // one thread per polarization from here on
     if (p >= P || done)
         return;
-    if (t < 0 || value < threshold || count >= limit) {   // clean.py:1065-1066
+    if (t < 0 || value < threshold || count >= limit || (MASKED && value == 0.0f)) {   // clean.py:1065-1066
         if (p == 0)
             state->done = 1;
         return;
@@ -320,9 +369,33 @@ __global__ __launch_bounds__(1024) void cycle_find_peak_kernel(
     }
 }
 
+template <int MODE>
+__global__ __launch_bounds__(1024) void cycle_find_peak_kernel(
+    const float *__restrict__ dirty, float *__restrict__ model, int64_t row_stride,
+    int64_t pol_stride, int P, const float *__restrict__ tile_max,
+    const int32_t *__restrict__ tile_pos, int num_tiles, float loop_gain,
+    clean_state *__restrict__ state, float *__restrict__ log)
+{
+    cycle_find_peak<false>(dirty, model, row_stride, pol_stride, P, tile_max, tile_pos, num_tiles,
+                           loop_gain, state, log);
+}
+
+// (does not depend on the mode: one instantiation serves both)
+__global__ __launch_bounds__(1024) void cycle_find_peak_masked_kernel(
+    const float *__restrict__ dirty, float *__restrict__ model, int64_t row_stride,
+    int64_t pol_stride, int P, const float *__restrict__ tile_max,
+    const int32_t *__restrict__ tile_pos, int num_tiles, float loop_gain,
+    clean_state *__restrict__ state, float *__restrict__ log)
+{
+    cycle_find_peak<true>(dirty, model, row_stride, pol_stride, P, tile_max, tile_pos, num_tiles,
+                          loop_gain, state, log);
+}
+
 // One workgroup per 32x32 block of the tile lattice that the PSF patch can touch: subtract
 // the scaled PSF from the block's pixels that lie in the patch, then (if the block is a real
 // tile) rescan the tile.  Fuses _subtract_psf + _update_tile of clean.py:1067-1074.
+// MASKED form: the subtraction is the same (masked pixels included); only allowed pixels are
+// candidates of the rescan (see tile_peak).
 template <int MODE>
 __global__ __launch_bounds__(256) void cycle_subtract_update_kernel(
     float *__restrict__ dirty, int64_t row_stride, int64_t pol_stride, int width, int height,
@@ -331,81 +404,27 @@ __global__ __launch_bounds__(256) void cycle_subtract_update_kernel(
     float *__restrict__ tile_max, int32_t *__restrict__ tile_pos, int tiles_x, int tiles_y,
     const clean_state *__restrict__ state)
 {
-    // one round trip for all the state words (they share a cache line)
-    const int4 st = *reinterpret_cast<const int4 *>(state);    // count, done, limit, threshold
-    const int2 pos = *reinterpret_cast<const int2 *>(&state->pos_y);
-    const int done = st.y, py = pos.x, px = pos.y;
-    const float4 sc = *reinterpret_cast<const float4 *>(state->scale);
-    const float scale[4] = {sc.x, sc.y, sc.z, sc.w};
-    if (done)
-        return;
-    const int x0 = px - patch_w / 2, y0 = py - patch_h / 2;      // clean.py:1024-1027
-    // floor division: the lattice extends into the border with negative indices
-    const int bx0 = (x0 - border) >= 0 ? (x0 - border) / TILE : -((border - x0 + TILE - 1) / TILE);
-    const int by0 = (y0 - border) >= 0 ? (y0 - border) / TILE : -((border - y0 + TILE - 1) / TILE);
-    const int tx = bx0 + (int) blockIdx.x, ty = by0 + (int) blockIdx.y;
-    const int ox = tx * TILE + border, oy = ty * TILE + border;
-    const int psf_dx = psf_w / 2 - px, psf_dy = psf_h / 2 - py;  // psf index = image index + d
-    const bool is_tile = tx >= 0 && tx < tiles_x && ty >= 0 && ty < tiles_y;
+#define KIMG_LOAD_ALLOWED(y, x)
+#define KIMG_AND_ALLOWED(y, x)
+#include "clean_subtract_update.inc"
+#undef KIMG_LOAD_ALLOWED
+#undef KIMG_AND_ALLOWED
+}
 
-    best_t b = {0.0f, INT_MAX};
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int idx = threadIdx.x + k * 256;
-        const int x = ox + (idx & 31), y = oy + (idx >> 5);
-        if (x < 0 || x >= width || y < 0 || y >= height)
-            continue;
-        const int64_t ia = (int64_t) y * row_stride + x;
-        const bool in_patch = x >= x0 && x < x0 + patch_w && y >= y0 && y < y0 + patch_h;
-        const bool in_tile = is_tile && x < width - border && y < height - border;
-        float metric = 0.0f;
-        if (MODE == KIMG_CLEAN_I) {
-            float d = dirty[ia];
-            if (in_patch) {
-                const float t = scale[0] * psf[(int64_t) (y + psf_dy) * psf_row_stride + (x + psf_dx)];
-                d -= t;
-                dirty[ia] = d;
-                for (int p = 1; p < P; p++) {
-                    const float tp = scale[p] * psf[p * psf_pol_stride
-                                                    + (int64_t) (y + psf_dy) * psf_row_stride + (x + psf_dx)];
-                    dirty[p * pol_stride + ia] -= tp;
-                }
-            }
-            metric = fabsf(d);
-        } else {
-            for (int p = 0; p < P; p++) {
-                float d = dirty[p * pol_stride + ia];
-                if (in_patch) {
-                    const float t = scale[p] * psf[p * psf_pol_stride
-                                                   + (int64_t) (y + psf_dy) * psf_row_stride + (x + psf_dx)];
-                    d -= t;
-                    dirty[p * pol_stride + ia] = d;
-                }
-                metric += d * d;
-            }
-        }
-        if (in_tile && metric > b.value) {
-            b.value = metric;
-            b.idx = idx;
-        }
-    }
-    if (!is_tile)
-        return;
-    __shared__ key_t s_keys[16];
-    const key_t kb = block_max_key(b.idx == INT_MAX ? 0 : make_key(b.value, b.idx), s_keys);
-    if (threadIdx.x == 0) {
-        const int t = ty * tiles_x + tx;
-        if (kb == 0) {                      // clean.py:950 best_pos = (x0, y0), value 0
-            tile_max[t] = 0.0f;
-            tile_pos[2 * t] = ox;
-            tile_pos[2 * t + 1] = oy;
-        } else {
-            const int idx = ~(int) (unsigned) kb;
-            tile_max[t] = __uint_as_float((unsigned) (kb >> 32));
-            tile_pos[2 * t] = oy + (idx >> 5);
-            tile_pos[2 * t + 1] = ox + (idx & 31);
-        }
-    }
+template <int MODE>
+__global__ __launch_bounds__(256) void cycle_subtract_update_masked_kernel(
+    float *__restrict__ dirty, int64_t row_stride, int64_t pol_stride, int width, int height,
+    int P, const float *__restrict__ psf, int64_t psf_row_stride, int64_t psf_pol_stride,
+    int psf_w, int psf_h, int patch_w, int patch_h, int border,
+    float *__restrict__ tile_max, int32_t *__restrict__ tile_pos, int tiles_x, int tiles_y,
+    const clean_state *__restrict__ state, const uint8_t *__restrict__ mask,
+    int64_t mask_row_stride)
+{
+#define KIMG_LOAD_ALLOWED(y, x) const bool allowed = mask[(int64_t) (y) * mask_row_stride + (x)] != 0;
+#define KIMG_AND_ALLOWED(y, x) && allowed
+#include "clean_subtract_update.inc"
+#undef KIMG_LOAD_ALLOWED
+#undef KIMG_AND_ALLOWED
 }
 
 // ---- one launch per minor cycle ----------------------------------------------------------
@@ -630,13 +649,17 @@ constexpr int ROLE_LATTICE = 0, ROLE_KEEPER = 1, ROLE_FOLDER = 2;
 // The cycle of one channel, executed by the workgroup that serves lattice block (blk_x, blk_y) of
 // its PSF patch, or by one of the channel's two bookkeeping workgroups.  Two kernels call it: one
 // channel per launch (cycle_fused_kernel) and several channels per launch (cycle_fused_batch_kernel).
-template <int MODE>
+// MASKED (one channel per launch only): candidates of the rescan are the allowed pixels, and a best
+// metric of exactly 0 ends the loop whatever the threshold -- every workgroup of the launch finds
+// that out for itself, like the threshold test.
+template <int MODE, bool MASKED>
 __device__ __attribute__((always_inline)) inline void fused_cycle(
     float *dirty, float *model, int64_t row_stride, int64_t pol_stride, int width, int height,
     int P, const float *__restrict__ psf, int64_t psf_row_stride, int64_t psf_pol_stride,
     int psf_w, int psf_h, int patch_w, int patch_h, int border, float *tile_max,
     int32_t *tile_pos, int tiles_x, int tiles_y, float loop_gain,
-    fused_scratch *scratch, int parity, float *log, int blk_x, int blk_y, int role)
+    fused_scratch *scratch, int parity, float *log, int blk_x, int blk_y, int role,
+    const uint8_t *__restrict__ mask, int64_t mask_row_stride)
 {
     __shared__ key_t s_keys[16];
     __shared__ int s_pos[2];
@@ -728,7 +751,7 @@ __device__ __attribute__((always_inline)) inline void fused_cycle(
     STAMP(2);
     KSTAMP(2);
     const float value = __uint_as_float((unsigned) (best >> 32));
-    if (best == 0 || value < threshold || count >= limit) {     // clean.py:1065-1066
+    if (best == 0 || value < threshold || count >= limit || (MASKED && value == 0.0f)) {     // clean.py:1065-1066
         if (keeper && tid == 0)
             *reinterpret_cast<int4 *>(next) = make_int4(count, 1, limit, st.w);
         return;
@@ -860,8 +883,12 @@ __device__ __attribute__((always_inline)) inline void fused_cycle(
     const bool inside = x >= 0 && x < width && y >= 0 && y < height;
     const int64_t ia = (int64_t) y * row_stride + x;
     const bool in_patch = inside && x >= x0 && x < x0 + patch_w && y >= y0 && y < y0 + patch_h;
-    const bool in_tile = inside && is_tile && x < width - border && y < height - border;
+    bool in_tile = inside && is_tile && x < width - border && y < height - border;
     float dv[4] = {0.0f, 0.0f, 0.0f, 0.0f}, pv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    // (the mask byte travels with the pixel loads: no round trip of its own)
+    uint8_t allowed = 1;
+    if (MASKED && in_tile)
+        allowed = mask[(int64_t) y * mask_row_stride + x];
     if (inside)
         for (int p = 0; p < P; p++)
             dv[p] = dirty[p * pol_stride + ia];
@@ -889,6 +916,8 @@ __device__ __attribute__((always_inline)) inline void fused_cycle(
     }
     if (!is_tile)
         return;
+    if (MASKED)
+        in_tile = in_tile && allowed;
     // first strict maximum in row-major order; only positive metrics count (clean.py:953-958)
     const key_t tb = block_max_key((in_tile && metric > 0.0f) ? make_key(metric, tid) : 0, s_keys);
     const int widx = ~(int) (unsigned) tb;
@@ -941,10 +970,32 @@ __global__ __launch_bounds__(1024) void cycle_fused_kernel(
             return;
         role = blockIdx.x == 0 ? ROLE_KEEPER : ROLE_FOLDER;
     }
-    fused_cycle<MODE>(dirty, model, row_stride, pol_stride, width, height, P, psf, psf_row_stride,
-                      psf_pol_stride, psf_w, psf_h, patch_w, patch_h, border, tile_max, tile_pos,
-                      tiles_x, tiles_y, loop_gain, scratch, parity, log, (int) blockIdx.x,
-                      (int) blockIdx.y - 1, role);
+    fused_cycle<MODE, false>(dirty, model, row_stride, pol_stride, width, height, P, psf,
+                             psf_row_stride, psf_pol_stride, psf_w, psf_h, patch_w, patch_h, border,
+                             tile_max, tile_pos, tiles_x, tiles_y, loop_gain, scratch, parity, log,
+                             (int) blockIdx.x, (int) blockIdx.y - 1, role, nullptr, 0);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(1024) void cycle_fused_masked_kernel(
+    float *dirty, float *model, int64_t row_stride, int64_t pol_stride, int width, int height,
+    int P, const float *__restrict__ psf, int64_t psf_row_stride, int64_t psf_pol_stride,
+    int psf_w, int psf_h, int patch_w, int patch_h, int border, float *tile_max,
+    int32_t *tile_pos, int tiles_x, int tiles_y, float loop_gain,
+    fused_scratch *scratch, int parity, float *log, const uint8_t *__restrict__ mask,
+    int64_t mask_row_stride)
+{
+    // (the grid of cycle_fused_kernel)
+    int role = ROLE_LATTICE;
+    if (blockIdx.y == 0) {
+        if (blockIdx.x > 1)
+            return;
+        role = blockIdx.x == 0 ? ROLE_KEEPER : ROLE_FOLDER;
+    }
+    fused_cycle<MODE, true>(dirty, model, row_stride, pol_stride, width, height, P, psf,
+                            psf_row_stride, psf_pol_stride, psf_w, psf_h, patch_w, patch_h, border,
+                            tile_max, tile_pos, tiles_x, tiles_y, loop_gain, scratch, parity, log,
+                            (int) blockIdx.x, (int) blockIdx.y - 1, role, mask, mask_row_stride);
 }
 
 // ---- several channels per launch -------------------------------------------------------------
@@ -989,10 +1040,10 @@ __global__ __launch_bounds__(1024) void cycle_fused_batch_kernel(
         blk_x -= bx;
         blk_y++;
     }
-    fused_cycle<MODE>(ch.dirty, ch.model, row_stride, pol_stride, width, height, P, ch.psf,
-                      psf_row_stride, psf_pol_stride, psf_w, psf_h, ch.patch_w, ch.patch_h, border,
-                      ch.tile_max, ch.tile_pos, tiles_x, tiles_y, loop_gain, ch.scratch, parity,
-                      ch.log, blk_x, blk_y, role);
+    fused_cycle<MODE, false>(ch.dirty, ch.model, row_stride, pol_stride, width, height, P, ch.psf,
+                             psf_row_stride, psf_pol_stride, psf_w, psf_h, ch.patch_w, ch.patch_h,
+                             border, ch.tile_max, ch.tile_pos, tiles_x, tiles_y, loop_gain,
+                             ch.scratch, parity, ch.log, blk_x, blk_y, role, nullptr, 0);
 }
 
 // ---- the whole minor-cycle loop in ONE launch ----------------------------------------------
@@ -2003,19 +2054,34 @@ dim3 region_grid(int width, int height, int max_blocks = 2048)
 
 } // namespace
 
-extern "C" int kimg_update_tiles(const float *dirty, int64_t row_stride, int64_t pol_stride,
-                                 int width, int height, int num_polarizations, int border,
-                                 int mode, float *tile_max, int32_t *tile_pos, int tiles_x,
-                                 int tiles_y, int tile_x0, int tile_y0, int tile_x1, int tile_y1,
-                                 void *stream)
+// kimg_update_tiles and kimg_update_tiles_masked (mask null: unmasked)
+static int update_tiles(const float *dirty, int64_t row_stride, int64_t pol_stride,
+                        int width, int height, int num_polarizations, int border,
+                        int mode, float *tile_max, int32_t *tile_pos, int tiles_x,
+                        int tiles_y, int tile_x0, int tile_y0, int tile_x1, int tile_y1,
+                        const uint8_t *mask, int64_t mask_row_stride, void *stream)
 {
     KIMG_CHECK_ARG(dirty && tile_max && tile_pos && width > 0 && height > 0);
     KIMG_CHECK_ARG(num_polarizations >= 1 && num_polarizations <= 4 && border >= 0);
     KIMG_CHECK_ARG(tile_x0 >= 0 && tile_y0 >= 0 && tile_x1 <= tiles_x && tile_y1 <= tiles_y);
     if (tile_x0 >= tile_x1 || tile_y0 >= tile_y1)
         return 0;                                           // clean.py:462
+    KIMG_CHECK_ARG(mask == nullptr || mask_row_stride >= width);
     dim3 g(tile_x1 - tile_x0, tile_y1 - tile_y0);
     hipStream_t s = (hipStream_t) stream;
+    if (mask != nullptr) {
+        if (mode == KIMG_CLEAN_I)
+            update_tiles_masked_kernel<KIMG_CLEAN_I><<<g, 256, 0, s>>>(
+                dirty, row_stride, pol_stride, width, height, num_polarizations, border, tile_max,
+                tile_pos, tiles_x, tile_x0, tile_y0, mask, mask_row_stride);
+        else if (mode == KIMG_CLEAN_SUMSQ)
+            update_tiles_masked_kernel<KIMG_CLEAN_SUMSQ><<<g, 256, 0, s>>>(
+                dirty, row_stride, pol_stride, width, height, num_polarizations, border, tile_max,
+                tile_pos, tiles_x, tile_x0, tile_y0, mask, mask_row_stride);
+        else
+            return KIMG_EINVAL;
+        return kimg_launch_status();
+    }
     if (mode == KIMG_CLEAN_I)
         update_tiles_kernel<KIMG_CLEAN_I><<<g, 256, 0, s>>>(
             dirty, row_stride, pol_stride, width, height, num_polarizations, border, tile_max,
@@ -2029,18 +2095,68 @@ extern "C" int kimg_update_tiles(const float *dirty, int64_t row_stride, int64_t
     return kimg_launch_status();
 }
 
+extern "C" int kimg_update_tiles(const float *dirty, int64_t row_stride, int64_t pol_stride,
+                                 int width, int height, int num_polarizations, int border,
+                                 int mode, float *tile_max, int32_t *tile_pos, int tiles_x,
+                                 int tiles_y, int tile_x0, int tile_y0, int tile_x1, int tile_y1,
+                                 void *stream)
+{
+    return update_tiles(dirty, row_stride, pol_stride, width, height, num_polarizations, border, mode,
+                        tile_max, tile_pos, tiles_x, tiles_y, tile_x0, tile_y0, tile_x1, tile_y1,
+                        nullptr, 0, stream);
+}
+
+extern "C" int kimg_update_tiles_masked(const float *dirty, int64_t row_stride, int64_t pol_stride,
+                                        int width, int height, int num_polarizations, int border,
+                                        int mode, float *tile_max, int32_t *tile_pos, int tiles_x,
+                                        int tiles_y, int tile_x0, int tile_y0, int tile_x1,
+                                        int tile_y1, void *stream, const uint8_t *mask,
+                                        int64_t mask_row_stride)
+{
+    return update_tiles(dirty, row_stride, pol_stride, width, height, num_polarizations, border, mode,
+                        tile_max, tile_pos, tiles_x, tiles_y, tile_x0, tile_y0, tile_x1, tile_y1,
+                        mask, mask_row_stride, stream);
+}
+
+// kimg_find_peak and kimg_find_peak_masked (mask null: unmasked)
+static int find_peak_call(const float *dirty, int64_t row_stride, int64_t pol_stride,
+                          int num_polarizations, const float *tile_max,
+                          const int32_t *tile_pos, int tiles_x, int tiles_y,
+                          float *peak_value, int32_t *peak_pos, float *peak_pixel,
+                          const uint8_t *mask, void *stream)
+{
+    KIMG_CHECK_ARG(dirty && tile_max && tile_pos && peak_value && peak_pos && peak_pixel);
+    KIMG_CHECK_ARG(tiles_x > 0 && tiles_y > 0 && num_polarizations >= 1);
+    if (mask != nullptr)
+        find_peak_masked_kernel<<<1, 1024, 0, (hipStream_t) stream>>>(
+            dirty, row_stride, pol_stride, num_polarizations, tile_max, tile_pos, tiles_x * tiles_y,
+            peak_value, peak_pos, peak_pixel);
+    else
+        find_peak_kernel<<<1, 1024, 0, (hipStream_t) stream>>>(
+            dirty, row_stride, pol_stride, num_polarizations, tile_max, tile_pos, tiles_x * tiles_y,
+            peak_value, peak_pos, peak_pixel);
+    return kimg_launch_status();
+}
+
 extern "C" int kimg_find_peak(const float *dirty, int64_t row_stride, int64_t pol_stride,
                               int num_polarizations, const float *tile_max,
                               const int32_t *tile_pos, int tiles_x, int tiles_y,
                               float *peak_value, int32_t *peak_pos, float *peak_pixel,
                               void *stream)
 {
-    KIMG_CHECK_ARG(dirty && tile_max && tile_pos && peak_value && peak_pos && peak_pixel);
-    KIMG_CHECK_ARG(tiles_x > 0 && tiles_y > 0 && num_polarizations >= 1);
-    find_peak_kernel<<<1, 1024, 0, (hipStream_t) stream>>>(
-        dirty, row_stride, pol_stride, num_polarizations, tile_max, tile_pos, tiles_x * tiles_y,
-        peak_value, peak_pos, peak_pixel);
-    return kimg_launch_status();
+    return find_peak_call(dirty, row_stride, pol_stride, num_polarizations, tile_max, tile_pos, tiles_x,
+                          tiles_y, peak_value, peak_pos, peak_pixel, nullptr, stream);
+}
+
+extern "C" int kimg_find_peak_masked(const float *dirty, int64_t row_stride, int64_t pol_stride,
+                                     int num_polarizations, const float *tile_max,
+                                     const int32_t *tile_pos, int tiles_x, int tiles_y,
+                                     float *peak_value, int32_t *peak_pos, float *peak_pixel,
+                                     void *stream, const uint8_t *mask, int64_t mask_row_stride)
+{
+    (void) mask_row_stride;     // (the peak step needs to know THAT a mask is bound, not its bytes)
+    return find_peak_call(dirty, row_stride, pol_stride, num_polarizations, tile_max, tile_pos, tiles_x,
+                          tiles_y, peak_value, peak_pos, peak_pixel, mask, stream);
 }
 
 extern "C" int kimg_subtract_psf(float *dirty, float *model, int64_t row_stride,
@@ -2105,6 +2221,8 @@ struct cycle_args {
     int tiles_x, tiles_y;
     clean_state *state;
     float *log;
+    const uint8_t *mask;    // null: unmasked (never set for a batch)
+    int64_t mask_row_stride;
     int fused;              // one launch per cycle (state is then a fused_scratch)
     int batch;              // > 0: that many channels per launch, described by `tab` (the fields
                             // dirty .. log, patch_width / patch_height above are then unused)
@@ -2134,6 +2252,21 @@ int enqueue_cycle(const cycle_args &a, hipStream_t s, int index)
     if (a.fused) {
         fused_scratch *fs = reinterpret_cast<fused_scratch *>(a.state);
         g.y += 1;               // the bookkeeping workgroup's row
+        if (a.mask != nullptr) {
+            if (a.mode == KIMG_CLEAN_I)
+                cycle_fused_masked_kernel<KIMG_CLEAN_I><<<g, 1024, 0, s>>>(
+                    a.dirty, a.model, a.row_stride, a.pol_stride, a.width, a.height, a.P, a.psf,
+                    a.psf_row_stride, a.psf_pol_stride, a.psf_width, a.psf_height, a.patch_width,
+                    a.patch_height, a.border, a.tile_max, a.tile_pos, a.tiles_x, a.tiles_y,
+                    a.loop_gain, fs, index & 1, a.log, a.mask, a.mask_row_stride);
+            else
+                cycle_fused_masked_kernel<KIMG_CLEAN_SUMSQ><<<g, 1024, 0, s>>>(
+                    a.dirty, a.model, a.row_stride, a.pol_stride, a.width, a.height, a.P, a.psf,
+                    a.psf_row_stride, a.psf_pol_stride, a.psf_width, a.psf_height, a.patch_width,
+                    a.patch_height, a.border, a.tile_max, a.tile_pos, a.tiles_x, a.tiles_y,
+                    a.loop_gain, fs, index & 1, a.log, a.mask, a.mask_row_stride);
+            return kimg_launch_status();
+        }
         if (a.mode == KIMG_CLEAN_I)
             cycle_fused_kernel<KIMG_CLEAN_I><<<g, 1024, 0, s>>>(
                 a.dirty, a.model, a.row_stride, a.pol_stride, a.width, a.height, a.P, a.psf,
@@ -2146,6 +2279,22 @@ int enqueue_cycle(const cycle_args &a, hipStream_t s, int index)
                 a.psf_row_stride, a.psf_pol_stride, a.psf_width, a.psf_height, a.patch_width,
                 a.patch_height, a.border, a.tile_max, a.tile_pos, a.tiles_x, a.tiles_y,
                 a.loop_gain, fs, index & 1, a.log);
+        return kimg_launch_status();
+    }
+    if (a.mask != nullptr) {
+        cycle_find_peak_masked_kernel<<<1, 1024, 0, s>>>(
+            a.dirty, a.model, a.row_stride, a.pol_stride, a.P, a.tile_max, a.tile_pos, num_tiles,
+            a.loop_gain, a.state, a.log);
+        if (a.mode == KIMG_CLEAN_I)
+            cycle_subtract_update_masked_kernel<KIMG_CLEAN_I><<<g, 256, 0, s>>>(
+                a.dirty, a.row_stride, a.pol_stride, a.width, a.height, a.P, a.psf, a.psf_row_stride,
+                a.psf_pol_stride, a.psf_width, a.psf_height, a.patch_width, a.patch_height, a.border,
+                a.tile_max, a.tile_pos, a.tiles_x, a.tiles_y, a.state, a.mask, a.mask_row_stride);
+        else
+            cycle_subtract_update_masked_kernel<KIMG_CLEAN_SUMSQ><<<g, 256, 0, s>>>(
+                a.dirty, a.row_stride, a.pol_stride, a.width, a.height, a.P, a.psf, a.psf_row_stride,
+                a.psf_pol_stride, a.psf_width, a.psf_height, a.patch_width, a.patch_height, a.border,
+                a.tile_max, a.tile_pos, a.tiles_x, a.tiles_y, a.state, a.mask, a.mask_row_stride);
         return kimg_launch_status();
     }
     if (a.mode == KIMG_CLEAN_I) {
@@ -2297,13 +2446,15 @@ extern "C" int kimg_clean_major_cycles(float *dirty, float *model, int64_t row_s
                                 first_peak);
 }
 
-extern "C" int kimg_clean_cycles(float *dirty, float *model, int64_t row_stride,
-                                 int64_t pol_stride, int width, int height, int num_polarizations,
-                                 const float *psf, int64_t psf_row_stride, int64_t psf_pol_stride,
-                                 int psf_width, int psf_height, int patch_width, int patch_height,
-                                 int border, int mode, float loop_gain, float threshold,
-                                 float *tile_max, int32_t *tile_pos, int tiles_x, int tiles_y,
-                                 int max_cycles, int form, void *state, float *log, void *stream)
+// kimg_clean_cycles and kimg_clean_cycles_masked (mask null: unmasked)
+static int clean_cycles(float *dirty, float *model, int64_t row_stride,
+                        int64_t pol_stride, int width, int height, int num_polarizations,
+                        const float *psf, int64_t psf_row_stride, int64_t psf_pol_stride,
+                        int psf_width, int psf_height, int patch_width, int patch_height,
+                        int border, int mode, float loop_gain, float threshold,
+                        float *tile_max, int32_t *tile_pos, int tiles_x, int tiles_y,
+                        int max_cycles, int form, void *state, float *log, void *stream,
+                        const uint8_t *mask, int64_t mask_row_stride)
 {
     KIMG_CHECK_ARG(dirty && model && psf && tile_max && tile_pos && state && log);
     KIMG_CHECK_ARG(num_polarizations >= 1 && num_polarizations <= 4 && max_cycles >= 0);
@@ -2318,10 +2469,16 @@ extern "C" int kimg_clean_cycles(float *dirty, float *model, int64_t row_stride,
     KIMG_CHECK_ARG(form == KIMG_CLEAN_FORM_AUTO || form == KIMG_CLEAN_FORM_TWO_LAUNCH
                    || form == KIMG_CLEAN_FORM_ONE_LAUNCH || form == KIMG_CLEAN_FORM_PERSISTENT
                    || form == KIMG_CLEAN_FORM_ONE_WORKGROUP || form == KIMG_CLEAN_FORM_MULTI);
+    const bool masked = mask != nullptr;
+    KIMG_CHECK_ARG(!masked || mask_row_stride >= width);
+    // with a mask: two launches or one launch per cycle only (before anything is enqueued)
+    if (masked && (form == KIMG_CLEAN_FORM_MULTI || form == KIMG_CLEAN_FORM_PERSISTENT
+                   || form == KIMG_CLEAN_FORM_ONE_WORKGROUP))
+        return KIMG_EUNSUPPORTED;
     hipStream_t s = (hipStream_t) stream;
     // several components per launch where the patch leaves room for at least two lattices among
     // the 256 records of a launch (a call of a few cycles is not worth the host-paced loop)
-    {
+    if (!masked) {
         const int m = kimg_clean_multi_components(patch_width, patch_height, tiles_x, tiles_y);
         if (max_cycles > 0 && (form == KIMG_CLEAN_FORM_MULTI ? m >= 1
                                                              : form == KIMG_CLEAN_FORM_AUTO && m >= 2
@@ -2347,7 +2504,7 @@ extern "C" int kimg_clean_cycles(float *dirty, float *model, int64_t row_stride,
     // patch fit LDS
     const size_t solo_lds = (((size_t) tiles_x * tiles_y * 6 + 15) & ~(size_t) 15)
                             + (size_t) (patch_width + 2 * SOLO_PAD) * patch_height * sizeof(float);
-    const bool solo_ok = num_polarizations == 1 && bx <= SOLO_MAX_BX && by <= 32
+    const bool solo_ok = !masked && num_polarizations == 1 && bx <= SOLO_MAX_BX && by <= 32
                          && bx * by <= SOLO_MAX_BLOCKS
                          && (uint64_t) height * (uint64_t) row_stride < (1u << 30)
                          && solo_lds <= SOLO_LDS_LIMIT && max_cycles > 0;
@@ -2421,6 +2578,7 @@ extern "C" int kimg_clean_cycles(float *dirty, float *model, int64_t row_stride,
     a.patch_height = patch_height; a.border = border; a.mode = mode; a.loop_gain = loop_gain;
     a.tile_max = tile_max; a.tile_pos = tile_pos; a.tiles_x = tiles_x;
     a.tiles_y = tiles_y; a.state = static_cast<clean_state *>(state); a.log = log;
+    a.mask = mask; a.mask_row_stride = masked ? mask_row_stride : 0;
     a.fused = fused;
     int done = 0;
     if (max_cycles >= GRAPH_CYCLES / 2) {
@@ -2446,6 +2604,36 @@ extern "C" int kimg_clean_cycles(float *dirty, float *model, int64_t row_stride,
         apply_deltas_kernel<<<1, 1024, 0, s>>>(static_cast<fused_scratch *>(state), tile_max,
                                                tile_pos);
     return kimg_launch_status();
+}
+
+extern "C" int kimg_clean_cycles(float *dirty, float *model, int64_t row_stride,
+                                 int64_t pol_stride, int width, int height, int num_polarizations,
+                                 const float *psf, int64_t psf_row_stride, int64_t psf_pol_stride,
+                                 int psf_width, int psf_height, int patch_width, int patch_height,
+                                 int border, int mode, float loop_gain, float threshold,
+                                 float *tile_max, int32_t *tile_pos, int tiles_x, int tiles_y,
+                                 int max_cycles, int form, void *state, float *log, void *stream)
+{
+    return clean_cycles(dirty, model, row_stride, pol_stride, width, height, num_polarizations, psf,
+                        psf_row_stride, psf_pol_stride, psf_width, psf_height, patch_width,
+                        patch_height, border, mode, loop_gain, threshold, tile_max, tile_pos, tiles_x,
+                        tiles_y, max_cycles, form, state, log, stream, nullptr, 0);
+}
+
+extern "C" int kimg_clean_cycles_masked(float *dirty, float *model, int64_t row_stride,
+                                        int64_t pol_stride, int width, int height,
+                                        int num_polarizations, const float *psf,
+                                        int64_t psf_row_stride, int64_t psf_pol_stride, int psf_width,
+                                        int psf_height, int patch_width, int patch_height, int border,
+                                        int mode, float loop_gain, float threshold, float *tile_max,
+                                        int32_t *tile_pos, int tiles_x, int tiles_y, int max_cycles,
+                                        int form, void *state, float *log, void *stream,
+                                        const uint8_t *mask, int64_t mask_row_stride)
+{
+    return clean_cycles(dirty, model, row_stride, pol_stride, width, height, num_polarizations, psf,
+                        psf_row_stride, psf_pol_stride, psf_width, psf_height, patch_width,
+                        patch_height, border, mode, loop_gain, threshold, tile_max, tile_pos, tiles_x,
+                        tiles_y, max_cycles, form, state, log, stream, mask, mask_row_stride);
 }
 
 extern "C" int kimg_clean_cycles_batch(const kimg_clean_channel *channels_in, int num_channels,

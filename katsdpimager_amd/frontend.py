@@ -78,7 +78,7 @@ def slice_mid_w(image_p, grid_p):
 
 def process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type,
                     vis_block, major, degrid, subtract_model=False, batched_clean=True,
-                    fit_beam=False, clean_batcher=None):
+                    fit_beam=False, clean_batcher=None, clean_mask=None):
     """The loop of frontend.process_channel (frontend.py:497-585) from "Compute imaging
     weights" to the end of the last major cycle.
 
@@ -94,10 +94,25 @@ def process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p, weigh
     (no host round trip per cycle); the result is identical to the per-cycle loop.
     ``clean_batcher`` (:class:`clean.CleanBatcher`, set by :func:`process_channels`) lets those
     cycles share their launches with the other channels in flight.
+
+    ``clean_mask`` (``Imaging.set_clean_mask``: a host bool / uint8 array of image shape or a device
+    array; nonzero = a component may be placed on the pixel) restricts the components of THIS call
+    to the allowed pixels; the imager gets back afterwards whatever mask it had.  The minor cycles
+    then run per channel (no one-call major cycles, no shared launches).  None (the default) leaves
+    everything as it is, a mask set on the imager beforehand included.
     """
     if not any(reader.len(rel_channel, s) for s in range(reader.num_w_slices(rel_channel))):
         return None
     _check_imager_parameters(imager, image_p, grid_p)
+    if clean_mask is not None:
+        before = imager.clean_mask
+        imager.set_clean_mask(clean_mask)
+        try:
+            return process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p,
+                                   weight_type, vis_block, major, degrid, subtract_model,
+                                   batched_clean, fit_beam, clean_batcher)
+        finally:
+            imager.set_clean_mask(before)
     import contextlib
     if clean_batcher is not None and getattr(clean_batcher, 'phased', False):
         try:
@@ -227,6 +242,8 @@ def _process_channel_stages(reader, rel_channel, imager, image_p, grid_p, clean_
             with trace.range('first_cycle'):
                 imager.clean_reset()
                 peak_value = imager.clean_cycle(psf_patch)
+        if peak_value is None:
+            break       # (only under a CLEAN mask: no allowed pixel with a metric above 0 is left)
         out['peaks'].append(peak_value)
         peak_power = clean.metric_to_power(clean_p.mode, peak_value)
         mgain_threshold = (1.0 - clean_p.major_gain) * peak_power

@@ -689,6 +689,37 @@ class Imaging(accel.OperationSequence):
         return self._noise_est()
 
     @_serial
+    def set_clean_mask(self, mask):
+        """Restrict the CLEAN components to the allowed pixels of ``mask`` (clean windows;
+        include/kimg.h, "CLEAN masks"): a host bool / uint8 array of shape (height, width) -- one
+        plane for all polarizations, nonzero = allowed --, a device uint8 array of that shape, or
+        None to clear.  The tile records kept from before do not know about it: it takes effect with
+        the next :meth:`clean_reset` (which ``frontend.process_channel`` calls at the start of every
+        major cycle).  With a mask the minor cycles run per channel in the two-launch or one-launch
+        form (:meth:`clean_major_cycles` returns None, a ``batcher`` runs the channel on its own)."""
+        self._ready()
+        if mask is None:
+            self._clean.bind(mask=None)
+            return
+        shape = self.buffer('dirty').shape[1:]
+        if isinstance(mask, accel.DeviceArray):
+            if mask.shape != shape or mask.dtype != np.uint8:
+                raise ValueError('a device mask must be uint8 of shape {}'.format(shape))
+            self._clean.bind(mask=mask)
+            return
+        host = np.asarray(mask)
+        if host.shape != shape or host.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
+            raise ValueError('a mask must be bool or uint8 of shape {}'.format(shape))
+        device = accel.DeviceArray(self.template.context, shape, np.uint8, queue=self.command_queue)
+        device.set(self.command_queue, np.ascontiguousarray(host != 0, dtype=np.uint8))
+        self._clean.bind(mask=device)
+
+    @property
+    def clean_mask(self):
+        """The device array :meth:`set_clean_mask` bound, or None."""
+        return self._clean.buffer('mask')
+
+    @_serial
     def clean_reset(self):
         self._ready()
         self._clean.reset()
