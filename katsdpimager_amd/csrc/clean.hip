@@ -9,9 +9,9 @@
 //  - subtraction is dirty -= (loop_gain*pixel) * psf with separately rounded multiply and
 //    subtract (clean.py:1044-1046): this file is built with -ffp-contract=off.
 #include "kimg_common.h"
+#include "kimg_graph_cache.h"
 #include <limits.h>
 #include <string.h>
-#include <mutex>
 
 namespace {
 
@@ -2069,30 +2069,17 @@ static int update_tiles(const float *dirty, int64_t row_stride, int64_t pol_stri
     KIMG_CHECK_ARG(mask == nullptr || mask_row_stride >= width);
     dim3 g(tile_x1 - tile_x0, tile_y1 - tile_y0);
     hipStream_t s = (hipStream_t) stream;
-    if (mask != nullptr) {
-        if (mode == KIMG_CLEAN_I)
-            update_tiles_masked_kernel<KIMG_CLEAN_I><<<g, 256, 0, s>>>(
-                dirty, row_stride, pol_stride, width, height, num_polarizations, border, tile_max,
-                tile_pos, tiles_x, tile_x0, tile_y0, mask, mask_row_stride);
-        else if (mode == KIMG_CLEAN_SUMSQ)
-            update_tiles_masked_kernel<KIMG_CLEAN_SUMSQ><<<g, 256, 0, s>>>(
+    const bool known = kimg_for_clean_mode(mode, [&](auto m) {
+        constexpr int MODE = decltype(m)::value;
+        if (mask != nullptr)
+            update_tiles_masked_kernel<MODE><<<g, 256, 0, s>>>(
                 dirty, row_stride, pol_stride, width, height, num_polarizations, border, tile_max,
                 tile_pos, tiles_x, tile_x0, tile_y0, mask, mask_row_stride);
         else
-            return KIMG_EINVAL;
-        return kimg_launch_status();
-    }
-    if (mode == KIMG_CLEAN_I)
-        update_tiles_kernel<KIMG_CLEAN_I><<<g, 256, 0, s>>>(
-            dirty, row_stride, pol_stride, width, height, num_polarizations, border, tile_max,
-            tile_pos, tiles_x, tile_x0, tile_y0);
-    else if (mode == KIMG_CLEAN_SUMSQ)
-        update_tiles_kernel<KIMG_CLEAN_SUMSQ><<<g, 256, 0, s>>>(
-            dirty, row_stride, pol_stride, width, height, num_polarizations, border, tile_max,
-            tile_pos, tiles_x, tile_x0, tile_y0);
-    else
-        return KIMG_EINVAL;
-    return kimg_launch_status();
+            update_tiles_kernel<MODE><<<g, 256, 0, s>>>(
+                dirty, row_stride, pol_stride, width, height, num_polarizations, border, tile_max,
+                tile_pos, tiles_x, tile_x0, tile_y0); });
+    return known ? kimg_launch_status() : KIMG_EINVAL;
 }
 
 extern "C" int kimg_update_tiles(const float *dirty, int64_t row_stride, int64_t pol_stride,
@@ -2230,96 +2217,61 @@ struct cycle_args {
     batch_table tab;
 };
 
-// One minor cycle = two dependent launches (peak + threshold test, then subtract + tile update).
+// One minor cycle: one launch for a batch or the one-launch form, else two dependent launches (peak +
+// threshold test, then subtract + tile update).  (Callers have checked the mode.)
 int enqueue_cycle(const cycle_args &a, hipStream_t s, int index)
 {
-    if (a.batch > 0) {
-        const dim3 gb(a.batch_blocks + 2, 1, a.batch);          // + the two bookkeeping workgroups
-        if (a.mode == KIMG_CLEAN_I)
-            cycle_fused_batch_kernel<KIMG_CLEAN_I><<<gb, 1024, 0, s>>>(
+    kimg_for_clean_mode(a.mode, [&](auto m) {
+        constexpr int MODE = decltype(m)::value;
+        if (a.batch > 0) {
+            const dim3 gb(a.batch_blocks + 2, 1, a.batch);          // + the two bookkeeping workgroups
+            cycle_fused_batch_kernel<MODE><<<gb, 1024, 0, s>>>(
                 a.tab, a.row_stride, a.pol_stride, a.width, a.height, a.P, a.psf_row_stride,
                 a.psf_pol_stride, a.psf_width, a.psf_height, a.border, a.tiles_x, a.tiles_y,
                 a.loop_gain, index & 1);
-        else
-            cycle_fused_batch_kernel<KIMG_CLEAN_SUMSQ><<<gb, 1024, 0, s>>>(
-                a.tab, a.row_stride, a.pol_stride, a.width, a.height, a.P, a.psf_row_stride,
-                a.psf_pol_stride, a.psf_width, a.psf_height, a.border, a.tiles_x, a.tiles_y,
-                a.loop_gain, index & 1);
-        return kimg_launch_status();
-    }
-    dim3 g(kimg_divup(a.patch_width, TILE) + 1, kimg_divup(a.patch_height, TILE) + 1);
-    const int num_tiles = a.tiles_x * a.tiles_y;
-    if (a.fused) {
-        fused_scratch *fs = reinterpret_cast<fused_scratch *>(a.state);
-        g.y += 1;               // the bookkeeping workgroup's row
-        if (a.mask != nullptr) {
-            if (a.mode == KIMG_CLEAN_I)
-                cycle_fused_masked_kernel<KIMG_CLEAN_I><<<g, 1024, 0, s>>>(
+            return;
+        }
+        dim3 g(kimg_divup(a.patch_width, TILE) + 1, kimg_divup(a.patch_height, TILE) + 1);
+        if (a.fused) {
+            fused_scratch *fs = reinterpret_cast<fused_scratch *>(a.state);
+            g.y += 1;               // the bookkeeping workgroup's row
+            if (a.mask != nullptr)
+                cycle_fused_masked_kernel<MODE><<<g, 1024, 0, s>>>(
                     a.dirty, a.model, a.row_stride, a.pol_stride, a.width, a.height, a.P, a.psf,
                     a.psf_row_stride, a.psf_pol_stride, a.psf_width, a.psf_height, a.patch_width,
                     a.patch_height, a.border, a.tile_max, a.tile_pos, a.tiles_x, a.tiles_y,
                     a.loop_gain, fs, index & 1, a.log, a.mask, a.mask_row_stride);
             else
-                cycle_fused_masked_kernel<KIMG_CLEAN_SUMSQ><<<g, 1024, 0, s>>>(
+                cycle_fused_kernel<MODE><<<g, 1024, 0, s>>>(
                     a.dirty, a.model, a.row_stride, a.pol_stride, a.width, a.height, a.P, a.psf,
                     a.psf_row_stride, a.psf_pol_stride, a.psf_width, a.psf_height, a.patch_width,
                     a.patch_height, a.border, a.tile_max, a.tile_pos, a.tiles_x, a.tiles_y,
-                    a.loop_gain, fs, index & 1, a.log, a.mask, a.mask_row_stride);
-            return kimg_launch_status();
+                    a.loop_gain, fs, index & 1, a.log);
+            return;
         }
-        if (a.mode == KIMG_CLEAN_I)
-            cycle_fused_kernel<KIMG_CLEAN_I><<<g, 1024, 0, s>>>(
-                a.dirty, a.model, a.row_stride, a.pol_stride, a.width, a.height, a.P, a.psf,
-                a.psf_row_stride, a.psf_pol_stride, a.psf_width, a.psf_height, a.patch_width,
-                a.patch_height, a.border, a.tile_max, a.tile_pos, a.tiles_x, a.tiles_y,
-                a.loop_gain, fs, index & 1, a.log);
-        else
-            cycle_fused_kernel<KIMG_CLEAN_SUMSQ><<<g, 1024, 0, s>>>(
-                a.dirty, a.model, a.row_stride, a.pol_stride, a.width, a.height, a.P, a.psf,
-                a.psf_row_stride, a.psf_pol_stride, a.psf_width, a.psf_height, a.patch_width,
-                a.patch_height, a.border, a.tile_max, a.tile_pos, a.tiles_x, a.tiles_y,
-                a.loop_gain, fs, index & 1, a.log);
-        return kimg_launch_status();
-    }
-    if (a.mask != nullptr) {
-        cycle_find_peak_masked_kernel<<<1, 1024, 0, s>>>(
-            a.dirty, a.model, a.row_stride, a.pol_stride, a.P, a.tile_max, a.tile_pos, num_tiles,
-            a.loop_gain, a.state, a.log);
-        if (a.mode == KIMG_CLEAN_I)
-            cycle_subtract_update_masked_kernel<KIMG_CLEAN_I><<<g, 256, 0, s>>>(
+        const int num_tiles = a.tiles_x * a.tiles_y;
+        if (a.mask != nullptr) {
+            cycle_find_peak_masked_kernel<<<1, 1024, 0, s>>>(
+                a.dirty, a.model, a.row_stride, a.pol_stride, a.P, a.tile_max, a.tile_pos, num_tiles,
+                a.loop_gain, a.state, a.log);
+            cycle_subtract_update_masked_kernel<MODE><<<g, 256, 0, s>>>(
                 a.dirty, a.row_stride, a.pol_stride, a.width, a.height, a.P, a.psf, a.psf_row_stride,
                 a.psf_pol_stride, a.psf_width, a.psf_height, a.patch_width, a.patch_height, a.border,
                 a.tile_max, a.tile_pos, a.tiles_x, a.tiles_y, a.state, a.mask, a.mask_row_stride);
-        else
-            cycle_subtract_update_masked_kernel<KIMG_CLEAN_SUMSQ><<<g, 256, 0, s>>>(
+        } else {
+            cycle_find_peak_kernel<MODE><<<1, 1024, 0, s>>>(
+                a.dirty, a.model, a.row_stride, a.pol_stride, a.P, a.tile_max, a.tile_pos, num_tiles,
+                a.loop_gain, a.state, a.log);
+            cycle_subtract_update_kernel<MODE><<<g, 256, 0, s>>>(
                 a.dirty, a.row_stride, a.pol_stride, a.width, a.height, a.P, a.psf, a.psf_row_stride,
                 a.psf_pol_stride, a.psf_width, a.psf_height, a.patch_width, a.patch_height, a.border,
-                a.tile_max, a.tile_pos, a.tiles_x, a.tiles_y, a.state, a.mask, a.mask_row_stride);
-        return kimg_launch_status();
-    }
-    if (a.mode == KIMG_CLEAN_I) {
-        cycle_find_peak_kernel<KIMG_CLEAN_I><<<1, 1024, 0, s>>>(
-            a.dirty, a.model, a.row_stride, a.pol_stride, a.P, a.tile_max, a.tile_pos, num_tiles,
-            a.loop_gain, a.state, a.log);
-        cycle_subtract_update_kernel<KIMG_CLEAN_I><<<g, 256, 0, s>>>(
-            a.dirty, a.row_stride, a.pol_stride, a.width, a.height, a.P, a.psf, a.psf_row_stride,
-            a.psf_pol_stride, a.psf_width, a.psf_height, a.patch_width, a.patch_height, a.border,
-            a.tile_max, a.tile_pos, a.tiles_x, a.tiles_y, a.state);
-    } else {
-        cycle_find_peak_kernel<KIMG_CLEAN_SUMSQ><<<1, 1024, 0, s>>>(
-            a.dirty, a.model, a.row_stride, a.pol_stride, a.P, a.tile_max, a.tile_pos, num_tiles,
-            a.loop_gain, a.state, a.log);
-        cycle_subtract_update_kernel<KIMG_CLEAN_SUMSQ><<<g, 256, 0, s>>>(
-            a.dirty, a.row_stride, a.pol_stride, a.width, a.height, a.P, a.psf, a.psf_row_stride,
-            a.psf_pol_stride, a.psf_width, a.psf_height, a.patch_width, a.patch_height, a.border,
-            a.tile_max, a.tile_pos, a.tiles_x, a.tiles_y, a.state);
-    }
+                a.tile_max, a.tile_pos, a.tiles_x, a.tiles_y, a.state);
+        } });
     return kimg_launch_status();
 }
 
-// hipGraph of GRAPH_CYCLES minor cycles, cached per argument set: the minor-cycle loop is
-// launch-bound, and replaying a captured graph costs far less host time than 2 launches
-// per cycle.  The device-side `limit` makes surplus cycles of the last replay no-ops.
+// hipGraph of GRAPH_CYCLES minor cycles, cached per argument set (kimg_graph_cache.h).  The
+// device-side `limit` makes surplus cycles of the last replay no-ops.
 #ifndef KIMG_GRAPH_CYCLES
 #define KIMG_GRAPH_CYCLES 64
 #endif
@@ -2327,91 +2279,92 @@ constexpr int GRAPH_CYCLES = KIMG_GRAPH_CYCLES;
 // the one-launch form alternates two state / delta buffers by launch parity and must leave the
 // final state in st[0]: a replay has to be an even number of launches
 static_assert(GRAPH_CYCLES >= 2 && GRAPH_CYCLES % 2 == 0, "KIMG_GRAPH_CYCLES must be even");
-constexpr int GRAPH_CACHE = 32;     // argument sets (channels in flight x patch sizes)
+// 32 argument sets (channels in flight x patch sizes)
+kimg_graph_cache<cycle_args, 32> graph_cache;
 
-struct graph_entry {
-    bool valid;
-    int users;              // calls that hold `exec` and have not finished enqueuing its replays
-    cycle_args args;
-    hipGraphExec_t exec;
-    hipEvent_t last_use;    // recorded after the last replay enqueued by a finished call
-    bool used;
-    int device;             // the device `last_use` (and the graph) belongs to
-};
-graph_entry graph_cache[GRAPH_CACHE];
-std::mutex graph_mutex;         // channels imaged concurrently share the cache
-
-// The cached (or newly captured) graph for `a`; the entry stays pinned until graph_release().
-// An entry is only evicted when no call is using it and the replays enqueued from it have
-// completed (its event has fired), so a graph is never destroyed while it is in flight.
-graph_entry *cycles_graph(const cycle_args &a, hipStream_t s)
+// `max_cycles` minor cycles on `s`: replays of the cached graph when the call is long enough to be
+// worth one (and the cache has one to give), plain launches otherwise.
+int run_cycles(const cycle_args &a, int max_cycles, hipStream_t s)
 {
-    std::lock_guard<std::mutex> lock(graph_mutex);
-    for (int i = 0; i < GRAPH_CACHE; i++)
-        if (graph_cache[i].valid && memcmp(&graph_cache[i].args, &a, sizeof(a)) == 0) {
-            graph_cache[i].users++;
-            return &graph_cache[i];
-        }
-    graph_entry *slot = nullptr;
-    for (int i = 0; i < GRAPH_CACHE && !slot; i++)
-        if (!graph_cache[i].valid)
-            slot = &graph_cache[i];
-    for (int i = 0; i < GRAPH_CACHE && !slot; i++)
-        if (graph_cache[i].users == 0
-            && (!graph_cache[i].used || hipEventQuery(graph_cache[i].last_use) == hipSuccess))
-            slot = &graph_cache[i];
-    if (!slot)
-        return nullptr;             // every entry busy: the caller enqueues plain launches
-    hipGraph_t graph = nullptr;
-    // (captured on the library's own stream of this thread, launched on the caller's: see
-    // kimg_capture_stream)
-    hipStream_t cs = kimg_capture_stream();
-    if (cs == nullptr || hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) != hipSuccess)
-        return nullptr;
-    int rc = 0;
-    for (int i = 0; i < GRAPH_CYCLES && rc == 0; i++)
-        rc = enqueue_cycle(a, cs, i);
-    const hipError_t ended = hipStreamEndCapture(cs, &graph);
-    if (ended != hipSuccess || rc != 0) {
-        if (ended == hipSuccess && graph != nullptr)
-            (void) hipGraphDestroy(graph);      // (a launch failed during the capture)
-        return nullptr;
-    }
-    hipGraphExec_t exec = nullptr;
-    hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void) hipGraphDestroy(graph);
-    if (e != hipSuccess)
-        return nullptr;
-    // (imagers on several devices may share this process: an event is recorded on streams of the
-    // device it was created on, so a slot taken over from another device gets a new one)
-    int device = 0;
-    (void) hipGetDevice(&device);
-    if (slot->valid) {
-        (void) hipGraphExecDestroy(slot->exec);
-        if (slot->device != device) {
-            (void) hipEventDestroy(slot->last_use);
-            slot->valid = false;
+    int done = 0;
+    if (max_cycles >= GRAPH_CYCLES / 2) {
+        auto *entry = graph_cache.acquire(a, [&](hipStream_t cs) {
+            int rc = 0;
+            for (int i = 0; i < GRAPH_CYCLES && rc == 0; i++)
+                rc = enqueue_cycle(a, cs, i);
+            return rc; });
+        if (entry) {
+            hipError_t e = hipSuccess;
+            for (; done < max_cycles && e == hipSuccess; done += GRAPH_CYCLES)
+                e = hipGraphLaunch(entry->exec, s);
+            graph_cache.release(entry, s);
+            if (e != hipSuccess)
+                return -(int) e;
+            done = max_cycles;
         }
     }
-    if (!slot->valid && hipEventCreateWithFlags(&slot->last_use, hipEventDisableTiming) != hipSuccess) {
-        (void) hipGraphExecDestroy(exec);
-        return nullptr;
+    // (an even number of launches, so that the one-launch form leaves its state in st[0]; the
+    // device-side limit makes the surplus one a no-op)
+    for (int i = 0; done < max_cycles || (i & 1); done++, i++) {
+        const int rc = enqueue_cycle(a, s, i);
+        if (rc)
+            return rc;
     }
-    slot->device = device;
-    slot->valid = true;
-    slot->used = false;
-    slot->users = 1;
-    slot->args = a;
-    slot->exec = exec;
-    return slot;
+    return 0;
 }
 
-void graph_release(graph_entry *entry, hipStream_t s)
+// The fields of `a` that a single channel's call and a batch share.  (The memset comes first: padding
+// bytes take part in the cache key comparison.)
+void fill_shared(cycle_args &a, int64_t row_stride, int64_t pol_stride, int width, int height, int P,
+                 int64_t psf_row_stride, int64_t psf_pol_stride, int psf_width, int psf_height,
+                 int border, int mode, float loop_gain, int tiles_x, int tiles_y, bool fused)
 {
-    std::lock_guard<std::mutex> lock(graph_mutex);
-    (void) hipEventRecord(entry->last_use, s);
-    entry->used = true;
-    entry->users--;
+    memset(&a, 0, sizeof(a));
+    a.row_stride = row_stride; a.pol_stride = pol_stride; a.width = width; a.height = height;
+    a.P = P; a.psf_row_stride = psf_row_stride; a.psf_pol_stride = psf_pol_stride;
+    a.psf_width = psf_width; a.psf_height = psf_height; a.border = border; a.mode = mode;
+    a.loop_gain = loop_gain; a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.fused = fused;
+}
+
+// One launch per cycle: when the patch touches few lattice blocks (every workgroup then repeats the
+// global peak search) ...
+bool patch_fits_one_launch(int patch_width, int patch_height)
+{
+    const int bx = kimg_divup(patch_width, TILE) + 1, by = kimg_divup(patch_height, TILE) + 1;
+    return bx * (by + 1) <= FUSED_MAX_BLOCKS && bx <= 32 && by <= 32;
+}
+
+// ... and the tiles' owners (one per 32 x 32 tiles) fit the scratch
+bool tiles_fit_one_launch(int tiles_x, int tiles_y)
+{
+    return kimg_divup(tiles_x, 32) * kimg_divup(tiles_y, 32) <= FUSED_MAX_SLOTS;
+}
+
+// One channel's scratch at the start of a call: the loop's limit and threshold and, for the one-launch
+// form, the peak pixels of every tile ...
+int begin_state(const cycle_args &a, void *state, int max_cycles, float threshold, const float *dirty,
+                const int32_t *tile_pos, hipStream_t s)
+{
+    KIMG_HIP(hipMemsetAsync(state, 0, sizeof(fused_scratch), s));
+    init_state_kernel<<<1, 1, 0, s>>>(static_cast<clean_state *>(state), max_cycles, threshold);
+    if (a.fused)
+        tile_pix_kernel<<<kimg_divup(a.tiles_x * a.tiles_y, 256), 256, 0, s>>>(
+            dirty, a.row_stride, a.pol_stride, a.width, a.height, a.P, tile_pos, a.tiles_x * a.tiles_y,
+            static_cast<fused_scratch *>(state));
+    return 0;
+}
+
+// ... then every owner's best two tiles, before the first cycle of the one-launch form ...
+void begin_owners(const cycle_args &a, void *state, float *tile_max, int32_t *tile_pos, hipStream_t s)
+{
+    owner_best_kernel<<<1, 1024, 0, s>>>(tile_max, tile_pos, a.tiles_x, a.tiles_y,
+                                         static_cast<fused_scratch *>(state));
+}
+
+// ... and after its last one, the tile records brought up to date
+void end_state(void *state, float *tile_max, int32_t *tile_pos, hipStream_t s)
+{
+    apply_deltas_kernel<<<1, 1024, 0, s>>>(static_cast<fused_scratch *>(state), tile_max, tile_pos);
 }
 
 } // namespace
@@ -2494,12 +2447,9 @@ static int clean_cycles(float *dirty, float *model, int64_t row_stride,
         if (form == KIMG_CLEAN_FORM_MULTI)
             form = KIMG_CLEAN_FORM_AUTO;
     }
-    // one launch per cycle when the patch touches few lattice blocks (every workgroup then
-    // repeats the global peak search)
     const int bx = kimg_divup(patch_width, TILE) + 1, by = kimg_divup(patch_height, TILE) + 1;
-    const bool fused = bx * (by + 1) <= FUSED_MAX_BLOCKS && bx <= 32 && by <= 32
-                       && kimg_divup(tiles_x, 32) * kimg_divup(tiles_y, 32) <= FUSED_MAX_SLOTS
-                       && form != KIMG_CLEAN_FORM_TWO_LAUNCH;
+    const bool fused = patch_fits_one_launch(patch_width, patch_height)
+                       && tiles_fit_one_launch(tiles_x, tiles_y) && form != KIMG_CLEAN_FORM_TWO_LAUNCH;
     // the whole loop in one workgroup when the patch is small and the tile records and the PSF
     // patch fit LDS
     const size_t solo_lds = (((size_t) tiles_x * tiles_y * 6 + 15) & ~(size_t) 15)
@@ -2510,30 +2460,27 @@ static int clean_cycles(float *dirty, float *model, int64_t row_stride,
                          && solo_lds <= SOLO_LDS_LIMIT && max_cycles > 0;
     if (solo_ok && (form == KIMG_CLEAN_FORM_ONE_WORKGROUP
                     || (form == KIMG_CLEAN_FORM_AUTO && bx * by <= SOLO_AUTO_BLOCKS))) {
-#define SOLO(MODE) do { \
-        { \
-            const int lds_rc = kimg_dynamic_lds(reinterpret_cast<const void *>(&cycle_solo_kernel<MODE>), \
-                                                SOLO_LDS_LIMIT); \
-            if (lds_rc) \
-                return lds_rc; \
-        } \
-        cycle_solo_kernel<MODE><<<1, 1024, solo_lds, s>>>( \
-            dirty, model, row_stride, width, height, psf, psf_row_stride, psf_width, psf_height, \
-            patch_width, patch_height, border, tile_max, tile_pos, tiles_x, tiles_y, loop_gain, \
-            threshold, max_cycles, static_cast<fused_scratch *>(state), log); } while (0)
-        if (mode == KIMG_CLEAN_I)
-            SOLO(KIMG_CLEAN_I);
-        else
-            SOLO(KIMG_CLEAN_SUMSQ);
-#undef SOLO
-        return kimg_launch_status();
+        int rc = 0;
+        kimg_for_clean_mode(mode, [&](auto m) {
+            constexpr int MODE = decltype(m)::value;
+            rc = kimg_dynamic_lds(reinterpret_cast<const void *>(&cycle_solo_kernel<MODE>), SOLO_LDS_LIMIT);
+            if (rc == 0)
+                cycle_solo_kernel<MODE><<<1, 1024, solo_lds, s>>>(
+                    dirty, model, row_stride, width, height, psf, psf_row_stride, psf_width, psf_height,
+                    patch_width, patch_height, border, tile_max, tile_pos, tiles_x, tiles_y, loop_gain,
+                    threshold, max_cycles, static_cast<fused_scratch *>(state), log); });
+        return rc ? rc : kimg_launch_status();
     }
-    KIMG_HIP(hipMemsetAsync(state, 0, sizeof(fused_scratch), s));
-    init_state_kernel<<<1, 1, 0, s>>>(static_cast<clean_state *>(state), max_cycles, threshold);
-    if (fused)
-        tile_pix_kernel<<<kimg_divup(tiles_x * tiles_y, 256), 256, 0, s>>>(
-            dirty, row_stride, pol_stride, width, height, num_polarizations, tile_pos,
-            tiles_x * tiles_y, static_cast<fused_scratch *>(state));
+    cycle_args a;
+    fill_shared(a, row_stride, pol_stride, width, height, num_polarizations, psf_row_stride,
+                psf_pol_stride, psf_width, psf_height, border, mode, loop_gain, tiles_x, tiles_y, fused);
+    a.dirty = dirty; a.model = model; a.psf = psf; a.patch_width = patch_width;
+    a.patch_height = patch_height; a.tile_max = tile_max; a.tile_pos = tile_pos;
+    a.state = static_cast<clean_state *>(state); a.log = log;
+    a.mask = mask; a.mask_row_stride = masked ? mask_row_stride : 0;
+    int rc = begin_state(a, state, max_cycles, threshold, dirty, tile_pos, s);
+    if (rc)
+        return rc;
     // the whole loop in one launch when the patch's lattice blocks can all be resident and the
     // tile maxima fit LDS
     const size_t persist_lds = (((size_t) tiles_x * tiles_y * 4 + 15) & ~(size_t) 15)
@@ -2546,63 +2493,28 @@ static int clean_cycles(float *dirty, float *model, int64_t row_stride,
         replica_t *replicas = reinterpret_cast<replica_t *>(base + sizeof(persist_header));
         KIMG_HIP(hipMemsetAsync(hdr, 0, sizeof(persist_header), s));
         const dim3 g(bx, by);
-#define PERSIST(MODE) do { \
-        { \
-            const int lds_rc = kimg_dynamic_lds(reinterpret_cast<const void *>(&cycle_persistent_kernel<MODE>), \
-                                                PERSIST_LDS_LIMIT); \
-            if (lds_rc) \
-                return lds_rc; \
-        } \
-        cycle_persistent_kernel<MODE><<<g, 1024, persist_lds, s>>>( \
-            dirty, model, row_stride, pol_stride, width, height, num_polarizations, psf, \
-            psf_row_stride, psf_pol_stride, psf_width, psf_height, patch_width, patch_height, border, \
-            tile_max, tile_pos, tiles_x, tiles_y, loop_gain, threshold, max_cycles, \
-            static_cast<fused_scratch *>(state), hdr, replicas, log); } while (0)
-        if (mode == KIMG_CLEAN_I)
-            PERSIST(KIMG_CLEAN_I);
-        else
-            PERSIST(KIMG_CLEAN_SUMSQ);
-#undef PERSIST
+        kimg_for_clean_mode(mode, [&](auto m) {
+            constexpr int MODE = decltype(m)::value;
+            rc = kimg_dynamic_lds(reinterpret_cast<const void *>(&cycle_persistent_kernel<MODE>),
+                                  PERSIST_LDS_LIMIT);
+            if (rc == 0)
+                cycle_persistent_kernel<MODE><<<g, 1024, persist_lds, s>>>(
+                    dirty, model, row_stride, pol_stride, width, height, num_polarizations, psf,
+                    psf_row_stride, psf_pol_stride, psf_width, psf_height, patch_width, patch_height, border,
+                    tile_max, tile_pos, tiles_x, tiles_y, loop_gain, threshold, max_cycles,
+                    static_cast<fused_scratch *>(state), hdr, replicas, log); });
+        if (rc)
+            return rc;
         persist_status_kernel<<<1, 1, 0, s>>>(static_cast<fused_scratch *>(state), hdr);
         return kimg_launch_status();
     }
     if (fused)
-        owner_best_kernel<<<1, 1024, 0, s>>>(tile_max, tile_pos, tiles_x, tiles_y,
-                                             static_cast<fused_scratch *>(state));
-    cycle_args a;
-    memset(&a, 0, sizeof(a));       // padding bytes take part in the cache key comparison
-    a.dirty = dirty; a.model = model; a.row_stride = row_stride; a.pol_stride = pol_stride;
-    a.width = width; a.height = height; a.P = num_polarizations; a.psf = psf;
-    a.psf_row_stride = psf_row_stride; a.psf_pol_stride = psf_pol_stride;
-    a.psf_width = psf_width; a.psf_height = psf_height; a.patch_width = patch_width;
-    a.patch_height = patch_height; a.border = border; a.mode = mode; a.loop_gain = loop_gain;
-    a.tile_max = tile_max; a.tile_pos = tile_pos; a.tiles_x = tiles_x;
-    a.tiles_y = tiles_y; a.state = static_cast<clean_state *>(state); a.log = log;
-    a.mask = mask; a.mask_row_stride = masked ? mask_row_stride : 0;
-    a.fused = fused;
-    int done = 0;
-    if (max_cycles >= GRAPH_CYCLES / 2) {
-        graph_entry *entry = cycles_graph(a, s);
-        if (entry) {
-            hipError_t e = hipSuccess;
-            for (; done < max_cycles && e == hipSuccess; done += GRAPH_CYCLES)
-                e = hipGraphLaunch(entry->exec, s);
-            graph_release(entry, s);
-            if (e != hipSuccess)
-                return -(int) e;
-            done = max_cycles;
-        }
-    }
-    // (an even number of launches, so that the fused form leaves its state in st[0]; the
-    // device-side limit makes the surplus one a no-op)
-    for (int i = 0; done < max_cycles || (i & 1); done++, i++) {
-        int rc = enqueue_cycle(a, s, i);
-        if (rc)
-            return rc;
-    }
+        begin_owners(a, state, tile_max, tile_pos, s);
+    rc = run_cycles(a, max_cycles, s);
+    if (rc)
+        return rc;
     if (fused)
-        apply_deltas_kernel<<<1, 1024, 0, s>>>(static_cast<fused_scratch *>(state), tile_max,
-                                               tile_pos);
+        end_state(state, tile_max, tile_pos, s);
     return kimg_launch_status();
 }
 
@@ -2648,9 +2560,10 @@ extern "C" int kimg_clean_cycles_batch(const kimg_clean_channel *channels_in, in
     KIMG_CHECK_ARG(mode == KIMG_CLEAN_I || mode == KIMG_CLEAN_SUMSQ);
     hipStream_t s = (hipStream_t) stream;
     cycle_args a;
-    memset(&a, 0, sizeof(a));       // padding bytes take part in the cache key comparison
+    fill_shared(a, row_stride, pol_stride, width, height, num_polarizations, psf_row_stride,
+                psf_pol_stride, psf_width, psf_height, border, mode, loop_gain, tiles_x, tiles_y, true);
     int max_cycles = 0;
-    if (kimg_divup(tiles_x, 32) * kimg_divup(tiles_y, 32) > FUSED_MAX_SLOTS)
+    if (!tiles_fit_one_launch(tiles_x, tiles_y))
         return KIMG_EUNSUPPORTED;
     // The order of the channels does not matter to the results, but the captured graph is cached
     // per argument set: channels that meet in another order (threads arriving at a rendezvous)
@@ -2674,9 +2587,9 @@ extern "C" int kimg_clean_cycles_batch(const kimg_clean_channel *channels_in, in
         for (int o = 0; o < c; o++)     // channels are cleaned concurrently: no shared buffers
             KIMG_CHECK_ARG(channels[o].dirty != ch.dirty && channels[o].state != ch.state
                            && channels[o].tile_max != ch.tile_max && channels[o].log != ch.log);
-        const int bx = kimg_divup(ch.patch_width, TILE) + 1, by = kimg_divup(ch.patch_height, TILE) + 1;
-        if (!(bx * (by + 1) <= FUSED_MAX_BLOCKS && bx <= 32 && by <= 32))
+        if (!patch_fits_one_launch(ch.patch_width, ch.patch_height))
             return KIMG_EUNSUPPORTED;
+        const int bx = kimg_divup(ch.patch_width, TILE) + 1, by = kimg_divup(ch.patch_height, TILE) + 1;
         a.batch_blocks = bx * by > a.batch_blocks ? bx * by : a.batch_blocks;
         max_cycles = ch.max_cycles > max_cycles ? ch.max_cycles : max_cycles;
         batch_channel &b = a.tab.ch[c];
@@ -2691,48 +2604,21 @@ extern "C" int kimg_clean_cycles_batch(const kimg_clean_channel *channels_in, in
         b.patch_h = ch.patch_height;
     }
     a.batch = num_channels;
-    a.row_stride = row_stride; a.pol_stride = pol_stride; a.width = width; a.height = height;
-    a.P = num_polarizations; a.psf_row_stride = psf_row_stride; a.psf_pol_stride = psf_pol_stride;
-    a.psf_width = psf_width; a.psf_height = psf_height; a.border = border; a.mode = mode;
-    a.loop_gain = loop_gain; a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.fused = 1;
-    // per channel, as kimg_clean_cycles does for the one-launch form: state, peak pixels of every
-    // tile, every owner's best two tiles
+    // per channel, in the order of a single channel's call
     for (int c = 0; c < num_channels; c++) {
         const kimg_clean_channel &ch = channels[c];
-        KIMG_HIP(hipMemsetAsync(ch.state, 0, sizeof(fused_scratch), s));
-        init_state_kernel<<<1, 1, 0, s>>>(static_cast<clean_state *>(ch.state), ch.max_cycles,
-                                          ch.threshold);
-        tile_pix_kernel<<<kimg_divup(tiles_x * tiles_y, 256), 256, 0, s>>>(
-            ch.dirty, row_stride, pol_stride, width, height, num_polarizations, ch.tile_pos,
-            tiles_x * tiles_y, static_cast<fused_scratch *>(ch.state));
-        owner_best_kernel<<<1, 1024, 0, s>>>(ch.tile_max, ch.tile_pos, tiles_x, tiles_y,
-                                             static_cast<fused_scratch *>(ch.state));
-    }
-    int rc = kimg_launch_status();
-    if (rc)
-        return rc;
-    int done = 0;
-    if (max_cycles >= GRAPH_CYCLES / 2) {
-        graph_entry *entry = cycles_graph(a, s);
-        if (entry) {
-            hipError_t e = hipSuccess;
-            for (; done < max_cycles && e == hipSuccess; done += GRAPH_CYCLES)
-                e = hipGraphLaunch(entry->exec, s);
-            graph_release(entry, s);
-            if (e != hipSuccess)
-                return -(int) e;
-            done = max_cycles;
-        }
-    }
-    // (an even number of launches: the final state is then in st[0], see kimg_clean_cycles)
-    for (int i = 0; done < max_cycles || (i & 1); done++, i++) {
-        rc = enqueue_cycle(a, s, i);
+        const int rc = begin_state(a, ch.state, ch.max_cycles, ch.threshold, ch.dirty, ch.tile_pos, s);
         if (rc)
             return rc;
+        begin_owners(a, ch.state, ch.tile_max, ch.tile_pos, s);
     }
+    int rc = kimg_launch_status();
+    if (rc == 0)
+        rc = run_cycles(a, max_cycles, s);
+    if (rc)
+        return rc;
     for (int c = 0; c < num_channels; c++)
-        apply_deltas_kernel<<<1, 1024, 0, s>>>(static_cast<fused_scratch *>(channels[c].state),
-                                               channels[c].tile_max, channels[c].tile_pos);
+        end_state(channels[c].state, channels[c].tile_max, channels[c].tile_pos, s);
     return kimg_launch_status();
 }
 

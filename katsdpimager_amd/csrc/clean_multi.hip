@@ -65,6 +65,7 @@
 // start-up kernel's estimate (how many steps the eight best tiles could take before they are down
 // to the ninth) or the components per launch it sees say that the field is a dominated one.
 #include "kimg_common.h"
+#include "kimg_graph_cache.h"
 #include <limits.h>
 #include <string.h>
 #include <sched.h>
@@ -1859,6 +1860,8 @@ struct multi_args {
     int repeats;            // the kernel built for repeated steps (else: single steps)
 };
 
+template <int N> using int_c = std::integral_constant<int, N>;
+
 // One launch.  `repeats`: with the kernel that plans up to `rmax` steps per lattice (rmax = 1: that
 // kernel, which reads any plan, leaving a plan of single steps behind, which either kernel reads).
 int enqueue_launch(const multi_args &a, hipStream_t s, int parity, bool repeats, int rmax)
@@ -1866,106 +1869,38 @@ int enqueue_launch(const multi_args &a, hipStream_t s, int parity, bool repeats,
     const dim3 grid(a.g.lat_x, a.g.lat_y, 1 + 2 * a.g.mmax);
     mc_geom g = a.g;
     g.rmax = repeats ? rmax : 1;
-#define LAUNCH(MODE, PMAX, STEPS) cycle_multi_kernel<MODE, PMAX, STEPS><<<grid, MC_THREADS, 0, s>>>( \
-        a.dirty, a.model, a.psf, a.tile_max, a.tile_pos, g, a.scratch, parity, a.log, a.progress)
-#define LAUNCH2(MODE, PMAX) do { if (repeats) LAUNCH(MODE, PMAX, (PMAX == 1 ? MC_STEPS : MC_STEPS / 2)); \
-                                 else LAUNCH(MODE, PMAX, 1); } while (0)
-    if (a.mode == KIMG_CLEAN_I && a.g.P == 1)
-        LAUNCH2(KIMG_CLEAN_I, 1);
-    else if (a.mode == KIMG_CLEAN_I)
-        LAUNCH2(KIMG_CLEAN_I, 4);
-    else if (a.g.P == 1)
-        LAUNCH2(KIMG_CLEAN_SUMSQ, 1);
-    else
-        LAUNCH2(KIMG_CLEAN_SUMSQ, 4);
-#undef LAUNCH2
-#undef LAUNCH
+    kimg_for_clean_mode(a.mode, [&](auto m) {
+        auto launch = [&](auto pmax, auto steps) {
+            cycle_multi_kernel<decltype(m)::value, decltype(pmax)::value, decltype(steps)::value>
+                <<<grid, MC_THREADS, 0, s>>>(a.dirty, a.model, a.psf, a.tile_max, a.tile_pos, g, a.scratch,
+                                             parity, a.log, a.progress); };
+        // (PMAX: 1 or room for all 4 polarizations; STEPS: 1 or as many as that PMAX allows)
+        if (a.g.P == 1 && repeats)
+            launch(int_c<1>{}, int_c<MC_STEPS>{});
+        else if (a.g.P == 1)
+            launch(int_c<1>{}, int_c<1>{});
+        else if (repeats)
+            launch(int_c<4>{}, int_c<MC_STEPS / 2>{});
+        else
+            launch(int_c<4>{}, int_c<1>{}); });
     return kimg_launch_status();
 }
 
-// hipGraphs of MULTI_GRAPH launches, cached per argument set (as cycles_graph in clean.hip)
+// hipGraphs of MULTI_GRAPH launches, cached per argument set (kimg_graph_cache.h)
 constexpr int MULTI_GRAPH = 16;
 static_assert(MULTI_GRAPH % 2 == 0, "launches alternate two state buffers");
-constexpr int MULTI_CACHE = 32;
+using multi_cache_t = kimg_graph_cache<multi_args, 32>;
+multi_cache_t multi_cache;
 
-struct multi_graph {
-    bool valid, used;
-    int users, device;
-    multi_args args;
-    hipGraphExec_t exec;
-    hipEvent_t last_use;
-};
-multi_graph multi_cache[MULTI_CACHE];
-std::mutex multi_mutex;
-
-multi_graph *multi_graph_for(const multi_args &a, hipStream_t s)
+multi_cache_t::entry *multi_graph_for(const multi_args &a)
 {
-    std::lock_guard<std::mutex> lock(multi_mutex);
-    for (int i = 0; i < MULTI_CACHE; i++)
-        if (multi_cache[i].valid && memcmp(&multi_cache[i].args, &a, sizeof(a)) == 0) {
-            multi_cache[i].users++;
-            return &multi_cache[i];
-        }
-    multi_graph *slot = nullptr;
-    for (int i = 0; i < MULTI_CACHE && !slot; i++)
-        if (!multi_cache[i].valid)
-            slot = &multi_cache[i];
-    for (int i = 0; i < MULTI_CACHE && !slot; i++)
-        if (multi_cache[i].users == 0
-            && (!multi_cache[i].used || hipEventQuery(multi_cache[i].last_use) == hipSuccess))
-            slot = &multi_cache[i];
-    if (!slot)
-        return nullptr;                 // every entry busy: the caller enqueues plain launches
-    hipGraph_t graph = nullptr;
-    // (captured on the library's own stream of this thread, launched on the caller's: see
-    // kimg_capture_stream)
-    hipStream_t cs = kimg_capture_stream();
-    if (cs == nullptr || hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) != hipSuccess)
-        return nullptr;
-    int rc = 0;
-    // (the last launch of a graph of the repeated-steps kernel plans single steps: whatever comes
-    // next, of either kind, can read what it leaves behind)
-    for (int i = 0; i < MULTI_GRAPH && rc == 0; i++)
-        rc = enqueue_launch(a, cs, i & 1, a.repeats != 0, i == MULTI_GRAPH - 1 ? 1 : a.g.rmax);
-    const hipError_t ended = hipStreamEndCapture(cs, &graph);
-    if (ended != hipSuccess || rc != 0) {
-        if (ended == hipSuccess && graph != nullptr)
-            (void) hipGraphDestroy(graph);
-        return nullptr;
-    }
-    hipGraphExec_t exec = nullptr;
-    const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void) hipGraphDestroy(graph);
-    if (e != hipSuccess)
-        return nullptr;
-    int device = 0;
-    (void) hipGetDevice(&device);
-    if (slot->valid) {
-        (void) hipGraphExecDestroy(slot->exec);
-        if (slot->device != device) {
-            (void) hipEventDestroy(slot->last_use);
-            slot->valid = false;
-        }
-    }
-    if (!slot->valid && hipEventCreateWithFlags(&slot->last_use, hipEventDisableTiming) != hipSuccess) {
-        (void) hipGraphExecDestroy(exec);
-        return nullptr;
-    }
-    slot->device = device;
-    slot->valid = true;
-    slot->used = false;
-    slot->users = 1;
-    slot->args = a;
-    slot->exec = exec;
-    return slot;
-}
-
-void multi_graph_release(multi_graph *entry, hipStream_t s)
-{
-    std::lock_guard<std::mutex> lock(multi_mutex);
-    (void) hipEventRecord(entry->last_use, s);
-    entry->used = true;
-    entry->users--;
+    return multi_cache.acquire(a, [&](hipStream_t cs) {
+        int rc = 0;
+        // (the last launch of a graph of the repeated-steps kernel plans single steps: whatever comes
+        // next, of either kind, can read what it leaves behind)
+        for (int i = 0; i < MULTI_GRAPH && rc == 0; i++)
+            rc = enqueue_launch(a, cs, i & 1, a.repeats != 0, i == MULTI_GRAPH - 1 ? 1 : a.g.rmax);
+        return rc; });
 }
 
 // Progress words the keeper writes for the host: pinned, host-coherent memory, one word (on a
@@ -2125,7 +2060,7 @@ int kimg_clean_multi_run(float *dirty, float *model, int64_t row_stride, int64_t
     // for as long as repeated steps are a fifth of what gets committed, judged over windows of
     // launches that ran wholly under the choice; a try that did not help is not repeated for a while
     // (twice as long each time in a row).
-    multi_graph *graphs[2] = {nullptr, nullptr};
+    multi_cache_t::entry *graphs[2] = {nullptr, nullptr};
     multi_args variants[2] = {a, a};
     variants[1].repeats = 1;
     const bool can_repeat = a.g.rmax > 1 && !always_repeat;
@@ -2217,7 +2152,7 @@ int kimg_clean_multi_run(float *dirty, float *model, int64_t row_stride, int64_t
         }
 #ifndef KIMG_MC_NO_GRAPH
         if (need >= MULTI_GRAPH && !graphs[v])
-            graphs[v] = multi_graph_for(variants[v], s);
+            graphs[v] = multi_graph_for(variants[v]);
 #endif
         if (need >= MULTI_GRAPH && graphs[v]) {
             he = hipGraphLaunch(graphs[v]->exec, s);
@@ -2290,7 +2225,7 @@ int kimg_clean_multi_run(float *dirty, float *model, int64_t row_stride, int64_t
     }
     for (int v = 0; v < 2; v++)
         if (graphs[v])
-            multi_graph_release(graphs[v], s);
+            multi_cache.release(graphs[v], s);
     progress_release(slot);
     return rc;
 }

@@ -122,6 +122,17 @@ template <class F> inline void kimg_for_pols(int P, F &&f)
     }
 }
 
+// f(std::integral_constant<int, MODE>{}) for KIMG_CLEAN_I / KIMG_CLEAN_SUMSQ; false (and no call) for
+// any other mode
+template <class F> inline bool kimg_for_clean_mode(int mode, F &&f)
+{
+    switch (mode) {
+    case KIMG_CLEAN_I: f(std::integral_constant<int, KIMG_CLEAN_I>{}); return true;
+    case KIMG_CLEAN_SUMSQ: f(std::integral_constant<int, KIMG_CLEAN_SUMSQ>{}); return true;
+    }
+    return false;
+}
+
 constexpr int WAVE = 64;    // gfx950 wavefront
 
 // Wave-wide sum by DPP-backed shuffles; result valid in every lane.
