@@ -21,7 +21,7 @@
 // per-visibility gathers of different table rows fall on different banks).
 //
 // Algorithmic work per visibility: 8*K*K*P flop; executed 2 MFMA x 4096 flop per polarization.
-#include "kimg_common.h"
+#include "kimg_window_launch.h"
 #include <limits.h>
 #include <stdlib.h>
 
@@ -29,7 +29,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int WIN = 32;
 // LDS table rows: TAPS = 64 (32 zero-padded taps stored twice: the tap index needs no wrap) when
 // the table fits, else TAPS = 32 (wrap = 2 more VALU per read); one pad tap per row either way.
 template <int TAPS>
@@ -73,16 +72,11 @@ struct window_regs {
 };
 
 // Kernel widths above 32 are degridded as 2 x 2 blocks of taps, one launch per block, each
-// subtracting its partial sum (see grid_mfma.hip): row taps [tv0, tv0 + Kv) and column taps
-// [tu0, tu0 + Ku) of the K-tap kernel; off-diagonal blocks need TWO tables in LDS.
-struct tap_split {
-    int K;
-    int tv0, Kv;
-    int tu0, Ku;
-};
+// subtracting its partial sum (tap_split, kimg_window_launch.h); off-diagonal blocks need TWO
+// tables, in LDS or in HBM.
 
 // TG: table(s) too large for LDS (hundreds of W planes) stay in HBM as [rows][32] zero-padded
-// taps (pad_rows_kernel, rebuilt per call in the caller's workspace).  Each wave copies the 2 x 16
+// taps (pad_table_kernel<32>, rebuilt per call in the caller's workspace).  Each wave copies the 2 x 16
 // rows its current 16 visibilities need into a private LDS cache (coalesced 16-byte loads: a row
 // is 256 bytes) and then works exactly like the single-row LDS form (TAPS must be 32).
 // ---- fp16 hi/lo form (F16 = true; one polarization, table in LDS) ---------------------------
@@ -182,7 +176,7 @@ __global__ __launch_bounds__(NW * 64) void degrid_mfma_kernel(
     __syncthreads();
     float S_kv = 1.0f;
     if (F16 && TG) {
-        S_kv = dg_scale_for(*tab_max);          // table in HBM: maximum found by dg_table_max_kernel
+        S_kv = dg_scale_for(*tab_max);          // table in HBM: maximum found by kimg_table_max
     } else if (F16) {
         // largest |component| of the row-tap table (block reduction; the staging area is still free)
         unsigned *s_max = reinterpret_cast<unsigned *>(rec_base);
@@ -597,96 +591,11 @@ __global__ __launch_bounds__(NW * 64) void degrid_mfma_kernel(
     }
 }
 
-// HBM copy of the table in the LDS row layout: (TAPS + 1) taps per row, the 32 zero-padded taps
-// of [tap0, tap0 + Kp) once (TAPS = 32) or twice (TAPS = 64).
-template <int TAPS>
-__global__ __launch_bounds__(256) void pad_table_kernel(
-    const float2 *__restrict__ kern, int rows, int K, int tap0, int Kp, float2 *__restrict__ out)
-{
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= rows * (TAPS + 1))
-        return;
-    const int row = idx / (TAPS + 1), c = idx % (TAPS + 1), t = c & 31;
-    out[idx] = (c < TAPS && t < Kp) ? kern[(int64_t) row * K + tap0 + t] : make_float2(0.0f, 0.0f);
-}
-
-// Largest |component| of the raw table (bit pattern), for the fp16 form with the table in HBM.
-__global__ __launch_bounds__(256) void dg_table_max_kernel(const float *__restrict__ kern, int64_t n,
-                                                            unsigned *__restrict__ out)
-{
-    unsigned m = 0;
-    for (int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x; i < n;
-         i += (int64_t) gridDim.x * blockDim.x)
-        m = max(m, __float_as_uint(kern[i]) & 0x7fffffffu);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        m = max(m, (unsigned) __shfl_xor((int) m, off, WAVE));
-    if ((threadIdx.x & 63) == 0 && m)
-        atomicMax(out, m);
-}
-
-// TG: [rows][32] zero-padded taps (256-byte rows).
-__global__ __launch_bounds__(256) void pad_rows_kernel(
-    const float2 *__restrict__ kern, int rows, int K, int tap0, int Kp, float2 *__restrict__ out)
-{
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= rows * 32)
-        return;
-    const int row = idx >> 5, t = idx & 31;
-    out[idx] = t < Kp ? kern[(int64_t) row * K + tap0 + t] : make_float2(0.0f, 0.0f);
-}
-
 size_t lds_bytes(int NW, int W, int OV, int taps, int tables = 1)
 {
     return (size_t) tables * W * OV * (taps + 1) * 8 + (size_t) NW * 64 * sizeof(int4);
 }
 
-constexpr size_t LDS_LIMIT = 160 * 1024;
-
-// The chunk counter of the call in progress on this host thread (in the workspace's tail, see
-// kimg_degrid_mfma): handed to launch() this way because every launch site is a macro.
-thread_local unsigned long long *tls_queue = nullptr;
-
-template <int P, int NW, int TAPS, bool TWO, bool TG = false, bool F16 = false>
-int launch(const float *grid, int64_t row_stride, int64_t pol_stride, int Gg, const int16_t *uv,
-           const int16_t *w_plane, const float *weights, float *vis, int64_t num_vis,
-           const float2 *kern, int W, int OV, const tap_split &ts, int p_total, hipStream_t stream,
-           unsigned char *padded = nullptr, size_t tab_max_offset = 0)
-{
-    const size_t lds = TG ? lds_bytes(NW, 0, 0, TAPS) + (size_t) NW * 2 * BATCH * 272
-                          : lds_bytes(NW, W, OV, TAPS, TWO ? 2 : 1);
-    unsigned *tab_max = nullptr;
-    if (TG) {
-        const int rows = W * OV;
-        float2 *out = reinterpret_cast<float2 *>(padded);
-        if (F16) {
-            // (the last 256 bytes of the workspace hold the table maximum)
-            tab_max = reinterpret_cast<unsigned *>(padded + tab_max_offset);
-            KIMG_HIP(hipMemsetAsync(tab_max, 0, sizeof(unsigned), stream));
-            const int64_t n = (int64_t) rows * ts.K * 2;
-            dg_table_max_kernel<<<kimg_divup(n, 256 * 8), 256, 0, stream>>>(
-                reinterpret_cast<const float *>(kern), n, tab_max);
-        }
-        pad_rows_kernel<<<kimg_divup(rows * 32, 256), 256, 0, stream>>>(kern, rows, ts.K, ts.tv0,
-                                                                       ts.Kv, out);
-        if (TWO)
-            pad_rows_kernel<<<kimg_divup(rows * 32, 256), 256, 0, stream>>>(
-                kern, rows, ts.K, ts.tu0, ts.Ku, out + (size_t) rows * 32);
-    }
-    {
-        const int rc = kimg_dynamic_lds(
-            reinterpret_cast<const void *>(&degrid_mfma_kernel<P, NW, TAPS, TWO, TG, F16>), LDS_LIMIT);
-        if (rc)
-            return rc;
-    }
-    const int blocks_max = kimg_window_cus_now();
-    int64_t vis_per_block = (num_vis + blocks_max - 1) / blocks_max;
-    vis_per_block = (vis_per_block + 63) / 64 * 64;
-    if (vis_per_block < 64 * NW)
-        vis_per_block = 64 * NW;
-    const int blocks = (int) ((num_vis + vis_per_block - 1) / vis_per_block);
-    // long launches: work by the chunk (see batch_pos in the kernel)
-    const int64_t waves = (int64_t) blocks * NW;
 // (512 until round 3: on a W-slice of the resident store -- 6-7 M records, three chunks of ~700 per
 // wave -- the waves' last chunks ended up to 170 us apart; 256 measures 4-6 % faster there, 384 / 192 /
 // 128 do not; a chunk's end costs the degridder no flush, only a window reload)
@@ -696,18 +605,77 @@ int launch(const float *grid, int64_t row_stride, int64_t pol_stride, int Gg, co
 #ifndef KIMG_DEGRID_MAX_PARTS
 #define KIMG_DEGRID_MAX_PARTS 32
 #endif
-    int64_t parts = num_vis / (waves * KIMG_DEGRID_MIN_CHUNK);
-    parts = parts > KIMG_DEGRID_MAX_PARTS ? KIMG_DEGRID_MAX_PARTS : parts;
-    int64_t chunk = 0;
-    if (parts >= 2)
-        chunk = ((num_vis + waves * parts - 1) / (waves * parts) + 63) / 64 * 64;
-    unsigned long long *queue = chunk > 0 ? tls_queue : nullptr;
+
+// What every launch of one kimg_degrid_mfma call over (up to) two polarizations is given
+struct degrid_call {
+    const float *g;                 // (the first of these polarizations)
+    int64_t row_stride, pol_stride;
+    int Gg;
+    const int16_t *uv, *w_plane;
+    const float *weights;
+    float *vis;
+    int64_t num_vis;
+    const float2 *kern;
+    int W, OV, p_total;             // (p_total: polarizations per record of the stream)
+    hipStream_t stream;
+    window_tail tail;
+};
+
+template <int P, int NW, int TAPS, bool TWO, bool TG, bool F16>
+int launch(const degrid_call &c, const tap_split &ts)
+{
+    const size_t lds = TG ? lds_bytes(NW, 0, 0, TAPS) + (size_t) NW * 2 * BATCH * 272
+                          : lds_bytes(NW, c.W, c.OV, TAPS, TWO ? 2 : 1);
+    const unsigned *tab_max = (TG && F16) ? c.tail.tab_max : nullptr;
+    if (TG) {
+        // [rows][32] zero-padded taps (256-byte rows)
+        const int rows = c.W * c.OV;
+        auto pad = [&](int tap0, int Kp, float2 *out) {
+            pad_table_kernel<32><<<kimg_divup(rows * 32, 256), 256, 0, c.stream>>>(
+                c.kern, rows, ts.K, tap0, Kp, out);
+        };
+        if (const int rc = window_tables_to_hbm(c.tail, c.kern, rows, 32, ts, TWO, F16, c.stream, pad))
+            return rc;
+    }
+    if (const int rc = kimg_dynamic_lds(
+            reinterpret_cast<const void *>(&degrid_mfma_kernel<P, NW, TAPS, TWO, TG, F16>), LDS_LIMIT))
+        return rc;
+    // one block per CU; long launches in chunks of at least KIMG_DEGRID_MIN_CHUNK visibilities, up
+    // to KIMG_DEGRID_MAX_PARTS per wave
+    const window_partition part = window_partition_of(
+        c.num_vis, NW, kimg_window_cus_now(), KIMG_DEGRID_MIN_CHUNK, KIMG_DEGRID_MAX_PARTS, false);
+    unsigned long long *queue = part.chunk > 0 ? c.tail.queue : nullptr;
     if (queue != nullptr)
-        KIMG_HIP(hipMemsetAsync(queue, 0, sizeof(unsigned long long), stream));
-    degrid_mfma_kernel<P, NW, TAPS, TWO, TG, F16><<<blocks, NW * 64, lds, stream>>>(
-        grid, row_stride, pol_stride, Gg, uv, w_plane, weights, vis, num_vis, kern, W, OV, ts,
-        vis_per_block, p_total, padded, tab_max, chunk, queue);
+        KIMG_HIP(hipMemsetAsync(queue, 0, sizeof(unsigned long long), c.stream));
+    degrid_mfma_kernel<P, NW, TAPS, TWO, TG, F16><<<part.blocks, NW * 64, lds, c.stream>>>(
+        c.g, c.row_stride, c.pol_stride, c.Gg, c.uv, c.w_plane, c.weights, c.vis, c.num_vis, c.kern,
+        c.W, c.OV, ts, part.vis_per_block, c.p_total, c.tail.padded, tab_max, part.chunk, queue);
     return kimg_launch_status();
+}
+
+// The kernel of a launch, but for its arithmetic form
+template <int TAPS_, bool TWO_, bool TG_>
+struct degrid_leaf {
+    static constexpr int TAPS = TAPS_;
+    static constexpr bool TWO = TWO_, TG = TG_;
+};
+
+// f(degrid_leaf) for one tap block; `two`: an off-diagonal block, with a table for the row taps
+// and one for the column taps.
+template <class F>
+int degrid_choose_leaf(bool two, int W, int OV, F &&f)
+{
+    auto fits = [&](int taps, int tables) { return lds_bytes(12, W, OV, taps, tables) <= LDS_LIMIT; };
+    // two tables: single rows in LDS if both fit, else in HBM
+    if (two)
+        return fits(32, 2) ? f(degrid_leaf<32, true, false>{}) : f(degrid_leaf<32, true, true>{});
+    // one table (a diagonal block of a wide kernel is handled exactly like a narrow kernel):
+    // doubled rows in LDS, single rows in LDS, or in HBM (each wave caches the rows it needs)
+    if (fits(64, 1))
+        return f(degrid_leaf<64, false, false>{});
+    if (fits(32, 1))
+        return f(degrid_leaf<32, false, false>{});
+    return f(degrid_leaf<32, false, true>{});
 }
 
 } // namespace
@@ -723,8 +691,8 @@ bool kimg_degrid_mfma_supported(int P, int w_planes, int oversample, int kernel_
            && (int64_t) w_planes * oversample < 65536;        // row index packed in 16 bits
 }
 
-// Scratch: the padded HBM copy of the table (none when the tables fit LDS) and a tail of 256
-// bytes (table maximum of the fp16 form at its start, the chunk counter of long launches 128 bytes in).
+// Scratch: the padded HBM copy of the table (none when the tables fit LDS) and the tail of 256
+// bytes (window_tail, kimg_window_launch.h).
 size_t kimg_degrid_mfma_workspace_bytes(int P, int w_planes, int oversample, int kernel_width)
 {
     if (!kimg_degrid_mfma_supported(P, w_planes, oversample, kernel_width))
@@ -740,88 +708,43 @@ int kimg_degrid_mfma(const void *grid, int64_t grid_row_stride, int64_t grid_pol
                      int w_planes, int oversample, int kernel_width, void *workspace,
                      size_t workspace_bytes, int arith, hipStream_t stream)
 {
-    const bool f16 = arith == KIMG_ARITH_SPLIT_FP16;
     const bool in_lds = tables_fit_lds(w_planes, oversample, kernel_width);
     if (!in_lds && (workspace == nullptr
                     || workspace_bytes < kimg_degrid_mfma_workspace_bytes(P, w_planes, oversample,
                                                                          kernel_width)))
         return KIMG_EWORKSPACE;
-    unsigned char *padded = static_cast<unsigned char *>(workspace);
-    tls_queue = (workspace != nullptr && workspace_bytes >= 256)
-        ? reinterpret_cast<unsigned long long *>(padded + workspace_bytes - 128) : nullptr;
-    const int K = kernel_width;
-    const bool wide = K > WIN;
-    const int Kh = wide ? (K + 1) / 2 : K;
-    const int nblk = wide ? 2 : 1;
+    const window_tail tail = window_tail_of(workspace, workspace_bytes);
     // instantiated for 1 and 2 polarizations; 3 or 4 run as 2 + 1 / 2 + 2 (register budget)
     for (int p0 = 0; p0 < P; p0 += 2) {
-        const int pn = P - p0 >= 2 ? 2 : 1;
-        const float *g = (const float *) grid + 2 * p0 * grid_pol_stride;
-        for (int jb = 0; jb < nblk; jb++)
-            for (int kb = 0; kb < nblk; kb++) {
-                tap_split ts;
-                ts.K = K;
-                ts.tv0 = jb * Kh;
-                ts.Kv = jb ? K - Kh : Kh;
-                ts.tu0 = kb * Kh;
-                ts.Ku = kb ? K - Kh : Kh;
-                int rc;
-#define LAUNCH(PP, NWV, TAPSV, TWOV) rc = launch<PP, NWV, TAPSV, TWOV>(g, grid_row_stride, \
-        grid_pol_stride, grid_size, uv, w_plane, weights + p0, (float *) vis + 2 * p0, num_vis, \
-        (const float2 *) convolve_kernel, w_planes, oversample, ts, P, stream)
-                const bool doubled = lds_bytes(12, w_planes, oversample, 64) <= LDS_LIMIT;
-#define LAUNCH_TG(PP, NWV, TAPSV, TWOV) do { if (f16_tg) rc = launch<PP, NWV, TAPSV, TWOV, true, true>(g, \
-        grid_row_stride, grid_pol_stride, grid_size, uv, w_plane, weights + p0, (float *) vis + 2 * p0, \
-        num_vis, (const float2 *) convolve_kernel, w_planes, oversample, ts, P, stream, padded, \
-        tab_max_offset); else rc = launch<PP, NWV, TAPSV, TWOV, true, false>(g, grid_row_stride, \
-        grid_pol_stride, grid_size, uv, w_plane, weights + p0, (float *) vis + 2 * p0, num_vis, \
-        (const float2 *) convolve_kernel, w_planes, oversample, ts, P, stream, padded, 0); } while (0)
-                const bool f16_tg = f16;
-                const size_t tab_max_offset = workspace_bytes >= 256 ? workspace_bytes - 256 : 0;
-                // Diagonal blocks of a wide kernel use the same taps for rows and columns: one
-                // table, handled exactly like a narrow kernel's.
-                const bool two = wide && jb != kb;
-                const bool single_in_lds = lds_bytes(12, w_planes, oversample, 32) <= LDS_LIMIT;
-                if (two) {
-                    if (!in_lds) {
-                        if (pn == 1) LAUNCH_TG(1, 12, 32, true); else LAUNCH_TG(2, 8, 32, true);
-                    } else {
-                        if (pn == 1) LAUNCH(1, 12, 32, true); else LAUNCH(2, 8, 32, true);
-                    }
-                } else if (!single_in_lds) {
-                    if (pn == 1) LAUNCH_TG(1, 12, 32, false); else LAUNCH_TG(2, 8, 32, false);
-                } else if (pn == 1) {
-                    // KIMG_ARITH_SPLIT_FP16: fp16 hi/lo form (two window rows per matrix instruction)
-                    if (f16) {
-                        if (doubled)
-                            rc = launch<1, 12, 64, false, false, true>(g, grid_row_stride, grid_pol_stride,
-                                grid_size, uv, w_plane, weights + p0, (float *) vis + 2 * p0, num_vis,
-                                (const float2 *) convolve_kernel, w_planes, oversample, ts, P, stream);
-                        else
-                            rc = launch<1, 12, 32, false, false, true>(g, grid_row_stride, grid_pol_stride,
-                                grid_size, uv, w_plane, weights + p0, (float *) vis + 2 * p0, num_vis,
-                                (const float2 *) convolve_kernel, w_planes, oversample, ts, P, stream);
-                    } else if (doubled) LAUNCH(1, 12, 64, false); else LAUNCH(1, 12, 32, false);
-                } else {
-                    if (f16) {
-                        if (doubled)
-                            rc = launch<2, 8, 64, false, false, true>(g, grid_row_stride, grid_pol_stride,
-                                grid_size, uv, w_plane, weights + p0, (float *) vis + 2 * p0, num_vis,
-                                (const float2 *) convolve_kernel, w_planes, oversample, ts, P, stream);
-                        else
-                            rc = launch<2, 8, 32, false, false, true>(g, grid_row_stride, grid_pol_stride,
-                                grid_size, uv, w_plane, weights + p0, (float *) vis + 2 * p0, num_vis,
-                                (const float2 *) convolve_kernel, w_planes, oversample, ts, P, stream);
-                    } else if (doubled) LAUNCH(2, 8, 64, false); else LAUNCH(2, 8, 32, false);
-                }
-#undef LAUNCH
-#undef LAUNCH_TG
-                if (rc)
-                    return rc;
-            }
+        const bool one_pol = P - p0 < 2;
+        const degrid_call c = {
+            (const float *) grid + 2 * p0 * grid_pol_stride, grid_row_stride, grid_pol_stride,
+            grid_size, uv, w_plane, weights + p0, (float *) vis + 2 * p0, num_vis,
+            (const float2 *) convolve_kernel, w_planes, oversample, P, stream, tail};
+        const int rc = kimg_for_tap_blocks(kernel_width, [&](const tap_split &ts, bool two) {
+            return degrid_choose_leaf(two, w_planes, oversample, [&](auto leaf) {
+                using L = decltype(leaf);
+                // 12-wave blocks for one polarization, 8-wave blocks for two
+                auto go = [&](auto f16) {
+                    constexpr bool F16 = decltype(f16)::value;
+                    return one_pol ? launch<1, 12, L::TAPS, L::TWO, L::TG, F16>(c, ts)
+                                   : launch<2, 8, L::TAPS, L::TWO, L::TG, F16>(c, ts);
+                };
+                // KIMG_ARITH_SPLIT_FP16: the fp16 hi/lo form (two window rows per matrix
+                // instruction) -- except for a wide kernel's off-diagonal blocks with both tables
+                // in LDS, which run the exact fp32 form whatever `arith` says (the fp16 form has
+                // never been instantiated for two tables in LDS).
+                if constexpr (L::TWO && !L::TG)
+                    return go(std::false_type{});
+                else
+                    return arith == KIMG_ARITH_SPLIT_FP16 ? go(std::true_type{}) : go(std::false_type{});
+            });
+        });
+        if (rc)
+            return rc;
     }
     return 0;
 }
 
 // (kimg_preload, api.hip)
-KIMG_PRELOAD_THIS_UNIT(dg_table_max_kernel)
+KIMG_PRELOAD_THIS_UNIT(pad_table_kernel<32>)

@@ -44,7 +44,7 @@
 //    KIMG_ARITH_NO_FOLD switches it off.
 // Algorithmic work per visibility: 8*K*K*P flop (complex MAC per tap) + 6*K*P (a-vector);
 // executed: 2 MFMA x 2048 MAC per visibility per polarization (32x32 window).
-#include "kimg_common.h"
+#include "kimg_window_launch.h"
 #include <limits.h>
 #include <string.h>
 #include <type_traits>
@@ -53,8 +53,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int WIN = 32;
 
 // Accumulators of one 32x32 window of complex cells, as two MFMA tiles of 32 rows x 16
 // complex columns with (re, im) interleaved along the MFMA N dimension:
@@ -278,19 +276,11 @@ __device__ inline int group8_max(int v)
     return v;
 }
 
-// Kernel widths above 32 are gridded as 2 x 2 blocks of taps, one launch per block: the
-// launch handles row taps [tv0, tv0 + Kv) and column taps [tu0, tu0 + Ku) of the K-tap kernel
-// (each at most 32 wide), which is itself a gridding with a narrower kernel and a shifted
-// origin.  Off-diagonal blocks need different row and column taps, hence TWO tables in LDS.
-struct tap_split {
-    int K;              // full kernel width (row stride of the table in HBM, uv_bias)
-    int tv0, Kv;        // row (v) taps of this launch
-    int tu0, Ku;        // column (u) taps of this launch
-};
-
+// TWO: an off-diagonal tap block of a kernel wider than 32 (tap_split, kimg_window_launch.h), with
+// a table for the row taps and one for the column taps; such a launch always reads them from HBM.
 // TG: the padded table(s) do not fit LDS (many W planes: the reference's default w-step gives
 // hundreds per slice) and are read from a zero-padded copy in HBM instead ([rows][32] taps,
-// built per call by pad_table_kernel; served by L1/L2 -- rows recur along a track).  Everything
+// built per call by pad_table_kernel / pad_table_f16_kernel; served by L1/L2 -- rows recur along a track).  Everything
 // else is unchanged; only the operand reads are global loads.
 // ---- fp16 hi/lo formulation (F16 = true) ------------------------------------------------------
 // Each fp32 operand x is carried as two halfs, hi = fp16(x) and lo = fp16(x - hi) (22 bits), and
@@ -381,14 +371,14 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
 #ifdef KIMG_GRID_TIMING
     const long long t_begin = wall_clock64();
 #endif
-    static_assert(!TWO || ROW == 32 || TG, "two tables only fit LDS with single rows");
+    static_assert(!TWO || TG, "two tables are read from HBM");
     static_assert(!F16 || SUB % 2 == 0, "fp16 form: visibilities go in pairs");
     static_assert(!PAIR || (!F16 && SUB % 2 == 0), "pair form: float32, visibilities go in pairs");
     extern __shared__ __align__(16) unsigned char smem[];
     const int table_rows = W * OV;
     const int table_bytes = table_rows * ROW * (int) sizeof(float2);
     const int u_table = TWO ? table_bytes : 0;           // byte offset of the column-tap table
-    unsigned char *rec_base = smem + (TG ? 0 : (size_t) table_bytes * (TWO ? 2 : 1));
+    unsigned char *rec_base = smem + (TG ? 0 : (size_t) table_bytes);
     // wave index: uniform by construction, but the compiler must be told (readfirstlane),
     // or every loop below is lowered to divergent (exec-masked) control flow
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -576,15 +566,12 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
             }
         }
     };
-    if (!TG) {
+    if (!TG)
         stage_table(smem, ts.tv0, ts.Kv);
-        if (TWO)
-            stage_table(smem + table_bytes, ts.tu0, ts.Ku);
-    }
     __syncthreads();
     float S_scale = 1.0f;
     if (F16 && TG) {
-        // table in HBM: already split by pad_table_kernel, with S from the same maximum
+        // table in HBM: already split by pad_table_f16_kernel, with S from the same maximum
         const unsigned m = *tab_max;
         const int e = (int) (m >> 23) - 127;
         S_scale = m ? __uint_as_float((unsigned) (13 - e + 127) << 23) : 1.0f;
@@ -592,7 +579,7 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
         // largest |component| of the table -> S, then every tap is split in place
         unsigned *s_tabmax = reinterpret_cast<unsigned *>(rec_base);   // (staging area, not yet in use)
         const unsigned *words = reinterpret_cast<const unsigned *>(smem);
-        const int nwords = table_bytes * (TWO ? 2 : 1) / 4;
+        const int nwords = table_bytes / 4;
         unsigned m = 0;
         for (int i = threadIdx.x; i < nwords; i += NW * 64)
             m = max(m, words[i] & 0x7fffffffu);
@@ -1333,48 +1320,24 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
 #endif
 }
 
-template <int P>
-constexpr int waves_per_block()
-{
-    return 8;
-}
-
-// Zero-padded copy of taps [tap0, tap0 + Kp) of every table row: [rows][ROW] float2 (ROW = 64:
-// the 32 taps twice).
-// F16: taps scaled by S (from the largest |component| of the whole table, *tab_max) and split
-// into fp16 hi/lo pairs, as the kernel does in LDS for tables that live there.
-template <int ROW, bool F16 = false>
-__global__ __launch_bounds__(256) void pad_table_kernel(
+// The fp16 form's tables in HBM: pad_table_kernel (kimg_window_launch.h) with the taps scaled by S
+// (from the largest |component| of the whole table, *tab_max) and split into fp16 hi/lo pairs, as
+// the kernel does in LDS for tables that live there.
+template <int ROW>
+__global__ __launch_bounds__(256) void pad_table_f16_kernel(
     const float2 *__restrict__ kern, int rows, int K, int tap0, int Kp, float2 *__restrict__ out,
-    const unsigned *__restrict__ tab_max = nullptr)
+    const unsigned *__restrict__ tab_max)
 {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= rows * ROW)
         return;
     const int row = idx / ROW, t = idx & 31;
-    float2 v = t < Kp ? kern[(int64_t) row * K + tap0 + t] : make_float2(0.0f, 0.0f);
-    if (F16) {
-        const unsigned m = *tab_max;
-        const int e = (int) (m >> 23) - 127;
-        const float S = m ? __uint_as_float((unsigned) (13 - e + 127) << 23) : 1.0f;
-        const uint2 t = split_tap(v.x * S, v.y * S);
-        v = make_float2(__uint_as_float(t.x), __uint_as_float(t.y));
-    }
-    out[idx] = v;
-}
-
-__global__ __launch_bounds__(256) void table_max_kernel(const float *__restrict__ kern, int64_t n,
-                                                         unsigned *__restrict__ out)
-{
-    unsigned m = 0;
-    for (int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x; i < n;
-         i += (int64_t) gridDim.x * blockDim.x)
-        m = max(m, __float_as_uint(kern[i]) & 0x7fffffffu);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        m = max(m, (unsigned) __shfl_xor((int) m, off, WAVE));
-    if ((threadIdx.x & 63) == 0 && m)
-        atomicMax(out, m);
+    const float2 v = t < Kp ? kern[(int64_t) row * K + tap0 + t] : make_float2(0.0f, 0.0f);
+    const unsigned m = *tab_max;
+    const int e = (int) (m >> 23) - 127;
+    const float S = m ? __uint_as_float((unsigned) (13 - e + 127) << 23) : 1.0f;
+    const uint2 split = split_tap(v.x * S, v.y * S);
+    out[idx] = make_float2(__uint_as_float(split.x), __uint_as_float(split.y));
 }
 
 size_t lds_bytes(int P, int NW, int W, int OV, int row, int tables = 1)
@@ -1383,7 +1346,6 @@ size_t lds_bytes(int P, int NW, int W, int OV, int row, int tables = 1)
            + (size_t) NW * 64 * (sizeof(int2) + P * sizeof(float4) + sizeof(int2));
 }
 
-constexpr size_t LDS_LIMIT = 160 * 1024;
 // (512 until round 3; 384 measures 3-4 % faster on launches of ~7 M records -- a W-slice of the
 // re-ordered resident store, where a wave only gets four or five chunks and the tail of the launch
 // is one chunk long -- and the same on 50 M-record launches, whose chunks the cap below sets)
@@ -1396,93 +1358,114 @@ constexpr size_t LDS_LIMIT = 160 * 1024;
 constexpr int64_t INTERLEAVE_MIN_CHUNK = KIMG_INTERLEAVE_MIN_CHUNK;     // visibilities: bounds the extra window flushes
 constexpr int64_t INTERLEAVE_MAX_PARTS = KIMG_INTERLEAVE_MAX_PARTS;
 
-template <int P, int ROW, int NW, bool TWO, bool TG = false, bool F16 = false, bool PAIR = false>
-int launch(float *grid, int64_t row_stride, int64_t pol_stride, int Gg, const float *wg,
-           int64_t wg_row_stride, int64_t wg_pol_stride, const int16_t *uv,
-           const int16_t *w_plane, const float2 *vis, int64_t num_vis, const float2 *kern,
-           int W, int OV, const tap_split &ts, int p_total, hipStream_t stream,
-           unsigned char *padded = nullptr, size_t tab_max_offset = 0,
-           unsigned long long *queue = nullptr, bool fold = true)
+// What every launch of one kimg_grid_mfma call over (up to) two polarizations is given
+struct grid_call {
+    float *g;                       // (the first of these polarizations)
+    int64_t row_stride, pol_stride;
+    int Gg;
+    const float *wg;
+    int64_t wg_row_stride, wg_pol_stride;
+    const int16_t *uv, *w_plane;
+    const float2 *vis;
+    int64_t num_vis;
+    const float2 *kern;
+    int W, OV, p_total;             // (p_total: polarizations per record of the stream)
+    hipStream_t stream;
+    window_tail tail;
+    bool fold;
+};
+
+template <int P, int ROW, int NW, bool TWO, bool TG, bool F16, bool PAIR>
+int launch(const grid_call &c, const tap_split &ts)
 {
+    static_assert(!TWO || TG, "off-diagonal tap blocks read their two tables from HBM");
     constexpr int SUB = (P == 1 && NW <= 12) ? 4 : 2;       // pipeline depth bounded by the VGPR budget
-    const size_t lds = TG ? lds_bytes(P, NW, 0, 0, ROW) : lds_bytes(P, NW, W, OV, ROW, TWO ? 2 : 1);
-    unsigned *tab_max = nullptr;
+    const size_t lds = TG ? lds_bytes(P, NW, 0, 0, ROW) : lds_bytes(P, NW, c.W, c.OV, ROW);
+    const unsigned *tab_max = (TG && F16) ? c.tail.tab_max : nullptr;
     if (TG) {
-        // the padded table(s) of this launch: row taps first, column taps behind them
-        const int rows = W * OV;
-        float2 *out = reinterpret_cast<float2 *>(padded);
-        if (F16) {
-            // (the last 256 bytes of the workspace hold the table maximum)
-            tab_max = reinterpret_cast<unsigned *>(padded + tab_max_offset);
-            KIMG_HIP(hipMemsetAsync(tab_max, 0, sizeof(unsigned), stream));
-            const int64_t n = (int64_t) rows * ts.K * 2;
-            table_max_kernel<<<kimg_divup(n, 256 * 8), 256, 0, stream>>>(
-                reinterpret_cast<const float *>(kern), n, tab_max);
-        }
-        pad_table_kernel<ROW, F16><<<kimg_divup(rows * ROW, 256), 256, 0, stream>>>(
-            kern, rows, ts.K, ts.tv0, ts.Kv, out, tab_max);
-        if (TWO)
-            pad_table_kernel<ROW, F16><<<kimg_divup(rows * ROW, 256), 256, 0, stream>>>(
-                kern, rows, ts.K, ts.tu0, ts.Ku, out + (size_t) rows * ROW, tab_max);
-    }
-    {
-        const int rc = kimg_dynamic_lds(
-            reinterpret_cast<const void *>(&grid_mfma_kernel<P, NW, SUB, ROW, TWO, TG, F16, PAIR>), LDS_LIMIT);
-        if (rc)
+        const int rows = c.W * c.OV;
+        auto pad = [&](int tap0, int Kp, float2 *out) {
+            if (F16)
+                pad_table_f16_kernel<ROW><<<kimg_divup(rows * ROW, 256), 256, 0, c.stream>>>(
+                    c.kern, rows, ts.K, tap0, Kp, out, tab_max);
+            else
+                pad_table_kernel<ROW><<<kimg_divup(rows * ROW, 256), 256, 0, c.stream>>>(
+                    c.kern, rows, ts.K, tap0, Kp, out);
+        };
+        if (const int rc = window_tables_to_hbm(c.tail, c.kern, rows, ROW, ts, TWO, F16, c.stream, pad))
             return rc;
     }
+    if (const int rc = kimg_dynamic_lds(
+            reinterpret_cast<const void *>(&grid_mfma_kernel<P, NW, SUB, ROW, TWO, TG, F16, PAIR>), LDS_LIMIT))
+        return rc;
     // bits 8-15: span stagger of a SIMD's waves, percent.  Bits 0-1 (test builds with
     // -DKIMG_NO_ATOMICS, the counterpart of the reference's NO_ATOMICS switch,
     // imager_kernels/atomic.mako:29-40): no end flush / no window flushes -- wrong results, for
     // measuring what the float atomics cost.  Bit 2: runs of records with one sub-cell are NOT folded
     // (KIMG_ARITH_NO_FOLD).
 #ifdef KIMG_NO_ATOMICS
-    const int dbg = (12 << 8) | 3 | (fold ? 0 : 4);
+    const int dbg = (12 << 8) | 3 | (c.fold ? 0 : 4);
 #else
-    const int dbg = (12 << 8) | (fold ? 0 : 4);
+    const int dbg = (12 << 8) | (c.fold ? 0 : 4);
 #endif
-    // as many blocks resident per CU as the LDS (kernel table + staging) allows;
-    // every block streams a contiguous span (a multiple of 64).
+    // as many blocks resident per CU as the LDS (kernel table + staging) allows.  Long launches:
+    // chunks of at least INTERLEAVE_MIN_CHUNK visibilities, up to INTERLEAVE_MAX_PARTS per wave
     const int per_cu = (!TG && lds <= LDS_LIMIT / 2) ? 2 : 1;
-    const int blocks_max = kimg_window_cus_now() * per_cu;
-    int64_t vis_per_block = (num_vis + blocks_max - 1) / blocks_max;
-    vis_per_block = (vis_per_block + 63) / 64 * 64;
-    if (vis_per_block < 64 * NW)
-        vis_per_block = 64 * NW;
-    const int blocks = (int) ((num_vis + vis_per_block - 1) / vis_per_block);
-    // Long launches: every wave takes its work from up to 16 places of the stream (chunks of at
-    // least ~1000 visibilities, see batch_pos in the kernel) instead of one contiguous range
-    const int64_t waves = (int64_t) blocks * NW;
-    int64_t parts = num_vis / (waves * INTERLEAVE_MIN_CHUNK);
-    parts = parts > INTERLEAVE_MAX_PARTS ? INTERLEAVE_MAX_PARTS : parts;
-    int64_t chunk = 0;
-    if (parts >= 2)
-        chunk = ((num_vis + waves * parts - 1) / (waves * parts) + 63) / 64 * 64;
-    // chunk numbers are scrambled by a multiplier coprime to their count
-    int64_t scramble = 1;
-    if (chunk > 0) {
-        const int64_t total = (num_vis + chunk - 1) / chunk;
-        static const int64_t primes[] = {7919, 7907, 7901, 7883, 7879, 7877, 7873};
-        for (int64_t m : primes)
-            if (total % m != 0) {
-                scramble = m;
-                break;
-            }
-    }
-    if (chunk > 0 && queue != nullptr)
-        KIMG_HIP(hipMemsetAsync(queue, 0, sizeof(unsigned long long), stream));
-    grid_mfma_kernel<P, NW, SUB, ROW, TWO, TG, F16, PAIR><<<blocks, NW * 64, lds, stream>>>(
-        grid, row_stride, pol_stride, Gg, wg, wg_row_stride, wg_pol_stride, uv, w_plane, vis,
-        num_vis, kern, W, OV, ts, vis_per_block, p_total, dbg, padded, tab_max, chunk, scramble,
-        chunk > 0 ? queue : nullptr);
+    const window_partition part = window_partition_of(
+        c.num_vis, NW, kimg_window_cus_now() * per_cu, INTERLEAVE_MIN_CHUNK, INTERLEAVE_MAX_PARTS, true);
+    unsigned long long *queue = part.chunk > 0 ? c.tail.queue : nullptr;
+    if (queue != nullptr)
+        KIMG_HIP(hipMemsetAsync(queue, 0, sizeof(unsigned long long), c.stream));
+    grid_mfma_kernel<P, NW, SUB, ROW, TWO, TG, F16, PAIR><<<part.blocks, NW * 64, lds, c.stream>>>(
+        c.g, c.row_stride, c.pol_stride, c.Gg, c.wg, c.wg_row_stride, c.wg_pol_stride, c.uv, c.w_plane,
+        c.vis, c.num_vis, c.kern, c.W, c.OV, ts, part.vis_per_block, c.p_total, dbg, c.tail.padded,
+        tab_max, part.chunk, part.scramble, queue);
     return kimg_launch_status();
+}
+
+// The kernel of a launch, but for its arithmetic form
+template <int P_, int ROW_, int NW_, bool TWO_, bool TG_>
+struct grid_leaf {
+    static constexpr int P = P_, ROW = ROW_, NW = NW_;
+    static constexpr bool TWO = TWO_, TG = TG_;
+};
+
+// f(grid_leaf) for a launch over pn (1 or 2) polarizations of one tap block; `two`: an off-diagonal
+// block, whose two tables are in HBM whatever their size; `in_lds`: where the one table of any other
+// block is.
+template <class F>
+int grid_choose_leaf(int pn, bool two, bool in_lds, int W, int OV, F &&f)
+{
+    auto fits = [&](int P, int NW, int row) { return lds_bytes(P, NW, W, OV, row) <= LDS_LIMIT; };
+    // tables in HBM: doubled rows (5 % faster than single rows), 12-wave blocks (P = 1) as for the
+    // LDS form
+    if (two)
+        return pn == 1 ? f(grid_leaf<1, 64, 12, true, true>{}) : f(grid_leaf<2, 64, 8, true, true>{});
+    if (!in_lds)
+        return pn == 1 ? f(grid_leaf<1, 64, 12, false, true>{}) : f(grid_leaf<2, 64, 8, false, true>{});
+    // table in LDS: doubled rows when they leave room for the staging area, single rows otherwise
+    if (pn == 2)
+        return fits(2, 8, 64) ? f(grid_leaf<2, 64, 8, false, false>{})
+                              : f(grid_leaf<2, 32, 8, false, false>{});
+    // 12-wave blocks, one per CU (LDS-bound), when the doubled table leaves room
+#ifdef KIMG_GRID_NW16
+    if (fits(1, 16, 64))
+        return f(grid_leaf<1, 64, 16, false, false>{});
+#endif
+    if (fits(1, 12, 64))
+        return f(grid_leaf<1, 64, 12, false, false>{});
+    if (fits(1, 8, 64))
+        return f(grid_leaf<1, 64, 8, false, false>{});
+    return f(grid_leaf<1, 32, 8, false, false>{});
 }
 
 } // namespace
 
 // The kernels are instantiated for 1 and 2 polarizations (32 accumulator registers each keep
 // two waves per SIMD without spills); 3 or 4 polarizations run as 2 + 1 / 2 + 2.  Kernel widths
-// 33..64 run as 2 x 2 tap blocks with two single-row tables in LDS.
+// 33..64 run as 2 x 2 tap blocks: the diagonal blocks like a narrow kernel, with one single-row or
+// doubled table in LDS when it fits, the off-diagonal ones with two doubled tables in HBM.  Their
+// workspace is sized by whether two single-row tables would fit LDS:
 static bool tables_fit_lds(int P, int w_planes, int oversample, int kernel_width)
 {
     const int tables = kernel_width > WIN ? 2 : 1;
@@ -1504,10 +1487,8 @@ static bool table_in_lds(int P, int w_planes, int oversample, int kernel_width)
     return tables_fit_lds(P, w_planes, oversample, kernel_width) && kernel_width <= WIN;
 }
 
-// Scratch: the padded table copy (none when the kernel reads its table from LDS) and a tail of 256
-// bytes -- the table's maximum (fp16 form, tables in HBM) at its start, the chunk counter of long
-// launches 128 bytes in.  (A caller that gives a kernel with its table in LDS no scratch still
-// works: its waves then take their chunks in a fixed order.)
+// Scratch: the padded table copy (none when the kernel reads its table from LDS) and the tail of
+// 256 bytes (window_tail, kimg_window_launch.h).
 size_t kimg_grid_mfma_workspace_bytes(int P, int w_planes, int oversample, int kernel_width)
 {
     if (!kimg_grid_mfma_supported(P, w_planes, oversample, kernel_width))
@@ -1526,97 +1507,37 @@ int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
 {
     const bool fold = !(arith & KIMG_ARITH_NO_FOLD);
     arith &= ~KIMG_ARITH_NO_FOLD;
-    const bool f16 = arith == KIMG_ARITH_SPLIT_FP16;
-    const bool pair = arith == KIMG_ARITH_FP32;         // (KIMG_ARITH_FP32_32X32: one visibility per instruction)
     const bool in_lds = table_in_lds(P, w_planes, oversample, kernel_width);
     if (!in_lds && (workspace == nullptr
                     || workspace_bytes < kimg_grid_mfma_workspace_bytes(P, w_planes, oversample,
                                                                        kernel_width)))
         return KIMG_EWORKSPACE;
-    unsigned char *padded = static_cast<unsigned char *>(workspace);
-    unsigned long long *queue = (workspace != nullptr && workspace_bytes >= 256)
-        ? reinterpret_cast<unsigned long long *>(padded + workspace_bytes - 128) : nullptr;
-    const int K = kernel_width;
-    const bool wide = K > WIN;
-    const int Kh = wide ? (K + 1) / 2 : K;              // taps per block along one axis
-    const int nblk = wide ? 2 : 1;
+    const window_tail tail = window_tail_of(workspace, workspace_bytes);
     for (int p0 = 0; p0 < P; p0 += 2) {
         const int pn = P - p0 >= 2 ? 2 : 1;
-        float *g = (float *) grid + 2 * p0 * grid_pol_stride;
-        const float *wg = weights_grid + p0 * wg_pol_stride;
-        const float2 *v = (const float2 *) vis + p0;
-        const float2 *kern = (const float2 *) convolve_kernel;
-        for (int jb = 0; jb < nblk; jb++)
-            for (int kb = 0; kb < nblk; kb++) {
-                tap_split ts;
-                ts.K = K;
-                ts.tv0 = jb * Kh;
-                ts.Kv = jb ? K - Kh : Kh;
-                ts.tu0 = kb * Kh;
-                ts.Ku = kb ? K - Kh : Kh;
-                int rc;
-                // GO(P, ROW, NW, TWO, TG): exact-fp32 instruction, or with KIMG_ARITH_SPLIT_FP16 the
-                // fp16 hi/lo form (two visibilities per matrix instruction)
-#define GO(PP, ROWV, NWV, TWOV, TGV) do { \
-        if (f16) rc = launch<PP, ROWV, NWV, TWOV, TGV, true>(g, grid_row_stride, grid_pol_stride, \
-            grid_size, wg, wg_row_stride, wg_pol_stride, uv, w_plane, v, num_vis, kern, w_planes, \
-            oversample, ts, P, stream, padded, tab_max_offset, queue, fold); \
-        else if (pair) rc = launch<PP, ROWV, NWV, TWOV, TGV, false, true>(g, grid_row_stride, \
-            grid_pol_stride, grid_size, wg, wg_row_stride, wg_pol_stride, uv, w_plane, v, num_vis, \
-            kern, w_planes, oversample, ts, P, stream, padded, tab_max_offset, queue, fold); \
-        else rc = launch<PP, ROWV, NWV, TWOV, TGV, false>(g, grid_row_stride, grid_pol_stride, \
-            grid_size, wg, wg_row_stride, wg_pol_stride, uv, w_plane, v, num_vis, kern, w_planes, \
-            oversample, ts, P, stream, padded, tab_max_offset, queue, fold); } while (0)
-                const size_t tab_max_offset = workspace_bytes >= 256 ? workspace_bytes - 256 : 0;
-                // Diagonal blocks of a wide kernel take row and column taps from the same half of
-                // the table: one table, which fits LDS whenever a narrow kernel's would.
-                const bool two = wide && jb != kb;
-                const bool single_in_lds = two ? false
-                    : wide ? lds_bytes(pn, 8, w_planes, oversample, 32) <= LDS_LIMIT
-                           : in_lds;
-                if (two) {
-                    // two tables: doubled rows in HBM, 12-wave blocks (P = 1) as for the LDS form
-                    if (!in_lds) {
-                        if (pn == 1)
-                            GO(1, 64, 12, true, true);
-                        else
-                            GO(2, 64, 8, true, true);
-                    } else if (pn == 1) {
-                        if (lds_bytes(1, 12, w_planes, oversample, 32, 2) <= LDS_LIMIT)
-                            GO(1, 32, 12, true, false);
-                        else
-                            GO(1, 32, 8, true, false);
-                    } else {
-                        GO(2, 32, 8, true, false);
-                    }
-                } else if (!single_in_lds) {
-                    if (pn == 1)
-                        GO(1, 64, 12, false, true);     // doubled rows: 5 % faster than single rows
-                    else
-                        GO(2, 64, 8, false, true);
-                } else if (pn == 1) {
-                    // 12-wave blocks, one per CU (LDS-bound), when the doubled table leaves room
-#ifdef KIMG_GRID_NW16
-                    if (lds_bytes(1, 16, w_planes, oversample, 64) <= LDS_LIMIT)
-                        GO(1, 64, 16, false, false);
-                    else
-#endif
-                    if (lds_bytes(1, 12, w_planes, oversample, 64) <= LDS_LIMIT)
-                        GO(1, 64, 12, false, false);
-                    else if (lds_bytes(1, 8, w_planes, oversample, 64) <= LDS_LIMIT)
-                        GO(1, 64, 8, false, false);
-                    else
-                        GO(1, 32, 8, false, false);
-                } else {
-                    if (lds_bytes(2, 8, w_planes, oversample, 64) <= LDS_LIMIT)
-                        GO(2, 64, 8, false, false);
-                    else
-                        GO(2, 32, 8, false, false);
-                }
-#undef GO
-                if (rc)
-                    return rc;
-            }
+        const grid_call c = {
+            (float *) grid + 2 * p0 * grid_pol_stride, grid_row_stride, grid_pol_stride, grid_size,
+            weights_grid + p0 * wg_pol_stride, wg_row_stride, wg_pol_stride, uv, w_plane,
+            (const float2 *) vis + p0, num_vis, (const float2 *) convolve_kernel, w_planes,
+            oversample, P, stream, tail, fold};
+        // The one table of a wide kernel's diagonal blocks fits LDS whenever a narrow kernel's
+        // would, by the budget of this launch's polarizations.
+        const bool one_in_lds = kernel_width > WIN
+            ? lds_bytes(pn, 8, w_planes, oversample, 32) <= LDS_LIMIT : in_lds;
+        const int rc = kimg_for_tap_blocks(kernel_width, [&](const tap_split &ts, bool two) {
+            return grid_choose_leaf(pn, two, one_in_lds, w_planes, oversample, [&](auto leaf) {
+                using L = decltype(leaf);
+                // <..., F16, PAIR>: the fp16 hi/lo form or the float32 pair form (two visibilities
+                // per matrix instruction), else the exact-fp32 instruction of KIMG_ARITH_FP32_32X32
+                if (arith == KIMG_ARITH_SPLIT_FP16)
+                    return launch<L::P, L::ROW, L::NW, L::TWO, L::TG, true, false>(c, ts);
+                if (arith == KIMG_ARITH_FP32)
+                    return launch<L::P, L::ROW, L::NW, L::TWO, L::TG, false, true>(c, ts);
+                return launch<L::P, L::ROW, L::NW, L::TWO, L::TG, false, false>(c, ts);
+            });
+        });
+        if (rc)
+            return rc;
     }
     return 0;
 }
@@ -1630,4 +1551,4 @@ extern "C" int kimg_debug_grid_timing(void *buffer)
 #endif
 
 // (kimg_preload, api.hip)
-KIMG_PRELOAD_THIS_UNIT(table_max_kernel)
+KIMG_PRELOAD_THIS_UNIT(pad_table_kernel<64>)

@@ -82,6 +82,11 @@ int kimg_degrid_mfma(const void *grid, int64_t grid_row_stride, int64_t grid_pol
                      size_t workspace_bytes, int arith, hipStream_t stream);
 bool kimg_degrid_mfma_supported(int P, int w_planes, int oversample, int kernel_width);
 size_t kimg_degrid_mfma_workspace_bytes(int P, int w_planes, int oversample, int kernel_width);
+// *out = the bit pattern of the largest |component| among the n floats of a kernel table (ktable.hip):
+// the fp16 hi/lo forms of the window kernels choose their table scale from it when the table is in
+// HBM.  (Hidden: a helper between two units of the library, no part of its dynamic symbol table.)
+__attribute__((visibility("hidden")))
+int kimg_table_max(const float *kern, int64_t n, unsigned *out, hipStream_t stream);
 // ... and the float64 ones (grid_f64.hip)
 int kimg_grid_window_f64(double *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
                          int grid_size, int P, const float *weights_grid, int64_t wg_row_stride,

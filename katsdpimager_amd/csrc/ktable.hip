@@ -125,5 +125,32 @@ extern "C" int kimg_kernel_table(void *table, const double *ws, int w_planes, in
     return kimg_launch_status();
 }
 
+namespace {
+
+// Largest |component| of a table (bit pattern; *out zero beforehand), for the window kernels' fp16
+// forms with the table in HBM (kimg_window_launch.h)
+__global__ __launch_bounds__(256) void table_max_kernel(const float *__restrict__ kern, int64_t n,
+                                                         unsigned *__restrict__ out)
+{
+    unsigned m = 0;
+    for (int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x; i < n;
+         i += (int64_t) gridDim.x * blockDim.x)
+        m = max(m, __float_as_uint(kern[i]) & 0x7fffffffu);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        m = max(m, (unsigned) __shfl_xor((int) m, off, WAVE));
+    if ((threadIdx.x & 63) == 0 && m)
+        atomicMax(out, m);
+}
+
+} // namespace
+
+int kimg_table_max(const float *kern, int64_t n, unsigned *out, hipStream_t stream)
+{
+    KIMG_HIP(hipMemsetAsync(out, 0, sizeof(unsigned), stream));
+    table_max_kernel<<<kimg_divup(n, 256 * 8), 256, 0, stream>>>(kern, n, out);
+    return kimg_launch_status();
+}
+
 // (kimg_preload, api.hip)
 KIMG_PRELOAD_THIS_UNIT(kernel_table_kernel)
