@@ -12,6 +12,8 @@
  *    ends in `_host`; nothing is allocated or freed here except FFT plans;
  *  - arrays come with explicit element strides (row, polarization) exactly
  *    like the reference kernels' arguments;
+ *  - a row stride below the row's width is KIMG_EINVAL, before anything is enqueued;
+ *  - a pointer needs only the alignment of its element type unless its argument says otherwise;
  *  - `stream` is a hipStream_t (NULL = default stream); all calls are
  *    asynchronous on it and may be captured into a hipGraph unless noted;
  *  - return value: 0 on success, a negated hipError_t on a HIP failure, or a

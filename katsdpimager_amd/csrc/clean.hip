@@ -2061,7 +2061,7 @@ static int update_tiles(const float *dirty, int64_t row_stride, int64_t pol_stri
                         int tiles_y, int tile_x0, int tile_y0, int tile_x1, int tile_y1,
                         const uint8_t *mask, int64_t mask_row_stride, void *stream)
 {
-    KIMG_CHECK_ARG(dirty && tile_max && tile_pos && width > 0 && height > 0);
+    KIMG_CHECK_ARG(dirty && tile_max && tile_pos && width > 0 && height > 0 && row_stride >= width);
     KIMG_CHECK_ARG(num_polarizations >= 1 && num_polarizations <= 4 && border >= 0);
     KIMG_CHECK_ARG(tile_x0 >= 0 && tile_y0 >= 0 && tile_x1 <= tiles_x && tile_y1 <= tiles_y);
     if (tile_x0 >= tile_x1 || tile_y0 >= tile_y1)
@@ -2158,6 +2158,7 @@ extern "C" int kimg_subtract_psf(float *dirty, float *model, int64_t row_stride,
     KIMG_CHECK_ARG(patch_width > 0 && patch_height > 0 && patch_width <= psf_width
                    && patch_height <= psf_height);
     KIMG_CHECK_ARG(pos_x >= 0 && pos_x < width && pos_y >= 0 && pos_y < height);
+    KIMG_CHECK_ARG(row_stride >= width && psf_row_stride >= psf_width);
     const int psf_x0 = psf_width / 2 - patch_width / 2;     // clean.py:699-700
     const int psf_y0 = psf_height / 2 - patch_height / 2;
     dim3 g(kimg_divup(patch_width, 64), kimg_divup(patch_height, 4));
@@ -2386,6 +2387,7 @@ extern "C" int kimg_clean_major_cycles(float *dirty, float *model, int64_t row_s
     KIMG_CHECK_ARG(patch_width > 0 && patch_height > 0 && patch_width <= psf_width
                    && patch_height <= psf_height && tiles_x > 0 && tiles_y > 0);
     KIMG_CHECK_ARG(mode == KIMG_CLEAN_I || mode == KIMG_CLEAN_SUMSQ);
+    KIMG_CHECK_ARG(row_stride >= width && psf_row_stride >= psf_width);
     KIMG_CHECK_ARG(noise_threshold == noise_threshold && left_for_next == left_for_next);      // (not NaN)
     const int kind = form & 0xff;
     KIMG_CHECK_ARG(kind == KIMG_CLEAN_FORM_AUTO || kind == KIMG_CLEAN_FORM_MULTI);
@@ -2414,6 +2416,7 @@ static int clean_cycles(float *dirty, float *model, int64_t row_stride,
     KIMG_CHECK_ARG(patch_width > 0 && patch_height > 0 && patch_width <= psf_width
                    && patch_height <= psf_height && tiles_x > 0 && tiles_y > 0);
     KIMG_CHECK_ARG(mode == KIMG_CLEAN_I || mode == KIMG_CLEAN_SUMSQ);
+    KIMG_CHECK_ARG(row_stride >= width && psf_row_stride >= psf_width);
     const int components = (form >> 8) & 0xff;      // KIMG_CLEAN_FORM_MULTI: lattices per launch
     // ... and steps per lattice (0: as many as the form takes); bit 4: the repeated-steps kernel from
     // the first launch on, whatever the field looks like (tests)
@@ -2558,6 +2561,7 @@ extern "C" int kimg_clean_cycles_batch(const kimg_clean_channel *channels_in, in
     KIMG_CHECK_ARG(channels_in && num_channels >= 1 && num_channels <= KIMG_CLEAN_BATCH_MAX);
     KIMG_CHECK_ARG(num_polarizations >= 1 && num_polarizations <= 4 && tiles_x > 0 && tiles_y > 0);
     KIMG_CHECK_ARG(mode == KIMG_CLEAN_I || mode == KIMG_CLEAN_SUMSQ);
+    KIMG_CHECK_ARG(row_stride >= width && psf_row_stride >= psf_width);
     hipStream_t s = (hipStream_t) stream;
     cycle_args a;
     fill_shared(a, row_stride, pol_stride, width, height, num_polarizations, psf_row_stride,
@@ -2627,6 +2631,7 @@ extern "C" int kimg_psf_patch(const float *psf, int64_t row_stride, int64_t pol_
                               int mid_x, int mid_y, float threshold, int32_t *bound, void *stream)
 {
     KIMG_CHECK_ARG(psf && bound && num_polarizations >= 1 && max_x >= min_x && max_y >= min_y);
+    KIMG_CHECK_ARG(row_stride > max_x);     // (the call has no width: the region must fit a row)
     hipStream_t s = (hipStream_t) stream;
     KIMG_HIP(hipMemsetAsync(bound, 0, 2 * sizeof(int32_t), s));
     psf_patch_kernel<<<region_grid(max_x - min_x + 1, max_y - min_y + 1), 256, 0, s>>>(
@@ -2641,6 +2646,7 @@ extern "C" int kimg_abs_histogram(const float *image, int64_t row_stride, int64_
 {
     KIMG_CHECK_ARG(image && hist && pass >= 0 && pass <= 3 && border >= 0);
     KIMG_CHECK_ARG(width > 2 * border && height > 2 * border && num_polarizations >= 1);
+    KIMG_CHECK_ARG(row_stride >= width);
     hipStream_t s = (hipStream_t) stream;
     KIMG_HIP(hipMemsetAsync(hist, 0, 256 * sizeof(uint32_t), s));
     abs_histogram_kernel<<<region_grid(width - 2 * border, height - 2 * border, 2048), 256, 0, s>>>(
@@ -2653,7 +2659,7 @@ extern "C" int kimg_abs_count_le(const float *image, int64_t row_stride, int64_t
                                  float value, uint32_t *out, void *stream)
 {
     KIMG_CHECK_ARG(image && out && border >= 0 && num_polarizations >= 1);
-    KIMG_CHECK_ARG(width > 2 * border && height > 2 * border);
+    KIMG_CHECK_ARG(width > 2 * border && height > 2 * border && row_stride >= width);
     hipStream_t s = (hipStream_t) stream;
     static const uint32_t init[2] = {0u, 0xffffffffu};
     KIMG_HIP(hipMemcpyAsync(out, init, sizeof(init), hipMemcpyHostToDevice, s));
@@ -2833,7 +2839,7 @@ extern "C" int kimg_noise_est(const float *image, int64_t row_stride, int64_t po
                               float median_to_rms, void *scratch, float *out, void *stream)
 {
     KIMG_CHECK_ARG(image && scratch && out && border >= 0 && num_polarizations >= 1);
-    KIMG_CHECK_ARG(width > 2 * border && height > 2 * border);
+    KIMG_CHECK_ARG(width > 2 * border && height > 2 * border && row_stride >= width);
     const int64_t n64 = (int64_t) (width - 2 * border) * (height - 2 * border) * num_polarizations;
     KIMG_CHECK_ARG(n64 < ((int64_t) 1 << 32));
     const uint32_t n = (uint32_t) n64;

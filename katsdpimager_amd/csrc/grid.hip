@@ -237,6 +237,7 @@ extern "C" int kimg_grid(void *grid, int64_t grid_row_stride, int64_t grid_pol_s
                          int arith, void *stream)
 {
     KIMG_CHECK_ARG(grid && weights_grid && uv && w_plane && vis && convolve_kernel);
+    KIMG_CHECK_ARG(grid_row_stride >= grid_size && wg_row_stride >= grid_size);
     const int form = arith & ~KIMG_ARITH_NO_FOLD;       // (the window kernels take the bit themselves)
     KIMG_CHECK_ARG(form == KIMG_ARITH_FP32 || form == KIMG_ARITH_SPLIT_FP16
                    || form == KIMG_ARITH_FP32_32X32);
@@ -301,6 +302,7 @@ extern "C" int kimg_degrid(const void *grid, int64_t grid_row_stride, int64_t gr
                            size_t workspace_bytes, int variant, int arith, void *stream)
 {
     KIMG_CHECK_ARG(grid && uv && w_plane && weights && vis && convolve_kernel);
+    KIMG_CHECK_ARG(grid_row_stride >= grid_size);
     KIMG_CHECK_ARG(arith == KIMG_ARITH_FP32 || arith == KIMG_ARITH_SPLIT_FP16);
     KIMG_CHECK_ARG(variant >= 0 && (variant >> 8) <= 256);
     const kimg_window_cus_scope cus(variant >> 8);

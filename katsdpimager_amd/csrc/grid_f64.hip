@@ -399,6 +399,7 @@ extern "C" int kimg_grid_f64(void *grid, int64_t grid_row_stride, int64_t grid_p
                              int variant, void *stream)
 {
     KIMG_CHECK_ARG(grid && weights_grid && uv && w_plane && vis && convolve_kernel);
+    KIMG_CHECK_ARG(grid_row_stride >= grid_size && wg_row_stride >= grid_size);
     int rc = check_f64_args(grid_size, num_polarizations, num_vis, w_planes, oversample,
                             kernel_width, variant);
     if (rc)
@@ -446,6 +447,7 @@ extern "C" int kimg_degrid_f64(const void *grid, int64_t grid_row_stride, int64_
                                size_t workspace_bytes, int variant, void *stream)
 {
     KIMG_CHECK_ARG(grid && uv && w_plane && weights && vis && convolve_kernel);
+    KIMG_CHECK_ARG(grid_row_stride >= grid_size);
     int rc = check_f64_args(grid_size, num_polarizations, num_vis, w_planes, oversample,
                             kernel_width, variant);
     if (rc)

@@ -1003,6 +1003,7 @@ extern "C" int kimg_grid_to_layer(void *layer, int layer_size, const void *grid,
 {
     KIMG_CHECK_ARG(layer && grid && layer_size > 0 && grid_size > 0 && grid_size <= layer_size);
     KIMG_CHECK_ARG(layer_size % 2 == 0 && grid_size % 2 == 0);      // image.py:655-656
+    KIMG_CHECK_ARG(grid_row_stride >= grid_size);
     dim3 g(kimg_divup(layer_size, 256), layer_size);
     grid_to_layer_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
         (float2 *) layer, layer_size, (const float2 *) grid, grid_row_stride, grid_size);
@@ -1061,7 +1062,7 @@ extern "C" int kimg_layer_to_grid(void *grid, int64_t grid_row_stride, int grid_
                                   const void *layer, int layer_size, void *stream)
 {
     KIMG_CHECK_ARG(layer && grid && layer_size > 0 && grid_size > 0 && grid_size <= layer_size);
-    KIMG_CHECK_ARG(layer_size % 2 == 0 && grid_size % 2 == 0);
+    KIMG_CHECK_ARG(layer_size % 2 == 0 && grid_size % 2 == 0 && grid_row_stride >= grid_size);
     dim3 g(kimg_divup(grid_size, 256), grid_size);
     layer_to_grid_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
         (float2 *) grid, grid_row_stride, grid_size, (const float2 *) layer, layer_size);
@@ -1073,6 +1074,7 @@ extern "C" int kimg_layer_to_image(float *image, int64_t image_row_stride, const
                                    float lm_bias, float w, void *stream)
 {
     KIMG_CHECK_ARG(image && layer && kernel1d && size > 0 && size % 2 == 0);   // image.py:127-128
+    KIMG_CHECK_ARG(image_row_stride >= size);
     dim3 g(kimg_divup(size, 256), size);
     layer_to_image_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
         image, image_row_stride, (const float2 *) layer, size, kernel1d, lm_scale, lm_bias, w);
@@ -1083,7 +1085,8 @@ extern "C" int kimg_image_to_layer(void *layer, const float *image, int64_t imag
                                    int size, const float *kernel1d, float lm_scale,
                                    float lm_bias, float w, void *stream)
 {
-    KIMG_CHECK_ARG(image && layer && kernel1d && size > 0 && size % 2 == 0);
+    KIMG_CHECK_ARG(image && layer && kernel1d && size > 0 && size % 2 == 0
+                   && image_row_stride >= size);
     dim3 g(kimg_divup(size, 256), size);
     image_to_layer_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
         (float2 *) layer, image, image_row_stride, size, kernel1d, lm_scale, lm_bias, w);
@@ -1094,6 +1097,7 @@ extern "C" int kimg_scale(float *image, int64_t row_stride, int64_t pol_stride, 
                           int height, int num_polarizations, const float *scale_host, void *stream)
 {
     KIMG_CHECK_ARG(image && scale_host && width > 0 && height > 0);
+    KIMG_CHECK_ARG(row_stride >= width);
     if (num_polarizations < 1 || num_polarizations > 4)
         return KIMG_EUNSUPPORTED;
     scale_t<float> sc = {};
@@ -1110,6 +1114,7 @@ extern "C" int kimg_pixel_reciprocal(const float *image, int64_t row_stride, int
                                      float *out, void *stream)
 {
     KIMG_CHECK_ARG(image && out && x >= 0 && x < width && y >= 0 && y < height);
+    KIMG_CHECK_ARG(row_stride >= width);
     if (num_polarizations < 1 || num_polarizations > 4)
         return KIMG_EUNSUPPORTED;
     pixel_reciprocal_kernel<<<1, 64, 0, (hipStream_t) stream>>>(image, pol_stride, (int64_t) y * row_stride + x,
@@ -1121,6 +1126,7 @@ extern "C" int kimg_scale_device(float *image, int64_t row_stride, int64_t pol_s
                                  int height, int num_polarizations, const float *scale, void *stream)
 {
     KIMG_CHECK_ARG(image && scale && width > 0 && height > 0);
+    KIMG_CHECK_ARG(row_stride >= width);
     if (num_polarizations < 1 || num_polarizations > 4)
         return KIMG_EUNSUPPORTED;
     dim3 g(kimg_divup(width, 256), height);
@@ -1134,6 +1140,7 @@ extern "C" int kimg_add_image(float *dest, int64_t dest_row_stride, int64_t dest
                               int width, int height, int num_polarizations, void *stream)
 {
     KIMG_CHECK_ARG(dest && src && width > 0 && height > 0 && num_polarizations > 0);
+    KIMG_CHECK_ARG(dest_row_stride >= width && src_row_stride >= width);
     dim3 g(kimg_divup(width, 256), height);
     add_image_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
         dest, dest_row_stride, dest_pol_stride, src, src_row_stride, src_pol_stride, width,
@@ -1147,6 +1154,7 @@ extern "C" int kimg_apply_primary_beam(float *image, int64_t row_stride, int64_t
                                        float threshold, float replacement, void *stream)
 {
     KIMG_CHECK_ARG(image && beam_power && width > 0 && height > 0 && num_polarizations > 0);
+    KIMG_CHECK_ARG(row_stride >= width && beam_row_stride >= width);
     dim3 g(kimg_divup(width, 256), height);
     apply_primary_beam_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
         image, row_stride, pol_stride, beam_power, beam_row_stride, width, num_polarizations,
@@ -1209,6 +1217,7 @@ extern "C" int kimg_scale_f64(double *image, int64_t row_stride, int64_t pol_str
                               void *stream)
 {
     KIMG_CHECK_ARG(image && scale_host && width > 0 && height > 0);
+    KIMG_CHECK_ARG(row_stride >= width);
     if (num_polarizations < 1 || num_polarizations > 4)
         return KIMG_EUNSUPPORTED;
     scale_t<double> sc = {};
@@ -1226,6 +1235,7 @@ extern "C" int kimg_add_image_f64(double *dest, int64_t dest_row_stride, int64_t
                                   int num_polarizations, void *stream)
 {
     KIMG_CHECK_ARG(dest && src && width > 0 && height > 0 && num_polarizations > 0);
+    KIMG_CHECK_ARG(dest_row_stride >= width && src_row_stride >= width);
     const dim3 g(kimg_divup(width, 256), height);
     add_image_kernel<double><<<g, 256, 0, (hipStream_t) stream>>>(
         dest, dest_row_stride, dest_pol_stride, src, src_row_stride, src_pol_stride, width,
@@ -1239,6 +1249,7 @@ extern "C" int kimg_apply_primary_beam_f64(double *image, int64_t row_stride, in
                                            double threshold, double replacement, void *stream)
 {
     KIMG_CHECK_ARG(image && beam_power && width > 0 && height > 0 && num_polarizations > 0);
+    KIMG_CHECK_ARG(row_stride >= width && beam_row_stride >= width);
     const dim3 g(kimg_divup(width, 256), height);
     apply_primary_beam_kernel<double><<<g, 256, 0, (hipStream_t) stream>>>(
         image, row_stride, pol_stride, beam_power, beam_row_stride, width, num_polarizations,
@@ -1368,6 +1379,7 @@ extern "C" int kimg_image_peak(const float *image, int64_t row_stride, int64_t p
                                int num_polarizations, float noise, float *peak, void *stream)
 {
     KIMG_CHECK_ARG(image && peak && width > 0 && height > 0 && num_polarizations >= 1);
+    KIMG_CHECK_ARG(row_stride >= width && (pbeam == nullptr || beam_row_stride >= width));
     hipStream_t s = (hipStream_t) stream;
     KIMG_HIP(hipMemsetAsync(peak, 0, sizeof(float), s));
     int by = height < 64 ? height : 64;
@@ -1384,6 +1396,7 @@ extern "C" int kimg_image_nansum(const float *image, int64_t row_stride, int64_t
 {
     KIMG_CHECK_ARG(image && sums && width > 0 && height > 0 && num_polarizations >= 1
                    && num_polarizations <= 65535);
+    KIMG_CHECK_ARG(row_stride >= width);
     hipStream_t s = (hipStream_t) stream;
     KIMG_HIP(hipMemsetAsync(sums, 0, sizeof(double) * num_polarizations, s));
     int by = height < 32 ? height : 32;

@@ -162,6 +162,7 @@ extern "C" int kimg_grid_weights(float *grid, int64_t row_stride, int64_t pol_st
 {
     KIMG_CHECK_ARG(grid && uv && weights && num_vis >= 0 && width > 0 && height > 0);
     KIMG_CHECK_ARG(width % 2 == 0 && height % 2 == 0);     // weight.py:131-132
+    KIMG_CHECK_ARG(row_stride >= width);
     if (num_vis == 0)
         return 0;
     if (num_polarizations < 1 || num_polarizations > 4)
@@ -187,7 +188,7 @@ static dim3 image_grid(int width, int height)
 extern "C" int kimg_mean_weight(double *sums, const float *grid, int64_t row_stride, int width,
                                 int height, void *stream)
 {
-    KIMG_CHECK_ARG(sums && grid && width > 0 && height > 0);
+    KIMG_CHECK_ARG(sums && grid && width > 0 && height > 0 && row_stride >= width);
     hipStream_t s = (hipStream_t) stream;
     KIMG_HIP(hipMemsetAsync(sums, 0, 2 * sizeof(double), s));
     mean_weight_kernel<<<image_grid(width, height), 256, 0, s>>>(sums, grid, row_stride, width, height);
@@ -199,6 +200,7 @@ extern "C" int kimg_density_weights(double *sums, float *grid, int64_t row_strid
                                     int num_polarizations, float a, float b, void *stream)
 {
     KIMG_CHECK_ARG(sums && grid && width > 0 && height > 0 && num_polarizations > 0);
+    KIMG_CHECK_ARG(row_stride >= width);
     hipStream_t s = (hipStream_t) stream;
     KIMG_HIP(hipMemsetAsync(sums, 0, 3 * sizeof(double), s));
     density_weights_kernel<<<image_grid(width, height), 256, 0, s>>>(
@@ -212,6 +214,7 @@ extern "C" int kimg_density_weights_robust(double *sums, float *grid, int64_t ro
                                            double robust, float b, void *stream)
 {
     KIMG_CHECK_ARG(sums && grid && mean_sums && width > 0 && height > 0 && num_polarizations > 0);
+    KIMG_CHECK_ARG(row_stride >= width);
     hipStream_t s = (hipStream_t) stream;
     KIMG_HIP(hipMemsetAsync(sums, 0, 3 * sizeof(double), s));
     density_weights_kernel<<<image_grid(width, height), 256, 0, s>>>(

@@ -97,3 +97,83 @@ def taper_zones(taper1d, threshold=1e-2):
     t2 = np.outer(taper1d, taper1d).astype(np.float64)
     good = t2 >= threshold * t2.max()
     return good, ~good, t2
+
+
+# ---------------------------------------------------------------------------------------------
+# padded C ABI layouts
+
+# Padding values: huge, finite, never NaN (the peak and nansum kernels skip NaNs, which would hide
+# a read of padding), so that one padding element read wrecks a sum, a peak, a median or a CLEAN
+# component.  A mask's padding is 1 = allowed: a kernel that reads it takes the huge dirty padding
+# next to it for a candidate.
+SENTINELS = {
+    np.dtype(np.float32): np.float32(-3.0e38),
+    np.dtype(np.float64): np.float64(-1.0e300),
+    np.dtype(np.complex64): np.complex64(-3.0e38 + 2.5e38j),
+    np.dtype(np.complex128): np.complex128(-1.0e300 + 2.5e299j),
+    np.dtype(np.uint8): np.uint8(1),
+    np.dtype(np.int32): np.int32(0x5a5a5a5a),
+    np.dtype(np.uint32): np.uint32(0xa5a5a5a5),
+}
+
+
+class _HostBuffer:
+    """Stand-in for accel.DeviceArray on a CPU tensor (Padded without a device)."""
+
+    def __init__(self, host):
+        import torch
+        self.tensor = torch.from_numpy(np.ascontiguousarray(host).view(np.uint8).reshape(-1).copy())
+        self._shape, self._dtype = host.shape, host.dtype
+
+    @property
+    def ptr(self):
+        return self.tensor.data_ptr()
+
+    def get(self, q=None):
+        return self.tensor.numpy().copy().view(self._dtype).reshape(self._shape)
+
+
+class Padded:
+    """An inner [P][H][W] (or 2-D [H][W]) array of any dtype inside a larger buffer, as a C caller
+    hands over a sub-image: row stride ox + W + rpad, polarization stride (oy + H + vpad) * row
+    stride, the interior starting at row oy, column ox of every plane (`origin`), everything
+    around it filled with `sentinel` (default: SENTINELS of the dtype).
+
+    .ptr is the address of the interior's first element (element-aligned only once ox != 0),
+    .row / .pol the element strides, .dev the whole buffer.  .get(q) asserts that every byte
+    outside the interior is what it was and returns the interior.  ctx = None keeps the buffer in a
+    CPU tensor (no device needed)."""
+
+    def __init__(self, ctx, q, inner, rpad=0, vpad=0, sentinel=None, origin=(0, 0)):
+        inner = np.asarray(inner)
+        self.planar = inner.ndim == 2
+        if self.planar:
+            inner = inner[np.newaxis]
+        P, H, W = inner.shape
+        oy, ox = origin
+        if sentinel is None:
+            sentinel = SENTINELS[inner.dtype]
+        self.row = ox + W + rpad
+        self.pol = (oy + H + vpad) * self.row
+        host = np.full((P, oy + H + vpad, self.row), sentinel, inner.dtype)
+        self.inside = np.s_[:, oy:oy + H, ox:ox + W]
+        host[self.inside] = inner
+        self.host = host
+        self.G = W
+        self.shape = (P, H, W)
+        self.offset = oy * self.row + ox            # elements from the buffer's start to .ptr
+        if ctx is None:
+            self.dev = _HostBuffer(host)
+        else:
+            from katsdpimager_amd import accel
+            self.dev = accel.DeviceArray(ctx, host.shape, host.dtype)
+            self.dev.set(q, host)
+        self.ptr = self.dev.ptr + self.offset * host.dtype.itemsize
+
+    def get(self, q=None):
+        out = self.dev.get(q)
+        pad = out.copy()
+        pad[self.inside] = self.host[self.inside]
+        assert np.array_equal(pad.view(np.uint8), self.host.view(np.uint8)), 'padding changed'
+        out = out[self.inside]
+        return out[0] if self.planar else out

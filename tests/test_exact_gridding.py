@@ -61,7 +61,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
-from helpers import context_queue        # noqa: E402
+from helpers import Padded, context_queue        # noqa: E402
 
 EXACT = float(1 << 24)
 WIN = 32                                # window of the MFMA kernels (grid_mfma.hip, degrid_mfma.hip)
@@ -567,27 +567,6 @@ def _workspace(ctx, nbytes):
     if nbytes == 0:
         return None, 0
     return accel.DeviceArray(ctx, (int(nbytes),), np.uint8), int(nbytes)
-
-
-class Padded:
-    """A [P][G][G] array inside a larger buffer (row stride G + rpad, polarization stride
-    (G + vpad) * row stride), the padding filled with `sentinel`."""
-
-    def __init__(self, ctx, q, inner, rpad, vpad, sentinel):
-        P, G, _ = inner.shape
-        self.row, self.pol = G + rpad, (G + vpad) * (G + rpad)
-        host = np.full((P, G + vpad, G + rpad), sentinel, inner.dtype)
-        host[:, :G, :G] = inner
-        self.host = host
-        self.G = G
-        self.dev = _dev(ctx, q, host)
-
-    def get(self, q):
-        out = self.dev.get(q)
-        pad = out.copy()
-        pad[:, :self.G, :self.G] = self.host[:, :self.G, :self.G]
-        assert np.array_equal(pad.view(np.uint8), self.host.view(np.uint8)), 'padding changed'
-        return out[:, :self.G, :self.G]
 
 
 def run_grid(ctx, q, case, inp, variant, arith, prefill=None, rpad=0, vpad=0, wg_pad=(0, 0),
