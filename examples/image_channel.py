@@ -34,11 +34,19 @@ def main(argv=None):
     ap.add_argument('--output', help='write the restored image to this FITS file')
     ap.add_argument('--mask-radius', type=int, default=0,
                     help='CLEAN only within this many pixels of a source (a mask of disks); 0 = no mask')
+    ap.add_argument('--auto-mask', metavar='SIGMA[,RADIUS]',
+                    help='build the CLEAN mask from the residual in every major cycle: the pixels SIGMA '
+                         'noise estimates above it, grown by RADIUS pixels (default 3); cut to the '
+                         '--mask-radius mask if both are given')
     args = ap.parse_args(argv)
     import torch
     import scipy.optimize       # noqa: F401  (used by beam.fit_beam; imported here, outside the timings)
     import synth
-    from katsdpimager_amd import accel, beam, frontend, imaging, parameters, preprocess, weight
+    from katsdpimager_amd import accel, beam, frontend, imaging, mask, parameters, preprocess, weight
+    auto_mask = None
+    if args.auto_mask:
+        sigma, _, radius = args.auto_mask.partition(',')
+        auto_mask = mask.AutoMaskParameters(float(sigma), int(radius) if radius else 3)
 
     ctx = accel.create_some_context()
     queue = ctx.create_command_queue()
@@ -85,11 +93,13 @@ def main(argv=None):
                            <= args.mask_radius ** 2)
     stats = frontend.process_channel(reader, 0, imager, image_p, grid_p, clean_p,
                                      weight_p.weight_type, args.vis_block, args.major, True,
-                                     fit_beam=True, clean_mask=clean_mask)
+                                     fit_beam=True, clean_mask=clean_mask, auto_mask=auto_mask)
     queue.finish()
     t2 = time.perf_counter()
     print('imaged in {:.1f} ms: {} major / {} minor cycles, PSF patch {}, noise {:.3g}'.format(
         (t2 - t1) * 1e3, stats['major'], stats['minor'], stats['psf_patch'], stats['noise']))
+    if auto_mask is not None:
+        print('auto mask ({}): allowed pixels per major cycle {}'.format(auto_mask, stats['mask_pixels']))
 
     print('restoring beam: {}'.format(stats['restoring_beam']))
     beam.restore(imager, stats['restoring_beam'])

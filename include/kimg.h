@@ -742,6 +742,42 @@ int kimg_clean_cycles_masked(float *dirty, float *model, int64_t row_stride, int
                              int max_cycles, int form, void *state, float *log, void *stream,
                              const uint8_t *mask, int64_t mask_row_stride);
 
+/* ---- CLEAN auto-masks: a clean mask built on the device from the residual image.  Masks have the
+ * layout of "CLEAN masks": uint8 [height][width] with a row pitch in bytes (>= width), one plane
+ * for all polarizations, nonzero = allowed.  Every byte these calls write is exactly 0 or 1; bytes
+ * of the row padding (x >= width) are never written.  A pitch is what the other calls name a
+ * stride: the distance between rows (or polarization planes), in elements of the array, at least
+ * the width (KIMG_EINVAL otherwise, before anything is enqueued).  Pitches and widths are arbitrary.
+ *
+ * kimg_mask_threshold: mask[y][x] = 1 where the pixel is inside the border (border <= x < width -
+ *   border, the same for y; a border of half the image or more leaves no such pixel) and
+ *   metric(y, x) > threshold, else 0.  metric is the CLEAN metric of `mode`: |pol 0| for
+ *   KIMG_CLEAN_I, the sum of squares over the polarizations, in polarization order and every
+ *   operation rounded on its own, for KIMG_CLEAN_SUMSQ.  The comparison is strict: threshold 0
+ *   selects the pixels with a nonzero metric, a negative threshold every pixel inside the border, a
+ *   NaN metric or a NaN threshold nothing.  num_polarizations is 1 to 4.
+ *
+ * kimg_mask_dilate: out = ((in (+) disk(radius)) | or_with) & and_with, where (+) is the dilation
+ *   by the Euclidean disk {(dy, dx): dy^2 + dx^2 <= radius^2} (integers), clipped at the edges of
+ *   the plane: out is set where a nonzero byte of `in` lies within the disk around the pixel.
+ *   radius is 0 to KIMG_MASK_MAX_RADIUS; radius 0 is a copy (to 0 / 1) followed by the combination.
+ *   A NULL or_with or and_with drops that term; nonzero bytes of either count as set.
+ *   count, if not NULL, receives the number of set pixels of `out` (device uint32; the call zeroes
+ *   it on the stream, the kernel adds to it once per workgroup).
+ *   Aliasing: or_with may be `out` itself (every byte is read before it is written, by the same
+ *   thread: a cumulative mask).  `in` and and_with must not overlap `out`; in == out and
+ *   and_with == out are KIMG_EINVAL before anything is enqueued.
+ *   The cost per pixel is linear in the radius. */
+#define KIMG_MASK_MAX_RADIUS 64
+int kimg_mask_threshold(const float *image, int64_t row_pitch, int64_t pol_pitch,
+                        int width, int height, int num_polarizations, int border, int mode,
+                        float threshold, uint8_t *mask, int64_t mask_row_pitch, void *stream);
+int kimg_mask_dilate(const uint8_t *in, int64_t in_row_pitch, uint8_t *out,
+                     int64_t out_row_pitch, int width, int height, int radius,
+                     const uint8_t *or_with, int64_t or_row_pitch,
+                     const uint8_t *and_with, int64_t and_row_pitch, uint32_t *count,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

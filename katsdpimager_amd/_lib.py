@@ -97,6 +97,9 @@ PROTOTYPES = {
     'kimg_find_peak_masked': (c_int, [P, L, L, I, P, P, I, I, P, P, P, P, P, L]),
     'kimg_clean_cycles_masked': (c_int, [P, P, L, L, I, I, I, P, L, L, I, I, I, I, I, I, F, F,
                                          P, P, I, I, I, I, P, P, P, P, L]),
+    # CLEAN auto-masks
+    'kimg_mask_threshold': (c_int, [P, L, L, I, I, I, I, I, F, P, L, P]),
+    'kimg_mask_dilate': (c_int, [P, L, P, L, I, I, I, P, L, P, L, P, P]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),

@@ -78,7 +78,7 @@ def slice_mid_w(image_p, grid_p):
 
 def process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type,
                     vis_block, major, degrid, subtract_model=False, batched_clean=True,
-                    fit_beam=False, clean_batcher=None, clean_mask=None):
+                    fit_beam=False, clean_batcher=None, clean_mask=None, auto_mask=None):
     """The loop of frontend.process_channel (frontend.py:497-585) from "Compute imaging
     weights" to the end of the last major cycle.
 
@@ -100,19 +100,47 @@ def process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p, weigh
     to the allowed pixels; the imager gets back afterwards whatever mask it had.  The minor cycles
     then run per channel (no one-call major cycles, no shared launches).  None (the default) leaves
     everything as it is, a mask set on the imager beforehand included.
+
+    ``auto_mask`` (:class:`mask.AutoMaskParameters`) has the imager build the clean mask itself
+    (``Imaging.auto_mask``), after the noise estimate of every major cycle: the pixels that stand
+    ``sigma`` noise estimates out of the residual, grown by ``radius`` pixels, with ``cumulative``
+    joined with the masks of this call's earlier major cycles, and cut to the user's mask
+    (``clean_mask``, or the mask the imager had on entry) where there is one.  The minor cycles run as
+    under any mask; the imager gets back the mask it had.  The result then has ``auto_mask`` -- the
+    last mask, a device array of the imager's that its next auto-masked call rewrites (None if no major
+    cycle ran) -- and ``mask_pixels``, the allowed pixels of every major cycle's mask.  None (the default) changes
+    nothing.
     """
     if not any(reader.len(rel_channel, s) for s in range(reader.num_w_slices(rel_channel))):
         return None
     _check_imager_parameters(imager, image_p, grid_p)
-    if clean_mask is not None:
+    if clean_mask is not None or auto_mask is not None:
         before = imager.clean_mask
-        imager.set_clean_mask(clean_mask)
+        if clean_mask is not None:
+            imager.set_clean_mask(clean_mask)
         try:
-            return process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p,
-                                   weight_type, vis_block, major, degrid, subtract_model,
-                                   batched_clean, fit_beam, clean_batcher)
+            if auto_mask is not None:
+                imager.auto_mask_reset()
+                auto_mask = (auto_mask, imager.auto_mask_restriction())    # (cut to the user's mask)
+            out = _process_channel_masked(
+                reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type, vis_block,
+                major, degrid, subtract_model, batched_clean, fit_beam, clean_batcher, auto_mask)
+            if auto_mask is not None and out is not None:
+                out.setdefault('auto_mask', None)
+                out['mask_pixels'] = imager.auto_mask_counts()
+            return out
         finally:
             imager.set_clean_mask(before)
+    return _process_channel_masked(
+        reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type, vis_block, major,
+        degrid, subtract_model, batched_clean, fit_beam, clean_batcher, None)
+
+
+def _process_channel_masked(reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type,
+                            vis_block, major, degrid, subtract_model, batched_clean, fit_beam,
+                            clean_batcher, auto_mask):
+    """:func:`process_channel` with the imager's mask as it stands; ``auto_mask``: None, or
+    (parameters, the user's mask on the device or None)."""
     import contextlib
     if clean_batcher is not None and getattr(clean_batcher, 'phased', False):
         try:
@@ -120,12 +148,13 @@ def process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p, weigh
             return _process_channel_stages(
                 reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type, vis_block,
                 major, degrid, subtract_model, batched_clean, fit_beam, clean_batcher,
-                clean_batcher.device_phase)
+                clean_batcher.device_phase, auto_mask)
         finally:
             clean_batcher.idle()        # (nobody waits for this thread until its next stage)
     return _process_channel_stages(
         reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type, vis_block, major,
-        degrid, subtract_model, batched_clean, fit_beam, clean_batcher, contextlib.nullcontext)
+        degrid, subtract_model, batched_clean, fit_beam, clean_batcher, contextlib.nullcontext,
+        auto_mask)
 
 
 def _check_imager_parameters(imager, image_p, grid_p):
@@ -153,7 +182,7 @@ def _check_imager_parameters(imager, image_p, grid_p):
 
 def _process_channel_stages(reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type,
                             vis_block, major, degrid, subtract_model, batched_clean, fit_beam,
-                            clean_batcher, device_phase):
+                            clean_batcher, device_phase, auto_mask=None):
     num_pols = len(image_p.fixed.polarizations)
     with device_phase():
         imager.clear_model()
@@ -217,6 +246,11 @@ def _process_channel_stages(reader, rel_channel, imager, image_p, grid_p, clean_
             if np.any(np.isinf(scale)):
                 return None             # (a central pixel of 0: frontend.py:543-544)
             out.update(psf_patch=tuple(int(x) for x in psf_patch), scale=scale)
+        if auto_mask is not None:
+            # the mask of this major cycle, from the residual and its noise estimate: on the device,
+            # bound for the clean_reset below
+            with trace.range('auto_mask'):
+                out['auto_mask'] = imager.auto_mask(noise, auto_mask[0], restrict=auto_mask[1])
         noise_threshold = noise * clean.noise_threshold_scale(clean_p.mode, clean_p.threshold,
                                                               num_pols)
         values = None

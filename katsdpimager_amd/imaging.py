@@ -16,7 +16,7 @@ import functools
 
 import numpy as np
 
-from . import accel, clean, grid, image, predict, types, weight
+from . import accel, clean, grid, image, mask, predict, types, weight
 
 
 class ImagingTemplate:
@@ -47,6 +47,9 @@ class ImagingTemplate:
         self.noise_est = clean.NoiseEstTemplate(context, dtype, num_pols)
         self.clean = clean.CleanTemplate(context, clean_parameters, dtype, num_pols,
                                          tuning.get('clean'))
+        self.mask_threshold = mask.MaskThresholdTemplate(context, dtype, num_pols,
+                                                         clean_parameters.mode)
+        self.mask_dilate = mask.MaskDilateTemplate(context)
         self.scale = image.ScaleTemplate(context, dtype, num_pols)
         self.add_image = image.AddImageTemplate(context, dtype, num_pols)
         self.apply_primary_beam = image.ApplyPrimaryBeamTemplate(context, dtype, num_pols)
@@ -230,6 +233,7 @@ class Imaging(accel.OperationSequence):
         self._kept_scale = None         # device float32 [P]: 1 / the PSF's central pixel
         self._small_stream = None       # (small read-backs next to the queue's work)
         self._dirty_cleared = False
+        self._auto = None               # the auto-mask operators and planes (:meth:`auto_mask`)
         operations = [
             ('weights', self._weights), ('gridder', self._gridder), ('predict', self._predict),
             ('continuum_predict', self._continuum_predict),
@@ -698,26 +702,118 @@ class Imaging(accel.OperationSequence):
         major cycle).  With a mask the minor cycles run per channel in the two-launch or one-launch
         form (:meth:`clean_major_cycles` returns None, a ``batcher`` runs the channel on its own)."""
         self._ready()
+        self._clean.bind(mask=self._device_mask(mask))
+
+    def _device_mask(self, mask):
+        """A mask as :meth:`set_clean_mask` takes it, on the device (None stays None)."""
         if mask is None:
-            self._clean.bind(mask=None)
-            return
+            return None
         shape = self.buffer('dirty').shape[1:]
         if isinstance(mask, accel.DeviceArray):
             if mask.shape != shape or mask.dtype != np.uint8:
                 raise ValueError('a device mask must be uint8 of shape {}'.format(shape))
-            self._clean.bind(mask=mask)
-            return
+            return mask
         host = np.asarray(mask)
         if host.shape != shape or host.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
             raise ValueError('a mask must be bool or uint8 of shape {}'.format(shape))
         device = accel.DeviceArray(self.template.context, shape, np.uint8, queue=self.command_queue)
         device.set(self.command_queue, np.ascontiguousarray(host != 0, dtype=np.uint8))
-        self._clean.bind(mask=device)
+        return device
 
     @property
     def clean_mask(self):
         """The device array :meth:`set_clean_mask` bound, or None."""
         return self._clean.buffer('mask')
+
+    # ---- auto-masks (mask.py; include/kimg.h, "CLEAN auto-masks") ------------------------------
+    #: device pixel counts kept between two read-backs (:meth:`auto_mask_counts`)
+    AUTO_MASK_COUNTS = 64
+
+    def auto_mask_reset(self):
+        """Forget the auto mask of the calls so far (a new channel): the next :meth:`auto_mask`
+        starts from an empty mask, and :meth:`auto_mask_counts` from an empty list."""
+        if self._auto is not None:
+            self._auto['live'] = False
+            self._auto['calls'] = 0
+            del self._auto['counted'][:]
+
+    def _detached(self, mask):
+        """``mask``, or a device copy of it if it is the auto-mask plane itself, which the next
+        :meth:`auto_mask` rewrites."""
+        auto = self._auto
+        if auto is None or mask is None or mask is not auto['dilate'].buffer('dest'):
+            return mask
+        if 'restrict' not in auto:
+            auto['restrict'] = accel.DeviceArray(self.template.context, mask.shape, np.uint8,
+                                                 queue=self.command_queue)
+        mask.copy_region(self.command_queue, auto['restrict'], np.s_[:], np.s_[:])
+        return auto['restrict']
+
+    @_serial
+    def auto_mask_restriction(self):
+        """The mask bound now (:attr:`clean_mask`) in a form that stays what it is over a series of
+        :meth:`auto_mask` calls, for their ``restrict``: the mask itself, or a copy where it is the
+        auto mask of an earlier call."""
+        self._ready()
+        return self._detached(self.clean_mask)
+
+    @_serial
+    def auto_mask(self, noise, params, restrict=None):
+        """Build the clean mask of the coming minor cycles from the dirty image and bind it (as
+        :meth:`set_clean_mask` does: it takes effect with the next :meth:`clean_reset`).
+
+        ``noise``: the noise estimate (:meth:`noise_est`); ``params``:
+        :class:`mask.AutoMaskParameters`.  The seeds are the pixels inside the border whose CLEAN
+        metric exceeds ``noise * clean.noise_threshold_scale(mode, params.sigma, P)`` -- the
+        arithmetic of the stopping threshold -- grown by a disk of ``params.radius`` pixels; with
+        ``params.cumulative`` the auto mask of the calls since :meth:`auto_mask_reset` is added;
+        ``restrict`` (a mask as :meth:`set_clean_mask` takes it) cuts the result.  With ``restrict``
+        None or a device array everything happens on the device, in two launches (a host array is
+        uploaded first, at every call: hand in a device array where it matters); the number of
+        allowed pixels stays on the device until :meth:`auto_mask_counts`.  ``restrict`` may be the
+        auto mask of an earlier call itself (what :attr:`clean_mask` is after one): it is copied
+        first, on the device.  Returns the mask: a device array of the imager's own, rewritten by
+        the next call."""
+        self._ready()
+        cp = self.template.clean_parameters
+        dirty = self.buffer('dirty')
+        power = noise * clean.noise_threshold_scale(cp.mode, params.sigma, dirty.shape[0])
+        threshold = clean.power_to_metric(cp.mode, power)
+        restrict = self._device_mask(restrict)
+        if self._auto is None:
+            t, q, shape = self.template, self.command_queue, dirty.shape
+            self._auto = dict(
+                threshold=t.mask_threshold.instantiate(q, shape, cp.border),
+                dilate=t.mask_dilate.instantiate(q, shape[1:], self.AUTO_MASK_COUNTS),
+                live=False, calls=0, counted=[])
+            self._auto['threshold'].ensure_all_bound()      # (the seed plane)
+            self._auto['dilate'].bind(src=self._auto['threshold'].buffer('mask'))
+            self._auto['dilate'].ensure_all_bound()         # (the auto mask, the counts)
+        auto = self._auto
+        result = auto['dilate'].buffer('dest')
+        restrict = self._detached(restrict)     # (the kernel cannot cut a mask by itself in place)
+        if auto['calls'] == self.AUTO_MASK_COUNTS:
+            self.auto_mask_counts()                         # (makes room: a read-back)
+        auto['threshold'](threshold, image=dirty)
+        auto['dilate'](params.radius, auto['calls'],
+                       accumulate=result if params.cumulative and auto['live'] else None,
+                       restrict=restrict)
+        auto['calls'] += 1
+        auto['live'] = True
+        self._clean.bind(mask=result)
+        return result
+
+    def auto_mask_counts(self):
+        """Allowed pixels of the mask each :meth:`auto_mask` since :meth:`auto_mask_reset` built, in
+        call order (one read-back for all of them)."""
+        auto = self._auto
+        if auto is None:
+            return []
+        if auto['calls']:
+            counts = auto['dilate'].buffer('count').get(self.command_queue)
+            auto['counted'].extend(int(n) for n in counts[:auto['calls']])
+            auto['calls'] = 0
+        return list(auto['counted'])
 
     @_serial
     def clean_reset(self):
