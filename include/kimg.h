@@ -652,7 +652,11 @@ int kimg_clean_cycles(float *dirty, float *model, int64_t row_stride, int64_t po
  *     max(noise_threshold, left_for_next * power of the first peak)      (frontend.py:568-575)
  * -- or do not run at all if the first peak itself is not above that -- worked out on the device in
  * the host's arithmetic (doubles; a metric as a flux and back as clean.py:166-184 has it), so that the
- * host round trip between the first cycle and the others is gone.  Arguments as kimg_clean_cycles;
+ * host round trip between the first cycle and the others is gone.  On every route -- this call, or
+ * a host that makes the threshold itself and passes it to kimg_clean_cycles and its kin -- the
+ * threshold is that float64 expression rounded ONCE to the float32 the metrics are compared with
+ * (a cycle stops at metric < threshold); the float32 peak and noise estimate enter it as doubles.
+ * Arguments as kimg_clean_cycles;
  * noise_threshold = noise estimate x the clean threshold (in sigma), left_for_next = 1 - major gain;
  * max_cycles counts the first cycle.  The log's first row is the first cycle's.  Runs where the
  * multi-component form does (form: KIMG_CLEAN_FORM_AUTO or _MULTI with its caps); KIMG_EUNSUPPORTED

@@ -476,7 +476,9 @@ class Clean(accel.OperationSequence):
             both = torch.cat([parts[0].tensor, parts[1].tensor.view(torch.float32),
                               parts[2].tensor]).cpu().numpy()
         peak_value = both[:1]
-        if peak_value[0] < threshold:
+        # (the float32 the loop's forms are handed through the C ABI: a float64 threshold compared
+        # as it is would stop at a metric equal to its float32 rounding)
+        if peak_value[0] < np.float32(threshold):
             return None, None, None
         peak_pos = tuple(int(x) for x in both[1:3].view(np.int32))
         if peak_pos[0] < 0:         # (only with a mask: metric 0, no allowed pixel left to take)

@@ -251,8 +251,11 @@ def _process_channel_stages(reader, rel_channel, imager, image_p, grid_p, clean_
             # bound for the clean_reset below
             with trace.range('auto_mask'):
                 out['auto_mask'] = imager.auto_mask(noise, auto_mask[0], restrict=auto_mask[1])
-        noise_threshold = noise * clean.noise_threshold_scale(clean_p.mode, clean_p.threshold,
-                                                              num_pols)
+        # the threshold is a float64 expression, rounded once to float32 where it meets a metric, on
+        # every route: the float32 scalars the device hands back enter it as doubles (next to a
+        # Python float a NumPy float32 scalar would keep the arithmetic in float32)
+        noise_threshold = float(noise) * clean.noise_threshold_scale(clean_p.mode, clean_p.threshold,
+                                                                     num_pols)
         values = None
         if batched_clean and getattr(imager, 'one_call_major_cycles', False) is True \
                 and noise_threshold == noise_threshold:         # (not NaN)
@@ -279,7 +282,7 @@ def _process_channel_stages(reader, rel_channel, imager, image_p, grid_p, clean_
         if peak_value is None:
             break       # (only under a CLEAN mask: no allowed pixel with a metric above 0 is left)
         out['peaks'].append(peak_value)
-        peak_power = clean.metric_to_power(clean_p.mode, peak_value)
+        peak_power = clean.metric_to_power(clean_p.mode, float(peak_value))
         mgain_threshold = (1.0 - clean_p.major_gain) * peak_power
         threshold = max(noise_threshold, mgain_threshold)
         if peak_power <= threshold:
