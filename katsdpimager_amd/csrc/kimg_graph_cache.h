@@ -25,7 +25,8 @@ public:
     // The cached graph for `a`, or one newly captured from what `enqueue_all(capture_stream)` launches
     // (0, or the code of the launch that failed); the entry stays pinned until release().  An entry is
     // only evicted when no call is using it and the replays enqueued from it have completed (its
-    // event has fired), so a graph is never destroyed while it is in flight.
+    // event has fired), so a graph is never destroyed while it is in flight.  (An event whose query
+    // fails with anything but "not ready" counts as not fired: its entry stays, and is still found.)
     // Null: every entry is busy, or the graph could not be made; the caller enqueues plain launches.
     template <class F> entry *acquire(const ARGS &a, F &&enqueue_all)
     {
@@ -39,10 +40,19 @@ public:
         for (int i = 0; i < SLOTS && !slot; i++)
             if (!slots[i].valid)
                 slot = &slots[i];
-        for (int i = 0; i < SLOTS && !slot; i++)
-            if (slots[i].users == 0
-                && (!slots[i].used || hipEventQuery(slots[i].last_use) == hipSuccess))
-                slot = &slots[i];
+        if (!slot) {
+            // (a query that answers "not ready", or fails, may stay behind as the thread's last error,
+            // depending on the runtime; the caller's kimg_launch_status() would take it for a failed
+            // launch.  It is read here -- unless an error from before this call is waiting, which is
+            // not this call's to swallow)
+            const bool clean = hipPeekAtLastError() == hipSuccess;
+            for (int i = 0; i < SLOTS && !slot; i++)
+                if (slots[i].users == 0
+                    && (!slots[i].used || hipEventQuery(slots[i].last_use) == hipSuccess))
+                    slot = &slots[i];
+            if (clean)
+                (void) hipGetLastError();
+        }
         if (!slot)
             return nullptr;
         hipGraph_t graph = nullptr;
