@@ -38,11 +38,17 @@ def main(argv=None):
                     help='build the CLEAN mask from the residual in every major cycle: the pixels SIGMA '
                          'noise estimates above it, grown by RADIUS pixels (default 3); cut to the '
                          '--mask-radius mask if both are given')
+    ap.add_argument('--multiscale', metavar='FWHM,FWHM,...',
+                    help='run the minor cycles through multi-scale CLEAN with these Gaussian scales '
+                         '(FWHM in pixels, ascending, the first one 0), e.g. 0,4,9')
     args = ap.parse_args(argv)
     import torch
     import scipy.optimize       # noqa: F401  (used by beam.fit_beam; imported here, outside the timings)
     import synth
-    from katsdpimager_amd import accel, beam, frontend, imaging, mask, parameters, preprocess, weight
+    from katsdpimager_amd import accel, beam, frontend, imaging, mask, multiscale, parameters, preprocess, weight
+    scales = None
+    if args.multiscale:
+        scales = multiscale.MultiScaleParameters([float(s) for s in args.multiscale.split(',')])
     auto_mask = None
     if args.auto_mask:
         sigma, _, radius = args.auto_mask.partition(',')
@@ -93,7 +99,8 @@ def main(argv=None):
                            <= args.mask_radius ** 2)
     stats = frontend.process_channel(reader, 0, imager, image_p, grid_p, clean_p,
                                      weight_p.weight_type, args.vis_block, args.major, True,
-                                     fit_beam=True, clean_mask=clean_mask, auto_mask=auto_mask)
+                                     fit_beam=True, clean_mask=clean_mask, auto_mask=auto_mask,
+                                     multiscale=scales)
     queue.finish()
     t2 = time.perf_counter()
     print('imaged in {:.1f} ms: {} major / {} minor cycles, PSF patch {}, noise {:.3g}'.format(

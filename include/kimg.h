@@ -782,6 +782,79 @@ int kimg_mask_dilate(const uint8_t *in, int64_t in_row_pitch, uint8_t *out,
                      const uint8_t *and_with, int64_t and_row_pitch, uint32_t *count,
                      void *stream);
 
+/* ---- Multi-scale CLEAN: Gaussian scales beside the Hogbom minor cycle (clean_scales.hip).  The
+ * reference has none; the semantics are this library's, and katsdpimager_amd/multiscale.py holds
+ * them once more as numpy (MultiScaleCleanHost), which the device matches bit for bit.  float32,
+ * KIMG_CLEAN_I only.  Every a * b + c below is a rounded multiply and then a rounded add.
+ *
+ * Scales.  Scale k has a radius R_k (0 .. KIMG_CLEAN_SCALES_MAX_RADIUS, R_0 = 0) and 2 R_k + 1
+ *   taps t_k (scale 0: the single tap 1).  The caller makes the taps (float64, normalised to sum
+ *   1, rounded once) and, for every pair j <= k, the cross taps t_jk of radius R_j + R_k (the
+ *   float64 convolution of the unrounded t_j and t_k, rounded once).  At most
+ *   KIMG_CLEAN_SCALES_MAX scales.  More scales or a larger radius: KIMG_EUNSUPPORTED.
+ * conv(img, t), kimg_image_convolve_separable: a horizontal pass from `in` into `tmp`, then a
+ *   vertical pass from `tmp` into `out`; each pass is acc = 0, then acc = acc + t[i] * in[c - R + i]
+ *   for i = 0 .. 2 R in this order, taps that fall outside the image skipped; every polarization
+ *   plane on its own.  taps: DEVICE float [2 R + 1].  `out` may be `in`; `tmp` is neither.  Bytes
+ *   of the row padding are never written.
+ * Set-up.  n_k = conv(psf, t_kk)[0][centre][centre], inv_k = 1.0f / n_k.  The residual of scale k
+ *   is conv(dirty, t_k) * inv_k for k >= 1 and the dirty image ITSELF for k = 0: the PSF's central
+ *   pixel (polarization 0) must be exactly 1 (KIMG_EINVAL otherwise; the set-up reads it back).
+ *   The cross patch X_jk = crop(conv(psf, t_jk)) * inv_j, the crop being the centred box of
+ *   (patch + 2 (R_j + R_k)) pixels a side -- from centre - size / 2, as the Hogbom calls place the
+ *   patch -- clipped to the image.  The PSF has the image's width and height.
+ *   what: KIMG_CLEAN_SCALES_PSF (taps, n, inv, X: once per PSF) | KIMG_CLEAN_SCALES_RESIDUALS (the
+ *   residuals of the scales k >= 1 from the dirty image as it stands, and every tile record; with
+ *   `mask` only allowed pixels are candidates, as under "CLEAN masks").
+ *   taps_host: HOST float [num_scales][192], cross_taps_host: HOST float [pairs][320], the pairs
+ *   (j, k), j <= k, in row-major order; rows are padded with anything.
+ * A cycle.  Peak of every scale from its tile records (the Hogbom tile structure over |residual of
+ *   polarization 0|); the scale k* with the largest biases[k] * peak_k (a float32 product; ties to
+ *   the smallest k); stop if the unbiased peak < threshold, or, with a mask, if it is 0;
+ *   a[p] = loop_gain * residual_k*[p][pos]; for every scale j, residual_j[p] -= a[p] * X_j,k*[p]
+ *   over the box of X_j,k* centred on pos, clipped to the image (and to what X holds);
+ *   model[p] += a[p] * (t_k*[dy] * t_k*[dx]) over the (2 R_k* + 1)^2 box, clipped; the touched
+ *   tiles of every scale rescanned.  Log row: (k*, y, x as int32 bit patterns, peak, a[0 .. P-1]),
+ *   4 + P floats; log holds max_cycles rows.
+ *   kimg_clean_scales_cycles runs up to max_cycles cycles with plain launches, in chunks of 64; it
+ *   reads the device's `done` word between chunks (a stream synchronisation per chunk, none per
+ *   component) and returns with the stream idle and *cycles_done set.  model has the dirty image's
+ *   pitches.  radii, biases: HOST arrays [num_scales].  mode KIMG_CLEAN_SUMSQ: KIMG_EUNSUPPORTED.
+ * Workspace (16-byte aligned; KIMG_EWORKSPACE if too small): sections in this order, each a multiple
+ *   of 64 floats: state 64 | n at 0 and inv at 8 of 64 | taps 6 * 192 | cross taps 21 * 320 rounded
+ *   up | tile_max [K][T'] | tile_pos [K][T'][2] int32, T' = tiles_x * tiles_y rounded up |
+ *   residuals k = 1 .. K-1, each [P][height][width] dense, rounded up | X_jk for j, k row-major,
+ *   each [P][crop height][crop width] dense, rounded up | two images of scratch.  The state's first
+ *   two int32 are (cycles done, done). */
+#define KIMG_CLEAN_SCALES_MAX 6
+#define KIMG_CLEAN_SCALES_MAX_RADIUS 64
+#define KIMG_CLEAN_SCALES_PSF 1
+#define KIMG_CLEAN_SCALES_RESIDUALS 2
+int kimg_image_convolve_separable(const float *in, int64_t in_row_pitch, int64_t in_pol_pitch,
+                                  float *out, int64_t out_row_pitch, int64_t out_pol_pitch,
+                                  float *tmp, int64_t tmp_row_pitch, int64_t tmp_pol_pitch,
+                                  int width, int height, int num_polarizations,
+                                  const float *taps, int radius, void *stream);
+size_t kimg_clean_scales_workspace_bytes(int width, int height, int num_polarizations,
+                                         int patch_width, int patch_height, int border,
+                                         int num_scales, const int *radii);
+int kimg_clean_scales_setup(float *dirty, int64_t row_pitch, int64_t pol_pitch,
+                            const float *psf, int64_t psf_row_pitch, int64_t psf_pol_pitch,
+                            int width, int height, int num_polarizations,
+                            int patch_width, int patch_height, int border,
+                            int num_scales, const int *radii, const float *taps_host,
+                            const float *cross_taps_host, int what,
+                            const uint8_t *mask, int64_t mask_row_pitch,
+                            void *workspace, size_t workspace_bytes, void *stream);
+int kimg_clean_scales_cycles(float *dirty, float *model, int64_t row_pitch, int64_t pol_pitch,
+                             int width, int height, int num_polarizations,
+                             int patch_width, int patch_height, int border, int mode,
+                             float loop_gain, float threshold, int num_scales, const int *radii,
+                             const float *biases, int max_cycles,
+                             const uint8_t *mask, int64_t mask_row_pitch,
+                             void *workspace, size_t workspace_bytes, float *log,
+                             int *cycles_done, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,13 @@ PROTOTYPES = {
     # CLEAN auto-masks
     'kimg_mask_threshold': (c_int, [P, L, L, I, I, I, I, I, F, P, L, P]),
     'kimg_mask_dilate': (c_int, [P, L, P, L, I, I, I, P, L, P, L, P, P]),
+    # multi-scale CLEAN
+    'kimg_image_convolve_separable': (c_int, [P, L, L, P, L, L, P, L, L, I, I, I, P, I, P]),
+    'kimg_clean_scales_workspace_bytes': (c_size_t, [I, I, I, I, I, I, I, P]),
+    'kimg_clean_scales_setup': (c_int, [P, L, L, P, L, L, I, I, I, I, I, I, I, P, P, P, I, P, L,
+                                        P, c_size_t, P]),
+    'kimg_clean_scales_cycles': (c_int, [P, P, L, L, I, I, I, I, I, I, I, F, F, I, P, P, I, P, L,
+                                         P, c_size_t, P, P, P]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),

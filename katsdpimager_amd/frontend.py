@@ -78,7 +78,8 @@ def slice_mid_w(image_p, grid_p):
 
 def process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type,
                     vis_block, major, degrid, subtract_model=False, batched_clean=True,
-                    fit_beam=False, clean_batcher=None, clean_mask=None, auto_mask=None):
+                    fit_beam=False, clean_batcher=None, multiscale=None, clean_mask=None,
+                    auto_mask=None):
     """The loop of frontend.process_channel (frontend.py:497-585) from "Compute imaging
     weights" to the end of the last major cycle.
 
@@ -110,7 +111,36 @@ def process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p, weigh
     last mask, a device array of the imager's that its next auto-masked call rewrites (None if no major
     cycle ran) -- and ``mask_pixels``, the allowed pixels of every major cycle's mask.  None (the default) changes
     nothing.
+
+    ``multiscale`` (:class:`multiscale.MultiScaleParameters`) runs the minor cycles of every major
+    cycle through the multi-scale operator (``Imaging.multiscale_cycles``) instead of the Hogbom
+    loop: the first cycle without a threshold, the threshold from its peak as always, then the
+    other ``minor - 1``.  ``clean_mask`` and ``auto_mask`` combine with it.  It needs
+    ``degrid=True`` (extended components cannot go through the DFT predictor's component
+    dictionary) and takes no ``clean_batcher``.  None (the default) changes nothing.
     """
+    if multiscale is not None:
+        if not degrid:
+            raise ValueError('multi-scale CLEAN needs degrid=True: its components are extended')
+        if clean_batcher is not None:
+            raise ValueError('multi-scale CLEAN does not share launches: no clean_batcher')
+        imager.set_multiscale(multiscale)
+        try:
+            return _process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p,
+                                    weight_type, vis_block, major, degrid, subtract_model,
+                                    batched_clean, fit_beam, clean_batcher, clean_mask, auto_mask,
+                                    True)
+        finally:
+            imager.set_multiscale(None)
+    return _process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type,
+                            vis_block, major, degrid, subtract_model, batched_clean, fit_beam,
+                            clean_batcher, clean_mask, auto_mask, False)
+
+
+def _process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type,
+                     vis_block, major, degrid, subtract_model, batched_clean, fit_beam,
+                     clean_batcher, clean_mask, auto_mask, multiscale):
+    """:func:`process_channel`; ``multiscale``: have the scales been set on the imager?"""
     if not any(reader.len(rel_channel, s) for s in range(reader.num_w_slices(rel_channel))):
         return None
     _check_imager_parameters(imager, image_p, grid_p)
@@ -124,7 +154,8 @@ def process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p, weigh
                 auto_mask = (auto_mask, imager.auto_mask_restriction())    # (cut to the user's mask)
             out = _process_channel_masked(
                 reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type, vis_block,
-                major, degrid, subtract_model, batched_clean, fit_beam, clean_batcher, auto_mask)
+                major, degrid, subtract_model, batched_clean, fit_beam, clean_batcher, auto_mask,
+                multiscale)
             if auto_mask is not None and out is not None:
                 out.setdefault('auto_mask', None)
                 out['mask_pixels'] = imager.auto_mask_counts()
@@ -133,12 +164,12 @@ def process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p, weigh
             imager.set_clean_mask(before)
     return _process_channel_masked(
         reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type, vis_block, major,
-        degrid, subtract_model, batched_clean, fit_beam, clean_batcher, None)
+        degrid, subtract_model, batched_clean, fit_beam, clean_batcher, None, multiscale)
 
 
 def _process_channel_masked(reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type,
                             vis_block, major, degrid, subtract_model, batched_clean, fit_beam,
-                            clean_batcher, auto_mask):
+                            clean_batcher, auto_mask, multiscale=False):
     """:func:`process_channel` with the imager's mask as it stands; ``auto_mask``: None, or
     (parameters, the user's mask on the device or None)."""
     import contextlib
@@ -148,13 +179,13 @@ def _process_channel_masked(reader, rel_channel, imager, image_p, grid_p, clean_
             return _process_channel_stages(
                 reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type, vis_block,
                 major, degrid, subtract_model, batched_clean, fit_beam, clean_batcher,
-                clean_batcher.device_phase, auto_mask)
+                clean_batcher.device_phase, auto_mask, multiscale)
         finally:
             clean_batcher.idle()        # (nobody waits for this thread until its next stage)
     return _process_channel_stages(
         reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type, vis_block, major,
         degrid, subtract_model, batched_clean, fit_beam, clean_batcher, contextlib.nullcontext,
-        auto_mask)
+        auto_mask, multiscale)
 
 
 def _check_imager_parameters(imager, image_p, grid_p):
@@ -182,7 +213,7 @@ def _check_imager_parameters(imager, image_p, grid_p):
 
 def _process_channel_stages(reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type,
                             vis_block, major, degrid, subtract_model, batched_clean, fit_beam,
-                            clean_batcher, device_phase, auto_mask=None):
+                            clean_batcher, device_phase, auto_mask=None, multiscale=False):
     num_pols = len(image_p.fixed.polarizations)
     with device_phase():
         imager.clear_model()
@@ -257,6 +288,29 @@ def _process_channel_stages(reader, rel_channel, imager, image_p, grid_p, clean_
         noise_threshold = float(noise) * clean.noise_threshold_scale(clean_p.mode, clean_p.threshold,
                                                                      num_pols)
         values = None
+        if multiscale:
+            # the multi-scale operator: the first cycle at threshold 0 for the peak, the threshold
+            # expression below as it is, then the other cycles
+            with trace.range('first_cycle'):
+                imager.multiscale_reset(new_psf=i == 0)
+                first = imager.multiscale_cycles(psf_patch, 0.0, 1)
+            if len(first) == 0:
+                break       # (only under a CLEAN mask: nothing allowed is left)
+            peak_value = first['peak'][0]
+            out['peaks'].append(peak_value)
+            peak_power = clean.metric_to_power(clean_p.mode, float(peak_value))
+            mgain_threshold = (1.0 - clean_p.major_gain) * peak_power
+            threshold = max(noise_threshold, mgain_threshold)
+            if peak_power <= threshold:
+                break
+            threshold_metric = clean.power_to_metric(clean_p.mode, threshold)
+            with trace.range('clean[%d]' % i):
+                log = imager.multiscale_cycles(psf_patch, threshold_metric, clean_p.minor - 1)
+            out['minor'] += len(log) + (1 if len(log) < clean_p.minor - 1 else 0)
+            if i == major - 1:
+                with trace.range('noise_est'):
+                    out['noise'] = imager.noise_est()
+            continue
         if batched_clean and getattr(imager, 'one_call_major_cycles', False) is True \
                 and noise_threshold == noise_threshold:         # (not NaN)
             # the first cycle and the others in one call: the threshold follows from the first

@@ -16,7 +16,7 @@ import functools
 
 import numpy as np
 
-from . import accel, clean, grid, image, mask, predict, types, weight
+from . import accel, clean, grid, image, mask, multiscale, predict, types, weight
 
 
 class ImagingTemplate:
@@ -234,6 +234,7 @@ class Imaging(accel.OperationSequence):
         self._small_stream = None       # (small read-backs next to the queue's work)
         self._dirty_cleared = False
         self._auto = None               # the auto-mask operators and planes (:meth:`auto_mask`)
+        self._multiscale = None         # (parameters, operator or None): :meth:`set_multiscale`
         operations = [
             ('weights', self._weights), ('gridder', self._gridder), ('predict', self._predict),
             ('continuum_predict', self._continuum_predict),
@@ -814,6 +815,45 @@ class Imaging(accel.OperationSequence):
             auto['counted'].extend(int(n) for n in counts[:auto['calls']])
             auto['calls'] = 0
         return list(auto['counted'])
+
+    # ---- multi-scale CLEAN (multiscale.py; include/kimg.h, "Multi-scale CLEAN") -----------------
+    def set_multiscale(self, params):
+        """Choose the scales of :meth:`multiscale_cycles` (:class:`multiscale.MultiScaleParameters`;
+        None drops them and the operator's memory).  Nothing is allocated or launched here: the
+        operator is made by the first :meth:`multiscale_reset`, its workspace by the first cycles."""
+        self._multiscale = None if params is None else (params, None)
+
+    def _multiscale_op(self):
+        if self._multiscale is None:
+            raise ValueError('no scales set (Imaging.set_multiscale)')
+        params, op = self._multiscale
+        if op is None:
+            t = self.template
+            num_pols = len(self.image_parameters.fixed.polarizations)
+            op = multiscale.MultiScaleCleanTemplate(
+                t.context, t.clean_parameters, params, self.image_parameters.fixed.real_dtype,
+                num_pols).instantiate(self.command_queue, self.image_parameters)
+            self._multiscale = (params, op)
+        op.bind(dirty=self.buffer('dirty'), model=self.buffer('model'), psf=self.buffer('psf'),
+                mask=self.clean_mask)
+        return op
+
+    @_serial
+    def multiscale_reset(self, new_psf=True):
+        """Call after populating dirty, psf and model and before the first multi-scale cycle of a
+        major cycle: the scale residuals and tiles are rebuilt from the dirty image and the clean
+        mask bound now, with ``new_psf`` (the default) also everything that follows from the PSF."""
+        self._ready()
+        self._multiscale_op().reset(new_psf)
+
+    @_serial
+    def multiscale_cycles(self, psf_patch, threshold, max_cycles):
+        """Up to ``max_cycles`` multi-scale minor cycles on the device; returns the log, a
+        structured array with ``scale``, ``y``, ``x``, ``peak`` and ``flux`` per component.  The
+        components are extended, so they are not added to the component dictionary of the DFT
+        predictor: the model image holds them (use degridding)."""
+        self._ready()
+        return self._multiscale_op().run_cycles(psf_patch, threshold, max_cycles)
 
     @_serial
     def clean_reset(self):
