@@ -37,9 +37,8 @@ extern "C" {
 #define KIMG_EINVAL (-10001)      /* bad argument (null pointer, negative size ...) */
 #define KIMG_EUNSUPPORTED (-10002) /* parameter combination not supported by this build */
 #define KIMG_EWORKSPACE (-10003)   /* workspace too small */
-#define KIMG_ETIMEOUT (-10004)     /* workgroups of a persistent kernel did not see each other in time
-                                    * (reported after the stream was synchronised by the caller: see
-                                    * kimg_clean_cycles) */
+#define KIMG_ETIMEOUT (-10004)     /* the host-paced loop of KIMG_CLEAN_FORM_MULTI saw no progress of the
+                                    * device in time (the return value of the call) */
 
 /* Arithmetic of the gridder / degridder matrix instructions (argument `arith`):
  *   KIMG_ARITH_FP32        every product and sum in float32, bit-identical to the fmaf chain of the
@@ -84,18 +83,8 @@ extern "C" {
 #define KIMG_CLEAN_FORM_AUTO 0      /* one launch per cycle when the patch's lattice blocks fit the CUs */
 #define KIMG_CLEAN_FORM_TWO_LAUNCH 1
 #define KIMG_CLEAN_FORM_ONE_LAUNCH 2    /* falls back to two launches when the patch is too large */
-#define KIMG_CLEAN_FORM_PERSISTENT 3    /* the whole loop in one launch of resident workgroups (small
-                                         * patches: at most 64 lattice blocks, tile maxima in LDS);
-                                         * falls back to ONE_LAUNCH otherwise.  Measured slower than
-                                         * ONE_LAUNCH (agent-scope hand-offs cost what the kernel
-                                         * boundary costs): AUTO does not take it. */
-#define KIMG_CLEAN_FORM_ONE_WORKGROUP 4 /* the whole loop in ONE workgroup: tile records and the PSF
-                                         * patch in its LDS, no kernel boundary and no hand-off per
-                                         * cycle.  One polarization, at most 8 x 8 lattice blocks,
-                                         * 6 bytes of LDS per tile + the patch; falls back to AUTO's
-                                         * choice otherwise.  Measured slower than ONE_LAUNCH (7.0 vs
-                                         * 6.3 us per cycle: one CU's memory pipe): AUTO does not
-                                         * take it. */
+#define KIMG_CLEAN_FORM_PERSISTENT 3    /* retired: measured slower, runs as ONE_LAUNCH */
+#define KIMG_CLEAN_FORM_ONE_WORKGROUP 4 /* retired: measured slower, runs as ONE_LAUNCH */
 
 #define KIMG_CLEAN_FORM_MULTI 5     /* SEVERAL components per launch: a launch verifies the components
                                      * the last one evaluated speculatively, commits the verified
@@ -634,9 +623,7 @@ int kimg_noise_est(const float *image, int64_t row_stride, int64_t pol_stride,
  *   log    device float32 [max_cycles][3 + P]: (metric, y, x as float bits, loop_gain*pixel[p])
  *   form   KIMG_CLEAN_FORM_*
  *   After the stream is synchronised, ((int32*)state)[0] holds the number of cycles done
- *   (stops early when the peak metric < threshold, clean.py:879-880); ((int32*)state)[1] is 2 if
- *   the persistent form gave up waiting (KIMG_ETIMEOUT for the caller to raise; the images are
- *   then undefined).
+ *   (stops early when the peak metric < threshold, clean.py:879-880).
  */
 size_t kimg_clean_state_bytes(int num_polarizations, int tiles_x, int tiles_y);
 int kimg_clean_cycles(float *dirty, float *model, int64_t row_stride, int64_t pol_stride,

@@ -370,8 +370,9 @@ class _SubtractPsf(accel.Operation):
         check(rc, 'kimg_subtract_psf')
 
 
+# KIMG_CLEAN_FORM_* ('persistent' and 'one_workgroup' are retired: they run as 'one_launch')
 CLEAN_FORMS = {'auto': 0, 'two_launch': 1, 'one_launch': 2, 'persistent': 3, 'one_workgroup': 4,
-               'multi': 5}     # KIMG_CLEAN_FORM_*
+               'multi': 5}
 
 
 class CleanTemplate:
@@ -613,9 +614,8 @@ class Clean(accel.OperationSequence):
     def _collect_cycle_arrays(self):
         """Read back what the device-resident loop logged (synchronises with the queue):
         (peak metrics float32 [n], positions int32 [n][2] as (y, x), model pixels float32 [n][P])."""
-        # (only the head of the state buffer: it also holds the persistent form's per-workgroup
-        # replicas, tens of megabytes)
-        # ... and state and log in ONE read-back (each is a host round trip)
+        # (only the head of the state buffer) ... and state and log in ONE read-back (each is a host
+        # round trip)
         import torch
         self._finish_read_back()
         if self._read_result is not None:
@@ -631,8 +631,6 @@ class Clean(accel.OperationSequence):
                 rows = min(self._log_rows, self._log.shape[0])
                 both = torch.cat([head, self._log.tensor[:rows].reshape(-1)]).cpu().numpy()
         state = both[:4].view(np.int32)
-        if int(state[1]) == 2:
-            check(-10004, 'kimg_clean_cycles')       # KIMG_ETIMEOUT: the persistent loop gave up
         count = int(state[0])
         log = both[4:].reshape(rows, self._log.shape[1])[:count]
         return log[:, 0].copy(), log[:, 1:3].copy().view(np.int32), log[:, 3:].copy()

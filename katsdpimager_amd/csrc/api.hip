@@ -131,7 +131,7 @@ extern "C" const char *kimg_error_string(int code)
     case KIMG_EINVAL: return "invalid argument";
     case KIMG_EUNSUPPORTED: return "unsupported parameter combination";
     case KIMG_EWORKSPACE: return "workspace too small";
-    case KIMG_ETIMEOUT: return "persistent kernel timed out waiting for its peer workgroups";
+    case KIMG_ETIMEOUT: return "the multi-component CLEAN loop saw no progress of the device in time";
     default:
         if (code < 0 && code > -10000)
             return hipGetErrorString((hipError_t) (-code));

@@ -10,126 +10,13 @@
 //    subtract (clean.py:1044-1046): this file is built with -ffp-contract=off.
 #include "kimg_common.h"
 #include "kimg_graph_cache.h"
+#include "kimg_peak_key.h"
 #include <limits.h>
 #include <string.h>
 
 namespace {
 
 constexpr int TILE = 32;            // clean.py:996
-
-struct best_t {
-    float value;
-    int idx;                        // row-major index; INT_MAX = none yet
-};
-
-__device__ inline bool better(const best_t &a, const best_t &b)
-{
-    return a.value > b.value || (a.value == b.value && a.idx < b.idx);
-}
-
-__device__ inline best_t wave_best(best_t b)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        best_t o;
-        o.value = __shfl_xor(b.value, off, WAVE);
-        o.idx = __shfl_xor(b.idx, off, WAVE);
-        if (better(o, b))
-            b = o;
-    }
-    return b;
-}
-
-// Block-wide argmax with the tie-break of better(); result valid in thread 0.
-__device__ inline best_t block_best(best_t b)
-{
-    __shared__ best_t scratch[16];
-    b = wave_best(b);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0)
-        scratch[wv] = b;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int nw = blockDim.x >> 6;
-        for (int w = 1; w < nw; w++)
-            if (better(scratch[w], b))
-                b = scratch[w];
-    }
-    return b;
-}
-
-// (value, index) as one unsigned key: larger value first, then smaller index.  Values are
-// non-negative floats (never NaN: a NaN metric never replaces a tile's best), whose bit patterns
-// order like the numbers.  Key 0 = nothing.
-typedef unsigned long long key_t;
-
-__device__ inline key_t make_key(float value, int idx)
-{
-    return ((key_t) __float_as_uint(value) << 32) | (unsigned) ~idx;
-}
-
-__device__ inline key_t key_max(key_t a, key_t b) { return a > b ? a : b; }
-
-template <int CTRL>
-__device__ inline key_t key_dpp(key_t k)
-{
-    const unsigned lo = __builtin_amdgcn_mov_dpp((unsigned) k, CTRL, 0xf, 0xf, true);
-    const unsigned hi = __builtin_amdgcn_mov_dpp((unsigned) (k >> 32), CTRL, 0xf, 0xf, true);
-    return ((key_t) hi << 32) | lo;
-}
-
-// Maximum over each 16-lane row, in every lane of the row (DPP butterflies: ALU latency only)
-__device__ inline key_t row_max_key(key_t k)
-{
-    k = key_max(k, key_dpp<0xB1>(k));       // quad_perm [1,0,3,2]
-    k = key_max(k, key_dpp<0x4E>(k));       // quad_perm [2,3,0,1]
-    k = key_max(k, key_dpp<0x141>(k));      // row_half_mirror
-    k = key_max(k, key_dpp<0x140>(k));      // row_mirror
-    return k;
-}
-
-__device__ inline key_t read_lane_key(key_t k, int lane)
-{
-    return ((key_t) (unsigned) __builtin_amdgcn_readlane((int) (k >> 32), lane) << 32)
-           | (unsigned) __builtin_amdgcn_readlane((int) k, lane);
-}
-
-// Maximum over a block of up to 1024 threads (a multiple of 64), the same (uniform) value in
-// every thread.  `s_keys` [16] is shared scratch; two uses must be separated by a barrier.
-__device__ inline key_t block_max_key(key_t k, key_t *s_keys)
-{
-    k = row_max_key(k);
-    const key_t w = key_max(key_max(read_lane_key(k, 0), read_lane_key(k, 16)),
-                            key_max(read_lane_key(k, 32), read_lane_key(k, 48)));
-    if ((threadIdx.x & 63) == 0)
-        s_keys[threadIdx.x >> 6] = w;
-    __syncthreads();
-    const int nw = blockDim.x >> 6, e = threadIdx.x & 15;
-    k = row_max_key(e < nw ? s_keys[e] : 0);
-    return read_lane_key(k, 0);
-}
-
-// A workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every global
-// store of the wave (its release semantics), which puts the latency of stores nobody is waiting
-// for on a latency-critical chain.
-__device__ inline void lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// block_max_key with that barrier
-__device__ inline key_t block_max_key_lds(key_t k, key_t *s_keys)
-{
-    k = row_max_key(k);
-    const key_t w = key_max(key_max(read_lane_key(k, 0), read_lane_key(k, 16)),
-                            key_max(read_lane_key(k, 32), read_lane_key(k, 48)));
-    if ((threadIdx.x & 63) == 0)
-        s_keys[threadIdx.x >> 6] = w;
-    lds_barrier();
-    const int nw = blockDim.x >> 6, e = threadIdx.x & 15;
-    k = row_max_key(e < nw ? s_keys[e] : 0);
-    return read_lane_key(k, 0);
-}
 
 template <int MODE>
 __device__ inline float clean_metric(const float *__restrict__ dirty, int64_t addr,
@@ -157,7 +44,8 @@ __device__ inline void tile_peak(const float *__restrict__ dirty, int64_t row_st
                                  const uint8_t *__restrict__ mask, int64_t mask_row_stride)
 {
     const int x0 = tx * TILE + border, y0 = ty * TILE + border;
-    best_t b = {0.0f, INT_MAX};
+    __shared__ key_t s_keys[4];
+    key_t b = 0;                        // only positive metrics count (clean.py:953-958)
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int idx = threadIdx.x + k * 256;
@@ -165,23 +53,14 @@ __device__ inline void tile_peak(const float *__restrict__ dirty, int64_t row_st
         if (x < width - border && y < height - border
             && (!MASKED || mask[(int64_t) y * mask_row_stride + x])) {
             float v = clean_metric<MODE>(dirty, (int64_t) y * row_stride + x, pol_stride, P);
-            if (v > b.value) {
-                b.value = v;
-                b.idx = idx;
-            }
+            if (v > 0.0f)
+                b = key_max(b, make_key(v, idx));
         }
     }
-    b = block_best(b);
+    b = block_max_key(b, s_keys);
     if (threadIdx.x == 0) {
         const int t = ty * tiles_x + tx;
-        tile_max[t] = b.value;
-        if (b.idx == INT_MAX) {             // clean.py:950 best_pos = (x0, y0)
-            tile_pos[2 * t] = x0;
-            tile_pos[2 * t + 1] = y0;
-        } else {
-            tile_pos[2 * t] = y0 + (b.idx >> 5);
-            tile_pos[2 * t + 1] = x0 + (b.idx & 31);
-        }
+        store_tile_record(b, x0, y0, tile_max, tile_pos, t);
     }
 }
 
@@ -607,20 +486,6 @@ struct owned_tiles {
     }
 };
 
-// (the whole-loop kernel further down keeps an owner's best two in registers)
-struct owner_best_t {
-    float v1;
-    int t1;
-    float v2;
-    int t2;
-};
-
-__device__ inline owner_best_t best_two(const owner3_t &b)
-{
-    owner_best_t o = {b.v[0], b.t[0], b.v[1], b.t[1]};
-    return o;
-}
-
 __device__ inline void apply_delta(const delta_t &d, float *tile_max, int32_t *tile_pos,
                                    float *tile_pix)
 {
@@ -742,7 +607,7 @@ __device__ __attribute__((always_inline)) inline void fused_cycle(
     KSTAMP(1);
     const key_t mykey = live ? make_key(d.value, d.tile) : 0;
     // (a barrier that orders LDS only: the keeper's table loads are still in flight)
-    key_t best = block_max_key_lds(mykey, s_keys);
+    key_t best = block_max_key<true>(mykey, s_keys);
     // (the rest never contains a tile that has a delta: keys of different tiles differ)
     const key_t rest_key = rest.value >= 0.0f ? make_key(rest.value, rest.tile) : 0;
     const bool from_rest = rest_key > best;
@@ -834,7 +699,7 @@ __device__ __attribute__((always_inline)) inline void fused_cycle(
         KSTAMP(3);
         // (barriers that order LDS only: __syncthreads() would wait for the record loads)
         lds_barrier();                          // (s_keys is free again)
-        const key_t rbest = block_max_key_lds(ckey, s_keys);
+        const key_t rbest = block_max_key<true>(ckey, s_keys);
         KSTAMP(4);
         rest_t *rout = &scratch->rest[parity ^ 1];
         if (rbest == 0) {
@@ -1044,811 +909,6 @@ __global__ __launch_bounds__(1024) void cycle_fused_batch_kernel(
                              psf_row_stride, psf_pol_stride, psf_w, psf_h, ch.patch_w, ch.patch_h,
                              border, ch.tile_max, ch.tile_pos, tiles_x, tiles_y, loop_gain,
                              ch.scratch, parity, ch.log, blk_x, blk_y, role, nullptr, 0);
-}
-
-// ---- the whole minor-cycle loop in ONE launch ----------------------------------------------
-// The one-launch-per-cycle form above still pays a kernel boundary per cycle (2.1 us between
-// dependent graph nodes + a cold first load).  Here the lattice workgroups of a small PSF patch
-// (at most PERSIST_MAX_WGS, all resident at once, one per CU) stay alive for the whole call and
-// hand their results to each other through memory:
-//   * after its subtraction a workgroup drains its pixel stores (every wave s_waitcnt vmcnt(0),
-//     barrier) and publishes ONE record -- the rewritten tile, or "no tile" -- as eight 8-byte
-//     {word, tag} granules, each written by a single write-through (sc1) store: a reader that sees
-//     all eight tags of cycle c has a consistent record and, because the pixel stores were
-//     write-through and drained first, may read those pixels (MI355X_MICROARCH.md, hand-offs with
-//     sc1 stores / loads and data-tagged granules);
-//   * at the top of a cycle the first waves poll the records of all workgroups (sc1 loads), route
-//     them through LDS to the threads that own the tiles, and every workgroup then finds the peak
-//     itself exactly as in the one-launch form -- so all agree on it without further exchange;
-//   * pixels are read and written with sc1 (L1-bypassing, write-through) accesses, since another
-//     workgroup's CU may have written them a cycle earlier;
-//   * everything a workgroup needs besides is PRIVATE to it: the tile maxima live in its LDS, the
-//     owners' best-two in registers, tile positions / peak pixels in a replica of its own in the
-//     scratch buffer (workgroup 0 uses the real arrays), all updated from the same records;
-//   * records are double-buffered by cycle parity: a workgroup can only be one cycle ahead of the
-//     slowest one.
-// Selection and arithmetic are those of the other forms, bit for bit.  Every wait is bounded: a
-// workgroup that does not see its peers within PERSIST_SPIN_LIMIT polls raises `error` and
-// everybody leaves (kimg_clean_cycles then reports KIMG_ETIMEOUT).
-//
-// MEASURED (MI355X, 4096^2, 111 x 133 patch = 30 workgroups; wall_clock64 stamps of workgroup 0,
-// build flag -DKIMG_CLEAN_STAMPS): 10.3-11.0 us per cycle against 6.2 for the one-launch-per-cycle
-// form, so KIMG_CLEAN_FORM_AUTO does NOT take this form; it stays selectable and tested.  Per cycle:
-// 2.6-3.0 us until the records of all peers are visible (an agent-scope hand-off is a fabric write
-// plus a fabric read, and the poll itself is a 1-us round trip), 0.4 routing / applying, 2.4-2.9
-// until the peak is known (the waves whose owners got a record rescan their tiles and fetch a
-// record before they reach the reduction's barrier -- work the one-launch form leaves to its
-// keeper workgroup, off the critical path), 1.05 for the block's pixels (sc1 loads are served from
-// the memory side), 1.0 subtract + rescan + stores, 0.1 drain.  Moving the rescan behind the
-// publication would bring it to about 5.7 us: the hand-off alone costs what the kernel boundary
-// cost, which is why none of the in-launch exchanges tried so far beat one launch per cycle.
-constexpr int PERSIST_MAX_WGS = 64;
-constexpr int PERSIST_SPIN_LIMIT = 1 << 21;
-constexpr size_t PERSIST_LDS_LIMIT = 160 * 1024 - 2048;
-
-struct persist_header {
-    unsigned long long records[2][PERSIST_MAX_WGS][8];      // {word | tag << 32}
-    int error;
-    int pad[15];
-    // replicas follow: [wgs - 1][tiles] x { int y, x; float pix[4] }
-};
-
-struct replica_t {
-    int y, x;
-    float pix[4];
-};
-
-__device__ inline float load_sc1(const float *p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ inline void store_sc1(float *p, float v)
-{
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <int MODE>
-__global__ __launch_bounds__(1024) void cycle_persistent_kernel(
-    float *dirty, float *model, int64_t row_stride, int64_t pol_stride, int width, int height,
-    int P, const float *__restrict__ psf, int64_t psf_row_stride, int64_t psf_pol_stride,
-    int psf_w, int psf_h, int patch_w, int patch_h, int border, float *tile_max,
-    int32_t *tile_pos, int tiles_x, int tiles_y, float loop_gain, float threshold, int limit,
-    fused_scratch *scratch, persist_header *hdr, replica_t *replicas, float *log)
-{
-    extern __shared__ __align__(16) unsigned char persist_smem[];
-    __shared__ key_t s_keys[16];
-    __shared__ int s_pos[2];
-    __shared__ float s_pix[4];
-    __shared__ int s_abort;
-    const int tiles = tiles_x * tiles_y;
-    float *s_tile_max = reinterpret_cast<float *>(persist_smem);
-    delta_t *s_delta = reinterpret_cast<delta_t *>(persist_smem + (((size_t) tiles * 4 + 15) & ~(size_t) 15));
-    float *tile_pix = reinterpret_cast<float *>(scratch + 1);
-    const int tid = threadIdx.x;
-    const int nwgs = gridDim.x * gridDim.y;
-    const int wg = blockIdx.y * gridDim.x + blockIdx.x;
-    // this workgroup's own copy of (tile position, peak pixels): workgroup 0 keeps the real arrays
-    replica_t *mine = wg ? replicas + (size_t) (wg - 1) * tiles : nullptr;
-
-    for (int i = tid; i < tiles; i += 1024) {
-        s_tile_max[i] = tile_max[i];
-        if (wg) {
-            replica_t r;
-            r.y = tile_pos[2 * i];
-            r.x = tile_pos[2 * i + 1];
-#pragma unroll
-            for (int p = 0; p < 4; p++)
-                r.pix[p] = tile_pix[4 * i + p];
-            mine[i] = r;
-        }
-    }
-    s_delta[tid].tag = 0;
-    if (tid == 0)
-        s_abort = 0;
-    __syncthreads();
-    owner_best_t ob;
-    {
-        owned_tiles walk(tid, tiles_x, tiles_y);
-        ob = best_two(walk.best(s_tile_max, -1, 0.0f));
-    }
-    // (position, peak pixels) of this owner's best tile, kept in registers: the peak search then
-    // needs no memory access at all
-    auto load_record = [&](int t) {
-        replica_t r;
-        if (wg) {
-            r = mine[t];
-        } else {
-            r.y = tile_pos[2 * t];
-            r.x = tile_pos[2 * t + 1];
-#pragma unroll
-            for (int p = 0; p < 4; p++)
-                r.pix[p] = tile_pix[4 * t + p];
-        }
-        return r;
-    };
-    replica_t best_rec = {0, 0, {0.0f, 0.0f, 0.0f, 0.0f}};
-    if (ob.v1 >= 0.0f)
-        best_rec = load_record(ob.t1);
-
-#ifdef KIMG_CLEAN_STAMPS
-    long long pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pt = wall_clock64();
-#define PSTAMP(i) do { if (wg == 0 && tid == 0) { const long long n_ = wall_clock64(); pacc[i] += n_ - pt; pt = n_; } } while (0)
-#else
-#define PSTAMP(i) do { } while (0)
-#endif
-    int count = 0;
-    for (;;) {
-        PSTAMP(0);
-        // ---- the records of the previous cycle ------------------------------------------------
-        delta_t d;
-        d.tag = 0;
-        if (count > 0) {
-            if (tid < nwgs) {
-                const unsigned long long *rec = hdr->records[(count - 1) & 1][tid];
-                const unsigned tag = (unsigned) count + 1;
-                unsigned long long g[8];
-                int spins = 0;
-                for (;;) {
-                    bool ok = true;
-#pragma unroll
-                    for (int k = 0; k < 8; k++) {
-                        g[k] = __hip_atomic_load(rec + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        ok &= (unsigned) (g[k] >> 32) == tag;
-                    }
-                    if (ok)
-                        break;
-                    if (++spins > PERSIST_SPIN_LIMIT
-                        || __hip_atomic_load(&hdr->error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                        __hip_atomic_store(&hdr->error, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        s_abort = 1;
-                        break;
-                    }
-                }
-                const int tile = (int) (unsigned) g[0];
-                if (!s_abort && tile >= 0) {
-                    // route the record to the thread that owns the tile
-                    delta_t o;
-                    o.tag = (int) tag;
-                    o.tile = tile;
-                    o.value = __uint_as_float((unsigned) g[1]);
-                    o.y = (int) (unsigned) g[2];
-                    o.x = (int) (unsigned) g[3];
-#pragma unroll
-                    for (int p = 0; p < 4; p++)
-                        o.pix[p] = __uint_as_float((unsigned) g[4 + p]);
-                    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-                    s_delta[(ty & 31) * 32 + (tx & 31)] = o;
-                }
-            }
-            PSTAMP(1);
-            __syncthreads();
-            if (s_abort)
-                return;
-            d = s_delta[tid];
-            if (d.tag == count + 1) {
-                s_tile_max[d.tile] = d.value;           // (only ever read by this thread: it owns the tile)
-                if (wg) {
-                    replica_t r;
-                    r.y = d.y;
-                    r.x = d.x;
-#pragma unroll
-                    for (int p = 0; p < 4; p++)
-                        r.pix[p] = d.pix[p];
-                    mine[d.tile] = r;
-                } else {
-                    tile_pos[2 * d.tile] = d.y;
-                    tile_pos[2 * d.tile + 1] = d.x;
-#pragma unroll
-                    for (int p = 0; p < 4; p++)
-                        tile_pix[4 * d.tile + p] = d.pix[p];
-                }
-                owned_tiles walk(tid, tiles_x, tiles_y);
-                ob = best_two(walk.best(s_tile_max, -1, 0.0f));
-                if (ob.v1 >= 0.0f) {
-                    if (ob.t1 == d.tile) {
-                        best_rec.y = d.y;
-                        best_rec.x = d.x;
-#pragma unroll
-                        for (int p = 0; p < 4; p++)
-                            best_rec.pix[p] = d.pix[p];
-                    } else {
-                        best_rec = load_record(ob.t1);
-                    }
-                }
-            }
-        }
-        if (count >= limit)
-            break;
-        PSTAMP(2);
-
-        // ---- the peak: every workgroup for itself ----------------------------------------------
-        const float bv = ob.v1;
-        const int bi = ob.t1;
-        const int2 cpos = make_int2(best_rec.y, best_rec.x);
-        const float4 cpix = make_float4(best_rec.pix[0], best_rec.pix[1], best_rec.pix[2], best_rec.pix[3]);
-        const key_t mykey = bv < 0.0f ? 0 : make_key(bv, bi);
-        const key_t best = block_max_key_lds(mykey, s_keys);
-        const float value = __uint_as_float((unsigned) (best >> 32));
-        PSTAMP(3);
-        if (best == 0 || value < threshold)                         // clean.py:1065-1066
-            break;
-        if (mykey == best) {        // exactly one thread: every tile has one owner
-            s_pos[0] = cpos.x;
-            s_pos[1] = cpos.y;
-            s_pix[0] = cpix.x;
-            s_pix[1] = cpix.y;
-            s_pix[2] = cpix.z;
-            s_pix[3] = cpix.w;
-        }
-        lds_barrier();
-        const int py = s_pos[0], px = s_pos[1];
-        if (value == 0.0f) {
-            // a tile without any positive metric won: its record holds the (x0, y0) start position
-            // of clean.py:950, whose pixel is read now, as the other forms do
-            __syncthreads();
-            if (tid < 4) {
-                const bool ok = py >= 0 && py < height && px >= 0 && px < width && tid < P;
-                s_pix[tid] = ok ? load_sc1(dirty + tid * pol_stride + (int64_t) py * row_stride + px) : 0.0f;
-            }
-            __syncthreads();
-        }
-        float scale[4];
-#pragma unroll
-        for (int p = 0; p < 4; p++)
-            scale[p] = loop_gain * s_pix[p];                            // clean.py:1044
-        if (wg == 0 && tid < P) {
-            float *entry = log + (int64_t) count * (3 + P);
-            float *mp = model + tid * pol_stride + (int64_t) py * row_stride + px;
-            if (tid == 0) {
-                entry[0] = value;
-                entry[1] = __int_as_float(py);
-                entry[2] = __int_as_float(px);
-            }
-            entry[3 + tid] = scale[tid];
-            *mp = *mp + scale[tid];                                     // clean.py:1047
-        }
-
-        // ---- this workgroup's lattice block ----------------------------------------------------
-        const int x0 = px - patch_w / 2, y0 = py - patch_h / 2;      // clean.py:1024-1027
-        const int bx0 = (x0 - border) >= 0 ? (x0 - border) / TILE : -((border - x0 + TILE - 1) / TILE);
-        const int by0 = (y0 - border) >= 0 ? (y0 - border) / TILE : -((border - y0 + TILE - 1) / TILE);
-        const int tx = bx0 + (int) blockIdx.x, ty = by0 + (int) blockIdx.y;
-        const int ox = tx * TILE + border, oy = ty * TILE + border;
-        const int psf_dx = psf_w / 2 - px, psf_dy = psf_h / 2 - py;
-        const bool is_tile = tx >= 0 && tx < tiles_x && ty >= 0 && ty < tiles_y;
-        const int x = ox + (tid & 31), y = oy + (tid >> 5);
-        const bool inside = x >= 0 && x < width && y >= 0 && y < height;
-        const int64_t ia = (int64_t) y * row_stride + x;
-        const bool in_patch = inside && x >= x0 && x < x0 + patch_w && y >= y0 && y < y0 + patch_h;
-        const bool in_tile = inside && is_tile && x < width - border && y < height - border;
-        float dv[4] = {0.0f, 0.0f, 0.0f, 0.0f}, pv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (inside)
-            for (int p = 0; p < P; p++)
-                dv[p] = load_sc1(dirty + p * pol_stride + ia);
-        if (in_patch)
-            for (int p = 0; p < P; p++)
-                pv[p] = psf[p * psf_pol_stride + (int64_t) (y + psf_dy) * psf_row_stride + (x + psf_dx)];
-        float metric = 0.0f;
-#ifdef KIMG_CLEAN_STAMPS
-        if (dv[0] + pv[0] == 12345.678f)
-            pacc[7] = 1;
-        PSTAMP(4);
-#endif
-        for (int p = 0; p < P; p++) {
-            if (in_patch) {
-                const float tp = scale[p] * pv[p];
-                dv[p] -= tp;
-                store_sc1(dirty + p * pol_stride + ia, dv[p]);
-            }
-            if (MODE == KIMG_CLEAN_I) {
-                if (p == 0)
-                    metric = fabsf(dv[0]);
-            } else {
-                metric += dv[p] * dv[p];
-            }
-        }
-        // first strict maximum in row-major order; only positive metrics count (clean.py:953-958)
-        // (the barrier inside also orders s_pos / s_pix against the next cycle's writes)
-        const key_t tb = block_max_key((in_tile && metric > 0.0f) ? make_key(metric, tid) : 0, s_keys);
-        const int widx = ~(int) (unsigned) tb;
-        PSTAMP(5);
-        // every wave's pixel stores have left the CU before the record says so
-        __builtin_amdgcn_s_waitcnt(0);
-        __syncthreads();
-        PSTAMP(6);
-        if (tb == 0 ? tid == 0 : tid == widx) {
-            unsigned w[8];
-            w[0] = (unsigned) (is_tile ? ty * tiles_x + tx : -1);
-            if (tb == 0) {
-                // no positive metric: value 0 and the (x0, y0) initial position of clean.py:950
-                w[1] = __float_as_uint(0.0f);
-                w[2] = (unsigned) ox;
-                w[3] = (unsigned) oy;
-                w[4] = w[5] = w[6] = w[7] = 0u;
-            } else {
-                w[1] = __float_as_uint(metric);
-                w[2] = (unsigned) y;
-                w[3] = (unsigned) x;
-#pragma unroll
-                for (int p = 0; p < 4; p++)
-                    w[4 + p] = __float_as_uint(dv[p]);
-            }
-            unsigned long long *rec = hdr->records[count & 1][wg];
-            const unsigned long long tag = (unsigned long long) (unsigned) (count + 2) << 32;
-#pragma unroll
-            for (int k = 0; k < 8; k++)
-                __hip_atomic_store(rec + k, tag | w[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        count++;
-    }
-    __syncthreads();        // (the owners' last updates of the LDS tile maxima, read by other threads below)
-    if (wg == 0) {
-        // the tile maxima go back to the caller's array; positions / peak pixels are already there
-        for (int i = tid; i < tiles; i += 1024)
-            tile_max[i] = s_tile_max[i];
-        if (tid == 0) {
-            scratch->st[0].count = count;
-            scratch->st[0].done = 1;
-#ifdef KIMG_CLEAN_STAMPS
-            for (int i = 0; i < 8; i++)
-                scratch->st[0].pad[i] = (int) (pacc[i] / (count > 0 ? count : 1));
-#endif
-        }
-    }
-}
-
-// state[1] := 2 when the persistent loop gave up (see kimg.h)
-__global__ void persist_status_kernel(fused_scratch *scratch, const persist_header *hdr)
-{
-    if (hdr->error)
-        scratch->st[0].done = 2;
-}
-
-// ---- the whole minor-cycle loop in ONE WORKGROUP ---------------------------------------------
-// For a small PSF patch a cycle moves little data (a 111 x 133 patch rewrites 59 KB and its 30
-// lattice tiles hold 123 KB) and is otherwise a chain of latencies.  The forms above pay a kernel
-// boundary (one launch per cycle) or a hand-off between workgroups (persistent form) per cycle;
-// one workgroup on one CU pays neither: everything it needs between cycles stays in its LDS, and
-// the only synchronisation is its own barrier.  What it pays instead is instruction issue: a wave
-// issues about one instruction per 5 clocks, so the ~31 K pixels of a cycle must cost few
-// instructions per wave.
-//   * LDS holds, per tile, the metric maximum (float) and a 16-bit record: the peak's index inside
-//     the tile, a flag for "no positive metric" (clean.py:950) and -- CLEAN_I -- the sign of the
-//     pixel there, so that the peak pixel is known without a load; and the PSF patch, its rows
-//     padded with zeros so that a pixel next to the patch subtracts exactly nothing;
-//   * thread (b, a) owns the tiles (ty % 32, tx % 32) = (b, a) and keeps their best two keys in
-//     registers; the global peak is one block reduction of registers; the owner of a rewritten
-//     tile gets its new best from the new record and those two, and looks at its (at most 16) LDS
-//     values again only later, while the next cycle's loads are in flight;
-//   * a wave takes whole rows of the patch's tile lattice, four pixels per lane (lane = tile
-//     column x 8 + group of four): one load, one store and one LDS read per row and lane, and
-//     everything that depends on the row (inside the image / the patch / a tile) is wave-uniform
-//     control flow.  Groups that straddle the image's edge go pixel by pixel;
-//   * all loads of a wave's rows are issued first, then one wait, then the arithmetic with its
-//     stores: loads and stores return out of order with respect to each other, so a wave that
-//     waits for a load while it has stores in flight waits for the stores, too.  The stores are
-//     only waited for (vmcnt(0) + barrier) after the NEXT peak search.
-// Selection and arithmetic are those of the other forms, bit for bit.
-//
-// MEASURED (MI355X, 4096^2, 111 x 133 patch; wall_clock64 stamps, build flag -DKIMG_CLEAN_STAMPS,
-// -DKIMG_SOLO_STAMP_TID=<thread>): 7.0 us per cycle against 6.3 for the one-launch-per-cycle form,
-// so KIMG_CLEAN_FORM_AUTO does NOT take this form; it stays selectable and tested.  Per cycle: peak
-// search 0.7 (two DPP/LDS reduction stages, the second behind the owners' update), store drain
-// 0.35, then per wave: 1.6 (first wave) to 3.1 us (ninth) until its twelve 640-byte row loads have
-// landed -- ONE CU pulls the ~150 KB of a cycle's lattice tiles out of L2 / MALL at only ~50 GB/s --
-// 1.25 for the patch rows (LDS PSF reads + 12 stores), 1.2 for the tile maxima (3 VALU
-// instructions per pixel: four waves per SIMD share one VALU, ~31 K pixels are ~2300 VALU clocks
-// per SIMD), and up to 3 us of waiting for the slowest wave (the rows of a wave are not equally
-// expensive).  Earlier layouts of the same idea: one pixel per lane with per-row predicates 16.1
-// us; units of 8 rows x 64 pixels double-buffered 9.3 (every wait for a load behind a store was a
-// wait for the store); the same with all loads first 7.8.  What would still help: loading only
-// the patch's pixels of tiles whose old maximum lies outside the patch (halves the bytes), rows
-// dealt out by cost.  Neither brings one CU below ~4.5 us: the form trades two microseconds of
-// kernel boundary for one CU's memory pipe and VALU, which is not a good trade at this patch size.
-constexpr size_t SOLO_LDS_LIMIT = 160 * 1024 - 1024;
-constexpr int SOLO_MAX_BX = 8;              // lattice columns of a patch: 8 lanes each
-constexpr int SOLO_MAX_BLOCKS = 64;         // lattice blocks of a patch
-constexpr int SOLO_AUTO_BLOCKS = 0;         // KIMG_CLEAN_FORM_AUTO takes this form up to here: never (see MEASURED)
-constexpr int SOLO_ROWS = 12;               // rows of a wave whose loads are issued together
-constexpr int SOLO_PAD = 4;                 // zeros either side of a PSF row in LDS
-constexpr unsigned SOLO_NONE = 0x4000, SOLO_SIGN = 0x8000;
-
-// tile-local key: metric, then lower index inside the tile; bit 0 carries the pixel's sign
-__device__ inline key_t solo_pixel_key(float metric, int idx, bool negative)
-{
-    return ((key_t) __float_as_uint(metric) << 32) | (unsigned) (((1023 - idx) << 1) | (negative ? 1 : 0));
-}
-
-// global key: metric, then lower (ty, tx) in row-major order (no division to get them back)
-__device__ inline key_t solo_tile_key(float value, int ty, int tx)
-{
-    return ((key_t) __float_as_uint(value) << 32) | (unsigned) ~((ty << 16) | tx);
-}
-
-struct solo_f4 { float v[4]; };             // four pixels, 4-byte aligned
-
-template <int MODE>
-__global__ __launch_bounds__(1024) void cycle_solo_kernel(
-    float *dirty, float *model, int64_t row_stride, int width, int height,
-    const float *__restrict__ psf, int64_t psf_row_stride, int psf_w, int psf_h, int patch_w,
-    int patch_h, int border, float *tile_max, int32_t *tile_pos, int tiles_x, int tiles_y,
-    float loop_gain, float threshold, int limit, fused_scratch *scratch, float *log)
-{
-    constexpr bool FAST = MODE == KIMG_CLEAN_I;     // the peak pixel is +-metric
-    extern __shared__ __align__(16) unsigned char solo_smem[];
-    __shared__ key_t s_keys[16];
-    __shared__ key_t s_tkey[SOLO_MAX_BLOCKS];       // per lattice block: best pixel key of the cycle
-    const int tiles = tiles_x * tiles_y;
-    float *s_val = reinterpret_cast<float *>(solo_smem);
-    unsigned short *s_rec = reinterpret_cast<unsigned short *>(solo_smem + (size_t) tiles * 4);
-    float *s_psf = reinterpret_cast<float *>(solo_smem + (((size_t) tiles * 6 + 15) & ~(size_t) 15));
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int own_x = tid & 31, own_y = tid >> 5;
-    const int ppx = psf_w / 2 - patch_w / 2, ppy = psf_h / 2 - patch_h / 2;   // patch origin in the PSF
-    const int pstride = patch_w + 2 * SOLO_PAD;
-
-    for (int t = tid; t < tiles; t += 1024) {
-        const float v = tile_max[t];
-        const int2 pos = *reinterpret_cast<const int2 *>(tile_pos + 2 * t);
-        const int ty = t / tiles_x, tx = t - ty * tiles_x;
-        unsigned rec = SOLO_NONE;
-        if (v != 0.0f) {
-            rec = (unsigned) ((pos.x - (ty * TILE + border)) * TILE + (pos.y - (tx * TILE + border)));
-            if (FAST && dirty[(int64_t) pos.x * row_stride + pos.y] < 0.0f)
-                rec |= SOLO_SIGN;
-        }
-        s_val[t] = v;
-        s_rec[t] = (unsigned short) rec;
-    }
-    for (int i = tid; i < pstride * patch_h; i += 1024) {
-        const int r = i / pstride, c = i - r * pstride - SOLO_PAD;
-        s_psf[i] = (c >= 0 && c < patch_w) ? psf[(int64_t) (ppy + r) * psf_row_stride + (ppx + c)] : 0.0f;
-    }
-    if (tid < SOLO_MAX_BLOCKS)
-        s_tkey[tid] = 0;
-    __syncthreads();
-
-    // The best two of this thread's tiles (keys; 0 = none), all (up to 16) LDS reads in flight.
-    // Tiles are visited in increasing key order of equal values, so plain key comparisons do.
-    key_t b1 = 0, b2 = 0;
-    const bool few_tiles = tiles_x <= 128 && tiles_y <= 128;
-    auto consider = [&](key_t k) {
-        const key_t lo = k > b1 ? b1 : k;
-        b1 = k > b1 ? k : b1;
-        b2 = lo > b2 ? lo : b2;
-    };
-    auto rescan = [&]() {
-        b1 = b2 = 0;
-        if (few_tiles) {
-#pragma unroll 1
-            for (int h = 0; h < 4; h++) {
-                const int ty = own_y + 32 * h;
-                float v[4];
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int tx = own_x + 32 * i;
-                    v[i] = s_val[(ty < tiles_y && tx < tiles_x) ? ty * tiles_x + tx : 0];
-                }
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int tx = own_x + 32 * i;
-                    consider((ty < tiles_y && tx < tiles_x) ? solo_tile_key(v[i], ty, tx) : 0);
-                }
-            }
-        } else {
-            for (int ty = own_y; ty < tiles_y; ty += 32)
-                for (int tx = own_x; tx < tiles_x; tx += 32)
-                    consider(solo_tile_key(s_val[ty * tiles_x + tx], ty, tx));
-        }
-    };
-    rescan();
-    bool stale = false;             // b1 / b2 have to be read again
-
-    const int nbx = (patch_w + TILE - 1) / TILE + 1, nby = (patch_h + TILE - 1) / TILE + 1;
-    // Work split: the lattice has nby * 32 rows of nbx * 32 pixels; the waves share the rows in
-    // consecutive runs.  Lane = (lattice column) * 8 + (group of four pixels).
-    const int lattice_rows = nby * TILE;
-    const int rows_per_wave = (lattice_rows + 15) >> 4;
-    const int row_begin = __builtin_amdgcn_readfirstlane(min(wave * rows_per_wave, lattice_rows));
-    const int row_end = __builtin_amdgcn_readfirstlane(min(row_begin + rows_per_wave, lattice_rows));
-    const int jx = (tid & 63) >> 3, grp = tid & 7;
-    const unsigned row_bytes = (unsigned) row_stride * 4u;
-
-#ifdef KIMG_CLEAN_STAMPS
-    long long sacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_t = wall_clock64();
-#ifndef KIMG_SOLO_STAMP_TID
-#define KIMG_SOLO_STAMP_TID 0
-#endif
-#define SSTAMP(i) do { if (tid == KIMG_SOLO_STAMP_TID) { const long long n_ = wall_clock64(); sacc[i] += n_ - st_t; st_t = n_; } } while (0)
-#else
-#define SSTAMP(i) do { } while (0)
-#endif
-    int count = 0;
-    for (;;) {
-        SSTAMP(0);
-        const key_t best = block_max_key_lds(b1, s_keys);
-        SSTAMP(1);
-        const float value = __uint_as_float((unsigned) (best >> 32));
-        if (best == 0 || value < threshold || count >= limit)      // clean.py:1065-1066
-            break;
-        const unsigned tcode = ~(unsigned) best;
-        const int pty = (int) (tcode >> 16), ptx = (int) (tcode & 0xffff);
-        const unsigned rec = s_rec[pty * tiles_x + ptx];
-        int py, px;
-        if (rec & SOLO_NONE) {              // clean.py:950 best_pos = (x0, y0)
-            py = ptx * TILE + border;
-            px = pty * TILE + border;
-        } else {
-            py = pty * TILE + border + (int) ((rec & 1023) >> 5);
-            px = ptx * TILE + border + (int) (rec & 31);
-        }
-        // every pixel store of the previous cycle must have landed before this cycle's loads
-        __syncthreads();
-        SSTAMP(2);
-        const bool pos_ok = py >= 0 && py < height && px >= 0 && px < width;
-        float pix;
-        if (FAST && !(rec & SOLO_NONE))
-            pix = (rec & SOLO_SIGN) ? -value : value;
-        else
-            pix = pos_ok ? dirty[(int64_t) py * row_stride + px] : 0.0f;
-        const float scale = loop_gain * pix;                        // clean.py:1044
-        float mod = 0.0f;
-        float *mp = model + (int64_t) py * row_stride + px;
-        if (tid == 0 && pos_ok)
-            mod = *mp;
-
-        const int x0 = px - patch_w / 2, y0 = py - patch_h / 2;    // clean.py:1024-1027
-        // floor division: the lattice extends into the border with negative indices
-        const int bx0 = (x0 - border) >= 0 ? (x0 - border) / TILE : -((border - x0 + TILE - 1) / TILE);
-        const int by0 = (y0 - border) >= 0 ? (y0 - border) / TILE : -((border - y0 + TILE - 1) / TILE);
-
-        // this lane's four pixels: the same for all rows.  "wide" lanes move them as one 16-byte
-        // access (lanes with nothing to do read a clamped address and never write); lanes whose
-        // group straddles the image's edge ("part") or the edge of the tile lattice (`t_part`)
-        // are served pixel by pixel in passes of their own that a wave without any skips.
-        const int tx = bx0 + jx;
-        const int x = tx * TILE + border + 4 * grp;
-        const bool lane_on = jx < nbx;
-        const bool part = lane_on && !(x >= 0 && x + 3 < width) && x + 3 >= 0 && x < width;
-        const bool wide_patch = lane_on && x >= 0 && x + 3 < width && x + 3 >= x0 && x < x0 + patch_w;
-        const bool tx_ok = lane_on && tx >= 0 && tx < tiles_x;
-        const bool t_all = tx_ok && x + 3 < width - border;
-        const bool t_part = tx_ok && !t_all && x < width - border;
-        const unsigned xoff = (unsigned) min(max(x, 0), width - 4) * 4u;
-        const int pidx0 = SOLO_PAD + (x - x0);
-        const bool any_part = __any(part), any_t_part = __any(t_part);
-        char *base = reinterpret_cast<char *>(dirty);
-        const int lattice_y = by0 * TILE + border;
-
-        // best of this lane's pixels in the (at most two) tile rows of its chunk: pixel (CLEAN_I)
-        // or metric, and where (row in chunk * 4 + pixel)
-        auto track = [&](float d, int code, float &bs, int &bc) {
-            // first strict maximum in row-major order; only positive metrics count
-            // (clean.py:953-958): rows come in increasing order, the comparison is strict
-            if (FAST) {
-                if (fabsf(d) > fabsf(bs)) {
-                    bs = d;
-                    bc = code;
-                }
-            } else {
-                const float m = 0.0f + d * d;
-                if (m > bs) {
-                    bs = m;
-                    bc = code;
-                }
-            }
-        };
-        auto bits = [](int lo, int hi) {        // bits [lo, hi) of a SOLO_ROWS-bit mask
-            lo = min(max(lo, 0), SOLO_ROWS);
-            hi = min(max(hi, lo), SOLO_ROWS);
-            return ((1u << hi) - 1u) & ~((1u << lo) - 1u);
-        };
-        for (int rb = row_begin; rb < row_end; rb += SOLO_ROWS) {
-            const int nr = min(SOLO_ROWS, row_end - rb);
-            const int yb = lattice_y + rb;              // image row of the chunk's first row
-            // rows of the chunk (bit r = row r): inside the image; patch rows; rows that count for
-            // the tiles of the chunk's first / second lattice tile row
-            const unsigned m_img = bits(-yb, min(height - yb, nr));
-            const unsigned m_patch = m_img & bits(y0 - yb, y0 + patch_h - yb);
-            const int trow_a = rb >> 5, split = ((trow_a + 1) << 5) - rb;   // rows [split, ..) are tile row b
-            const unsigned m_tile = m_img & bits(0, height - border - yb);
-            const bool ta_ok = by0 + trow_a >= 0 && by0 + trow_a < tiles_y;
-            const bool tb_ok = by0 + trow_a + 1 >= 0 && by0 + trow_a + 1 < tiles_y;
-            const unsigned m_a = ta_ok ? m_tile & bits(0, split) : 0u;
-            const unsigned m_b = tb_ok ? m_tile & bits(split, SOLO_ROWS) : 0u;
-            float dv[SOLO_ROWS][4];
-            // ---- loads: unconditional rows (clamped), nothing but loads in between
-#pragma unroll
-            for (int r = 0; r < SOLO_ROWS; r++) {
-                const int y = min(max(yb + min(r, nr - 1), 0), height - 1);     // uniform
-                solo_f4 v;
-                __builtin_memcpy(&v, base + ((unsigned) y * row_bytes + xoff), sizeof(v));
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-                    dv[r][i] = v.v[i];
-            }
-            if (any_part) {
-#pragma unroll
-                for (int r = 0; r < SOLO_ROWS; r++) {
-                    const int y = min(max(yb + min(r, nr - 1), 0), height - 1);
-                    const char *row = base + (size_t) ((unsigned) y * row_bytes);
-                    if (part) {
-#pragma unroll
-                        for (int i = 0; i < 4; i++) {
-                            dv[r][i] = 0.0f;
-                            if (x + i >= 0 && x + i < width)
-                                dv[r][i] = *reinterpret_cast<const float *>(row + (size_t) ((unsigned) (x + i) * 4u));
-                        }
-                    }
-                }
-            }
-            if (stale) {
-                // in the shadow of the loads: this owner's best two, with last cycle's record in
-                rescan();
-                stale = false;
-            }
-            // (the builtin, not inline assembly: the compiler's own wait-count bookkeeping must know
-            // that no load is pending any more, or it counts the stores against them)
-            __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0)
-            SSTAMP(5);
-            // ---- the patch rows: dirty -= (loop_gain * pixel) * psf, PSF rows fetched four at a time
-            if (m_patch) {
-#pragma unroll
-                for (int h = 0; h < SOLO_ROWS; h += 4) {
-                    solo_f4 pv[4];
-                    if (wide_patch || part) {
-#pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            // (rows outside the patch read a clamped row; they are not used)
-                            const int pr = min(max(yb + h + r - y0, 0), patch_h - 1);
-                            __builtin_memcpy(&pv[r], s_psf + pr * pstride + min(max(pidx0, 0), pstride - 4),
-                                             sizeof(solo_f4));
-                        }
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        if (!(m_patch & (1u << (h + r))))
-                            continue;
-                        const unsigned row_off = (unsigned) (yb + h + r) * row_bytes;
-                        char *row = base + (size_t) row_off;
-                        if (wide_patch) {
-                            solo_f4 v;
-#pragma unroll
-                            for (int i = 0; i < 4; i++) {
-                                const float t = scale * pv[r].v[i];
-                                dv[h + r][i] -= t;
-                                v.v[i] = dv[h + r][i];
-                            }
-                            __builtin_memcpy(base + (row_off + xoff), &v, sizeof(v));
-                        }
-                        if (any_part) {
-                            if (part) {
-#pragma unroll
-                                for (int i = 0; i < 4; i++)
-                                    if (x + i >= 0 && x + i < width && x + i >= x0 && x + i < x0 + patch_w) {
-                                        const float t = scale * pv[r].v[i];
-                                        dv[h + r][i] -= t;
-                                        *reinterpret_cast<float *>(row + (size_t) ((unsigned) (x + i) * 4u)) = dv[h + r][i];
-                                    }
-                            }
-                        }
-                    }
-                }
-            }
-            SSTAMP(6);
-            // ---- the tiles' maxima
-            float bs_a = 0.0f, bs_b = 0.0f;
-            int bc_a = 0, bc_b = 0;
-#pragma unroll
-            for (int r = 0; r < SOLO_ROWS; r++) {
-                if (m_a & (1u << r)) {
-                    if (t_all) {
-#pragma unroll
-                        for (int i = 0; i < 4; i++)
-                            track(dv[r][i], r * 4 + i, bs_a, bc_a);
-                    }
-                    if (any_t_part) {
-                        if (t_part) {
-#pragma unroll
-                            for (int i = 0; i < 4; i++)
-                                if (x + i < width - border)
-                                    track(dv[r][i], r * 4 + i, bs_a, bc_a);
-                        }
-                    }
-                }
-                if (m_b & (1u << r)) {
-                    if (t_all) {
-#pragma unroll
-                        for (int i = 0; i < 4; i++)
-                            track(dv[r][i], r * 4 + i, bs_b, bc_b);
-                    }
-                    if (any_t_part) {
-                        if (t_part) {
-#pragma unroll
-                            for (int i = 0; i < 4; i++)
-                                if (x + i < width - border)
-                                    track(dv[r][i], r * 4 + i, bs_b, bc_b);
-                        }
-                    }
-                }
-            }
-            // ---- the tiles' best keys of this chunk: 8 lanes per tile, then one LDS atomic
-            auto flush = [&](float bs, int bc, int trow) {
-                const float bm = FAST ? fabsf(bs) : bs;
-                const int idx = ((rb + (bc >> 2)) & 31) * TILE + 4 * grp + (bc & 3);
-                key_t k = bm > 0.0f ? solo_pixel_key(bm, idx, FAST && bs < 0.0f) : 0;
-                k = key_max(k, key_dpp<0xB1>(k));       // quad_perm [1,0,3,2]
-                k = key_max(k, key_dpp<0x4E>(k));       // quad_perm [2,3,0,1]
-                k = key_max(k, key_dpp<0x141>(k));      // row_half_mirror
-                if (grp == 0 && k != 0 && lane_on)
-                    atomicMax(&s_tkey[trow * nbx + jx], k);
-            };
-            if (m_a)
-                flush(bs_a, bc_a, trow_a);
-            if (m_b)
-                flush(bs_b, bc_b, trow_a + 1);
-        }
-        SSTAMP(3);
-        if (tid == 0) {
-            *reinterpret_cast<float4 *>(log + (int64_t) count * 4) =
-                make_float4(value, __int_as_float(py), __int_as_float(px), scale);
-            if (pos_ok)
-                *mp = mod + scale;                                  // clean.py:1047
-        }
-        count++;
-        lds_barrier();          // the chunks' keys are in LDS
-        SSTAMP(4);
-        // The owners of the rewritten tiles (a patch spans fewer than 32 tiles either way: at most
-        // one tile per owner) take the new record; their new best is the better of it and of the
-        // best of their other tiles, which is the first of (b1, b2) that is not this tile.
-        const int ojx = (own_x - bx0) & 31, ojy = (own_y - by0) & 31;
-        if (ojx < nbx && ojy < nby) {
-            const int otx = bx0 + ojx, oty = by0 + ojy;
-            if (otx >= 0 && otx < tiles_x && oty >= 0 && oty < tiles_y) {
-                const int t = oty * tiles_x + otx;
-                const key_t kt = s_tkey[ojy * nbx + ojx];
-                s_tkey[ojy * nbx + ojx] = 0;
-                float nv = 0.0f;
-                unsigned nrec = SOLO_NONE;
-                if (kt != 0) {
-                    const unsigned lo = (unsigned) kt;
-                    nv = __uint_as_float((unsigned) (kt >> 32));
-                    nrec = (1023 - ((lo >> 1) & 1023)) | ((lo & 1) ? SOLO_SIGN : 0);
-                }
-                s_val[t] = nv;
-                s_rec[t] = (unsigned short) nrec;
-                const unsigned code = ~(unsigned) ((oty << 16) | otx);
-                const key_t others = (unsigned) b1 == code ? b2 : b1;
-                b1 = key_max(others, solo_tile_key(nv, oty, otx));
-                stale = true;
-            }
-        }
-    }
-
-    __syncthreads();
-    for (int t = tid; t < tiles; t += 1024) {
-        const int ty = t / tiles_x, tx = t - ty * tiles_x;
-        const int ox = tx * TILE + border, oy = ty * TILE + border;
-        const unsigned rec = s_rec[t];
-        tile_max[t] = s_val[t];
-        int2 pos;
-        if (rec & SOLO_NONE)
-            pos = make_int2(ox, oy);        // clean.py:950 (x0, y0)
-        else
-            pos = make_int2(oy + (int) ((rec & 1023) >> 5), ox + (int) (rec & 31));
-        *reinterpret_cast<int2 *>(tile_pos + 2 * t) = pos;
-    }
-    if (tid == 0)
-        *reinterpret_cast<int4 *>(&scratch->st[0]) = make_int4(count, 1, limit, __float_as_int(threshold));
-#ifdef KIMG_CLEAN_STAMPS
-    if (tid == KIMG_SOLO_STAMP_TID) {
-        for (int i = 0; i < 8; i++)
-            scratch->st[0].pad[i] = (int) (sacc[i] * 100 / max(count, 1));     // 1/100 tick (0.1 ns) per cycle
-    }
-#endif
-#undef SSTAMP
 }
 
 // Pixel values at every tile's peak position (the part of a tile record the tile scan of
@@ -2169,21 +1229,14 @@ extern "C" int kimg_subtract_psf(float *dirty, float *model, int64_t row_stride,
     return kimg_launch_status();
 }
 
-// byte offset of the persistent form's header in the state buffer (behind fused_scratch + tile_pix)
-static size_t persist_offset(int tiles_x, int tiles_y)
-{
-    const size_t n = sizeof(fused_scratch) + (size_t) tiles_x * tiles_y * 4 * sizeof(float);
-    return (n + 255) / 256 * 256;
-}
-
 extern "C" size_t kimg_clean_state_bytes(int num_polarizations, int tiles_x, int tiles_y)
 {
     (void) num_polarizations;
     static_assert(sizeof(fused_scratch) >= sizeof(clean_state), "the two forms share the scratch");
     if (tiles_x <= 0 || tiles_y <= 0)
         return 0;
-    const size_t n = persist_offset(tiles_x, tiles_y) + sizeof(persist_header)
-                     + (size_t) (PERSIST_MAX_WGS - 1) * tiles_x * tiles_y * sizeof(replica_t);
+    // the one-launch form's scratch with its tile_pix[tiles][4]
+    const size_t n = sizeof(fused_scratch) + (size_t) tiles_x * tiles_y * 4 * sizeof(float);
     const size_t m = kimg_clean_multi_state_bytes(tiles_x, tiles_y);
     return n > m ? n : m;
 }
@@ -2450,30 +1503,9 @@ static int clean_cycles(float *dirty, float *model, int64_t row_stride,
         if (form == KIMG_CLEAN_FORM_MULTI)
             form = KIMG_CLEAN_FORM_AUTO;
     }
-    const int bx = kimg_divup(patch_width, TILE) + 1, by = kimg_divup(patch_height, TILE) + 1;
+    // (KIMG_CLEAN_FORM_PERSISTENT and _ONE_WORKGROUP are retired names of the one-launch form)
     const bool fused = patch_fits_one_launch(patch_width, patch_height)
                        && tiles_fit_one_launch(tiles_x, tiles_y) && form != KIMG_CLEAN_FORM_TWO_LAUNCH;
-    // the whole loop in one workgroup when the patch is small and the tile records and the PSF
-    // patch fit LDS
-    const size_t solo_lds = (((size_t) tiles_x * tiles_y * 6 + 15) & ~(size_t) 15)
-                            + (size_t) (patch_width + 2 * SOLO_PAD) * patch_height * sizeof(float);
-    const bool solo_ok = !masked && num_polarizations == 1 && bx <= SOLO_MAX_BX && by <= 32
-                         && bx * by <= SOLO_MAX_BLOCKS
-                         && (uint64_t) height * (uint64_t) row_stride < (1u << 30)
-                         && solo_lds <= SOLO_LDS_LIMIT && max_cycles > 0;
-    if (solo_ok && (form == KIMG_CLEAN_FORM_ONE_WORKGROUP
-                    || (form == KIMG_CLEAN_FORM_AUTO && bx * by <= SOLO_AUTO_BLOCKS))) {
-        int rc = 0;
-        kimg_for_clean_mode(mode, [&](auto m) {
-            constexpr int MODE = decltype(m)::value;
-            rc = kimg_dynamic_lds(reinterpret_cast<const void *>(&cycle_solo_kernel<MODE>), SOLO_LDS_LIMIT);
-            if (rc == 0)
-                cycle_solo_kernel<MODE><<<1, 1024, solo_lds, s>>>(
-                    dirty, model, row_stride, width, height, psf, psf_row_stride, psf_width, psf_height,
-                    patch_width, patch_height, border, tile_max, tile_pos, tiles_x, tiles_y, loop_gain,
-                    threshold, max_cycles, static_cast<fused_scratch *>(state), log); });
-        return rc ? rc : kimg_launch_status();
-    }
     cycle_args a;
     fill_shared(a, row_stride, pol_stride, width, height, num_polarizations, psf_row_stride,
                 psf_pol_stride, psf_width, psf_height, border, mode, loop_gain, tiles_x, tiles_y, fused);
@@ -2484,33 +1516,6 @@ static int clean_cycles(float *dirty, float *model, int64_t row_stride,
     int rc = begin_state(a, state, max_cycles, threshold, dirty, tile_pos, s);
     if (rc)
         return rc;
-    // the whole loop in one launch when the patch's lattice blocks can all be resident and the
-    // tile maxima fit LDS
-    const size_t persist_lds = (((size_t) tiles_x * tiles_y * 4 + 15) & ~(size_t) 15)
-                               + 1024 * sizeof(delta_t);
-    const bool persistent = fused && bx * by <= PERSIST_MAX_WGS && persist_lds <= PERSIST_LDS_LIMIT
-                            && form == KIMG_CLEAN_FORM_PERSISTENT && max_cycles > 0;
-    if (persistent) {
-        unsigned char *base = static_cast<unsigned char *>(state) + persist_offset(tiles_x, tiles_y);
-        persist_header *hdr = reinterpret_cast<persist_header *>(base);
-        replica_t *replicas = reinterpret_cast<replica_t *>(base + sizeof(persist_header));
-        KIMG_HIP(hipMemsetAsync(hdr, 0, sizeof(persist_header), s));
-        const dim3 g(bx, by);
-        kimg_for_clean_mode(mode, [&](auto m) {
-            constexpr int MODE = decltype(m)::value;
-            rc = kimg_dynamic_lds(reinterpret_cast<const void *>(&cycle_persistent_kernel<MODE>),
-                                  PERSIST_LDS_LIMIT);
-            if (rc == 0)
-                cycle_persistent_kernel<MODE><<<g, 1024, persist_lds, s>>>(
-                    dirty, model, row_stride, pol_stride, width, height, num_polarizations, psf,
-                    psf_row_stride, psf_pol_stride, psf_width, psf_height, patch_width, patch_height, border,
-                    tile_max, tile_pos, tiles_x, tiles_y, loop_gain, threshold, max_cycles,
-                    static_cast<fused_scratch *>(state), hdr, replicas, log); });
-        if (rc)
-            return rc;
-        persist_status_kernel<<<1, 1, 0, s>>>(static_cast<fused_scratch *>(state), hdr);
-        return kimg_launch_status();
-    }
     if (fused)
         begin_owners(a, state, tile_max, tile_pos, s);
     rc = run_cycles(a, max_cycles, s);

@@ -66,6 +66,7 @@
 // to the ninth) or the components per launch it sees say that the field is a dominated one.
 #include "kimg_common.h"
 #include "kimg_graph_cache.h"
+#include "kimg_peak_key.h"
 #include <limits.h>
 #include <string.h>
 #include <sched.h>
@@ -74,7 +75,7 @@
 
 namespace {
 
-typedef unsigned long long mkey_t;
+typedef key_t mkey_t;                   // (this form packs more than an index under the value: mc_key)
 
 constexpr int TILE = 32;                // clean.py:996
 constexpr int MC_MAX = 8;               // lattices per launch
@@ -129,44 +130,11 @@ __device__ inline mc_cand mc_decode(mkey_t k, int border)
     return c;
 }
 
-__device__ inline mkey_t kmax(mkey_t a, mkey_t b) { return a > b ? a : b; }
-
-template <int CTRL>
-__device__ inline mkey_t kdpp(mkey_t k)         // lanes without a source read 0
-{
-    const unsigned lo = __builtin_amdgcn_mov_dpp((unsigned) k, CTRL, 0xf, 0xf, true);
-    const unsigned hi = __builtin_amdgcn_mov_dpp((unsigned) (k >> 32), CTRL, 0xf, 0xf, true);
-    return ((mkey_t) hi << 32) | lo;
-}
-
-// maximum over each 16-lane row, in every lane of the row
-__device__ inline mkey_t row_max(mkey_t k)
-{
-    k = kmax(k, kdpp<0xB1>(k));         // quad_perm [1,0,3,2]
-    k = kmax(k, kdpp<0x4E>(k));         // quad_perm [2,3,0,1]
-    k = kmax(k, kdpp<0x141>(k));        // row_half_mirror
-    k = kmax(k, kdpp<0x140>(k));        // row_mirror
-    return k;
-}
-
-__device__ inline mkey_t lane_key(mkey_t k, int lane)
-{
-    return ((mkey_t) (unsigned) __builtin_amdgcn_readlane((int) (k >> 32), lane) << 32)
-           | (unsigned) __builtin_amdgcn_readlane((int) k, lane);
-}
-
-// workgroup barrier that orders LDS traffic only (a __syncthreads() also waits for the wave's
-// global stores, which nobody here is waiting for)
-__device__ inline void lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
 // number of keys of the 16-lane row that are larger than this lane's (all keys distinct)
 template <int N>
 __device__ inline int row_rank(mkey_t k)
 {
-    const mkey_t o = kdpp<0x120 + N>(k);        // row_ror:N
+    const mkey_t o = key_dpp<0x120 + N>(k);        // row_ror:N
     int r = o > k ? 1 : 0;
     if constexpr (N < 15)
         r += row_rank<N + 1>(k);
@@ -842,14 +810,13 @@ __device__ __attribute__((always_inline)) inline void mc_block(float *dirty, con
     }
     // (metric, lowest pixel index first)
     mkey_t k = best_k >= 0 ? ((mkey_t) __float_as_uint(best) << 32) | (unsigned) ~(tid + 256 * best_k) : 0;
-    k = row_max(k);
-    const mkey_t w = kmax(kmax(lane_key(k, 0), lane_key(k, 16)), kmax(lane_key(k, 32), lane_key(k, 48)));
+    const mkey_t w = wave_max_key(k);
     if ((tid & 63) == 0) {
         s.keys[tid >> 6] = w;
         s.fails[tid >> 6] = fail;       // (wave-uniform)
     }
     lds_barrier();
-    const mkey_t tb = kmax(kmax(s.keys[0], s.keys[1]), kmax(s.keys[2], s.keys[3]));
+    const mkey_t tb = key_max(key_max(s.keys[0], s.keys[1]), key_max(s.keys[2], s.keys[3]));
     const int widx = ~(int) (unsigned) tb;
     if (tb == 0 ? tid == 0 : tid == (widx & 255)) {
         mc_record o;
@@ -1013,7 +980,7 @@ __global__ __launch_bounds__(MC_THREADS) void cycle_multi_kernel(
     const int plx = lat_origin(pc.x, g.patch_w, g.border), ply = lat_origin(pc.y, g.patch_h, g.border);
     {
         // first exchange: the best record of every 16, with its pixel values; the fail bits
-        const mkey_t r = row_max(dkey);
+        const mkey_t r = row_max_key(dkey);
         if (e == 0)
             s.row[tid >> 4] = r;
         if (dkey != 0 && dkey == r)
@@ -1083,7 +1050,7 @@ __global__ __launch_bounds__(MC_THREADS) void cycle_multi_kernel(
                 arow = row;
             }
             afail |= valid ? f[i] : 0u;
-            mine = kmax(mine, r0 + i < q ? w[i] : 0);
+            mine = key_max(mine, r0 + i < q ? w[i] : 0);
         }
     }
     const float4 apix = *reinterpret_cast<const float4 *>(s.row_pix[arow & 15]);   // ... and its pixel values
@@ -1099,10 +1066,10 @@ __global__ __launch_bounds__(MC_THREADS) void cycle_multi_kernel(
         // lattices 1 .. i are all below its key (the same as the levels below say: the committed
         // steps are a prefix).  A plan without steps (lattices evaluated again) is all there.
         mkey_t pre = a;                 // inclusive prefix maximum over lanes 0 .. e of the row
-        pre = kmax(pre, kdpp<0x111>(pre));          // row_shr:1
-        pre = kmax(pre, kdpp<0x112>(pre));          // row_shr:2
-        pre = kmax(pre, kdpp<0x114>(pre));          // row_shr:4
-        const mkey_t before = kdpp<0x111>(pre);     // lattices 0 .. e - 1
+        pre = key_max(pre, key_dpp<0x111>(pre));          // row_shr:1
+        pre = key_max(pre, key_dpp<0x112>(pre));          // row_shr:2
+        pre = key_max(pre, key_dpp<0x114>(pre));          // row_shr:4
+        const mkey_t before = key_dpp<0x111>(pre);     // lattices 0 .. e - 1
         const bool ok = planned_lane && (lane == 0 || before < pkey);
         const unsigned run = (unsigned) __builtin_amdgcn_ballot_w64(ok) & 0xffu;
         const int j = steps_max == 0 ? 0 : __builtin_ctz(~run);       // leading run of ones
@@ -1125,8 +1092,8 @@ __global__ __launch_bounds__(MC_THREADS) void cycle_multi_kernel(
             }
             level = f ? cut - 1 : (a < last - 1 ? a : last - 1);
         }
-        level = row_max(level);
-        level = lane_key(level, 0);
+        level = row_max_key(level);
+        level = read_lane_key(level, 0);
         held = 0;
 #pragma unroll
         for (int st_ = 0; st_ < STEPS; st_++) {
@@ -1176,7 +1143,7 @@ __global__ __launch_bounds__(MC_THREADS) void cycle_multi_kernel(
         return;
     {
         const mkey_t second = (live && (fullm >> li & 1u) && dkey != mine) ? dkey : 0;
-        const mkey_t r = row_max(second);
+        const mkey_t r = row_max_key(second);
         if (e == 0)
             s.row2[tid >> 4] = r;
     }
@@ -1205,7 +1172,7 @@ __global__ __launch_bounds__(MC_THREADS) void cycle_multi_kernel(
     {
         const unsigned ninth = (unsigned) __builtin_amdgcn_ballot_w64(surv && srank == MC_POOL_REST);
         if (ninth)
-            list_floor = lane_key(pkey, __builtin_ctz(ninth)) | 0x3ffu;
+            list_floor = read_lane_key(pkey, __builtin_ctz(ninth)) | 0x3ffu;
     }
     const int nsurv = min(__builtin_popcount(smask), MC_POOL_REST);
     lds_barrier();
@@ -1222,7 +1189,7 @@ __global__ __launch_bounds__(MC_THREADS) void cycle_multi_kernel(
             v[i] = s.row2[(e * q + r0 + i) & 15];
 #pragma unroll
         for (int i = 0; i < 4; i++)
-            sec = kmax(sec, (e < MC_MAX && r0 + i < q && e * q + r0 + i < 16) ? v[i] : 0);
+            sec = key_max(sec, (e < MC_MAX && r0 + i < q && e * q + r0 + i < 16) ? v[i] : 0);
     }
     // the pool, one candidate per lane of the first row: the committed lattices' best records and
     // the surviving entries of the list.  After a misprediction: those records and the best
@@ -1237,7 +1204,7 @@ __global__ __launch_bounds__(MC_THREADS) void cycle_multi_kernel(
     float left_pix[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (mispredicted && !repair) {
         left = (planned_lane && held == 0 && pr > 0) ? pkey : 0;
-        left = lane_key(row_max(left), 0);
+        left = read_lane_key(row_max_key(left), 0);
         left_at = (unsigned) __builtin_amdgcn_ballot_w64(planned_lane && left >= MC_REAL && pkey == left);
 #pragma unroll
         for (int i = 0; i < 4; i++)
@@ -1307,13 +1274,13 @@ __global__ __launch_bounds__(MC_THREADS) void cycle_multi_kernel(
     // them), or the walk ends at or before it (and what ends the walk bounds everything after).
     if (role == ROLE_NEW)
         MC_STAMP(9);
-    const mkey_t overflow = lane_key(sk, MC_MAX);
-    mkey_t bound2 = kmax(list_floor, overflow >= MC_REAL ? overflow | 0x3ffu : 0);
+    const mkey_t overflow = read_lane_key(sk, MC_MAX);
+    mkey_t bound2 = key_max(list_floor, overflow >= MC_REAL ? overflow | 0x3ffu : 0);
     if (STEPS == 1) {
         // (single steps: every second-best record bounds)
-        bound2 = kmax(bound2, lane_key(row_max(s.row2[e]), 0));
+        bound2 = key_max(bound2, read_lane_key(row_max_key(s.row2[e]), 0));
     } else {
-        mkey_t second = lane_key(row_max(lane < MC_MAX ? sec : 0), 0);
+        mkey_t second = read_lane_key(row_max_key(lane < MC_MAX ? sec : 0), 0);
         if (second > bound2 && !mispredicted) {
             bool lifted = false;
             if (lane < MC_MAX && (fullm >> lane & 1u) && rank < MC_MAX) {
@@ -1326,9 +1293,9 @@ __global__ __launch_bounds__(MC_THREADS) void cycle_multi_kernel(
                     held_by_earlier = held_by_earlier || (k < rank && (m_ins[k] >> rank & 1u));
                 lifted = same && !held_by_earlier;
             }
-            second = lane_key(row_max((lane < MC_MAX && !lifted) ? sec : 0), 0);
+            second = read_lane_key(row_max_key((lane < MC_MAX && !lifted) ? sec : 0), 0);
         }
-        bound2 = kmax(bound2, second);
+        bound2 = key_max(bound2, second);
     }
     if (role == ROLE_NEW)
         MC_STAMP(10);
@@ -1348,7 +1315,7 @@ __global__ __launch_bounds__(MC_THREADS) void cycle_multi_kernel(
     } else {
         // (the first candidate is the largest tile of the image if it beats every tile that is not
         // listed; with an entry of the list in the pool it does)
-        const bool first_proven = nsurv > 0 || mispredicted || lane_key(sk, 0) > list_floor;
+        const bool first_proven = nsurv > 0 || mispredicted || read_lane_key(sk, 0) > list_floor;
         const unsigned room = (unsigned) min(mispredicted || first_alone ? 1 : g.mmax, limit - count);
         // the walk considers the candidates in order while each is real, proven to be next (above
         // everything outside the pool) and passes the threshold: a prefix of the positions
@@ -1416,10 +1383,10 @@ __global__ __launch_bounds__(MC_THREADS) void cycle_multi_kernel(
             // What the host goes by when it chooses between the two kernels: how many more steps the
             // planned peaks could take before they are down to what is not planned (each on its
             // own; the second-best records left aside: the other kernel mostly lifts them).
-            mkey_t level = kmax(list_floor, overflow >= MC_REAL ? overflow | 0x3ffu : 0);
+            mkey_t level = key_max(list_floor, overflow >= MC_REAL ? overflow | 0x3ffu : 0);
             const unsigned u = m_real & ~picked & ~skipped;
             if (u)
-                level = kmax(level, lane_key(sk, __builtin_ctz(u)) | 0x3ffu);
+                level = key_max(level, read_lane_key(sk, __builtin_ctz(u)) | 0x3ffu);
             float v[PMAX];
 #pragma unroll
             for (int p = 0; p < PMAX; p++)
@@ -1445,7 +1412,7 @@ __global__ __launch_bounds__(MC_THREADS) void cycle_multi_kernel(
         {
             const unsigned u = m_real & ~picked & ~skipped;
             if (u)
-                level = kmax(level, lane_key(sk, __builtin_ctz(u)) | 0x3ffu);
+                level = key_max(level, read_lane_key(sk, __builtin_ctz(u)) | 0x3ffu);
         }
         float v[PMAX];
 #pragma unroll
@@ -1490,8 +1457,8 @@ __global__ __launch_bounds__(MC_THREADS) void cycle_multi_kernel(
                 lev = 0;
             }
             {
-                const mkey_t r = row_max(mine_picked ? lev : 0);
-                level = kmax(level, lane_key(r, 0));
+                const mkey_t r = row_max_key(mine_picked ? lev : 0);
+                level = key_max(level, read_lane_key(r, 0));
             }
 #pragma unroll
             for (int st_ = 0; st_ < STEPS; st_++)

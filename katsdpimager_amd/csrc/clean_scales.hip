@@ -6,7 +6,7 @@
 // add rounded on its own: this file is built with -ffp-contract=off and uses no fmaf), so that
 // with the single scale 0 it takes the components the Hogbom loop takes, bit for bit.
 #include "kimg_common.h"
-#include <limits.h>
+#include "kimg_peak_key.h"
 #include <string.h>
 
 namespace {
@@ -174,61 +174,23 @@ __host__ __device__ inline void crop_range(int n, int patch, int R, int &lo, int
     hi = start + size < n ? start + size : n;
 }
 
-// (value, index) as one key: the larger value first, then the smaller index.  Values are
-// non-negative and never NaN (a NaN never replaces a best), so their bit patterns order like the
-// numbers.  Key 0 = nothing.
-typedef unsigned long long key_t;
-
-__device__ inline key_t make_key(float value, int idx)
-{
-    return ((key_t) __float_as_uint(value) << 32) | (unsigned) ~idx;
-}
-
-__device__ inline key_t wave_max_key(key_t k)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const key_t o = __shfl_xor(k, off, WAVE);
-        k = o > k ? o : k;
-    }
-    return k;
-}
-
 // Record of tile (tx, ty) of scale k from the four pixels (value, candidate) each of the 256
 // threads holds: thread t has the pixels 4 t .. 4 t + 3 of the tile in row-major order.
 __device__ inline void write_tile(const scales_desc &d, int k, int tx, int ty, const float v[4],
                                   const bool candidate[4], key_t *s_keys)
 {
     const int tid = threadIdx.x;
-    float best = 0.0f;
-    int idx = INT_MAX;
+    key_t key = 0;                      // only values above 0 count
 #pragma unroll
     for (int e = 0; e < 4; e++) {
         const float m = fabsf(v[e]);
-        if (candidate[e] && m > best) {
-            best = m;
-            idx = 4 * tid + e;
-        }
+        if (candidate[e] && m > 0.0f)
+            key = key_max(key, make_key(m, 4 * tid + e));
     }
-    key_t key = wave_max_key(idx == INT_MAX ? 0 : make_key(best, idx));
-    if ((tid & 63) == 0)
-        s_keys[tid >> 6] = key;
-    __syncthreads();
+    key = block_max_key(key, s_keys);
     if (tid == 0) {
-        for (int w = 1; w < 4; w++)
-            key = s_keys[w] > key ? s_keys[w] : key;
-        const int x0 = tx * TILE + d.border, y0 = ty * TILE + d.border;
         const int64_t t = k * d.tile_pitch + (int64_t) ty * d.tiles_x + tx;
-        if (key == 0) {                     // nothing above 0: the start position of the host scan
-            d.tile_max[t] = 0.0f;
-            d.tile_pos[2 * t] = x0;
-            d.tile_pos[2 * t + 1] = y0;
-        } else {
-            const int i = ~(int) (unsigned) key;
-            d.tile_max[t] = __uint_as_float((unsigned) (key >> 32));
-            d.tile_pos[2 * t] = y0 + (i >> 5);
-            d.tile_pos[2 * t + 1] = x0 + (i & 31);
-        }
+        store_tile_record(key, tx * TILE + d.border, ty * TILE + d.border, d.tile_max, d.tile_pos, t);
     }
 }
 
@@ -277,10 +239,7 @@ __global__ __launch_bounds__(1024) void scales_peak_kernel(scales_desc d, scales
     for (int k = 0; k < d.K; k++) {
         key_t best = 0;
         for (int t = tid; t < num_tiles; t += 1024)
-        {
-            const key_t c = make_key(d.tile_max[k * d.tile_pitch + t], t);
-            best = c > best ? c : best;
-        }
+            best = key_max(best, make_key(d.tile_max[k * d.tile_pitch + t], t));
         best = wave_max_key(best);
         if ((tid & 63) == 0)
             s_keys[k][tid >> 6] = best;

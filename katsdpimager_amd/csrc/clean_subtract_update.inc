@@ -21,7 +21,8 @@
     const int psf_dx = psf_w / 2 - px, psf_dy = psf_h / 2 - py;  // psf index = image index + d
     const bool is_tile = tx >= 0 && tx < tiles_x && ty >= 0 && ty < tiles_y;
 
-    best_t b = {0.0f, INT_MAX};
+    float best = 0.0f;
+    int best_idx = INT_MAX;             // row-major index within the tile; INT_MAX = none yet
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int idx = threadIdx.x + k * 256;
@@ -58,25 +59,16 @@
                 metric += d * d;
             }
         }
-        if (in_tile && metric > b.value) {
-            b.value = metric;
-            b.idx = idx;
+        if (in_tile && metric > best) {
+            best = metric;
+            best_idx = idx;
         }
     }
     if (!is_tile)
         return;
     __shared__ key_t s_keys[16];
-    const key_t kb = block_max_key(b.idx == INT_MAX ? 0 : make_key(b.value, b.idx), s_keys);
+    const key_t kb = block_max_key(best_idx == INT_MAX ? 0 : make_key(best, best_idx), s_keys);
     if (threadIdx.x == 0) {
         const int t = ty * tiles_x + tx;
-        if (kb == 0) {                      // clean.py:950 best_pos = (x0, y0), value 0
-            tile_max[t] = 0.0f;
-            tile_pos[2 * t] = ox;
-            tile_pos[2 * t + 1] = oy;
-        } else {
-            const int idx = ~(int) (unsigned) kb;
-            tile_max[t] = __uint_as_float((unsigned) (kb >> 32));
-            tile_pos[2 * t] = oy + (idx >> 5);
-            tile_pos[2 * t + 1] = ox + (idx & 31);
-        }
+        store_tile_record(kb, ox, oy, tile_max, tile_pos, t);
     }

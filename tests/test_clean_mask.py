@@ -179,7 +179,8 @@ def test_masked_symbols_declared_exported_prototyped():
 
 
 def test_unsupported_forms_with_a_mask_without_gpu():
-    """Multi-component, persistent and one-workgroup forms asked for with a mask: KIMG_EUNSUPPORTED,
+    """The multi-component form, and the retired persistent and one-workgroup names, asked for
+    with a mask: KIMG_EUNSUPPORTED,
     decided before any HIP call (there is no GPU here; the pointers are not device memory)."""
     from katsdpimager_amd import _lib
     lib = _lib.lib()

@@ -77,6 +77,18 @@ def test_argument_errors_without_gpu():
         _lib.check(-10001, 'kimg_fill')
 
 
+def test_clean_state_bytes_without_gpu():
+    """The CLEAN state buffer is the one-launch form's scratch or the multi-component form's,
+    whichever is larger: a few hundred KiB at 4096^2 (128 x 128 tiles), nothing per workgroup;
+    its head (what Clean.last_launches reads, 1660 words) fits at any size."""
+    from katsdpimager_amd import _lib
+    lib = _lib.lib()
+    assert 0 < lib.kimg_clean_state_bytes(1, 128, 128) < 1 << 20
+    assert lib.kimg_clean_state_bytes(1, 2, 2) >= 4 * 1660
+    for tiles in ((0, 4), (4, 0), (-1, 4), (4, -1), (0, 0)):
+        assert lib.kimg_clean_state_bytes(1, *tiles) == 0
+
+
 @pytest.mark.parametrize('name', list(gi.KERNEL_CONFIGS))
 def test_kernel_table_matches_reference(golden, name):
     """Host-side kernel generation (grid.ConvolutionKernel) vs the reference's table."""

@@ -1,5 +1,5 @@
 """CLEAN minor cycles per second of the device-resident loop for one PSF-patch size and every form of
-the loop that takes it (two launches per cycle, one launch, resident workgroups, one workgroup), on the
+the loop that takes it (two launches per cycle, one launch, what AUTO chooses), on the
 bench's CLEAN image (4096^2, 200 point sources (x) PSF + noise).
 
     python tools/exp_clean_patch.py [patch height] [patch width] [cycles]"""
