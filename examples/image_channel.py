@@ -3,6 +3,7 @@
 store -> imaging weights, PSF, major/minor cycles -> restored image, all on one MI355X.
 
     python examples/image_channel.py [--pixels 2048] [--vis 4000000] [--major 3]
+    python examples/image_channel.py --uvcontsub 1:6-9      (a 16-channel band; see uvcontsub_band)
 
 It follows the reference's per-channel flow (frontend.py:31-83 preprocess_visibilities,
 :465-658 process_channel) with the loaders and FITS output left out: the sky is three point
@@ -19,6 +20,68 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
+
+
+def uvcontsub_band(args):
+    """--uvcontsub ORDER[:first-last,...]: a synthetic band of 16 channels with a continuum source
+    whose flux slopes across the band and a line source in channels `first` to `last` (default 6-9),
+    through ``loader.preprocess_visibilities`` with and without ``continuum=``; prints the dirty
+    peak of a line-free channel before and after, and of a line channel after."""
+    import synth
+    from katsdpimager_amd import accel, continuum, frontend, imaging, loader, parameters, preprocess, weight
+    order, _, spans = args.uvcontsub.partition(':')
+    ranges = [(int(a), int(b) + 1) for a, b in (span.split('-') for span in (spans or '6-9').split(','))]
+    C = 16
+    params = continuum.UVContSubParameters(int(order), line_ranges=ranges)
+    free = params.mask(C)
+    ctx = accel.create_some_context()
+    queue = ctx.create_command_queue()
+    rows = max(args.vis // C, 1000)
+    obs = synth.make_observation(args.pixels, rows, args.w_planes, 1, device='cpu')
+    image_p, grid_p, array_p = synth.make_parameters(obs, 1, args.kernel_width, degrid=True)
+    uvw = obs.uvw.numpy()
+    uvw_wl = uvw.astype(np.float64) / obs.wavelength
+
+    def source(lp, mp):
+        l, m = lp * obs.pixel_size, mp * obs.pixel_size
+        n = math.sqrt(1 - l * l - m * m)
+        return np.exp(-2j * np.pi * (uvw_wl[:, 0] * l + uvw_wl[:, 1] * m + uvw_wl[:, 2] * (n - 1))) / n
+    x = continuum.legendre_basis(1, C)[1]
+    vis = source(40, -25)[:, None] * (1.0 + 0.3 * x)[None, :]       # 1 Jy at band centre, sloped
+    line_pos = (-120, 60)
+    vis[:, free == 0] += 0.5 * source(*line_pos)[:, None]
+    dataset = loader.LoaderArrays(uvw, vis[:, :, None].astype(np.complex64),
+                                  np.ones((rows, C, 1), np.float32), np.zeros(rows, np.int32),
+                                  _frequencies(obs, C), [0])
+    weight_p = parameters.WeightParameters(weight.WeightType.ROBUST, 0.0)
+    clean_p = parameters.CleanParameters(args.minor, 0.1, 0.85, 5.0, 0, 0.01, 0.5, 0.02)
+    template = imaging.ImagingTemplate(ctx, array_p, image_p.fixed, weight_p, grid_p.fixed, clean_p)
+    imager = template.instantiate(queue, image_p, grid_p, args.vis_block, 0, 1, streams=2)
+    imager.ensure_all_bound()
+    # only the first peak of each dirty image is wanted: the reference's own two steps, whatever the
+    # PSF patch of so short a synthetic track turns out to be
+    imager.one_call_major_cycles = False
+    ident = np.ones((1, 1), np.complex64)
+    line_free, line = int(np.flatnonzero(free)[0]), int(np.flatnonzero(free == 0)[0])
+    peaks = {}
+    for label, keyword in (('before', None), ('after', params)):
+        collector = preprocess.VisibilityCollectorDevice(queue, [image_p] * C, [grid_p] * C, args.vis_block)
+        loader.preprocess_visibilities(dataset, collector, 0, C, (ident, None), continuum=keyword)
+        if keyword is not None:
+            print('uvcontsub {}: {} samples fitted, {} flagged'.format(params, *collector.continuum_counts))
+        for channel in (line_free, line):
+            stats = frontend.process_channel(collector.reader(), channel, imager, image_p, grid_p, clean_p,
+                                             weight_p.weight_type, args.vis_block, 1, True)
+            peaks[label, channel] = float(stats['peaks'][0])
+    print('line-free channel {:2d}: dirty peak {:.6f} before, {:.2e} after'.format(
+        line_free, peaks['before', line_free], peaks['after', line_free]))
+    print('line channel      {:2d}: dirty peak {:.6f} before, {:.6f} after (the 0.5 Jy line source)'.format(
+        line, peaks['before', line], peaks['after', line]))
+    return peaks
+
+
+def _frequencies(obs, channels):
+    return 299792458.0 / obs.wavelength + 1.0e5 * np.arange(channels)
 
 
 def main(argv=None):
@@ -41,7 +104,12 @@ def main(argv=None):
     ap.add_argument('--multiscale', metavar='FWHM,FWHM,...',
                     help='run the minor cycles through multi-scale CLEAN with these Gaussian scales '
                          '(FWHM in pixels, ascending, the first one 0), e.g. 0,4,9')
+    ap.add_argument('--uvcontsub', metavar='ORDER[:first-last,...]',
+                    help='instead of the three-source channel: take a polynomial continuum of this order out of '
+                         'a synthetic 16-channel band in the uv plane, the listed channels (default 6-9) holding a line')
     args = ap.parse_args(argv)
+    if args.uvcontsub:
+        return uvcontsub_band(args)
     import torch
     import scipy.optimize       # noqa: F401  (used by beam.fit_beam; imported here, outside the timings)
     import synth

@@ -842,6 +842,49 @@ int kimg_clean_scales_cycles(float *dirty, float *model, int64_t row_pitch, int6
                              void *workspace, size_t workspace_bytes, float *log,
                              int *cycles_done, void *stream);
 
+/* ---- UV-plane continuum subtraction (contsub.hip): a low-order polynomial fitted across the
+ * line-free channels of every baseline sample of a block of RAW visibilities, and subtracted from
+ * all its channels, ahead of kimg_preprocess_convert (what CASA calls uvcontsub and MIRIAD uvlin).
+ * The reference has none; the semantics are this library's, and katsdpimager_amd/continuum.py holds
+ * them once more as numpy (uvcontsub_host).
+ *
+ * vis: complex64 [C][N][Q], weights: float32 [C][N][Q], C = num_channels, the loader's block layout.
+ *   The inner [N][Q] plane is dense (plane_elements = N * Q); each array has its own channel pitch,
+ *   the distance between channels in elements of the array (complex64 / float32), at least
+ *   plane_elements (KIMG_EINVAL otherwise).  Elements of the padding are neither read nor written.
+ *   Indices are 64-bit throughout: C * pitch may pass 2^31.
+ * fit_mask_host: HOST uint8 [C], nonzero = a line-free channel that enters the fit.  It is read
+ *   during the call and travels to the kernel by value, so a captured call keeps the mask it was
+ *   captured with and the array may be freed on return.
+ * basis: DEVICE float64 [K][C], K = order + 1, order 0 .. KIMG_UVCONTSUB_MAX_ORDER: the value of
+ *   basis function k at channel c.  The host makes it (continuum.legendre_basis: Legendre
+ *   polynomials of the channel index, or of the channel frequency, mapped linearly onto [-1, 1]).
+ * For every element (n, q), all in float64:
+ *   a channel is usable iff fit_mask[c] != 0, weights[c][n][q] > 0 and both parts of vis[c][n][q]
+ *   are finite; m = the number of usable channels.  Over the usable channels in ascending c,
+ *   A[k][l] = sum w B_k[c] B_l[c] (each term (w * B_k[c]) * B_l[c]) and b[k] = sum (w * B_k[c]) * v,
+ *   b complex.  A a = b is solved by Cholesky without pivoting.
+ *   m >= K: vis[c][n][q] = complex64((double) v - sum_k a[k] B_k[c]) for EVERY c, line channels
+ *     included; the sum runs in ascending k from 0 and each part is rounded to float32 once.
+ *     Non-finite visibilities outside the fit give whatever IEEE gives.  Weights are left alone.
+ *   m < K: the element cannot be fitted.  Its vis stays as it is and weights[c][n][q] = 0 for every
+ *     c, so that preprocessing drops it instead of imaging unsubtracted continuum.
+ * counts: DEVICE uint64 [2]: the number of fitted and of flagged elements of the call are ADDED to
+ *   it (one atomic add per wave and counter); the caller zeroes it.
+ * Returns, before anything is enqueued: KIMG_EINVAL for order < 0, order > 3 or C < 1; then
+ *   KIMG_EUNSUPPORTED when fewer than K entries of fit_mask_host are nonzero (nothing could ever be
+ *   fitted) or C > KIMG_UVCONTSUB_MAX_CHANNELS; then KIMG_EINVAL for null pointers, a negative
+ *   plane_elements or a pitch below it.  plane_elements = 0 is a successful call that does nothing.
+ * Asynchronous on `stream`, no allocation, capturable.  The accumulation order is fixed: equal
+ *   inputs give equal bits.  Traffic: 12 bytes per element and fit channel, 16 per element and
+ *   channel. */
+#define KIMG_UVCONTSUB_MAX_ORDER 3
+#define KIMG_UVCONTSUB_MAX_CHANNELS 16384
+int kimg_uvcontsub(void *vis, int64_t vis_channel_pitch, float *weights,
+                   int64_t weights_channel_pitch, int num_channels, int64_t plane_elements,
+                   const uint8_t *fit_mask_host, const double *basis, int order, uint64_t *counts,
+                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

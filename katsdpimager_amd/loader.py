@@ -165,17 +165,46 @@ def data_iter(dataset, vis_limit, vis_load, start_channel, stop_channel):
 
 
 def preprocess_visibilities(dataset, collector, start_channel, stop_channel, polarization_matrices,
-                            vis_load=32 * 1048576, vis_limit=None):
+                            vis_load=32 * 1048576, vis_limit=None, continuum=None):
     """frontend.preprocess_visibilities (frontend.py:40-84): feed every block of the loader, in
     loader order, to ``collector.add`` (a :class:`~.preprocess.VisibilityCollectorDevice`; its
     conversion and compression kernels run asynchronously on its queue, which plays the role of
     the reference's preprocessing thread).  ``polarization_matrices`` = (mueller_stokes,
     mueller_circular) as ``polarization.polarization_matrices`` returns them.  Closes the
-    collector and returns it."""
+    collector and returns it.
+
+    ``continuum`` (:class:`~.continuum.UVContSubParameters`; new here) takes the continuum out of
+    every block before the collector sees it: the block's visibilities and weights are moved to the
+    device once, a polynomial is fitted across the line-free channels of every sample and subtracted
+    (``continuum.UVContSub`` on the collector's queue), and the collector is handed the device
+    arrays.  The mask (and the frequencies, if given) span the loaded channels
+    ``start_channel:stop_channel``.  The collector then has ``continuum_counts``: the samples
+    (fitted, flagged for want of line-free channels) over all blocks.  None (the default) changes
+    nothing."""
+    if continuum is None:
+        try:
+            for chunk in data_iter(dataset, vis_limit, vis_load, start_channel, stop_channel):
+                collector.add(chunk['uvw'], chunk['weights'], chunk['vis'],
+                              chunk.get('feed_angle1'), chunk.get('feed_angle2'), *polarization_matrices)
+        finally:
+            collector.close()
+        return collector
+
+    from . import accel
+    from .continuum import UVContSubTemplate
+    queue = collector.queue
+    context = queue.context
+    subtract = UVContSubTemplate(context, continuum).instantiate(queue, stop_channel - start_channel)
     try:
         for chunk in data_iter(dataset, vis_limit, vis_load, start_channel, stop_channel):
-            collector.add(chunk['uvw'], chunk['weights'], chunk['vis'],
+            vis = accel.DeviceArray(context, chunk['vis'].shape, np.complex64, queue=queue)
+            weights = accel.DeviceArray(context, chunk['weights'].shape, np.float32, queue=queue)
+            vis.set(queue, chunk['vis'])
+            weights.set(queue, chunk['weights'])
+            subtract(vis, weights)
+            collector.add(chunk['uvw'], weights, vis,
                           chunk.get('feed_angle1'), chunk.get('feed_angle2'), *polarization_matrices)
+        collector.continuum_counts = subtract.counts()
     finally:
         collector.close()
     return collector
