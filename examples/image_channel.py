@@ -4,6 +4,7 @@ store -> imaging weights, PSF, major/minor cycles -> restored image, all on one 
 
     python examples/image_channel.py [--pixels 2048] [--vis 4000000] [--major 3]
     python examples/image_channel.py --uvcontsub 1:6-9      (a 16-channel band; see uvcontsub_band)
+    python examples/image_channel.py --phase-shift=-120,60  (a small field around a source; see phase_shift_field)
 
 It follows the reference's per-channel flow (frontend.py:31-83 preprocess_visibilities,
 :465-658 process_channel) with the loaders and FITS output left out: the sky is three point
@@ -80,6 +81,70 @@ def uvcontsub_band(args):
     return peaks
 
 
+def phase_shift_field(args):
+    """--phase-shift L,M: the three-source channel through ``loader.preprocess_visibilities`` twice:
+    as it is, imaged on the default field, and with ``phase_centre=`` the direction L, M pixels of
+    that field from its centre, imaged on a field a quarter as wide around the new centre.  Prints
+    the restored peak of the source nearest to (L, M) in both."""
+    import copy
+    import synth
+    from katsdpimager_amd import (accel, beam, frontend, imaging, loader, parameters, phaseshift,
+                                  preprocess, weight)
+    L, M = (int(x) for x in args.phase_shift.split(','))
+    ctx = accel.create_some_context()
+    queue = ctx.create_command_queue()
+    obs = synth.make_observation(args.pixels, args.vis, args.w_planes, 1, device='cpu')
+    small = copy.copy(obs)
+    small.pixels = max(args.pixels // 4, 128)
+    small.cell_size = obs.wavelength / (obs.pixel_size * small.pixels)      # (the same pixel size)
+    centre = (0.0, math.radians(-45.0))
+    new_centre = phaseshift.offset_to_radec(centre, L * obs.pixel_size, M * obs.pixel_size)
+    sources = [((40, -25), 1.0), ((-120, 60), 0.5), ((15, 200), 0.25)]      # (l, m) in pixels, Jy
+    uvw = obs.uvw.numpy()
+    uvw_wl = uvw.astype(np.float64) / obs.wavelength
+    vis = np.zeros(obs.n_vis, np.complex128)
+    for (lp, mp), flux in sources:
+        l, m = lp * obs.pixel_size, mp * obs.pixel_size
+        n = math.sqrt(1 - l * l - m * m)
+        vis += flux / n * np.exp(-2j * np.pi * (uvw_wl[:, 0] * l + uvw_wl[:, 1] * m + uvw_wl[:, 2] * (n - 1)))
+    dataset = loader.LoaderArrays(uvw, vis[:, None, None].astype(np.complex64),
+                                  np.ones((obs.n_vis, 1, 1), np.float32), np.zeros(obs.n_vis, np.int32),
+                                  _frequencies(obs, 1), [0], phase_centre=centre)
+    (lp, mp), flux = min(sources, key=lambda s: (s[0][0] - L) ** 2 + (s[0][1] - M) ** 2)
+    weight_p = parameters.WeightParameters(weight.WeightType.ROBUST, 0.0)
+    clean_p = parameters.CleanParameters(args.minor, 0.1, 0.85, 5.0, 0, 0.01, 0.5, 0.02)
+    ident = np.ones((1, 1), np.complex64)
+    peaks = {}
+    for label, field, keyword, offset in (('unshifted', obs, None, (lp, mp)),
+                                          ('shifted', small, new_centre, (lp - L, mp - M))):
+        image_p, grid_p, array_p = synth.make_parameters(field, 1, args.kernel_width, degrid=True)
+        collector = preprocess.VisibilityCollectorDevice(queue, [image_p], [grid_p], args.vis_block)
+        loader.preprocess_visibilities(dataset, collector, 0, 1, (ident, None), phase_centre=keyword)
+        template = imaging.ImagingTemplate(ctx, array_p, image_p.fixed, weight_p, grid_p.fixed, clean_p)
+        imager = template.instantiate(queue, image_p, grid_p, args.vis_block, 0, args.major, streams=2)
+        imager.ensure_all_bound()
+        queue.finish()
+        t0 = time.perf_counter()
+        stats = frontend.process_channel(collector.reader(), 0, imager, image_p, grid_p, clean_p,
+                                         weight_p.weight_type, args.vis_block, args.major, True,
+                                         fit_beam=True)
+        queue.finish()
+        t1 = time.perf_counter()
+        beam.restore(imager, stats['restoring_beam'])
+        restored = imager.get_buffer('dirty')[0]
+        G = field.pixels
+        # (the new frame's axes are turned against the old ones by the shift times sin(dec): a pixel
+        # or two at this distance, hence the box)
+        y, x = G // 2 + offset[1], G // 2 + offset[0]
+        box = restored[y - 3:y + 4, x - 3:x + 4]
+        peaks[label] = float(box.max())
+        print('{:9s}: {:4d} x {:4d} pixels around (ra, dec) = ({:.6f}, {:.6f}), imaged in {:.1f} ms; the '
+              '{:.2f} Jy source at ({}, {}) px of this field: restored peak {:.3f}'.format(
+                  label, G, G, *getattr(collector, 'phase_centre', centre), (t1 - t0) * 1e3, flux,
+                  offset[0], offset[1], peaks[label]))
+    return peaks
+
+
 def _frequencies(obs, channels):
     return 299792458.0 / obs.wavelength + 1.0e5 * np.arange(channels)
 
@@ -107,9 +172,14 @@ def main(argv=None):
     ap.add_argument('--uvcontsub', metavar='ORDER[:first-last,...]',
                     help='instead of the three-source channel: take a polynomial continuum of this order out of '
                          'a synthetic 16-channel band in the uv plane, the listed channels (default 6-9) holding a line')
+    ap.add_argument('--phase-shift', metavar='L,M',
+                    help='instead of the default field alone: re-phase the raw visibilities to the direction L,M '
+                         'pixels from its centre and image a field a quarter as wide around it, e.g. --phase-shift=-120,60')
     args = ap.parse_args(argv)
     if args.uvcontsub:
         return uvcontsub_band(args)
+    if args.phase_shift:
+        return phase_shift_field(args)
     import torch
     import scipy.optimize       # noqa: F401  (used by beam.fit_beam; imported here, outside the timings)
     import synth

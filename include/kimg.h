@@ -885,6 +885,56 @@ int kimg_uvcontsub(void *vis, int64_t vis_channel_pitch, float *weights,
                    const uint8_t *fit_mask_host, const double *basis, int order, uint64_t *counts,
                    void *stream);
 
+/* ---- Phase-centre shift (phaseshift.hip): the RAW visibilities of a block re-phased to another
+ * direction and the block's baseline coordinates rotated into that direction's frame, ahead of
+ * kimg_uvcontsub and kimg_preprocess_convert (CASA phaseshift / fixvis, WSClean's chgcentre, MIRIAD
+ * uvedit).  The reference has none; the semantics are this library's, and
+ * katsdpimager_amd/phaseshift.py holds them once more as numpy (phase_shift_host).
+ *
+ * Frames.  For a direction (ra, dec) the frame M(ra, dec) has the rows
+ *   e_u = (-sin ra, cos ra, 0), e_v = (-sin dec cos ra, -sin dec sin ra, cos dec),
+ *   e_w = (cos dec cos ra, cos dec sin ra, sin dec).
+ * Convention: a unit source at (l, m, n) of the frame gives exp(-2 pi i (l u + m v + (n - 1) w)),
+ *   uvw in wavelengths.
+ * Three directions: frame_centre, whose frame uvw_in (metres) is in; from_centre, the direction the
+ *   visibilities are phased to now (usually frame_centre); new_centre, the direction they are to be
+ *   phased to and whose frame uvw_out is in.  The host computes in float64
+ *   rotation = M(new) . M(frame)^T (3 x 3) and
+ *   delay[3] = lmn(new) - lmn(from), both directions' coordinates in the frame of frame_centre, each
+ *   n - 1 taken as -(l^2 + m^2) / (1 + n) and the third entry as the difference of those.  With
+ *   from == frame, delay = (l, m, n - 1) of the new centre and delay . uvw = w' - w.
+ *
+ * vis: complex64 [C][N][Q], C = num_channels, N = num_rows, Q = num_polarizations, updated in place.
+ *   The inner [N][Q] plane is dense; vis_channel_pitch is the distance between channels in complex64
+ *   elements, at least N * Q.  Elements of the padding are neither read nor written.  Indices are
+ *   64-bit throughout.
+ * uvw_in: DEVICE float32 [N][3], metres.  uvw_out: the same shape, or NULL: then only the
+ *   visibilities are rotated.  uvw_out must not overlap uvw_in (the row of a sample is read by the
+ *   threads of all its polarizations and written by one of them).
+ * inv_wavelength: DEVICE float64 [C], 1 / wavelength of every channel in 1 / metres (f_c / c0).
+ * params12_host: HOST float64 [12]: rotation row by row, then delay.  It is read during the call and
+ *   travels to the kernel by value, so a captured call keeps its parameters and the array may be
+ *   freed on return.
+ * For every row n, with (u, v, w) = (double) uvw_in[n]:
+ *   uvw_out[n][i] = (float) ((R[i][0] u + R[i][1] v) + R[i][2] w), one rounding per component;
+ *   d = (delay[0] u + delay[1] v) + delay[2] w, in float64;
+ * and for every channel c and polarization q
+ *   vis[c][n][q] = vis[c][n][q] * exp(+2 pi i t), t = d * inv_wavelength[c].
+ *   t is formed and reduced to [-0.5, 0.5] (t - rint(t)) in float64; only the reduced angle may go to
+ *   float32.  Each component of the result lies within 10 * 2^-24 |vis[c][n][q]| of the float64
+ *   value of this expression (DESIGN 5.15 derives it).
+ * Weights are not this call's business: every sample is rotated, whatever its weight.  A non-finite
+ *   coordinate makes the visibilities of its row and its rotated coordinates non-finite, a non-finite
+ *   visibility component makes that visibility non-finite, and nothing else changes.
+ * Returns KIMG_EINVAL, before any HIP call, for a null vis, uvw_in, inv_wavelength or params12_host,
+ *   C < 1, Q < 1, N < 0, a pitch below N * Q, or uvw arrays that overlap.  N = 0 is a successful
+ *   call that launches nothing.
+ * Asynchronous on `stream`, no allocation, capturable; equal inputs give equal bits.  Traffic: 16
+ *   bytes per element and channel, 12 per row read and 12 written. */
+int kimg_phase_shift(void *vis, int64_t vis_channel_pitch, int num_channels, int64_t num_rows,
+                     int num_polarizations, const float *uvw_in, float *uvw_out,
+                     const double *inv_wavelength, const double *params12_host, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

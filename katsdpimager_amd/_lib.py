@@ -109,6 +109,8 @@ PROTOTYPES = {
                                          P, c_size_t, P, P, P]),
     # UV-plane continuum subtraction
     'kimg_uvcontsub': (c_int, [P, L, P, L, I, L, P, P, I, P, P]),
+    # phase-centre shift
+    'kimg_phase_shift': (c_int, [P, L, I, L, I, P, P, P, P, P]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),

@@ -165,7 +165,8 @@ def data_iter(dataset, vis_limit, vis_load, start_channel, stop_channel):
 
 
 def preprocess_visibilities(dataset, collector, start_channel, stop_channel, polarization_matrices,
-                            vis_load=32 * 1048576, vis_limit=None, continuum=None):
+                            vis_load=32 * 1048576, vis_limit=None, continuum=None,
+                            phase_centre=None, continuum_centre=None):
     """frontend.preprocess_visibilities (frontend.py:40-84): feed every block of the loader, in
     loader order, to ``collector.add`` (a :class:`~.preprocess.VisibilityCollectorDevice`; its
     conversion and compression kernels run asynchronously on its queue, which plays the role of
@@ -180,7 +181,24 @@ def preprocess_visibilities(dataset, collector, start_channel, stop_channel, pol
     arrays.  The mask (and the frequencies, if given) span the loaded channels
     ``start_channel:stop_channel``.  The collector then has ``continuum_counts``: the samples
     (fitted, flagged for want of line-free channels) over all blocks.  None (the default) changes
-    nothing."""
+    nothing.
+
+    ``phase_centre`` = (ra, dec) in radians (new here) images around another direction T than the
+    dataset's ``phase_centre()`` O: every block goes to the device once, its visibilities are
+    re-phased and its uvw rotated from O to T (``phaseshift.PhaseShift`` on the collector's queue),
+    then ``continuum``, if given, runs, and the collector receives the device visibilities, weights
+    and new uvw.  ``continuum_centre`` = (ra, dec) (needs ``continuum``) puts the continuum fit, which
+    is exact only for a source at the phase centre, on a bright source S elsewhere: visibilities
+    only O -> S, the fit, then S -> T on the block's original uvw (T defaults to O, and then no
+    coordinates are written); coordinates are never rotated twice.  Either way the collector gets
+    ``phase_centre`` = T, for whoever writes the image header.  Feed angles pass unchanged, which is
+    valid for shifts small against a radian.  With neither keyword the function is what it was."""
+    if continuum_centre is not None and continuum is None:
+        raise ValueError('continuum_centre needs continuum')
+    if phase_centre is not None or continuum_centre is not None:
+        return _preprocess_shifted(dataset, collector, start_channel, stop_channel,
+                                   polarization_matrices, vis_load, vis_limit, continuum,
+                                   phase_centre, continuum_centre)
     if continuum is None:
         try:
             for chunk in data_iter(dataset, vis_limit, vis_load, start_channel, stop_channel):
@@ -205,6 +223,60 @@ def preprocess_visibilities(dataset, collector, start_channel, stop_channel, pol
             collector.add(chunk['uvw'], weights, vis,
                           chunk.get('feed_angle1'), chunk.get('feed_angle2'), *polarization_matrices)
         collector.continuum_counts = subtract.counts()
+    finally:
+        collector.close()
+    return collector
+
+
+def _preprocess_shifted(dataset, collector, start_channel, stop_channel, polarization_matrices,
+                        vis_load, vis_limit, continuum, phase_centre, continuum_centre):
+    """:func:`preprocess_visibilities` with ``phase_centre`` and / or ``continuum_centre``."""
+    from . import accel, phaseshift
+    from .continuum import UVContSubTemplate
+    queue = collector.queue
+    context = queue.context
+    origin = tuple(float(x) for x in dataset.phase_centre())
+    target = origin if phase_centre is None else tuple(float(x) for x in phase_centre)
+    inv_wavelength = phaseshift.inverse_wavelengths(
+        [dataset.frequency(channel) for channel in range(start_channel, stop_channel)])
+
+    def shifter(*centres, **kwargs):
+        params = phaseshift.PhaseShiftParameters(*centres, **kwargs)
+        return phaseshift.PhaseShiftTemplate(context, params).instantiate(queue, inv_wavelength)
+    try:
+        if continuum_centre is not None:
+            source = tuple(float(x) for x in continuum_centre)
+            before = shifter(origin, source)
+            after = shifter(origin, target, from_centre=source)
+        else:
+            before = shifter(origin, target)
+            after = None
+        subtract = None
+        if continuum is not None:
+            subtract = UVContSubTemplate(context, continuum).instantiate(queue, stop_channel - start_channel)
+        for chunk in data_iter(dataset, vis_limit, vis_load, start_channel, stop_channel):
+            vis = accel.DeviceArray(context, chunk['vis'].shape, np.complex64, queue=queue)
+            weights = accel.DeviceArray(context, chunk['weights'].shape, np.float32, queue=queue)
+            uvw = accel.DeviceArray(context, chunk['uvw'].shape, np.float32, queue=queue)
+            vis.set(queue, chunk['vis'])
+            weights.set(queue, chunk['weights'])
+            uvw.set(queue, chunk['uvw'])
+            if after is None:
+                uvw = before(vis, uvw)
+                if subtract is not None:
+                    subtract(vis, weights)
+            else:
+                before(vis, uvw, write_uvw=False)
+                subtract(vis, weights)
+                if after.template.params.writes_uvw:
+                    uvw = after(vis, uvw)
+                else:
+                    after(vis, uvw, write_uvw=False)
+            collector.add(uvw, weights, vis,
+                          chunk.get('feed_angle1'), chunk.get('feed_angle2'), *polarization_matrices)
+        if subtract is not None:
+            collector.continuum_counts = subtract.counts()
+        collector.phase_centre = target
     finally:
         collector.close()
     return collector
