@@ -60,12 +60,23 @@ extern "C" {
  * preprocessor does to such runs before its gridder sees them.  How long a folded run is is not
  * part of the contract (runs are cut wherever the kernel's batches end).  A stream without adjacent
  * duplicates is gridded exactly as before.
+ * Long calls (and calls with KIMG_ARITH_PREFOLD) whose workspace has the room fold such runs in a
+ * pass of its own ahead of the window kernel (kimg_fold_runs below), which sums the RAW samples of a
+ * run in float32; the window kernel then weights the sum: weights_grid * sum(vis) in place of
+ * sum(vis * weights_grid) -- all records of a run read the same weight.  Both are allowed.
  *   KIMG_ARITH_NO_FOLD     a bit OR-ed into any of the above (kimg_grid only): every record gets its
- *                          own update, as before the fold existed.  For comparison and tests. */
+ *                          own update, as before the fold existed.  For comparison and tests.
+ *   KIMG_ARITH_PREFOLD     a bit OR-ed into any of the forms (kimg_grid only): the MFMA variant takes
+ *                          the fold pre-pass whatever the number of records, when the workspace has
+ *                          room for it (see `workspace` of kimg_grid); without the bit only calls
+ *                          long enough for it to pay do.  For comparison and tests.  Together with
+ *                          KIMG_ARITH_NO_FOLD it is KIMG_EINVAL.  (0x400, not the next free bit:
+ *                          0x200 alone stays an invalid `arith`, as callers have been told.) */
 #define KIMG_ARITH_FP32 0
 #define KIMG_ARITH_SPLIT_FP16 1
 #define KIMG_ARITH_FP32_32X32 2
 #define KIMG_ARITH_NO_FOLD 0x100
+#define KIMG_ARITH_PREFOLD 0x400
 
 /* Kernel choice of kimg_grid / kimg_degrid (argument `variant`) */
 #define KIMG_VARIANT_AUTO 0     /* MFMA window kernel when the parameters allow it */
@@ -166,6 +177,12 @@ int kimg_kernel_table(void *table, const double *ws, int w_planes, int kernel_wi
  *                   plus, when the kernel table is too large for LDS -- more than 512 rows
  *                   w_planes*oversample for widths <= 32, 256 for 33..64 -- a zero-padded copy of it,
  *                   built there on every call.  One call at a time per workspace.
+ *                   For max N of 8 Mi records or more the size includes room for the fold pre-pass:
+ *                   kimg_fold_runs_workspace_bytes(P, max N / 2) more.  A call on N records takes
+ *                   the pre-pass when workspace_bytes is at least kimg_grid_workspace_bytes(0, ...)
+ *                   + kimg_fold_runs_workspace_bytes(P, N / 2), uv, w_plane, vis and workspace are
+ *                   16-byte aligned, and N >= 8 Mi or KIMG_ARITH_PREFOLD is set; with less -- the
+ *                   sizes of before the pre-pass existed, or NULL -- it silently goes without.
  *   variant         KIMG_VARIANT_*: automatic = MFMA window kernel when supported (kernel_width
  *                   <= 64), else the generic scatter kernel
  *   arith           KIMG_ARITH_* (above); anything else is KIMG_EINVAL
@@ -185,6 +202,24 @@ size_t kimg_grid_binned_workspace_bytes(int64_t max_vis, int num_polarizations, 
  * choose KIMG_VARIANT_BINNED when count / num_vis is more than a few percent. */
 int kimg_grid_jumps(const int16_t *uv, int64_t num_vis, int kernel_width, uint32_t *count,
                     void *stream);
+/* The fold pre-pass of kimg_grid on its own: runs of consecutive records with equal (u, v, sub_u,
+ * sub_v, w_plane) become one record each, with the float32 sum of the run's samples per polarization,
+ * in stream order (deterministic).  Runs are also cut at the boundaries of up to 1024 contiguous
+ * spans the stream is divided into, and nowhere else.  Two launches, asynchronous, capturable.
+ *   uv, w_plane, vis  as for kimg_grid, N >= 1 records, each pointer 16-byte aligned
+ *   capacity          records the output may hold
+ *   workspace         device memory, 16-byte aligned, kimg_fold_runs_workspace_bytes(P, capacity)
+ *                     bytes.  At its start a header: uint32 use_folded, uint32 spans, int64 H (the
+ *                     number of heads of runs), then three device pointers into the workspace --
+ *                     the compacted uv int16 [H][4], w_plane int16 [H], vis complex64 [H][P] -- and
+ *                     int64 capacity.
+ * If 2 H > N (folding would not halve the stream) or H > capacity, use_folded is 0 and no record is
+ * written; else use_folded is 1 and the H records are there.
+ * KIMG_EINVAL for null or misaligned pointers and N < 1, KIMG_EWORKSPACE for a short workspace. */
+size_t kimg_fold_runs_workspace_bytes(int num_polarizations, int64_t capacity);
+int kimg_fold_runs(const int16_t *uv, const int16_t *w_plane, const void *vis, int64_t num_vis,
+                   int num_polarizations, int64_t capacity, void *workspace, size_t workspace_bytes,
+                   void *stream);
 int kimg_grid(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride, int grid_size,
               int num_polarizations,
               const float *weights_grid, int64_t wg_row_stride, int64_t wg_pol_stride,

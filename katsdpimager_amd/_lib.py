@@ -29,6 +29,8 @@ PROTOTYPES = {
     'kimg_grid_workspace_bytes': (c_size_t, [L, I, I, I, I]),
     'kimg_grid_binned_workspace_bytes': (c_size_t, [L, I, I, I, I]),
     'kimg_grid_jumps': (c_int, [P, L, I, P, P]),
+    'kimg_fold_runs_workspace_bytes': (c_size_t, [I, L]),
+    'kimg_fold_runs': (c_int, [P, P, P, L, I, L, P, c_size_t, P]),
     'kimg_grid': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, I, P]),
     'kimg_degrid': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, I, P]),
     'kimg_degrid_workspace_bytes': (c_size_t, [I, I, I, I]),

@@ -224,8 +224,12 @@ int check_grid_args(int grid_size, int P, int64_t num_vis, int w_planes, int ove
 extern "C" size_t kimg_grid_workspace_bytes(int64_t max_vis, int num_polarizations, int w_planes,
                                            int oversample, int kernel_width)
 {
-    (void) max_vis;
-    return kimg_grid_mfma_workspace_bytes(num_polarizations, w_planes, oversample, kernel_width);
+    const size_t own = kimg_grid_mfma_workspace_bytes(num_polarizations, w_planes, oversample,
+                                                      kernel_width);
+    // room for the fold pre-pass, for callers whose launches are long enough to take it
+    if (own == 0 || max_vis < kimg_grid_prefold_min_vis())
+        return own;
+    return own + kimg_grid_prefold_workspace_bytes(max_vis, num_polarizations);
 }
 
 extern "C" int kimg_grid(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
@@ -238,7 +242,9 @@ extern "C" int kimg_grid(void *grid, int64_t grid_row_stride, int64_t grid_pol_s
 {
     KIMG_CHECK_ARG(grid && weights_grid && uv && w_plane && vis && convolve_kernel);
     KIMG_CHECK_ARG(grid_row_stride >= grid_size && wg_row_stride >= grid_size);
-    const int form = arith & ~KIMG_ARITH_NO_FOLD;       // (the window kernels take the bit themselves)
+    // (the window kernels take the two bits themselves)
+    const int form = arith & ~(KIMG_ARITH_NO_FOLD | KIMG_ARITH_PREFOLD);
+    KIMG_CHECK_ARG(!((arith & KIMG_ARITH_NO_FOLD) && (arith & KIMG_ARITH_PREFOLD)));
     KIMG_CHECK_ARG(form == KIMG_ARITH_FP32 || form == KIMG_ARITH_SPLIT_FP16
                    || form == KIMG_ARITH_FP32_32X32);
     KIMG_CHECK_ARG(variant >= 0 && (variant >> 8) <= 256);

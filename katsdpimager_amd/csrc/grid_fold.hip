@@ -1,0 +1,444 @@
+// Fold pre-pass of the window gridder: runs of consecutive records with equal (u, v, sub_u, sub_v,
+// w_plane) become ONE record with the float32 sum of their raw samples (kimg_fold_runs, include/kimg.h).
+//
+// All records of a run read the same density-weight cell and apply the same rank-1 matrix, so the
+// window kernel (grid_mfma.hip) can weight the sum, w * sum(v), where it would have summed the
+// weighted samples: it needs no new arithmetic, and the pre-pass no weight gather.  An uncompressed
+// track stream repeats its predecessor's sub-cell in 6 of 7 records; building those records inside
+// the window kernel costs issue slots that it shares with its matrix instructions, at 3 waves per
+// SIMD.  Here the same work is a memory stream: 256-thread workgroups at full occupancy, 10 bytes
+// per record read in the first launch, 10 + 8 P in the second.
+//
+// Two launches, no scan kernel, and NO workgroup ever waits for another one:
+//  * the stream is cut into at most 768 contiguous spans of whole tiles (a tile = 256 threads x 8
+//    records), one workgroup per span;
+//  * launch 1 counts the heads of runs in every span (a span's first record always heads a run:
+//    runs are cut at span boundaries, and only there);
+//  * launch 2: every workgroup sums the counts of the spans before its own (at most 1024 words) and
+//    walks its span tile by tile, carrying the output offset and the open run's partial sum from
+//    tile to tile.  Heads and sums are written in stream order: the output is deterministic.
+//    Every workgroup also sums ALL counts to H and takes the same decision from it: with
+//    2 H > N or H above the output's capacity the header says use_folded = 0 and no record is
+//    written -- a stream without duplicates costs the count pass only.
+// No allocation, no read-back, no synchronisation: the call is asynchronous and capturable.
+#include "kimg_common.h"
+
+namespace {
+
+constexpr int FOLD_THREADS = 256;
+constexpr int FOLD_RECORDS = 8;                             // consecutive records per thread
+constexpr int FOLD_TILE = FOLD_THREADS * FOLD_RECORDS;
+constexpr int FOLD_MAX_SPANS = 1024;                        // (what the counts' array holds)
+constexpr int FOLD_WAVES = FOLD_THREADS / WAVE;
+
+// workspace layout (bytes): header, the spans' counts, then the compacted uv, vis and w_plane
+constexpr size_t FOLD_HEADER_BYTES = 256;
+constexpr size_t FOLD_COUNTS_BYTES = FOLD_MAX_SPANS * sizeof(uint32_t);
+
+inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
+
+struct fold_plan {
+    int spans;
+    int64_t tiles_per_span;
+};
+
+// As many spans as workgroups of the compaction kernel are resident at once on 256 CUs -- three per
+// CU at the 132 (P = 1) and 139 (P = 2) registers it takes, two with more polarizations -- so that
+// a launch is one round of workgroups of equal length.
+inline fold_plan fold_plan_of(int64_t num_vis, int P)
+{
+    const int max_spans = P <= 2 ? 768 : 512;
+    static_assert(768 <= FOLD_MAX_SPANS, "the counts' array holds one word per span");
+    const int64_t tiles = (num_vis + FOLD_TILE - 1) / FOLD_TILE;
+    fold_plan p;
+    p.tiles_per_span = (tiles + max_spans - 1) / max_spans;
+    p.spans = (int) ((tiles + p.tiles_per_span - 1) / p.tiles_per_span);
+    return p;
+}
+
+// The keys of a thread's 8 records [i0, i0 + 8) and of the record before them
+struct fold_keys {
+    int2 uv[FOLD_RECORDS];
+    int wp[FOLD_RECORDS];
+    int2 prev_uv;
+    int prev_wp;
+};
+
+// (uv, w_plane 16-byte aligned; i0 a multiple of 8: whole 16-byte words while the thread's records
+// all exist, single clamped loads at the stream's end)
+__device__ __attribute__((always_inline)) inline void fold_load_keys(
+    const int16_t *__restrict__ uv, const int16_t *__restrict__ w_plane, int64_t i0, int64_t num_vis,
+    int64_t span_start, fold_keys &k)
+{
+    if (i0 + FOLD_RECORDS <= num_vis) {
+        const int4 *u4 = reinterpret_cast<const int4 *>(uv + 4 * i0);
+#pragma unroll
+        for (int j = 0; j < FOLD_RECORDS / 2; j++) {
+            const int4 t = u4[j];
+            k.uv[2 * j] = make_int2(t.x, t.y);
+            k.uv[2 * j + 1] = make_int2(t.z, t.w);
+        }
+        const int4 w4 = *reinterpret_cast<const int4 *>(w_plane + i0);
+        const int w[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            k.wp[2 * j] = (short) (w[j] & 0xffff);
+            k.wp[2 * j + 1] = w[j] >> 16;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < FOLD_RECORDS; j++) {
+            int64_t i = i0 + j;
+            i = i < num_vis ? i : num_vis - 1;
+            k.uv[j] = reinterpret_cast<const int2 *>(uv)[i];
+            k.wp[j] = w_plane[i];
+        }
+    }
+    k.prev_uv = k.uv[0];
+    k.prev_wp = k.wp[0];
+    if (i0 > span_start && i0 < num_vis) {
+        k.prev_uv = reinterpret_cast<const int2 *>(uv)[i0 - 1];
+        k.prev_wp = w_plane[i0 - 1];
+    }
+}
+
+// bit j: record i0 + j exists and heads a run
+__device__ __attribute__((always_inline)) inline unsigned fold_heads(
+    const fold_keys &k, int64_t i0, int64_t num_vis, int64_t span_start)
+{
+    unsigned heads = 0;
+#pragma unroll
+    for (int j = 0; j < FOLD_RECORDS; j++) {
+        const int2 puv = j ? k.uv[j - 1] : k.prev_uv;
+        const int pwp = j ? k.wp[j - 1] : k.prev_wp;
+        const bool differs = k.uv[j].x != puv.x || k.uv[j].y != puv.y || k.wp[j] != pwp;
+        const bool head = i0 + j < num_vis && (i0 + j == span_start || differs);
+        heads |= head ? 1u << j : 0u;
+    }
+    return heads;
+}
+
+// sum over the workgroup, valid in every thread (s_red: FOLD_WAVES words; ends with a barrier, so
+// that s_red can be used again at once)
+__device__ inline unsigned long long fold_block_sum(unsigned long long v, unsigned long long *s_red)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        v += __shfl_xor(v, off, WAVE);
+    if ((threadIdx.x & 63) == 0)
+        s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    unsigned long long sum = 0;
+#pragma unroll
+    for (int w = 0; w < FOLD_WAVES; w++)
+        sum += s_red[w];
+    __syncthreads();
+    return sum;
+}
+
+__global__ __launch_bounds__(FOLD_THREADS) void fold_count_kernel(
+    const int16_t *__restrict__ uv, const int16_t *__restrict__ w_plane, int64_t num_vis,
+    int64_t tiles_per_span, uint32_t *__restrict__ counts)
+{
+    __shared__ unsigned long long s_red[FOLD_WAVES];
+    const int64_t span_start = (int64_t) blockIdx.x * tiles_per_span * FOLD_TILE;
+    int64_t span_end = span_start + tiles_per_span * FOLD_TILE;
+    span_end = span_end < num_vis ? span_end : num_vis;
+    unsigned count = 0;
+#pragma unroll 2
+    for (int64_t tile = span_start; tile < span_end; tile += FOLD_TILE) {
+        const int64_t i0 = tile + (int64_t) threadIdx.x * FOLD_RECORDS;
+        if (i0 < num_vis) {
+            fold_keys k;
+            fold_load_keys(uv, w_plane, i0, num_vis, span_start, k);
+            count += __builtin_popcount(fold_heads(k, i0, num_vis, span_start));
+        }
+    }
+    const unsigned long long sum = fold_block_sum(count, s_red);
+    if (threadIdx.x == 0)
+        counts[blockIdx.x] = (uint32_t) sum;
+}
+
+// What the segmented scan over a tile's threads carries: heads seen, whether any, and the sum of the
+// samples since the last head (of all samples while there was none)
+template <int P>
+struct fold_elem {
+    int cnt, flag;
+    float2 s[P];
+};
+
+template <int P>
+__device__ __attribute__((always_inline)) inline fold_elem<P> fold_combine(
+    const fold_elem<P> &a, const fold_elem<P> &b)         // a: the earlier records
+{
+    fold_elem<P> r;
+    r.cnt = a.cnt + b.cnt;
+    r.flag = a.flag | b.flag;
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+        r.s[p].x = b.flag ? b.s[p].x : a.s[p].x + b.s[p].x;
+        r.s[p].y = b.flag ? b.s[p].y : a.s[p].y + b.s[p].y;
+    }
+    return r;
+}
+
+template <int P>
+__device__ __attribute__((always_inline)) inline fold_elem<P> fold_shfl_up(const fold_elem<P> &e, int d)
+{
+    fold_elem<P> r;
+    r.cnt = __shfl_up(e.cnt, d, WAVE);
+    r.flag = __shfl_up(e.flag, d, WAVE);
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+        r.s[p].x = __shfl_up(e.s[p].x, d, WAVE);
+        r.s[p].y = __shfl_up(e.s[p].y, d, WAVE);
+    }
+    return r;
+}
+
+// A thread's samples of one tile
+template <int P>
+struct fold_samples {
+    float2 v[FOLD_RECORDS][P];
+};
+
+template <int P>
+__device__ __attribute__((always_inline)) inline void fold_load_samples(
+    const float2 *__restrict__ vis, int64_t i0, int64_t num_vis, fold_samples<P> &s)
+{
+    if (i0 + FOLD_RECORDS <= num_vis) {
+        // 8 P complex samples = 4 P words of 16 bytes
+        const float4 *v4 = reinterpret_cast<const float4 *>(vis + i0 * P);
+#pragma unroll
+        for (int j = 0; j < FOLD_RECORDS * P / 2; j++) {
+            const float4 t = v4[j];
+            s.v[(2 * j) / P][(2 * j) % P] = make_float2(t.x, t.y);
+            s.v[(2 * j + 1) / P][(2 * j + 1) % P] = make_float2(t.z, t.w);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < FOLD_RECORDS; j++) {
+            int64_t i = i0 + j;
+            i = i < num_vis ? i : num_vis - 1;
+#pragma unroll
+            for (int p = 0; p < P; p++)
+                s.v[j][p] = vis[i * P + p];
+        }
+    }
+}
+
+template <int P>
+__global__ __launch_bounds__(FOLD_THREADS) void fold_compact_kernel(
+    const int16_t *__restrict__ uv, const int16_t *__restrict__ w_plane,
+    const float2 *__restrict__ vis, int64_t num_vis, int64_t tiles_per_span, int spans,
+    const uint32_t *__restrict__ counts, int64_t capacity, kimg_fold_header *__restrict__ header,
+    int2 *__restrict__ out_uv, int16_t *__restrict__ out_w, float2 *__restrict__ out_vis)
+{
+    __shared__ unsigned long long s_red[FOLD_WAVES];
+    __shared__ fold_elem<P> s_tot[2][FOLD_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+
+    // the records before this span, and all of them: every workgroup reads the same counts and
+    // takes the same decision
+    unsigned long long before = 0, all = 0;
+    for (int i = threadIdx.x; i < spans; i += FOLD_THREADS) {
+        const unsigned c = counts[i];
+        all += c;
+        before += i < (int) blockIdx.x ? c : 0u;
+    }
+    const int64_t offset = (int64_t) fold_block_sum(before, s_red);
+    const int64_t H = (int64_t) fold_block_sum(all, s_red);
+    const bool use = 2 * H <= num_vis && H <= capacity;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        header->use_folded = use ? 1u : 0u;
+        header->spans = (uint32_t) spans;
+        header->count = H;
+        header->uv = reinterpret_cast<const int16_t *>(out_uv);
+        header->w_plane = out_w;
+        header->vis = out_vis;
+        header->capacity = capacity;
+    }
+    if (!use)
+        return;
+
+    const int64_t span_start = (int64_t) blockIdx.x * tiles_per_span * FOLD_TILE;
+    int64_t span_end = span_start + tiles_per_span * FOLD_TILE;
+    span_end = span_end < num_vis ? span_end : num_vis;
+    // a tile's loads are issued before the tile before it is worked on (one polarization: with more
+    // the second set of registers would cost a wave per SIMD)
+    constexpr bool PREFETCH = P == 1;
+    fold_keys keys, next_keys;
+    fold_samples<P> smp, next_smp;
+    auto load_tile = [&](int64_t tile, fold_keys &k, fold_samples<P> &s) __attribute__((always_inline)) {
+        const int64_t i0 = tile + (int64_t) threadIdx.x * FOLD_RECORDS;
+        if (tile < span_end && i0 < num_vis) {
+            fold_load_keys(uv, w_plane, i0, num_vis, span_start, k);
+            fold_load_samples<P>(vis, i0, num_vis, s);
+        }
+    };
+    if (PREFETCH)
+        load_tile(span_start, keys, smp);
+
+    float2 carry[P];                // sum of the run that is open at the end of the tiles so far
+#pragma unroll
+    for (int p = 0; p < P; p++)
+        carry[p] = make_float2(0.0f, 0.0f);
+    int64_t run_base = offset;      // output index of the next tile's first head
+    int parity = 0;
+    for (int64_t tile = span_start; tile < span_end; tile += FOLD_TILE, parity ^= 1) {
+        const int64_t i0 = tile + (int64_t) threadIdx.x * FOLD_RECORDS;
+        if (PREFETCH)
+            load_tile(tile + FOLD_TILE, next_keys, next_smp);
+        else
+            load_tile(tile, keys, smp);
+        const unsigned heads = i0 < num_vis ? fold_heads(keys, i0, num_vis, span_start) : 0u;
+        // this thread's element: its heads and the sum since its last head
+        fold_elem<P> e;
+        e.cnt = __builtin_popcount(heads);
+        e.flag = heads != 0;
+#pragma unroll
+        for (int p = 0; p < P; p++)
+            e.s[p] = make_float2(0.0f, 0.0f);
+#pragma unroll
+        for (int j = 0; j < FOLD_RECORDS; j++) {
+            const bool valid = i0 + j < num_vis, head = (heads >> j) & 1u;
+#pragma unroll
+            for (int p = 0; p < P; p++) {
+                const float2 v = valid ? smp.v[j][p] : make_float2(0.0f, 0.0f);
+                e.s[p].x = head ? v.x : e.s[p].x + v.x;
+                e.s[p].y = head ? v.y : e.s[p].y + v.y;
+            }
+        }
+        // inclusive scan over the wave, the waves' totals through LDS
+        fold_elem<P> inc = e;
+#pragma unroll
+        for (int d = 1; d < WAVE; d *= 2) {
+            const fold_elem<P> o = fold_shfl_up<P>(inc, d);
+            if (lane >= d)
+                inc = fold_combine<P>(o, inc);
+        }
+        if (lane == WAVE - 1)
+            s_tot[parity][wave] = inc;
+        fold_elem<P> in = fold_shfl_up<P>(inc, 1);  // what precedes this thread in its wave
+        if (lane == 0) {
+            in.cnt = in.flag = 0;
+#pragma unroll
+            for (int p = 0; p < P; p++)
+                in.s[p] = make_float2(0.0f, 0.0f);
+        }
+        __syncthreads();        // (one per tile: s_tot alternates between two copies)
+        fold_elem<P> prefix;    // what precedes this thread's wave: earlier tiles' open run, earlier waves
+        prefix.cnt = prefix.flag = 0;
+#pragma unroll
+        for (int p = 0; p < P; p++)
+            prefix.s[p] = carry[p];
+        fold_elem<P> whole = prefix;
+#pragma unroll
+        for (int w = 0; w < FOLD_WAVES; w++) {
+            whole = fold_combine<P>(whole, s_tot[parity][w]);
+            if (w + 1 == wave)
+                prefix = whole;
+        }
+        in = fold_combine<P>(prefix, in);
+
+        // walk the records: a head closes the run before it (writes its sum) and opens its own
+        float2 acc[P];
+#pragma unroll
+        for (int p = 0; p < P; p++)
+            acc[p] = in.s[p];
+        int64_t r = run_base + in.cnt;
+#pragma unroll
+        for (int j = 0; j < FOLD_RECORDS; j++) {
+            const bool valid = i0 + j < num_vis, head = (heads >> j) & 1u;
+            if (head) {
+                if (r > offset && r <= capacity)
+#pragma unroll
+                    for (int p = 0; p < P; p++)
+                        out_vis[(r - 1) * P + p] = acc[p];
+                if (r < capacity) {
+                    out_uv[r] = keys.uv[j];
+                    out_w[r] = (int16_t) keys.wp[j];
+                }
+                r++;
+            }
+#pragma unroll
+            for (int p = 0; p < P; p++) {
+                const float2 v = valid ? smp.v[j][p] : make_float2(0.0f, 0.0f);
+                acc[p].x = head ? v.x : acc[p].x + v.x;
+                acc[p].y = head ? v.y : acc[p].y + v.y;
+            }
+        }
+        run_base += whole.cnt;
+#pragma unroll
+        for (int p = 0; p < P; p++)
+            carry[p] = whole.s[p];
+        if (PREFETCH) {
+            keys = next_keys;
+            smp = next_smp;
+        }
+    }
+    // the span's last run ends with the span
+    if (threadIdx.x == 0 && run_base > offset && run_base <= capacity)
+#pragma unroll
+        for (int p = 0; p < P; p++)
+            out_vis[(run_base - 1) * P + p] = carry[p];
+}
+
+bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+} // namespace
+
+size_t kimg_fold_workspace_bytes(int P, int64_t capacity)
+{
+    const size_t cap = capacity > 0 ? (size_t) capacity : 0;
+    return FOLD_HEADER_BYTES + FOLD_COUNTS_BYTES + align256(cap * sizeof(int2))
+           + align256(cap * P * sizeof(float2)) + align256(cap * sizeof(int16_t));
+}
+
+int kimg_fold_launch(const int16_t *uv, const int16_t *w_plane, const float2 *vis, int64_t num_vis,
+                     int P, int64_t capacity, void *workspace, hipStream_t stream)
+{
+    if (capacity < 0)
+        capacity = 0;
+    unsigned char *base = static_cast<unsigned char *>(workspace);
+    kimg_fold_header *header = reinterpret_cast<kimg_fold_header *>(base);
+    uint32_t *counts = reinterpret_cast<uint32_t *>(base + FOLD_HEADER_BYTES);
+    unsigned char *out = base + FOLD_HEADER_BYTES + FOLD_COUNTS_BYTES;
+    int2 *out_uv = reinterpret_cast<int2 *>(out);
+    out += align256((size_t) capacity * sizeof(int2));
+    float2 *out_vis = reinterpret_cast<float2 *>(out);
+    out += align256((size_t) capacity * P * sizeof(float2));
+    int16_t *out_w = reinterpret_cast<int16_t *>(out);
+    const fold_plan plan = fold_plan_of(num_vis, P);
+    fold_count_kernel<<<plan.spans, FOLD_THREADS, 0, stream>>>(uv, w_plane, num_vis,
+                                                               plan.tiles_per_span, counts);
+    kimg_for_pols(P, [&](auto p) {
+        fold_compact_kernel<decltype(p)::value><<<plan.spans, FOLD_THREADS, 0, stream>>>(
+            uv, w_plane, vis, num_vis, plan.tiles_per_span, plan.spans, counts, capacity, header,
+            out_uv, out_w, out_vis); });
+    return kimg_launch_status();
+}
+
+extern "C" size_t kimg_fold_runs_workspace_bytes(int num_polarizations, int64_t capacity)
+{
+    if (num_polarizations < 1 || num_polarizations > 4 || capacity < 0)
+        return 0;
+    return kimg_fold_workspace_bytes(num_polarizations, capacity);
+}
+
+extern "C" int kimg_fold_runs(const int16_t *uv, const int16_t *w_plane, const void *vis,
+                              int64_t num_vis, int num_polarizations, int64_t capacity,
+                              void *workspace, size_t workspace_bytes, void *stream)
+{
+    KIMG_CHECK_ARG(uv && w_plane && vis && workspace && num_vis >= 1 && capacity >= 0);
+    if (num_polarizations < 1 || num_polarizations > 4)
+        return KIMG_EUNSUPPORTED;
+    KIMG_CHECK_ARG(aligned16(uv) && aligned16(w_plane) && aligned16(vis) && aligned16(workspace));
+    if (workspace_bytes < kimg_fold_workspace_bytes(num_polarizations, capacity))
+        return KIMG_EWORKSPACE;
+    return kimg_fold_launch(uv, w_plane, static_cast<const float2 *>(vis), num_vis,
+                            num_polarizations, capacity, workspace, (hipStream_t) stream);
+}
+
+// (kimg_preload, api.hip)
+KIMG_PRELOAD_THIS_UNIT(fold_count_kernel)

@@ -357,9 +357,23 @@ struct pair32_ops {
     v2f b[SUBP][2];
 };
 
+// (512 until round 3; 384 measures 3-4 % faster on launches of ~7 M records -- a W-slice of the
+// re-ordered resident store, where a wave only gets four or five chunks and the tail of the launch
+// is one chunk long -- and the same on 50 M-record launches, whose chunks the cap below sets)
+#ifndef KIMG_INTERLEAVE_MIN_CHUNK
+#define KIMG_INTERLEAVE_MIN_CHUNK 384
+#endif
+#ifndef KIMG_INTERLEAVE_MAX_PARTS
+#define KIMG_INTERLEAVE_MAX_PARTS 16
+#endif
+constexpr int64_t INTERLEAVE_MIN_CHUNK = KIMG_INTERLEAVE_MIN_CHUNK;     // visibilities: bounds the extra window flushes
+constexpr int64_t INTERLEAVE_MAX_PARTS = KIMG_INTERLEAVE_MAX_PARTS;
+
+// The window kernel proper: what one workgroup does with the stream it is given (grid_mfma_kernel
+// below decides which stream that is).
 template <int P, int NW, int SUB, int ROW, bool TWO, bool TG = false, bool F16 = false,
           bool PAIR = false>
-__global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
+__device__ __attribute__((always_inline)) inline void grid_mfma_body(
     float *__restrict__ grid, int64_t row_stride, int64_t pol_stride, int Gg,
     const float *__restrict__ weights_grid, int64_t wg_row_stride, int64_t wg_pol_stride,
     const int16_t *__restrict__ uv, const int16_t *__restrict__ w_plane,
@@ -1320,6 +1334,43 @@ __global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
 #endif
 }
 
+// The kernel: the stream as the host gave it, or -- `folded` non-null and its use_folded set -- the one
+// the fold pre-pass (grid_fold.hip) compacted from it.  The host cannot know how many records that
+// one has, so the division of the stream follows the device's count: the host's plan keeps its
+// number of workgroups, the span of a workgroup, the chunk length and the scramble multiplier
+// (coprime to the DEVICE's number of chunks) are recomputed here, all of it uniform scalar work.
+// DEVICE_COUNT: the instance that a call with the pre-pass launches; calls without it launch the
+// other one, which has no prologue: the registers, scratch and occupancy of every such instance are
+// those of before the pre-pass existed, and all but five fp16-form instances also spill the same
+// number of SGPRs (profiles/prefold_gridder_resources.txt; the prologue's scalars, live through the
+// body, cost the other variant 2 to 30 more spilled SGPRs).  The price is twice the instances.
+template <int P, int NW, int SUB, int ROW, bool TWO, bool TG, bool F16, bool PAIR, bool DEVICE_COUNT>
+__global__ __launch_bounds__(NW * 64) void grid_mfma_kernel(
+    float *__restrict__ grid, int64_t row_stride, int64_t pol_stride, int Gg,
+    const float *__restrict__ weights_grid, int64_t wg_row_stride, int64_t wg_pol_stride,
+    const int16_t *__restrict__ uv, const int16_t *__restrict__ w_plane,
+    const float2 *__restrict__ vis, int64_t num_vis,
+    const float2 *__restrict__ kern, int W, int OV, tap_split ts, int64_t vis_per_block,
+    int p_total, int dbg, const unsigned char *__restrict__ padded,
+    const unsigned *__restrict__ tab_max, int64_t chunk, int64_t scramble, unsigned long long *queue,
+    const kimg_fold_header *__restrict__ folded)
+{
+    if (DEVICE_COUNT && folded->use_folded) {
+        // (bits 16-17 of dbg: the first polarization of this launch within a record)
+        uv = folded->uv;
+        w_plane = folded->w_plane;
+        vis = folded->vis + ((dbg >> 16) & 3);
+        num_vis = folded->count;
+        const int64_t waves = (int64_t) gridDim.x * NW;
+        vis_per_block = window_vis_per_block_of(num_vis, (int) gridDim.x, NW);
+        chunk = window_chunk_of(num_vis, waves, INTERLEAVE_MIN_CHUNK, INTERLEAVE_MAX_PARTS);
+        scramble = chunk > 0 ? window_scramble_of((num_vis + chunk - 1) / chunk) : 1;
+    }
+    grid_mfma_body<P, NW, SUB, ROW, TWO, TG, F16, PAIR>(
+        grid, row_stride, pol_stride, Gg, weights_grid, wg_row_stride, wg_pol_stride, uv, w_plane, vis,
+        num_vis, kern, W, OV, ts, vis_per_block, p_total, dbg, padded, tab_max, chunk, scramble, queue);
+}
+
 // The fp16 form's tables in HBM: pad_table_kernel (kimg_window_launch.h) with the taps scaled by S
 // (from the largest |component| of the whole table, *tab_max) and split into fp16 hi/lo pairs, as
 // the kernel does in LDS for tables that live there.
@@ -1346,18 +1397,6 @@ size_t lds_bytes(int P, int NW, int W, int OV, int row, int tables = 1)
            + (size_t) NW * 64 * (sizeof(int2) + P * sizeof(float4) + sizeof(int2));
 }
 
-// (512 until round 3; 384 measures 3-4 % faster on launches of ~7 M records -- a W-slice of the
-// re-ordered resident store, where a wave only gets four or five chunks and the tail of the launch
-// is one chunk long -- and the same on 50 M-record launches, whose chunks the cap below sets)
-#ifndef KIMG_INTERLEAVE_MIN_CHUNK
-#define KIMG_INTERLEAVE_MIN_CHUNK 384
-#endif
-#ifndef KIMG_INTERLEAVE_MAX_PARTS
-#define KIMG_INTERLEAVE_MAX_PARTS 16
-#endif
-constexpr int64_t INTERLEAVE_MIN_CHUNK = KIMG_INTERLEAVE_MIN_CHUNK;     // visibilities: bounds the extra window flushes
-constexpr int64_t INTERLEAVE_MAX_PARTS = KIMG_INTERLEAVE_MAX_PARTS;
-
 // What every launch of one kimg_grid_mfma call over (up to) two polarizations is given
 struct grid_call {
     float *g;                       // (the first of these polarizations)
@@ -1373,10 +1412,22 @@ struct grid_call {
     hipStream_t stream;
     window_tail tail;
     bool fold;
+    const kimg_fold_header *folded; // the fold pre-pass's header, or null: the stream as given
+    int p_first;                    // the first of these polarizations within a record
 };
+
+template <int P, int ROW, int NW, bool TWO, bool TG, bool F16, bool PAIR, bool DEVICE_COUNT>
+int launch_kernel(const grid_call &c, const tap_split &ts);
 
 template <int P, int ROW, int NW, bool TWO, bool TG, bool F16, bool PAIR>
 int launch(const grid_call &c, const tap_split &ts)
+{
+    return c.folded != nullptr ? launch_kernel<P, ROW, NW, TWO, TG, F16, PAIR, true>(c, ts)
+                               : launch_kernel<P, ROW, NW, TWO, TG, F16, PAIR, false>(c, ts);
+}
+
+template <int P, int ROW, int NW, bool TWO, bool TG, bool F16, bool PAIR, bool DEVICE_COUNT>
+int launch_kernel(const grid_call &c, const tap_split &ts)
 {
     static_assert(!TWO || TG, "off-diagonal tap blocks read their two tables from HBM");
     constexpr int SUB = (P == 1 && NW <= 12) ? 4 : 2;       // pipeline depth bounded by the VGPR budget
@@ -1396,17 +1447,19 @@ int launch(const grid_call &c, const tap_split &ts)
             return rc;
     }
     if (const int rc = kimg_dynamic_lds(
-            reinterpret_cast<const void *>(&grid_mfma_kernel<P, NW, SUB, ROW, TWO, TG, F16, PAIR>), LDS_LIMIT))
+            reinterpret_cast<const void *>(&grid_mfma_kernel<P, NW, SUB, ROW, TWO, TG, F16, PAIR, DEVICE_COUNT>),
+            LDS_LIMIT))
         return rc;
     // bits 8-15: span stagger of a SIMD's waves, percent.  Bits 0-1 (test builds with
     // -DKIMG_NO_ATOMICS, the counterpart of the reference's NO_ATOMICS switch,
     // imager_kernels/atomic.mako:29-40): no end flush / no window flushes -- wrong results, for
     // measuring what the float atomics cost.  Bit 2: runs of records with one sub-cell are NOT folded
-    // (KIMG_ARITH_NO_FOLD).
+    // (KIMG_ARITH_NO_FOLD).  Bits 16-17: the launch's first polarization within a record (for the
+    // compacted stream of the fold pre-pass, whose records keep all of them).
 #ifdef KIMG_NO_ATOMICS
-    const int dbg = (12 << 8) | 3 | (c.fold ? 0 : 4);
+    const int dbg = (c.p_first << 16) | (12 << 8) | 3 | (c.fold ? 0 : 4);
 #else
-    const int dbg = (12 << 8) | (c.fold ? 0 : 4);
+    const int dbg = (c.p_first << 16) | (12 << 8) | (c.fold ? 0 : 4);
 #endif
     // as many blocks resident per CU as the LDS (kernel table + staging) allows.  Long launches:
     // chunks of at least INTERLEAVE_MIN_CHUNK visibilities, up to INTERLEAVE_MAX_PARTS per wave
@@ -1416,10 +1469,10 @@ int launch(const grid_call &c, const tap_split &ts)
     unsigned long long *queue = part.chunk > 0 ? c.tail.queue : nullptr;
     if (queue != nullptr)
         KIMG_HIP(hipMemsetAsync(queue, 0, sizeof(unsigned long long), c.stream));
-    grid_mfma_kernel<P, NW, SUB, ROW, TWO, TG, F16, PAIR><<<part.blocks, NW * 64, lds, c.stream>>>(
+    grid_mfma_kernel<P, NW, SUB, ROW, TWO, TG, F16, PAIR, DEVICE_COUNT><<<part.blocks, NW * 64, lds, c.stream>>>(
         c.g, c.row_stride, c.pol_stride, c.Gg, c.wg, c.wg_row_stride, c.wg_pol_stride, c.uv, c.w_plane,
         c.vis, c.num_vis, c.kern, c.W, c.OV, ts, part.vis_per_block, c.p_total, dbg, c.tail.padded,
-        tab_max, part.chunk, part.scramble, queue);
+        tab_max, part.chunk, part.scramble, queue, c.folded);
     return kimg_launch_status();
 }
 
@@ -1488,7 +1541,8 @@ static bool table_in_lds(int P, int w_planes, int oversample, int kernel_width)
 }
 
 // Scratch: the padded table copy (none when the kernel reads its table from LDS) and the tail of
-// 256 bytes (window_tail, kimg_window_launch.h).
+// 256 bytes (window_tail, kimg_window_launch.h).  Between the two, when the caller gave that much
+// more, the fold pre-pass's workspace (kimg_grid_prefold_workspace_bytes).
 size_t kimg_grid_mfma_workspace_bytes(int P, int w_planes, int oversample, int kernel_width)
 {
     if (!kimg_grid_mfma_supported(P, w_planes, oversample, kernel_width))
@@ -1499,6 +1553,24 @@ size_t kimg_grid_mfma_workspace_bytes(int P, int w_planes, int oversample, int k
     return (size_t) w_planes * oversample * 64 * sizeof(float2) * (kernel_width > WIN ? 2 : 1) + 256;
 }
 
+// Below this many records a call does not take the fold pre-pass by itself (KIMG_ARITH_PREFOLD takes
+// it at any length).  On a stream without duplicates the count pass buys nothing, and it shows: with
+// the bound at 4 Mi the resident store's W-slices (6.85 and 7.25 M merged records) went from 0.681-0.684
+// to 0.705-0.716 ms and from 0.725-0.727 to 0.750-0.763 ms per launch (bench.py --full, three runs each
+// way), outside their own spread.  Track streams of 1 and 4 Mi records would gain (0.078 -> 0.065,
+// 0.250 -> 0.124 ms), but nothing cheap tells the two kinds apart before the count pass has run, so
+// the bound lies above the store's slices.  DESIGN 5.1 has the figures.
+#ifndef KIMG_PREFOLD_MIN_VIS
+#define KIMG_PREFOLD_MIN_VIS (8 << 20)
+#endif
+
+size_t kimg_grid_prefold_workspace_bytes(int64_t num_vis, int P)
+{
+    return kimg_fold_workspace_bytes(P, num_vis / 2);
+}
+
+int64_t kimg_grid_prefold_min_vis() { return KIMG_PREFOLD_MIN_VIS; }
+
 int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride, int grid_size,
                    int P, const float *weights_grid, int64_t wg_row_stride, int64_t wg_pol_stride,
                    const int16_t *uv, const int16_t *w_plane, const void *vis, int64_t num_vis,
@@ -1506,20 +1578,36 @@ int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
                    void *workspace, size_t workspace_bytes, int arith, hipStream_t stream)
 {
     const bool fold = !(arith & KIMG_ARITH_NO_FOLD);
-    arith &= ~KIMG_ARITH_NO_FOLD;
+    const bool prefold_always = (arith & KIMG_ARITH_PREFOLD) != 0;
+    arith &= ~(KIMG_ARITH_NO_FOLD | KIMG_ARITH_PREFOLD);
     const bool in_lds = table_in_lds(P, w_planes, oversample, kernel_width);
     if (!in_lds && (workspace == nullptr
                     || workspace_bytes < kimg_grid_mfma_workspace_bytes(P, w_planes, oversample,
                                                                        kernel_width)))
         return KIMG_EWORKSPACE;
     const window_tail tail = window_tail_of(workspace, workspace_bytes);
+    // The fold pre-pass, once for all the launches below, when the workspace has room for it between
+    // the tables and the tail (a workspace of the size before the pre-pass existed, or none: the call
+    // goes on without it).  Its kernels read 16 bytes at a time.
+    const kimg_fold_header *folded = nullptr;
+    const size_t own_bytes = kimg_grid_mfma_workspace_bytes(P, w_planes, oversample, kernel_width);
+    auto aligned16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (fold && (prefold_always || num_vis >= KIMG_PREFOLD_MIN_VIS) && workspace != nullptr
+        && workspace_bytes >= own_bytes + kimg_grid_prefold_workspace_bytes(num_vis, P)
+        && aligned16(uv) && aligned16(w_plane) && aligned16(vis) && aligned16(workspace)) {
+        void *fold_ws = static_cast<unsigned char *>(workspace) + (own_bytes - 256);
+        if (const int rc = kimg_fold_launch(uv, w_plane, (const float2 *) vis, num_vis, P, num_vis / 2,
+                                            fold_ws, stream))
+            return rc;
+        folded = static_cast<const kimg_fold_header *>(fold_ws);
+    }
     for (int p0 = 0; p0 < P; p0 += 2) {
         const int pn = P - p0 >= 2 ? 2 : 1;
         const grid_call c = {
             (float *) grid + 2 * p0 * grid_pol_stride, grid_row_stride, grid_pol_stride, grid_size,
             weights_grid + p0 * wg_pol_stride, wg_row_stride, wg_pol_stride, uv, w_plane,
             (const float2 *) vis + p0, num_vis, (const float2 *) convolve_kernel, w_planes,
-            oversample, P, stream, tail, fold};
+            oversample, P, stream, tail, fold, folded, p0};
         // The one table of a wide kernel's diagonal blocks fits LDS whenever a narrow kernel's
         // would, by the budget of this launch's polarizations.
         const bool one_in_lds = kernel_width > WIN

@@ -75,6 +75,10 @@ int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
                    void *workspace, size_t workspace_bytes, int arith, hipStream_t stream);
 bool kimg_grid_mfma_supported(int P, int w_planes, int oversample, int kernel_width);
 size_t kimg_grid_mfma_workspace_bytes(int P, int w_planes, int oversample, int kernel_width);
+// What kimg_grid_mfma needs ON TOP of the above to run the fold pre-pass on num_vis records, and the
+// length from which it does so unasked
+size_t kimg_grid_prefold_workspace_bytes(int64_t num_vis, int P);
+int64_t kimg_grid_prefold_min_vis();
 int kimg_degrid_mfma(const void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
                      int grid_size, int P, const int16_t *uv, const int16_t *w_plane,
                      const float *weights, void *vis, int64_t num_vis, const void *convolve_kernel,
@@ -82,6 +86,22 @@ int kimg_degrid_mfma(const void *grid, int64_t grid_row_stride, int64_t grid_pol
                      size_t workspace_bytes, int arith, hipStream_t stream);
 bool kimg_degrid_mfma_supported(int P, int w_planes, int oversample, int kernel_width);
 size_t kimg_degrid_mfma_workspace_bytes(int P, int w_planes, int oversample, int kernel_width);
+// The fold pre-pass (grid_fold.hip): runs of consecutive records with equal (u, v, sub_u, sub_v,
+// w_plane) compacted into one record each, with the sum of their samples.  Its header, in device
+// memory at the start of its workspace, is what the window gridder's kernel reads: whether to grid
+// the compacted stream, how long it is and where it lies.
+struct kimg_fold_header {
+    uint32_t use_folded;            // 0: grid the caller's stream (nothing else below is valid)
+    uint32_t spans;                 // workgroups' spans the stream was cut into
+    int64_t count;                  // H, heads of runs (whether or not they were written)
+    const int16_t *uv, *w_plane;    // the compacted stream: `count` records
+    const float2 *vis;              //   [count][P]
+    int64_t capacity;
+};
+size_t kimg_fold_workspace_bytes(int P, int64_t capacity);
+// (16-byte aligned uv, w_plane, vis and workspace; workspace of at least the size above)
+int kimg_fold_launch(const int16_t *uv, const int16_t *w_plane, const float2 *vis, int64_t num_vis,
+                     int P, int64_t capacity, void *workspace, hipStream_t stream);
 // *out = the bit pattern of the largest |component| among the n floats of a kernel table (ktable.hip):
 // the fp16 hi/lo forms of the window kernels choose their table scale from it when the table is in
 // HBM.  (Hidden: a helper between two units of the library, no part of its dynamic symbol table.)

@@ -4,6 +4,7 @@
 // is each file's own business (grid_leaf / degrid_leaf there).
 #pragma once
 #include "kimg_common.h"
+#include "kimg_window_plan.h"
 
 // Private to the including unit, like the kernels it serves (tap_split is a kernel parameter).
 namespace {
@@ -63,6 +64,8 @@ inline window_tail window_tail_of(void *workspace, size_t workspace_bytes)
 // records (a multiple of 64, at least one batch per wave), as many blocks as fill blocks_max.
 // Long launches work by the chunk instead (chunk > 0; batch_pos in the kernels): every wave takes
 // its work from up to max_parts places of the stream, in chunks of at least min_chunk records.
+// (The formulas are kimg_window_plan.h's: the gridder's kernel evaluates them again for a stream
+// whose length only the device knows.)
 struct window_partition {
     int blocks;
     int64_t vis_per_block, chunk, scramble;
@@ -72,28 +75,14 @@ inline window_partition window_partition_of(int64_t num_vis, int NW, int blocks_
                                             int64_t min_chunk, int64_t max_parts, bool want_scramble)
 {
     window_partition p;
-    p.vis_per_block = (num_vis + blocks_max - 1) / blocks_max;
-    p.vis_per_block = (p.vis_per_block + 63) / 64 * 64;
-    if (p.vis_per_block < 64 * NW)
-        p.vis_per_block = 64 * NW;
+    p.vis_per_block = window_vis_per_block_of(num_vis, blocks_max, NW);
     p.blocks = (int) ((num_vis + p.vis_per_block - 1) / p.vis_per_block);
     const int64_t waves = (int64_t) p.blocks * NW;
-    int64_t parts = num_vis / (waves * min_chunk);
-    parts = parts > max_parts ? max_parts : parts;
-    p.chunk = 0;
-    if (parts >= 2)
-        p.chunk = ((num_vis + waves * parts - 1) / (waves * parts) + 63) / 64 * 64;
+    p.chunk = window_chunk_of(num_vis, waves, min_chunk, max_parts);
     // (gridder) chunk numbers are scrambled by a multiplier coprime to their count
     p.scramble = 1;
-    if (want_scramble && p.chunk > 0) {
-        const int64_t total = (num_vis + p.chunk - 1) / p.chunk;
-        static const int64_t primes[] = {7919, 7907, 7901, 7883, 7879, 7877, 7873};
-        for (int64_t m : primes)
-            if (total % m != 0) {
-                p.scramble = m;
-                break;
-            }
-    }
+    if (want_scramble && p.chunk > 0)
+        p.scramble = window_scramble_of((num_vis + p.chunk - 1) / p.chunk);
     return p;
 }
 
