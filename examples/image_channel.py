@@ -5,6 +5,7 @@ store -> imaging weights, PSF, major/minor cycles -> restored image, all on one 
     python examples/image_channel.py [--pixels 2048] [--vis 4000000] [--major 3]
     python examples/image_channel.py --uvcontsub 1:6-9      (a 16-channel band; see uvcontsub_band)
     python examples/image_channel.py --phase-shift=-120,60  (a small field around a source; see phase_shift_field)
+    python examples/image_channel.py --uv-taper 30,20,30 --uv-range 0,3000  (see uv_taper_channel)
 
 It follows the reference's per-channel flow (frontend.py:31-83 preprocess_visibilities,
 :465-658 process_channel) with the loaders and FITS output left out: the sky is three point
@@ -145,6 +146,74 @@ def phase_shift_field(args):
     return peaks
 
 
+def parse_uv_taper(args):
+    """``weight.UVTaperParameters`` of --uv-taper ARCSEC[,ARCSEC,DEG] and --uv-range MIN,MAX (None
+    without either)."""
+    from katsdpimager_amd import weight
+    if not args.uv_taper and not args.uv_range:
+        return None
+    gaussian, angle, cuts = None, 0.0, {}
+    if args.uv_taper:
+        parts = [float(x) for x in args.uv_taper.split(',')]
+        if len(parts) not in (1, 3):
+            raise SystemExit('--uv-taper takes ARCSEC or ARCSEC,ARCSEC,DEG')
+        gaussian, angle = (parts[0:2], parts[2]) if len(parts) == 3 else (parts[0], 0.0)
+    if args.uv_range:
+        low, high = (float(x) for x in args.uv_range.split(','))
+        cuts = dict(min_uv=low or None, max_uv=high)
+    return weight.UVTaperParameters.from_arcsec(gaussian, angle, **cuts)
+
+
+def uv_taper_channel(args):
+    """--uv-taper / --uv-range: the three-source channel imaged twice from the same resident store,
+    robust weighting without and with the taper; prints the fitted restoring beam and the
+    normalized noise of both."""
+    import torch
+    import scipy.optimize       # noqa: F401
+    import synth
+    from katsdpimager_amd import accel, frontend, imaging, parameters, preprocess, weight
+    taper = parse_uv_taper(args)
+    ctx = accel.create_some_context()
+    queue = ctx.create_command_queue()
+    obs = synth.make_observation(args.pixels, args.vis, args.w_planes, 1, device=ctx.device)
+    image_p, grid_p, array_p = synth.make_parameters(obs, 1, args.kernel_width, degrid=True)
+    sources = [((40, -25), 1.0), ((-120, 60), 0.5), ((15, 200), 0.25)]      # (l, m) in pixels, Jy
+    uvw_wl = obs.uvw.to(torch.float64) / obs.wavelength
+    vis = torch.zeros(obs.n_vis, dtype=torch.complex128, device=ctx.device)
+    for (lp, mp), flux in sources:
+        l, m = lp * obs.pixel_size, mp * obs.pixel_size
+        n = math.sqrt(1 - l * l - m * m)
+        vis += flux / n * torch.exp(-2j * math.pi * (uvw_wl[:, 0] * l + uvw_wl[:, 1] * m + uvw_wl[:, 2] * (n - 1)))
+    vis = vis.to(torch.complex64)[None, :, None].contiguous()
+    weights = torch.ones((1, obs.n_vis, 1), dtype=torch.float32, device=ctx.device)
+    torch.cuda.synchronize()
+    collector = preprocess.VisibilityCollectorDevice(queue, [image_p], [grid_p], args.vis_block)
+    collector.add(accel.DeviceArray(ctx, (obs.n_vis, 3), np.float32, tensor=obs.uvw),
+                  accel.DeviceArray(ctx, weights.shape, np.float32, tensor=weights),
+                  accel.DeviceArray(ctx, vis.shape, np.complex64, tensor=vis),
+                  None, None, np.ones((1, 1), np.complex64), None)
+    collector.close()
+    reader = collector.reader()
+    clean_p = parameters.CleanParameters(args.minor, 0.1, 0.85, 5.0, 0, 0.01, 0.5, 0.02)
+    arcsec = math.degrees(image_p.pixel_size) * 3600.0
+    print('pixel {:.3f} arcsec, uv cell {:.2f} wavelengths; {}'.format(arcsec, 1.0 / image_p.image_size, taper))
+    results = {}
+    for label, keyword in (('untapered', None), ('tapered', taper)):
+        weight_p = parameters.WeightParameters(weight.WeightType.ROBUST, 0.0, keyword)
+        template = imaging.ImagingTemplate(ctx, array_p, image_p.fixed, weight_p, grid_p.fixed, clean_p)
+        imager = template.instantiate(queue, image_p, grid_p, args.vis_block, 0, args.major, streams=2)
+        imager.ensure_all_bound()
+        stats = frontend.process_channel(reader, 0, imager, image_p, grid_p, clean_p,
+                                         weight_p.weight_type, args.vis_block, args.major, True, fit_beam=True)
+        beam = stats['restoring_beam']
+        results[label] = stats
+        print('{:9s}: restoring beam {:.2f} x {:.2f} arcsec ({:.2f} x {:.2f} px) at {:.1f} deg, '
+              'normalized_noise {:.4f}, first peak {:.3f}'.format(
+                  label, beam.major * arcsec, beam.minor * arcsec, beam.major, beam.minor,
+                  math.degrees(beam.theta), stats['normalized_noise'], float(stats['peaks'][0])))
+    return results
+
+
 def _frequencies(obs, channels):
     return 299792458.0 / obs.wavelength + 1.0e5 * np.arange(channels)
 
@@ -175,7 +244,15 @@ def main(argv=None):
     ap.add_argument('--phase-shift', metavar='L,M',
                     help='instead of the default field alone: re-phase the raw visibilities to the direction L,M '
                          'pixels from its centre and image a field a quarter as wide around it, e.g. --phase-shift=-120,60')
+    ap.add_argument('--uv-taper', metavar='ARCSEC[,ARCSEC,DEG]',
+                    help='instead of the one image: image the channel without and with a Gaussian uv taper '
+                         'that alone would give a beam of this FWHM (major, minor, position angle), and print '
+                         'the fitted beams and normalized noise, e.g. --uv-taper 30,20,30')
+    ap.add_argument('--uv-range', metavar='MIN,MAX',
+                    help='with or without --uv-taper: keep only the cells between these radii (wavelengths)')
     args = ap.parse_args(argv)
+    if args.uv_taper or args.uv_range:
+        return uv_taper_channel(args)
     if args.uvcontsub:
         return uvcontsub_band(args)
     if args.phase_shift:

@@ -333,6 +333,48 @@ int kimg_density_weights(double *sums, float *grid, int64_t row_stride, int64_t 
 int kimg_density_weights_robust(double *sums, float *grid, int64_t row_stride, int64_t pol_stride,
                                 int width, int height, int num_polarizations,
                                 const double *mean_sums, double robust, float b, void *stream);
+/* UV taper and uv-range weighting fused into the density pass (CASA uvtaper / uvrange, WSClean
+ * -taper-gaussian, -minuv-l, -maxuv-l, -taper-inner-tukey, -taper-edge-tukey).  The reference has
+ * none; the semantics are this library's, and katsdpimager_amd/weight.py holds them once more as
+ * numpy (uv_taper_host).  One kernel for natural (a = 0, b = 1), uniform (a = 1, b = 0) and robust
+ * weighting: mean_sums NULL takes `a` as given, otherwise a = robust / (mean_sums[1] / mean_sums[0])
+ * as in kimg_density_weights_robust and `a` is ignored.
+ *
+ * Cell (x, y) stands at u = (x - width / 2) * u_step, v = (y - height / 2) * v_step wavelengths
+ * (the steps are 1 / image_size).  In float64, with r = sqrt(u u + v v):
+ *   G = exp(-((quad_uu u u + quad_uv u v) + quad_vv v v))
+ *   inner = 0 for r < min_uv; sin^2(pi/2 (r - min_uv) / inner_tukey) for r < min_uv + inner_tukey
+ *           (inner_tukey > 0); else 1            [= 0.5 (1 - cos(pi x)), the raised cosine]
+ *   outer = 0 for r > max_uv; sin^2(pi/2 (max_uv - r) / outer_tukey) for r > max_uv - outer_tukey
+ *           (outer_tukey > 0); else 1
+ *   t64 = G * inner * outer;  t = (float) t64, one rounding.
+ * For an image-plane Gaussian of FWHM major, minor (l/m units) whose major axis stands at angle
+ * theta from the m (v, row) axis towards the l (u, column) axis -- the angle beam.fit_beam reports --
+ * and k = pi^2 / (4 ln 2), c = cos theta, s = sin theta:
+ *   quad_uu = k (major^2 s^2 + minor^2 c^2), quad_uv = 2 k (major^2 - minor^2) s c,
+ *   quad_vv = k (major^2 c^2 + minor^2 s^2).
+ * No Gaussian: all three 0.  No cuts: min_uv = 0, max_uv = DBL_MAX (every field must be finite).
+ * Per cell, for every polarization: d as kimg_density_weights computes it (the same float32
+ * expression, 0 where w == 0); grid = d * t (float32 product).  Each stored value lies within
+ * 3 * 2^-24 of d * t64 relatively where t is a normal float32, within 2^-126 absolutely otherwise.
+ * sums over polarization 0: sums[0] = sum of w over the cells with t64 > 0 (a hard cut leaves the
+ * sums the same data would give without the cut cells), sums[1] = sum e w, sums[2] = sum e e w with
+ * e the stored float32.  The robust mean weight is the untapered one.
+ * *taper is a HOST struct, read during the call and handed to the kernel by value.
+ * KIMG_EINVAL, before anything is enqueued: a null pointer (mean_sums excepted), a non-finite or
+ * negative field (quad_uv may be negative), a non-finite step or one that is not above 0,
+ * row_pitch < width, an odd width or height.  (row_pitch, pol_pitch: the row and polarization
+ * strides of kimg_density_weights, in elements; tests/test_uv_taper_gpu.py holds this call's
+ * refusals, the row pitch below the width among them.) */
+typedef struct kimg_uv_taper {
+    double quad_uu, quad_uv, quad_vv;   /* the Gaussian's quadratic form, per wavelength^2 */
+    double min_uv, max_uv;              /* cut radii, wavelengths */
+    double inner_tukey, outer_tukey;    /* ramp widths, wavelengths */
+} kimg_uv_taper;
+int kimg_density_weights_taper(double *sums, float *grid, int64_t row_pitch, int64_t pol_pitch,
+                               int width, int height, int num_polarizations, float a, float b,
+                               const double *mean_sums, double robust, double u_step, double v_step,
+                               const kimg_uv_taper *taper, void *stream);
 int kimg_fill(float *data, int64_t count, float value, void *stream);
 
 /* ---- visibility preprocessing: preprocess.cpp:390-513 (visibility_collector<P>::add_impl2) and

@@ -40,6 +40,8 @@ PROTOTYPES = {
     'kimg_mean_weight': (c_int, [P, P, L, I, I, P]),
     'kimg_density_weights': (c_int, [P, P, L, L, I, I, I, F, F, P]),
     'kimg_density_weights_robust': (c_int, [P, P, L, L, I, I, I, P, c_double, F, P]),
+    # uv taper: kimg_density_weights' arguments, (mean_sums, robust), the cell steps, kimg_uv_taper *
+    'kimg_density_weights_taper': (c_int, [P, P, L, L, I, I, I, F, F, P, D, D, D, P, P]),
     'kimg_fill': (c_int, [P, L, F, P]),
     'kimg_preprocess_convert': (c_int, [I, I, L, P, P, P, P, P, P, P, F, I, I, I, F, P, P, P, P]),
     'kimg_preprocess_workspace_bytes': (ctypes.c_size_t, [L, I]),
@@ -137,6 +139,13 @@ class CleanChannel(ctypes.Structure):
 
 
 CLEAN_BATCH_MAX = 8     # KIMG_CLEAN_BATCH_MAX
+
+
+class UVTaper(ctypes.Structure):
+    """``kimg_uv_taper`` of include/kimg.h (the taper of kimg_density_weights_taper)."""
+    _fields_ = [('quad_uu', c_double), ('quad_uv', c_double), ('quad_vv', c_double),
+                ('min_uv', c_double), ('max_uv', c_double),
+                ('inner_tukey', c_double), ('outer_tukey', c_double)]
 
 
 class KimgLibraryError(RuntimeError):

@@ -2,6 +2,7 @@
 // density weights and fill.  Mirrors weight.py:155-176, 261-284, 357-376 of the reference
 // (kernels grid_weights.mako, density_weights.mako, mean_weight.mako); HBM-bound streams.
 #include "kimg_common.h"
+#include <cmath>
 
 namespace {
 
@@ -144,6 +145,80 @@ __global__ __launch_bounds__(256) void density_weights_kernel(
     block_accumulate<3>(acc, sums);
 }
 
+// kimg_density_weights_taper: density_weights_kernel with a uv taper t(x, y) on top.  d is the
+// expression above, t is worked out in float64 once per cell (the polarizations share it) and
+// rounded once to float32; e = d * t is what is stored and what enters the sums.  sums[0] counts w
+// where the float64 t is above 0: a hard cut leaves the sums of the same data without the cut cells.
+__device__ inline double uv_taper_value(const kimg_uv_taper &tp, double u, double v)
+{
+    double t = exp(-((tp.quad_uu * u * u + tp.quad_uv * u * v) + tp.quad_vv * v * v));
+    const double r = sqrt(u * u + v * v);
+    if (r < tp.min_uv || r > tp.max_uv)
+        return 0.0;
+    // raised-cosine ramps, 0.5 (1 - cos(pi x)) written as sin^2(pi x / 2): no cancellation at the foot
+    if (tp.inner_tukey > 0.0 && r < tp.min_uv + tp.inner_tukey) {
+        const double s = sinpi(0.5 * ((r - tp.min_uv) / tp.inner_tukey));
+        t *= s * s;
+    }
+    if (tp.outer_tukey > 0.0 && r > tp.max_uv - tp.outer_tukey) {
+        const double s = sinpi(0.5 * ((tp.max_uv - r) / tp.outer_tukey));
+        t *= s * s;
+    }
+    return t;
+}
+
+__global__ __launch_bounds__(256) void density_weights_taper_kernel(
+    double *__restrict__ sums, float *__restrict__ grid, int64_t row_stride, int64_t pol_stride,
+    int width, int height, int num_pols, float a, float b, const double *__restrict__ mean_sums,
+    double robust, double u_step, double v_step, kimg_uv_taper tp)
+{
+    if (mean_sums) {
+        const double mean_weight = mean_sums[1] / mean_sums[0];
+        a = (float) (robust / mean_weight);
+    }
+    double acc[3] = {0, 0, 0};
+    constexpr int ROWS = 4;
+    for (int y0 = blockIdx.y; y0 < height; y0 += gridDim.y * ROWS)
+        for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < width; x += gridDim.x * blockDim.x) {
+            const double u = (double) (x - width / 2) * u_step;
+            float t[ROWS];
+            bool counted[ROWS];
+#pragma unroll
+            for (int r = 0; r < ROWS; r++) {
+                const int y = y0 + r * gridDim.y;
+                const double t64 = y < height
+                    ? uv_taper_value(tp, u, (double) (y - height / 2) * v_step) : 0.0;
+                counted[r] = t64 > 0.0;
+                t[r] = (float) t64;
+            }
+            for (int p = 0; p < num_pols; p++) {
+                float w[ROWS];
+#pragma unroll
+                for (int r = 0; r < ROWS; r++) {
+                    const int y = y0 + r * gridDim.y;
+                    w[r] = y < height ? grid[(int64_t) y * row_stride + x + p * pol_stride] : 0.0f;
+                }
+#pragma unroll
+                for (int r = 0; r < ROWS; r++) {
+                    const int y = y0 + r * gridDim.y;
+                    if (y >= height)
+                        continue;
+                    const float d = (w[r] != 0.0f) ? 1.0f / (a * w[r] + b) : 0.0f;
+                    const float e = d * t[r];
+                    if (p == 0) {
+                        const double ew = (double) e * w[r];
+                        if (counted[r])
+                            acc[0] += w[r];
+                        acc[1] += ew;
+                        acc[2] += e * ew;
+                    }
+                    grid[(int64_t) y * row_stride + x + p * pol_stride] = e;
+                }
+            }
+        }
+    block_accumulate<3>(acc, sums);
+}
+
 __global__ __launch_bounds__(256) void fill_kernel(float *__restrict__ data, int64_t count, float value)
 {
     const int64_t vec_count = count & ~(int64_t) 3;
@@ -219,6 +294,30 @@ extern "C" int kimg_density_weights_robust(double *sums, float *grid, int64_t ro
     KIMG_HIP(hipMemsetAsync(sums, 0, 3 * sizeof(double), s));
     density_weights_kernel<<<image_grid(width, height), 256, 0, s>>>(
         sums, grid, row_stride, pol_stride, width, height, num_polarizations, 0.0f, b, mean_sums, robust);
+    return kimg_launch_status();
+}
+
+extern "C" int kimg_density_weights_taper(double *sums, float *grid, int64_t row_stride,
+                                          int64_t pol_stride, int width, int height,
+                                          int num_polarizations, float a, float b,
+                                          const double *mean_sums, double robust, double u_step,
+                                          double v_step, const kimg_uv_taper *taper, void *stream)
+{
+    KIMG_CHECK_ARG(sums && grid && taper && width > 0 && height > 0 && num_polarizations > 0);
+    KIMG_CHECK_ARG(row_stride >= width);
+    KIMG_CHECK_ARG(width % 2 == 0 && height % 2 == 0);     // (the origin is cell (W/2, H/2))
+    const double fields[] = {taper->quad_uu, taper->quad_uv, taper->quad_vv, taper->min_uv,
+                             taper->max_uv, taper->inner_tukey, taper->outer_tukey, u_step, v_step};
+    for (double f : fields)
+        KIMG_CHECK_ARG(std::isfinite(f));
+    KIMG_CHECK_ARG(taper->quad_uu >= 0 && taper->quad_vv >= 0 && taper->min_uv >= 0
+                   && taper->max_uv >= 0 && taper->inner_tukey >= 0 && taper->outer_tukey >= 0
+                   && u_step > 0 && v_step > 0);
+    hipStream_t s = (hipStream_t) stream;
+    KIMG_HIP(hipMemsetAsync(sums, 0, 3 * sizeof(double), s));
+    density_weights_taper_kernel<<<image_grid(width, height), 256, 0, s>>>(
+        sums, grid, row_stride, pol_stride, width, height, num_polarizations, a, b, mean_sums,
+        robust, u_step, v_step, *taper);
     return kimg_launch_status();
 }
 

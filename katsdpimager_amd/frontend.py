@@ -20,9 +20,11 @@ def _device_reader(reader):
 
 
 def make_weights(reader, rel_channel, imager, weight_type, vis_block):
-    """frontend.py:86-106.  Returns (noise, normalized_noise) of ``finalize_weights``."""
+    """frontend.py:86-106.  Returns (noise, normalized_noise) of ``finalize_weights``.  An imager
+    with a uv taper wants the weights on its grid under natural weighting too
+    (``Imaging.grids_weights``)."""
     imager.clear_weights()
-    if weight_type != weight.WeightType.NATURAL:
+    if weight_type != weight.WeightType.NATURAL or getattr(imager, 'grids_weights', False) is True:
         for w_slice in range(reader.num_w_slices(rel_channel)):
             if _device_reader(reader):
                 for chunk in reader.iter_slice_device(rel_channel, w_slice, vis_block):
@@ -79,7 +81,7 @@ def slice_mid_w(image_p, grid_p):
 def process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type,
                     vis_block, major, degrid, subtract_model=False, batched_clean=True,
                     fit_beam=False, clean_batcher=None, multiscale=None, clean_mask=None,
-                    auto_mask=None):
+                    uv_taper=None, auto_mask=None):
     """The loop of frontend.process_channel (frontend.py:497-585) from "Compute imaging
     weights" to the end of the last major cycle.
 
@@ -118,7 +120,17 @@ def process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p, weigh
     other ``minor - 1``.  ``clean_mask`` and ``auto_mask`` combine with it.  It needs
     ``degrid=True`` (extended components cannot go through the DFT predictor's component
     dictionary) and takes no ``clean_batcher``.  None (the default) changes nothing.
+
+    The uv taper (:class:`weight.UVTaperParameters`) belongs to the imager, which is made with it
+    (``parameters.WeightParameters.taper``) and with its ``image_size``; the weights grid itself is
+    rebuilt for every channel, so nothing finalised is carried from one channel to the next.  The
+    result has ``uv_taper``, the taper the weights were made with (None: none).  ``uv_taper`` here
+    states the taper the channel is meant to get: an imager made with another one is refused, as one
+    made for another ``image_size`` is.  None (the default) takes the imager's.
     """
+    if uv_taper is not None and uv_taper != getattr(imager, 'uv_taper', None):
+        raise ValueError('the imager was made for uv taper {!r}, the channel asks for {!r}'.format(
+            getattr(imager, 'uv_taper', None), uv_taper))
     if multiscale is not None:
         if not degrid:
             raise ValueError('multi-scale CLEAN needs degrid=True: its components are extended')
@@ -197,7 +209,8 @@ def _check_imager_parameters(imager, image_p, grid_p):
     own_grid = getattr(imager, 'grid_parameters', None)
     if own_image is None or own_grid is None:
         return
-    for name in ('pixels', 'pixel_size', 'cell_size', 'wavelength'):
+    # (image_size: the cell step of the weights grid, and with it where a uv taper falls)
+    for name in ('pixels', 'pixel_size', 'image_size', 'cell_size', 'wavelength'):
         a, b = getattr(own_image, name, None), getattr(image_p, name, None)
         if a is not None and b is not None and float(a) != float(b):
             raise ValueError('the imager was made for {} = {!r}, the channel has {!r}'.format(name, a, b))
@@ -244,7 +257,7 @@ def _process_channel_stages(reader, rel_channel, imager, image_p, grid_p, clean_
                 # may run next to another channel's gridding)
                 dirty.get_region(imager.command_queue, psf_peak, np.s_[:, centre, centre], np.s_[:])
     out = dict(weights_noise=weights_noise, normalized_noise=normalized_noise, major=0, minor=0,
-               peaks=[], noise=None)
+               peaks=[], noise=None, uv_taper=getattr(imager, 'uv_taper', None))
     if not deferred:
         with trace.range('psf_patch'):
             if np.any(psf_peak == 0):

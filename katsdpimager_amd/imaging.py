@@ -38,7 +38,8 @@ class ImagingTemplate:
         dtype = fixed_image_parameters.real_dtype
         num_pols = len(fixed_image_parameters.polarizations)
         tuning = tuning or {}
-        self.weights = weight.WeightsTemplate(context, weight_parameters.weight_type, num_pols)
+        self.weights = weight.WeightsTemplate(context, weight_parameters.weight_type, num_pols,
+                                              taper=getattr(weight_parameters, 'taper', None))
         self.gridder = grid.GridderTemplate(context, fixed_image_parameters,
                                             fixed_grid_parameters, tuning.get('gridder'))
         self.predict = predict.PredictTemplate(context, dtype, num_pols)
@@ -193,7 +194,8 @@ class Imaging(accel.OperationSequence):
         self._continuum_predict = template.predict.instantiate(
             command_queue, image_parameters, grid_parameters, max_vis, max_sources, allocator)
         grid_shape = self._gridder.slots['grid'].shape
-        self._weights = template.weights.instantiate(command_queue, grid_shape, max_vis, allocator)
+        self._weights = template.weights.instantiate(command_queue, grid_shape, max_vis, allocator,
+                                                     image_size=image_parameters.image_size)
         self._weights.robustness = template.weight_parameters.robustness
         self._grid_to_image = template.grid_image.instantiate_grid_to_image(
             command_queue, grid_shape, lm_scale, lm_bias, fft_plan, allocator)
@@ -341,6 +343,19 @@ class Imaging(accel.OperationSequence):
         if 'dirty' in kwargs and getattr(self, '_dirty_cleared', False) and getattr(self, '_bound', False):
             self._ready()
         super().bind(**kwargs)
+
+    @property
+    def uv_taper(self):
+        """The :class:`weight.UVTaperParameters` this imager's weights carry (None: no taper).  It
+        and the imager's ``image_size`` are fixed when the imager is made; the weights grid itself
+        is rebuilt by every channel's ``clear_weights`` ... ``finalize_weights``."""
+        return self._weights.taper
+
+    @property
+    def grids_weights(self):
+        """Does ``finalize_weights`` need the statistical weights on the grid first (everything
+        but natural weighting without a taper)?"""
+        return 'uv' in self._weights.slots
 
     # ---- visibilities ---------------------------------------------------------------
     @property

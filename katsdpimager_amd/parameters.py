@@ -119,10 +119,12 @@ def w_slices(image_parameters, max_w, eps_w, kernel_width, antialias_width=0):
 
 
 class WeightParameters:
-    """parameters.py:186-205."""
-    def __init__(self, weight_type, robustness=0.0):
+    """parameters.py:186-205.  ``taper``: a :class:`weight.UVTaperParameters` (uv taper and uv
+    range on top of the density weights) or None."""
+    def __init__(self, weight_type, robustness=0.0, taper=None):
         self.weight_type = weight_type
         self.robustness = robustness
+        self.taper = taper
 
 
 class FixedGridParameters:
