@@ -486,7 +486,7 @@ def make_imager(P, mode, major=2):
 
 
 @gpu
-@pytest.mark.parametrize('mode,P', [(0, 1), (1, 1), (0, 4), (1, 4)])
+@pytest.mark.parametrize('mode,P', [(0, 1), (1, 1), (0, 4), (1, 4), (1, 3), (0, 2)])
 def test_imaging_auto_mask(mode, P):
     """Imaging.auto_mask on the 256^2 problem of test_clean_mask: the restated mask exactly, and 200
     masked cycles under it that are MaskedClean's on the numpy mask, bit for bit."""

@@ -332,7 +332,7 @@ def run(fn, q, form, patch, threshold, cycles):
 
 @gpu
 @pytest.mark.parametrize('kind', MASKS)
-@pytest.mark.parametrize('mode,P', [(0, 1), (1, 1), (0, 4), (1, 4)])
+@pytest.mark.parametrize('mode,P', [(0, 1), (1, 1), (0, 4), (1, 4), (0, 2), (1, 2), (0, 3), (1, 3)])
 def test_masked_forms_vs_restatement(mode, P, kind):
     """200 cycles on 256^2 under every mask, in the per-call, two-launch and one-launch forms (and
     what `auto` takes with a mask): all of it the restatement's, bit for bit."""
@@ -411,7 +411,7 @@ def test_mask_runs_dry_then_stops():
 
 
 @gpu
-@pytest.mark.parametrize('mode,P', [(0, 1), (1, 4)])
+@pytest.mark.parametrize('mode,P', [(0, 1), (1, 4), (1, 3)])
 def test_threshold_stop_under_a_mask(mode, P):
     psf, dirty = problem(mode, P)
     patch = (P,) + PATCH

@@ -242,7 +242,7 @@ def test_multi_repeated_steps_continue_and_stop():
 
 
 @pytest.mark.parametrize('case', ['deep', 'stops after the first', 'noise decides', 'limit', 'one cycle'])
-@pytest.mark.parametrize('mode,P', [(0, 1), (1, 1), (1, 3), (0, 2)])
+@pytest.mark.parametrize('mode,P', [(0, 1), (1, 1), (1, 3), (0, 2), (0, 3), (0, 4), (1, 4)])
 def test_major_cycles_in_one_call(mode, P, case):
     """kimg_clean_major_cycles: the first cycle without a threshold and the others below
     max(noise threshold, (1 - major gain) x the first peak), worked out on the device -- against the

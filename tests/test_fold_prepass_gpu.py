@@ -144,8 +144,14 @@ def check_fold(uv, wp, vis, capacity, hdr, raw, what):
     assert same.sum() == H - heads_min, what
 
 
-@pytest.mark.parametrize('P', [1, 2, 4])
+@pytest.mark.parametrize('P', [1, 2, 3, 4])
 def test_fold_runs_contract(P):
+    """Every kind of stream at every length of SIZES.  SIZES already holds what three polarizations
+    need: lengths that are no multiple of 8 (63, 65, TILE - 1, TILE + 1, 5 TILE + 17, 300001), whose
+    last thread takes the clamped single loads of fold_load_samples, and TILE = 8 * 256 records
+    exactly, where every thread of one tile takes the 16-byte loads -- which at P = 3 (records of 24
+    bytes) straddle record boundaries -- and none the tail."""
+    assert any(n % 8 for n in SIZES) and 8 * 256 in SIZES
     ctx, q = context_queue()
     rs = np.random.RandomState(40 + P)
     for n in SIZES:
@@ -167,7 +173,7 @@ def test_fold_runs_contract(P):
                 assert hdr['use_folded'] == 1, what
 
 
-@pytest.mark.parametrize('P', [1, 2, 4])
+@pytest.mark.parametrize('P', [1, 2, 3, 4])
 def test_fold_runs_respects_the_capacity(P):
     """An output capacity below H: use_folded = 0 and nothing written, behind the capacity or before."""
     ctx, q = context_queue()
@@ -201,10 +207,11 @@ def long_lengths(rs, n, giant=20000):
     return lengths
 
 
-@pytest.mark.parametrize('P', [1, 2, 4])
+@pytest.mark.parametrize('P', [1, 2, 3, 4])
 def test_fold_runs_spans_of_several_tiles(P):
     """Spans of four tiles: the output offset and the open run carried from tile to tile, the scan's
-    LDS totals used a third and fourth time, the prefetched tile (P = 1) handed on."""
+    LDS totals used a third and fourth time, the prefetched tile (P = 1) handed on; P = 3 and 4
+    take the plan of 512 spans without the prefetch."""
     ctx, q = context_queue()
     rs = np.random.RandomState(90 + P)
     n = several_tiles_per_span(P)
@@ -330,6 +337,7 @@ def check_case(case, inp, ok, forms=FORMS, folds=True, want=None):
 GRID_CASES = [
     FoldCase('k28_p1', 28, 8, 4, 1, 6000, 168),
     FoldCase('k28_p2', 28, 8, 4, 2, 5 * TILE + 17, 168),
+    FoldCase('k28_p3', 28, 8, 4, 3, 6000, 168),         # (k28_p1 with three polarizations)
     FoldCase('k28_p4', 28, 8, 4, 4, TILE + 1, 168),
     FoldCase('k40_p1', 40, 8, 4, 1, 5000, 200),
     FoldCase('k40_p3', 40, 8, 4, 3, TILE, 200),

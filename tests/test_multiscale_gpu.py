@@ -1,6 +1,8 @@
 """Multi-scale CLEAN on the device (csrc/clean_scales.hip) against its numpy twin
 (multiscale.MultiScaleCleanHost): the separable convolution, the set-up, the minor cycles, the
-single scale 0 against the Hogbom loop, and the driver.  Every comparison with the twin is exact."""
+single scale 0 against the Hogbom loop, and the driver.  Every comparison with the twin is exact.
+Set-up and cycles run at 1, 2, 3 and 4 polarizations (DESIGN.md 5.17 lists which test launches which
+entry point of the library at which count)."""
 import numpy as np
 import pytest
 
@@ -109,10 +111,37 @@ def test_convolve_matches_twin(shape, R):
     np.testing.assert_array_equal(src.get(q), x)
 
 
+@gpu
+@pytest.mark.parametrize('P', [1, 3, 4])
+def test_convolve_matches_twin_pols(P):
+    """test_convolve_matches_twin (which runs P = 2) at the other counts, on the narrow shape with
+    the radii 7 and 64: every plane is its own convolution, through its own pitch."""
+    from katsdpimager_amd import accel
+    from katsdpimager_amd._lib import lib, check
+    ctx, q = context_queue()
+    H, W = 33, 200
+    aa = np.frombuffer(b'\xaa' * 4, np.float32)[0]
+    for R in (7, 64):
+        rng = np.random.default_rng(R * 1000 + W + P)
+        x = rng.standard_normal((P, H, W)).astype(np.float32)
+        taps = rng.standard_normal(2 * R + 1).astype(np.float32)
+        src = Padded(ctx, q, x, rpad=5, vpad=2, sentinel=aa, origin=(0, 3))
+        tmp = Padded(ctx, q, np.full_like(x, aa), rpad=1, vpad=0, sentinel=aa, origin=(0, 3))
+        out = Padded(ctx, q, np.full_like(x, aa), rpad=9, vpad=1, sentinel=aa, origin=(0, 3))
+        dtaps = accel.DeviceArray(ctx, taps.shape, np.float32, queue=q)
+        dtaps.set(q, taps)
+        check(lib().kimg_image_convolve_separable(
+            src.ptr, src.row, src.pol, out.ptr, out.row, out.pol, tmp.ptr, tmp.row, tmp.pol,
+            W, H, P, dtaps.ptr, R, q.handle), 'kimg_image_convolve_separable')
+        np.testing.assert_array_equal(tmp.get(q), ms._conv_axis(x, taps))
+        np.testing.assert_array_equal(out.get(q), ms.conv_host(x, taps))
+        np.testing.assert_array_equal(src.get(q), x)
+
+
 # ---- set-up ---------------------------------------------------------------------------------------
 
 @gpu
-@pytest.mark.parametrize('P', [1, 2])
+@pytest.mark.parametrize('P', [1, 2, 3, 4])
 def test_setup_matches_twin(P):
     G, border, patch = 96, 0.02, (P, 15, 17)
     dirty, psf = field(G, P, border, 7 + P)
@@ -151,7 +180,7 @@ def _run_both(op, twin, q, patch, threshold, cycles=CYCLES):
 
 
 @gpu
-@pytest.mark.parametrize('P', [1, 2])
+@pytest.mark.parametrize('P', [1, 2, 3, 4])
 def test_cycles_clipped_on_all_sides(P):
     """Threshold 0, noise plus blobs 3 pixels from the border: boxes clip on all four sides."""
     G, border, patch = 96, 0.02, (P, 15, 17)
@@ -181,8 +210,47 @@ def test_cycles_stop_mid_chunk():
 
 
 @gpu
+@pytest.mark.parametrize('P', [4])
+def test_cycles_stop_mid_chunk_pols(P):
+    """test_cycles_stop_mid_chunk (which runs P = 1) at four polarizations: the count is exact, the
+    last component's four fluxes end the log and nothing is subtracted from any plane after it.
+    P = 2 and 3 take no other code: the stopping rule reads polarization 0 alone, and a cycle's
+    per-polarization work runs at every count in test_cycles_clipped_on_all_sides."""
+    G, border, patch = 96, 0.02, (P, 15, 17)
+    dirty, psf = field(G, P, border, 22)
+    op, twin, q = make_op(G, P, [0, 4, 9], border, 0.1, dirty, psf)
+    probe = ms.MultiScaleCleanHost(twin.params, border, 0.1, CLEAN_I, dirty.copy(), psf,
+                                   np.zeros_like(dirty))
+    peaks = probe.run_cycles(patch, 0.0, 150)['peak']
+    threshold = float(np.nextafter(peaks[100], np.float32(np.inf)))
+    log = _run_both(op, twin, q, patch, threshold)
+    assert 0 < len(log) < CYCLES and len(log) % 64 != 0
+    assert np.all(log['peak'] >= np.float32(threshold))
+    assert log['flux'].shape == (len(log), P)
+
+
+@gpu
 def test_cycles_with_mask():
     G, P, border, patch = 96, 2, 0.02, (2, 15, 17)
+    dirty, psf = field(G, P, border, 23)
+    rng = np.random.default_rng(5)
+    mask = np.kron(rng.random((12, 12)) < 0.4, np.ones((8, 8), bool))
+    mask[:, 40:44] = True
+    op, twin, q = make_op(G, P, [0, 4, 9], border, 0.1, dirty, psf, mask=mask)
+    log = _run_both(op, twin, q, patch, 0.0)
+    assert len(log) == CYCLES
+    assert np.all(mask[log['y'], log['x']])
+    # nothing allowed: no component whatever the threshold
+    op2, twin2, q = make_op(G, P, [0, 4, 9], border, 0.1, dirty, psf, mask=np.zeros((G, G), bool))
+    assert len(_run_both(op2, twin2, q, patch, 0.0, 10)) == 0
+
+
+@gpu
+@pytest.mark.parametrize('P', [3, 4])
+def test_cycles_with_mask_pols(P):
+    """test_cycles_with_mask (which runs P = 2) at three and four polarizations.  P = 1 under a mask
+    takes no other code: the mask enters through is_candidate alone, which does not see the count."""
+    G, border, patch = 96, 0.02, (P, 15, 17)
     dirty, psf = field(G, P, border, 23)
     rng = np.random.default_rng(5)
     mask = np.kron(rng.random((12, 12)) < 0.4, np.ones((8, 8), bool))
@@ -268,6 +336,41 @@ def test_single_scale_is_the_existing_path(name):
     tmax, tpos = op.tile_records()
     np.testing.assert_array_equal(tmax[0], fn.buffer('tile_max').get(q))
     np.testing.assert_array_equal(tpos[0], fn.buffer('tile_pos').get(q))
+
+
+@gpu
+def test_single_scale_is_the_existing_path_four_polarizations():
+    """gi.CLEAN_CONFIGS has no problem with four polarizations in mode CLEAN_I, so this one is made
+    here: field(96, 4, ...) with scales = [0] against kimg_clean_cycles on the same data, exactly as
+    above; the four fluxes of every component included."""
+    from katsdpimager_amd import clean
+    G, P, border, loop_gain, patch, cycles = 96, 4, 0.02, 0.1, (4, 15, 17), 150
+    dirty, psf = field(G, P, border, 26)
+    op, twin, q = make_op(G, P, [0], border, loop_gain, dirty, psf)
+    op.reset()
+    log = op.run_cycles(patch, 0.0, cycles)
+    ctx, q = context_queue()
+    ip, cp = _params(G, P, border, loop_gain)
+    fn = clean.CleanTemplate(ctx, cp, np.float32, P).instantiate(q, ip)
+    fn.ensure_all_bound()
+    fn.buffer('dirty').set(q, dirty)
+    fn.buffer('psf').set(q, psf)
+    fn.buffer('model').zero(q)
+    fn.reset()
+    fn.run_cycles(patch, 0.0, cycles, collect=False)
+    values, pos, pix = fn._collect_cycle_arrays()
+    assert len(log) == len(values) == cycles
+    assert np.all(log['scale'] == 0)
+    np.testing.assert_array_equal(log['peak'], values)
+    np.testing.assert_array_equal(np.stack([log['y'], log['x']], axis=1), pos)
+    assert pix.shape == (cycles, P)
+    np.testing.assert_array_equal(log['flux'], pix)
+    np.testing.assert_array_equal(op.buffer('dirty').get(q), fn.buffer('dirty').get(q))
+    np.testing.assert_array_equal(op.buffer('model').get(q), fn.buffer('model').get(q))
+    tmax, tpos = op.tile_records()
+    np.testing.assert_array_equal(tmax[0], fn.buffer('tile_max').get(q))
+    np.testing.assert_array_equal(tpos[0], fn.buffer('tile_pos').get(q))
+    same_log(log, twin.run_cycles(patch, 0.0, cycles))
 
 
 # ---- the imager and the driver -------------------------------------------------------------------------

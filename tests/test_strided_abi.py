@@ -85,7 +85,7 @@ LAYOUTS = {
     'r3': (dict(rpad=3, vpad=2, origin=(0, 0)), dict(rpad=7, vpad=2, origin=(1, 1))),
     'r7_origin': (dict(rpad=7, vpad=2, origin=(1, 1)), dict(rpad=3, vpad=2, origin=(0, 0))),
 }
-SHAPES = [(300, 302, 1), (300, 302, 3), (300, 302, 4), (6, 10, 3)]
+SHAPES = [(300, 302, 1), (300, 302, 3), (300, 302, 4), (6, 10, 3), (6, 10, 2)]
 
 layouts = pytest.mark.parametrize('layout', list(LAYOUTS))
 shapes = pytest.mark.parametrize('H,W,P', SHAPES)
@@ -684,7 +684,7 @@ def test_image_nansum(H, W, P, layout):
 
 @gpu
 @layouts
-@pytest.mark.parametrize('H,W,P', [(300, 302, 1), (300, 302, 4), (6, 10, 3)])
+@pytest.mark.parametrize('H,W,P', [(300, 302, 1), (300, 302, 4), (6, 10, 3), (6, 10, 2)])
 def test_psf_patch(H, W, P, layout):
     """orc.psf_patch, exact, with and without a limit, on a non-square PSF; the pixels that
     decide the box sit in different polarizations."""

@@ -32,7 +32,7 @@ IMAGE_SIZE = 0.02           # cells 50 wavelengths apart
 
 SHAPES = [(2, 2), (6, 10), (254, 4), (258, 6), (64, 64), (2, 4100), (520, 1030)]      # (W, H)
 shapes = pytest.mark.parametrize('W,H', SHAPES)
-pols = pytest.mark.parametrize('P', [1, 2, 4])
+pols = pytest.mark.parametrize('P', [1, 2, 3, 4])
 ROBUST = (5 * 10 ** -0.5) ** 2
 
 
