@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libkimg.so')
 
-SOURCES = ['api.hip', 'grid.hip', 'grid_mfma.hip', 'grid_fold.hip', 'grid_binned.hip', 'degrid_mfma.hip', 'image.hip', 'fft.hip', 'weight.hip',
+SOURCES = ['api.hip', 'grid.hip', 'grid_mfma.hip', 'grid_fold.hip', 'grid_binned.hip', 'degrid_mfma.hip', 'image.hip', 'transform.hip', 'fft.hip', 'weight.hip',
            'clean.hip', 'clean_multi.hip', 'preprocess.hip', 'ktable.hip', 'store.hip',
            'grid_f64.hip', 'mask.hip', 'clean_scales.hip', 'contsub.hip', 'phaseshift.hip']
 
