@@ -6,6 +6,7 @@ store -> imaging weights, PSF, major/minor cycles -> restored image, all on one 
     python examples/image_channel.py --uvcontsub 1:6-9      (a 16-channel band; see uvcontsub_band)
     python examples/image_channel.py --phase-shift=-120,60  (a small field around a source; see phase_shift_field)
     python examples/image_channel.py --uv-taper 30,20,30 --uv-range 0,3000  (see uv_taper_channel)
+    python examples/image_channel.py --primary-beam 0.3     (see primary_beam_channel)
 
 It follows the reference's per-channel flow (frontend.py:31-83 preprocess_visibilities,
 :465-658 process_channel) with the loaders and FITS output left out: the sky is three point
@@ -214,6 +215,85 @@ def uv_taper_channel(args):
     return results
 
 
+def primary_beam_channel(args):
+    """--primary-beam FWHM_DEG[,CUTOFF]: the three-source channel as an antenna with a cosine-taper
+    beam of that width would see it -- every source attenuated by the beam power at its place --
+    imaged twice from the same resident store, without and with ``primary_beam=``; prints the
+    restored flux of every source before and after the correction next to its true value.  With
+    --output the corrected image and the beam are written."""
+    import torch
+    import scipy.optimize       # noqa: F401
+    import synth
+    from katsdpimager_amd import accel, beam, frontend, imaging, parameters, preprocess, primary_beam, weight
+    fwhm_deg, _, cutoff = args.primary_beam.partition(',')
+    fwhm = math.sin(math.radians(float(fwhm_deg)))
+    ctx = accel.create_some_context()
+    queue = ctx.create_command_queue()
+    obs = synth.make_observation(args.pixels, args.vis, args.w_planes, 1, device=ctx.device)
+    image_p, grid_p, array_p = synth.make_parameters(obs, 1, args.kernel_width, degrid=True)
+    frequency = primary_beam.SPEED_OF_LIGHT / image_p.wavelength
+    corner = math.sqrt(0.5) * image_p.image_size
+    model = primary_beam.RadialBeam.cosine_taper(
+        fwhm, frequency, [0.9 * frequency, 1.1 * frequency], fwhm / 256.0, min(corner, 2.0 * fwhm))
+    params = primary_beam.PrimaryBeamParameters(model, float(cutoff) if cutoff else 0.1)
+    G = args.pixels
+    lm_scale, lm_bias = image_p.pixel_size, -0.5 * G * image_p.pixel_size
+    sources = [((40, -25), 1.0), ((-120, 60), 0.5), ((15, 200), 0.25)]      # (l, m) in pixels, Jy
+    # the beam on the pixel grid, as the device samples it
+    beam_image = primary_beam.sample_host(model.row(frequency), model.step, G, G, lm_scale, lm_bias)
+    uvw_wl = obs.uvw.to(torch.float64) / obs.wavelength
+    vis = torch.zeros(obs.n_vis, dtype=torch.complex128, device=ctx.device)
+    for (lp, mp), flux in sources:
+        l, m = lp * obs.pixel_size, mp * obs.pixel_size
+        n = math.sqrt(1 - l * l - m * m)
+        power = float(beam_image[G // 2 + mp, G // 2 + lp])
+        vis += flux * power / n * torch.exp(
+            -2j * math.pi * (uvw_wl[:, 0] * l + uvw_wl[:, 1] * m + uvw_wl[:, 2] * (n - 1)))
+    vis = vis.to(torch.complex64)[None, :, None].contiguous()
+    weights = torch.ones((1, obs.n_vis, 1), dtype=torch.float32, device=ctx.device)
+    torch.cuda.synchronize()
+    collector = preprocess.VisibilityCollectorDevice(queue, [image_p], [grid_p], args.vis_block)
+    collector.add(accel.DeviceArray(ctx, (obs.n_vis, 3), np.float32, tensor=obs.uvw),
+                  accel.DeviceArray(ctx, weights.shape, np.float32, tensor=weights),
+                  accel.DeviceArray(ctx, vis.shape, np.complex64, tensor=vis),
+                  None, None, np.ones((1, 1), np.complex64), None)
+    collector.close()
+    reader = collector.reader()
+    weight_p = parameters.WeightParameters(weight.WeightType.ROBUST, 0.0)
+    clean_p = parameters.CleanParameters(args.minor, 0.1, 0.85, 5.0, 0, 0.01, 0.5, 0.02)
+    template = imaging.ImagingTemplate(ctx, array_p, image_p.fixed, weight_p, grid_p.fixed, clean_p)
+    imager = template.instantiate(queue, image_p, grid_p, args.vis_block, 0, args.major, streams=2)
+    imager.ensure_all_bound()
+    print('field {:.3f} deg across, beam FWHM {:.3f} deg at {:.1f} MHz, cutoff {}'.format(
+        math.degrees(image_p.image_size), float(fwhm_deg), frequency / 1e6, params.cutoff))
+    peaks = {}
+    for label, keyword in (('before', None), ('after', params)):
+        stats = frontend.process_channel(reader, 0, imager, image_p, grid_p, clean_p,
+                                         weight_p.weight_type, args.vis_block, args.major, True,
+                                         fit_beam=True, primary_beam=keyword)
+        beam.restore(imager, stats['restoring_beam'])
+        restored = imager.get_buffer('dirty')
+        for (lp, mp), flux in sources:
+            y, x = G // 2 + mp, G // 2 + lp
+            peaks[label, lp, mp] = float(np.nanmax(restored[0, y - 3:y + 4, x - 3:x + 4]))
+    print('pixels kept (beam power >= {}): {} of {}'.format(params.cutoff, stats['beam_valid'], G * G))
+    for (lp, mp), flux in sources:
+        print('source at (l, m) = ({:5d}, {:5d}) px, true {:.2f} Jy, beam power {:.3f}: restored peak '
+              '{:.3f} before, {:.3f} after the correction'.format(
+                  lp, mp, flux, float(beam_image[G // 2 + mp, G // 2 + lp]), peaks['before', lp, mp],
+                  peaks['after', lp, mp]))
+    if args.output:
+        from katsdpimager_amd import io, polarization
+        image_p.fixed.polarizations = [polarization.STOKES_I]
+        centre = (0.0, math.radians(-45.0))
+        io.write_fits_image(restored, image_p, args.output, 0, centre, beam=stats['restoring_beam'])
+        beam_name = os.path.splitext(args.output)[0] + '_primary_beam.fits'
+        io.write_fits_image(stats['beam_power'].get(queue)[np.newaxis], image_p, beam_name, 0, centre,
+                            bunit='')
+        print('wrote', args.output, 'and', beam_name)
+    return peaks
+
+
 def _frequencies(obs, channels):
     return 299792458.0 / obs.wavelength + 1.0e5 * np.arange(channels)
 
@@ -248,9 +328,15 @@ def main(argv=None):
                     help='instead of the one image: image the channel without and with a Gaussian uv taper '
                          'that alone would give a beam of this FWHM (major, minor, position angle), and print '
                          'the fitted beams and normalized noise, e.g. --uv-taper 30,20,30')
+    ap.add_argument('--primary-beam', metavar='FWHM_DEG[,CUTOFF]',
+                    help='instead of the one image: attenuate the sources by a cosine-taper primary beam of this '
+                         'FWHM, image the channel without and with the primary-beam correction (blanking below '
+                         'CUTOFF, default 0.1) and print every source\'s flux before and after, e.g. --primary-beam 0.3 (the default field is 1.2 degrees across)')
     ap.add_argument('--uv-range', metavar='MIN,MAX',
                     help='with or without --uv-taper: keep only the cells between these radii (wavelengths)')
     args = ap.parse_args(argv)
+    if args.primary_beam:
+        return primary_beam_channel(args)
     if args.uv_taper or args.uv_range:
         return uv_taper_channel(args)
     if args.uvcontsub:

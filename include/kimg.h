@@ -1012,6 +1012,47 @@ int kimg_phase_shift(void *vis, int64_t vis_channel_pitch, int num_channels, int
                      int num_polarizations, const float *uvw_in, float *uvw_out,
                      const double *inv_wavelength, const double *params12_host, void *stream);
 
+/* ---- Primary-beam correction: frontend.py:587-608 + primary_beam.py (_sample_impl) of the reference,
+ * whose host samples the beam with numba, uploads it and runs apply_primary_beam twice.  Here one
+ * pass samples a radially symmetric beam model on the pixel grid and divides the model and the
+ * residual image by its power.  katsdpimager_amd/primary_beam.py holds the contract once more as
+ * numpy (sample_host, correct_host); the device agrees with it bit for bit (the NaN set included).
+ *
+ * row: DEVICE float32 [num_samples], the voltage pattern at radius i / inv_step (sine projection) at
+ *   the channel's frequency; 2 <= num_samples <= KIMG_PRIMARY_BEAM_MAX_SAMPLES.  inv_step = the
+ *   float32 nearest to 1 / step, formed by the caller, above 0.
+ * Per pixel (x, y), in float32 with one rounding per operation (no fused multiply-add):
+ *   l = (float) x * lm_scale + lm_bias,  m = (float) y * lm_scale + lm_bias   (kimg_layer_to_image's)
+ *   s = sqrt(l * l + m * m) * inv_step
+ *   s < num_samples - 1:  pos = (int) s, frac = s - pos,
+ *                         v = row[pos] + (row[pos + 1] - row[pos]) * frac,  power = v * v
+ *   otherwise (beyond the last sample, or s NaN):  power = NaN
+ *   beam_power[y][x] = power                              (beam_power may be NULL: nothing stored)
+ *   keep = power >= threshold                             (false for a NaN power)
+ *   model[p][y][x] = keep ? model[p][y][x] / power : 0    for every polarization p
+ *   dirty[p][y][x] = keep ? dirty[p][y][x] / power : NaN
+ * A NaN beam blanks the model to 0 where kimg_apply_primary_beam on a NaN beam would leave NaN in
+ * it (a NaN in the model spreads over the whole image in the restore step's transform); everywhere
+ * else the pass equals sampling followed by kimg_apply_primary_beam on model (replacement 0) and
+ * dirty (replacement NaN).
+ * model and dirty: float32 [P][height][width] with the same row_pitch and pol_pitch (elements), both
+ *   given or both NULL (NULL: sample only; beam_power is then required).  They and beam_power must
+ *   not overlap.  Elements of the padding are neither read nor written.  Rows that start on 16-byte
+ *   boundaries (pointers 16-byte aligned, pitches multiples of 4) move 16 bytes per lane; anything
+ *   else is taken element by element, with the same results.
+ * KIMG_EINVAL, before any HIP call: a null row; width or height below 1; num_polarizations outside
+ *   1..4 (checked with or without images); num_samples outside 2..KIMG_PRIMARY_BEAM_MAX_SAMPLES;
+ *   inv_step not above 0; one image without the other; neither images nor beam_power; a row pitch of
+ *   a given array below the width; with P > 1, pol_pitch below (height - 1) * row_pitch + width.
+ * Asynchronous on `stream`, no allocation, capturable; equal inputs give equal bits.  Traffic: 4
+ *   bytes per pixel for the beam and 16 per pixel and polarization for the images. */
+#define KIMG_PRIMARY_BEAM_MAX_SAMPLES 4096
+int kimg_primary_beam(float *beam_power, int64_t beam_row_pitch,
+                      float *model, float *dirty, int64_t row_pitch, int64_t pol_pitch,
+                      int width, int height, int num_polarizations,
+                      const float *row, int num_samples, float inv_step,
+                      float lm_scale, float lm_bias, float threshold, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,9 @@ PROTOTYPES = {
     'kimg_uvcontsub': (c_int, [P, L, P, L, I, L, P, P, I, P, P]),
     # phase-centre shift
     'kimg_phase_shift': (c_int, [P, L, I, L, I, P, P, P, P, P]),
+    # primary-beam correction: (beam_power, pitch), (model, dirty, pitches), the shape, (row,
+    # num_samples, inv_step), lm_scale, lm_bias, threshold
+    'kimg_primary_beam': (c_int, [P, L, P, P, L, L, I, I, I, P, I, F, F, F, F, P]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
@@ -139,6 +142,7 @@ class CleanChannel(ctypes.Structure):
 
 
 CLEAN_BATCH_MAX = 8     # KIMG_CLEAN_BATCH_MAX
+PRIMARY_BEAM_MAX_SAMPLES = 4096     # KIMG_PRIMARY_BEAM_MAX_SAMPLES
 
 
 class UVTaper(ctypes.Structure):

@@ -13,6 +13,7 @@ reference's ``iter_slice`` works through the façade's host setters.
 import numpy as np
 
 from . import clean, trace, weight
+from .primary_beam import SPEED_OF_LIGHT
 
 
 def _device_reader(reader):
@@ -81,7 +82,7 @@ def slice_mid_w(image_p, grid_p):
 def process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type,
                     vis_block, major, degrid, subtract_model=False, batched_clean=True,
                     fit_beam=False, clean_batcher=None, multiscale=None, clean_mask=None,
-                    uv_taper=None, auto_mask=None):
+                    uv_taper=None, primary_beam=None, auto_mask=None):
     """The loop of frontend.process_channel (frontend.py:497-585) from "Compute imaging
     weights" to the end of the last major cycle.
 
@@ -127,7 +128,32 @@ def process_channel(reader, rel_channel, imager, image_p, grid_p, clean_p, weigh
     result has ``uv_taper``, the taper the weights were made with (None: none).  ``uv_taper`` here
     states the taper the channel is meant to get: an imager made with another one is refused, as one
     made for another ``image_size`` is.  None (the default) takes the imager's.
+
+    ``primary_beam`` (:class:`primary_beam.PrimaryBeamParameters`) ends the channel as the reference
+    does (frontend.py:587-608): after the last major cycle the beam model is sampled on the pixel
+    grid at the channel's frequency (from ``image_p.wavelength``) and the model and dirty images are
+    divided by its power, in one pass on the device (``Imaging.primary_beam_correct``); below the
+    cutoff, and where the model has no value, the model becomes 0 and the dirty image NaN.  The
+    result then has ``primary_beam`` (the parameters), ``beam_power`` -- the imager's device array,
+    as :func:`find_peak` takes it -- and ``beam_valid``, the number of pixels kept.  None (the
+    default) changes nothing.
     """
+    out = _process_channel_scales(reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type,
+                                  vis_block, major, degrid, subtract_model, batched_clean, fit_beam,
+                                  clean_batcher, multiscale, clean_mask, uv_taper, auto_mask)
+    if primary_beam is not None and out is not None:
+        with trace.range('primary_beam'):
+            frequency = SPEED_OF_LIGHT / float(image_p.wavelength)
+            out['primary_beam'] = primary_beam
+            out['beam_power'] = imager.primary_beam_correct(primary_beam, frequency)
+            out['beam_valid'] = imager.beam_valid(primary_beam.cutoff)
+    return out
+
+
+def _process_channel_scales(reader, rel_channel, imager, image_p, grid_p, clean_p, weight_type,
+                            vis_block, major, degrid, subtract_model, batched_clean, fit_beam,
+                            clean_batcher, multiscale, clean_mask, uv_taper, auto_mask):
+    """:func:`process_channel` up to the end of the last major cycle."""
     if uv_taper is not None and uv_taper != getattr(imager, 'uv_taper', None):
         raise ValueError('the imager was made for uv taper {!r}, the channel asks for {!r}'.format(
             getattr(imager, 'uv_taper', None), uv_taper))

@@ -16,7 +16,7 @@ import functools
 
 import numpy as np
 
-from . import accel, clean, grid, image, mask, multiscale, predict, types, weight
+from . import accel, clean, grid, image, mask, multiscale, predict, primary_beam, types, weight
 
 
 class ImagingTemplate:
@@ -54,6 +54,7 @@ class ImagingTemplate:
         self.scale = image.ScaleTemplate(context, dtype, num_pols)
         self.add_image = image.AddImageTemplate(context, dtype, num_pols)
         self.apply_primary_beam = image.ApplyPrimaryBeamTemplate(context, dtype, num_pols)
+        self.primary_beam = primary_beam.PrimaryBeamTemplate(context, dtype, num_pols)
         self.degridder = grid.DegridderTemplate(
             context, fixed_image_parameters, fixed_grid_parameters, tuning.get('degridder')) \
             if fixed_grid_parameters.degrid else None
@@ -209,6 +210,9 @@ class Imaging(accel.OperationSequence):
             command_queue, image_shape, 0.0, 0.0, allocator)
         self._apply_primary_beam_dirty = template.apply_primary_beam.instantiate(
             command_queue, image_shape, 0.0, np.nan, allocator)
+        self._primary_beam = template.primary_beam.instantiate(command_queue, image_shape, allocator)
+        self._primary_beam.lm_scale = lm_scale
+        self._primary_beam.lm_bias = lm_bias
 
         context = template.context
         taper1d = accel.DeviceArray(context, (pixels,), image_parameters.fixed.real_dtype)
@@ -244,7 +248,8 @@ class Imaging(accel.OperationSequence):
             ('noise_est', self._noise_est), ('clean', self._clean), ('scale', self._scale),
             ('add_image', self._add_image),
             ('apply_primary_beam_model', self._apply_primary_beam_model),
-            ('apply_primary_beam_dirty', self._apply_primary_beam_dirty)]
+            ('apply_primary_beam_dirty', self._apply_primary_beam_dirty),
+            ('primary_beam', self._primary_beam)]
         # buffer names of imaging.py:185-209
         compounds = {
             'weights': ['predict:weights', 'continuum_predict:weights'],
@@ -255,14 +260,15 @@ class Imaging(accel.OperationSequence):
             'grid': ['gridder:grid', 'grid_to_image:grid'],
             'layer': ['grid_to_image:layer'],
             'dirty': ['grid_to_image:image', 'noise_est:dirty', 'clean:dirty', 'scale:data',
-                      'add_image:dest', 'apply_primary_beam_dirty:data'],
-            'model': ['clean:model', 'apply_primary_beam_model:data', 'add_image:src'],
+                      'add_image:dest', 'apply_primary_beam_dirty:data', 'primary_beam:dirty'],
+            'model': ['clean:model', 'apply_primary_beam_model:data', 'add_image:src',
+                      'primary_beam:model'],
             'psf': ['clean:psf', 'psf_patch:psf'],
             'tile_max': ['clean:tile_max'], 'tile_pos': ['clean:tile_pos'],
             'peak_value': ['clean:peak_value'], 'peak_pos': ['clean:peak_pos'],
             'peak_pixel': ['clean:peak_pixel'],
             'beam_power': ['apply_primary_beam_model:beam_power',
-                           'apply_primary_beam_dirty:beam_power'],
+                           'apply_primary_beam_dirty:beam_power', 'primary_beam:beam_power'],
         }
         if 'uv' in self._weights.slots:
             compounds['weights'].insert(0, 'weights:weights')
@@ -624,6 +630,43 @@ class Imaging(accel.OperationSequence):
         self._apply_primary_beam_model()
         self._apply_primary_beam_dirty.threshold = threshold
         self._apply_primary_beam_dirty()
+
+    @_serial
+    def primary_beam_correct(self, params, frequency):
+        """Sample the beam model of ``params`` (:class:`primary_beam.PrimaryBeamParameters`) at
+        ``frequency`` (Hz) on the pixel grid and divide the model and dirty images by its power, in
+        one pass (``kimg_primary_beam``): the model's row for the frequency is all that travels to
+        the device.  Below ``params.cutoff``, and where the model has no value (beyond its last
+        sample, or at a frequency outside its range), the model becomes 0 and the dirty image NaN.
+        Returns the ``beam_power`` device array, as :func:`frontend.find_peak` takes it."""
+        self._ready()
+        op = self._primary_beam
+        op.set_model_row(params.model.row(frequency), params.model.step)
+        op.threshold = params.cutoff
+        op()
+        return self.buffer('beam_power')
+
+    @_serial
+    def beam_valid(self, cutoff):
+        """How many pixels of ``beam_power`` are at least ``cutoff`` (NaNs never are): the pixels
+        :meth:`primary_beam_correct` kept.  Counted on the device."""
+        from ._lib import lib, check
+        self._ready(keep_cleared=True)
+        beam = self.buffer('beam_power')
+        H, W = beam.shape
+        out = accel.DeviceArray(self.template.context, (2,), np.uint32, queue=self.command_queue)
+        below = np.nextafter(np.float32(cutoff), np.float32(-np.inf))
+        counts = []
+        # |power| <= value: everything that is not NaN, then what lies below the cutoff
+        for value in (np.float32(np.inf), below):
+            if value < 0:
+                counts.append(0)
+                continue
+            rc = lib().kimg_abs_count_le(beam.ptr, W, H * W, W, H, 1, 0, float(value), out.ptr,
+                                         self.command_queue.handle)
+            check(rc, 'kimg_abs_count_le')
+            counts.append(int(out.get(self.command_queue)[0]))
+        return counts[0] - counts[1]
 
     @_serial
     def dirty_to_psf(self):
