@@ -7,6 +7,7 @@ store -> imaging weights, PSF, major/minor cycles -> restored image, all on one 
     python examples/image_channel.py --phase-shift=-120,60  (a small field around a source; see phase_shift_field)
     python examples/image_channel.py --uv-taper 30,20,30 --uv-range 0,3000  (see uv_taper_channel)
     python examples/image_channel.py --primary-beam 0.3     (see primary_beam_channel)
+    python examples/image_channel.py --spectral hanning,2   (a band with a one-channel line; see spectral_line)
 
 It follows the reference's per-channel flow (frontend.py:31-83 preprocess_visibilities,
 :465-658 process_channel) with the loaders and FITS output left out: the sky is three point
@@ -294,6 +295,77 @@ def primary_beam_channel(args):
     return peaks
 
 
+def spectral_line(args):
+    """--spectral hanning[,N]: a synthetic band of 8 N channels with a 1 Jy line source in ONE input
+    channel, through ``loader.preprocess_visibilities`` without and with ``spectral=`` Hanning
+    smoothing (then N channels averaged to one); prints the dirty peak of the line in every output
+    channel it reaches next to the share of the input the filter's coefficients predict (1/4, 1/2, 1/4
+    for plain Hanning), and checks that the other output channels are empty."""
+    import synth
+    from katsdpimager_amd import accel, frontend, imaging, loader, parameters, preprocess, spectral, weight
+    name, _, n = args.spectral.partition(',')
+    if name != 'hanning':
+        raise SystemExit('--spectral takes hanning or hanning,N')
+    params = spectral.SpectralParameters.hanning(bin=int(n) if n else 1)
+    C = 8 * params.bin
+    C_out = params.output_channels(C)
+    line_channel = 4 * params.bin
+    g, offset, step = params.coefficients()
+    expected = np.zeros(C_out)
+    for o in range(C_out):
+        i = line_channel - (o * step - offset)
+        if 0 <= i < len(g):
+            expected[o] = g[i] / g.sum()
+    ctx = accel.create_some_context()
+    queue = ctx.create_command_queue()
+    rows = max(args.vis // C, 1000)
+    obs = synth.make_observation(args.pixels, rows, args.w_planes, 1, device='cpu')
+    image_p, grid_p, array_p = synth.make_parameters(obs, 1, args.kernel_width, degrid=True)
+    uvw = obs.uvw.numpy()
+    uvw_wl = uvw.astype(np.float64) / obs.wavelength
+    l, m = 40 * obs.pixel_size, -25 * obs.pixel_size
+    nn = math.sqrt(1 - l * l - m * m)
+    vis = np.zeros((rows, C, 1), np.complex64)
+    vis[:, line_channel, 0] = np.exp(
+        -2j * np.pi * (uvw_wl[:, 0] * l + uvw_wl[:, 1] * m + uvw_wl[:, 2] * (nn - 1))) / nn
+    dataset = loader.LoaderArrays(uvw, vis, np.ones((rows, C, 1), np.float32), np.zeros(rows, np.int32),
+                                  _frequencies(obs, C), [0])
+    weight_p = parameters.WeightParameters(weight.WeightType.ROBUST, 0.0)
+    clean_p = parameters.CleanParameters(args.minor, 0.1, 0.85, 5.0, 0, 0.01, 0.5, 0.02)
+    template = imaging.ImagingTemplate(ctx, array_p, image_p.fixed, weight_p, grid_p.fixed, clean_p)
+    imager = template.instantiate(queue, image_p, grid_p, args.vis_block, 0, 1, streams=2)
+    imager.ensure_all_bound()
+    imager.one_call_major_cycles = False        # (only the first peak of each dirty image is wanted)
+    ident = np.ones((1, 1), np.complex64)
+
+    def dirty_peak(collector, channel):
+        stats = frontend.process_channel(collector.reader(), channel, imager, image_p, grid_p, clean_p,
+                                         weight_p.weight_type, args.vis_block, 1, True)
+        return float(stats['peaks'][0])
+    raw = preprocess.VisibilityCollectorDevice(queue, [image_p] * C, [grid_p] * C, args.vis_block)
+    loader.preprocess_visibilities(dataset, raw, 0, C, (ident, None))
+    peak_in = dirty_peak(raw, line_channel)
+    filtered = preprocess.VisibilityCollectorDevice(queue, [image_p] * C_out, [grid_p] * C_out, args.vis_block)
+    loader.preprocess_visibilities(dataset, filtered, 0, C, (ident, None), spectral=params)
+    print('{}: {} channels to {}; {} output samples kept, {} flagged'.format(
+        params, C, C_out, *filtered.spectral_counts))
+    print('input channel {:2d}: dirty peak {:.6f}'.format(line_channel, peak_in))
+    reader = filtered.reader()
+    peaks = {'input': peak_in}
+    for o in range(C_out):
+        if expected[o] > 0:
+            peaks[o] = dirty_peak(filtered, o)
+            print('output channel {:2d}: dirty peak {:.6f} = {:.6f} of the input (coefficients: {:.6f})'.format(
+                o, peaks[o], peaks[o] / peak_in, expected[o]))
+        else:
+            largest = max((float(np.abs(piece['vis']).max()) for s in range(reader.num_w_slices(o))
+                           for piece in reader.iter_slice(o, s, None)), default=0.0)
+            peaks[o] = largest
+            print('output channel {:2d}: largest |vis| {:g}'.format(o, largest))
+    peaks['expected'] = expected
+    return peaks
+
+
 def _frequencies(obs, channels):
     return 299792458.0 / obs.wavelength + 1.0e5 * np.arange(channels)
 
@@ -334,7 +406,13 @@ def main(argv=None):
                          'CUTOFF, default 0.1) and print every source\'s flux before and after, e.g. --primary-beam 0.3 (the default field is 1.2 degrees across)')
     ap.add_argument('--uv-range', metavar='MIN,MAX',
                     help='with or without --uv-taper: keep only the cells between these radii (wavelengths)')
+    ap.add_argument('--spectral', metavar='hanning[,N]',
+                    help='instead of the three-source channel: Hanning-smooth (and average N channels to one) a '
+                         'synthetic band with a line in one channel, and print the line\'s dirty peak in every '
+                         'output channel')
     args = ap.parse_args(argv)
+    if args.spectral:
+        return spectral_line(args)
     if args.primary_beam:
         return primary_beam_channel(args)
     if args.uv_taper or args.uv_range:

@@ -1053,6 +1053,63 @@ int kimg_primary_beam(float *beam_power, int64_t beam_row_pitch,
                       const float *row, int num_samples, float inv_step,
                       float lm_scale, float lm_bias, float threshold, void *stream);
 
+/* ---- Spectral filter (spectral.hip): Hanning smoothing and channel averaging of a block of RAW
+ * visibilities, ahead of kimg_uvcontsub and kimg_preprocess_convert and after kimg_phase_shift (CASA
+ * hanningsmooth and mstransform(chanaverage=True) / split(width=n), MIRIAD hanning).  One operator: a
+ * short non-negative FIR along the channel axis followed by a decimation, weighted and aware of
+ * flags.  The reference has none; the semantics are this library's, and
+ * katsdpimager_amd/spectral.py holds them once more as numpy (filter_host).
+ *
+ * Parameters (the Python side): taps, K float64 values, K odd, 1 <= K <= KIMG_SPECTRAL_MAX_TAPS,
+ *   finite and >= 0, the centre tap h = K / 2 above 0; bin n, 1 <= n <= KIMG_SPECTRAL_MAX_BIN.  The
+ *   host forms, in float64, the combined filter g = taps (*) ones(n), a full convolution of length
+ *   L = K + n - 1 <= 72, and passes it as coeff_host with length = L, offset = h and step = n.
+ * coeff_host: HOST float64 [length].  It is read during the call and travels to the kernel by value,
+ *   so a captured call keeps its coefficients and the array may be freed on return.
+ * vis_in: complex64 [C_in][N][Q], weights_in: float32 [C_in][N][Q], the loader's block layout; vis_out
+ *   and weights_out: the same with C_out = num_channels_out channels, C_out * step <= C_in (the Python
+ *   side takes C_out = C_in / n, rounded down; the trailing C_in % n channels enter only through the
+ *   smoothing taps).  The inner [N][Q] plane is dense (plane_elements = N * Q); each of the four arrays
+ *   has its own channel pitch in elements of the array, at least plane_elements.  Elements of the
+ *   padding are neither read nor written, and the inputs are not written at all.  The operation is
+ *   out of place: no output may start inside an input.  Indices are 64-bit throughout.
+ * For every element (n, q) and output channel o, all in float64:
+ *   input i of the window is channel c = o * step - offset + i, i = 0 .. length - 1.  It is usable
+ *   iff 0 <= c < C_in, weights_in[c][n][q] > 0 and both parts of vis_in[c][n][q] are finite (the rule
+ *   of kimg_uvcontsub).  Over the usable inputs in ascending i, with w and v the input's weight and
+ *   visibility (w * v is exact in float64):
+ *     cov = sum g_i,  S1 = sum (g_i * w),  S2 = sum g_i * (g_i * w),  N = sum g_i * (w * v)
+ *   cov >= min_sum: the sample is kept,
+ *     vis_out[o][n][q] = complex64(N / S1), each part rounded to float32 once (the device multiplies
+ *     by 1 / S1, formed once: within 2^-52 of the quotient before that rounding);
+ *     weights_out[o][n][q] = float32((S1 * S1) / S2), the inverse variance of the weighted mean of
+ *     independent channels of variance 1 / w: sum w for plain averaging, w / 0.375 for Hanning on
+ *     equal weights.
+ *   otherwise it is flagged: vis_out = 0 and weights_out = 0 (preprocessing drops zero weights).
+ *   min_sum: the host's min_coverage * (sum of all g_i), in float64; min_coverage in (0, 1].  The
+ *   sums run in the stated order, so the kept set is the numpy statement's for any taps.
+ * counts: DEVICE uint64 [2]: the number of kept and of flagged output samples of the call are ADDED
+ *   to it (one atomic add per wave and counter); the caller zeroes it.
+ * Returns, before any HIP call: KIMG_EINVAL for a null pointer; for length < 1, step < 1 or offset
+ *   outside [0, length); then KIMG_EUNSUPPORTED for length > 72 or step > KIMG_SPECTRAL_MAX_BIN; then
+ *   KIMG_EINVAL for a negative or non-finite coefficient, a min_sum that is not finite or not above
+ *   0, num_channels_out < 1 or num_channels_out * step > num_channels_in, a negative plane_elements
+ *   or a pitch below it; KIMG_EUNSUPPORTED for a plane beyond the grid limit (2^31 - 1 workgroups of
+ *   256 elements) or more than 65535 * 64 output channels; KIMG_EINVAL for an output that starts
+ *   inside an input.  plane_elements = 0 is then a successful call that does nothing.
+ * Asynchronous on `stream`, no allocation, capturable; equal inputs give equal bits.  Traffic: 12
+ *   bytes per element and input channel, 12 per element and output channel (Hanning and pure
+ *   averaging read every input once; a smoothing filter with step > 1 re-reads the K - 1 channels
+ *   neighbouring windows share, through the cache). */
+#define KIMG_SPECTRAL_MAX_TAPS 9
+#define KIMG_SPECTRAL_MAX_BIN 64
+int kimg_spectral_filter(const void *vis_in, int64_t vis_in_channel_pitch, const float *weights_in,
+                         int64_t weights_in_channel_pitch, int num_channels_in, void *vis_out,
+                         int64_t vis_out_channel_pitch, float *weights_out,
+                         int64_t weights_out_channel_pitch, int num_channels_out,
+                         int64_t plane_elements, const double *coeff_host, int length, int offset,
+                         int step, double min_sum, uint64_t *counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,9 @@ PROTOTYPES = {
     # primary-beam correction: (beam_power, pitch), (model, dirty, pitches), the shape, (row,
     # num_samples, inv_step), lm_scale, lm_bias, threshold
     'kimg_primary_beam': (c_int, [P, L, P, P, L, L, I, I, I, P, I, F, F, F, F, P]),
+    # spectral filter: (vis_in, pitch, weights_in, pitch, C_in), (vis_out, pitch, weights_out, pitch,
+    # C_out), plane_elements, (coeff_host, length, offset, step), min_sum, counts, stream
+    'kimg_spectral_filter': (c_int, [P, L, P, L, I, P, L, P, L, I, L, P, I, I, I, D, P, P]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),

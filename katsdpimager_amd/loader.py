@@ -166,7 +166,7 @@ def data_iter(dataset, vis_limit, vis_load, start_channel, stop_channel):
 
 def preprocess_visibilities(dataset, collector, start_channel, stop_channel, polarization_matrices,
                             vis_load=32 * 1048576, vis_limit=None, continuum=None,
-                            phase_centre=None, continuum_centre=None):
+                            phase_centre=None, continuum_centre=None, spectral=None):
     """frontend.preprocess_visibilities (frontend.py:40-84): feed every block of the loader, in
     loader order, to ``collector.add`` (a :class:`~.preprocess.VisibilityCollectorDevice`; its
     conversion and compression kernels run asynchronously on its queue, which plays the role of
@@ -179,9 +179,9 @@ def preprocess_visibilities(dataset, collector, start_channel, stop_channel, pol
     device once, a polynomial is fitted across the line-free channels of every sample and subtracted
     (``continuum.UVContSub`` on the collector's queue), and the collector is handed the device
     arrays.  The mask (and the frequencies, if given) span the loaded channels
-    ``start_channel:stop_channel``.  The collector then has ``continuum_counts``: the samples
-    (fitted, flagged for want of line-free channels) over all blocks.  None (the default) changes
-    nothing.
+    ``start_channel:stop_channel`` -- with ``spectral``, the OUTPUT channels of the filter.  The
+    collector then has ``continuum_counts``: the samples (fitted, flagged for want of line-free
+    channels) over all blocks.  None (the default) changes nothing.
 
     ``phase_centre`` = (ra, dec) in radians (new here) images around another direction T than the
     dataset's ``phase_centre()`` O: every block goes to the device once, its visibilities are
@@ -192,14 +192,29 @@ def preprocess_visibilities(dataset, collector, start_channel, stop_channel, pol
     only O -> S, the fit, then S -> T on the block's original uvw (T defaults to O, and then no
     coordinates are written); coordinates are never rotated twice.  Either way the collector gets
     ``phase_centre`` = T, for whoever writes the image header.  Feed angles pass unchanged, which is
-    valid for shifts small against a radian.  With neither keyword the function is what it was."""
+    valid for shifts small against a radian.
+
+    ``spectral`` (:class:`~.spectral.SpectralParameters`; new here) smooths and averages the channel
+    axis of every block on the device (``spectral.SpectralFilter`` on the collector's queue): per
+    block the order is the phase shift, if any; the spectral filter; the continuum fit, if any.  The
+    loaded channels ``start_channel:stop_channel`` are the filter's input; the collector must have
+    been made for its ``spectral.output_channels(stop_channel - start_channel)`` output channels,
+    with image and grid parameters of ``spectral.output_frequencies`` (ValueError otherwise, before
+    any block is read), and gets ``spectral_counts``: the output samples (kept, flagged for want of
+    coverage) over all blocks.  With ``bin`` above 1 there is no ``continuum_centre``: its second
+    shift would need the averaged frequencies.
+
+    With none of the keywords the function is what it was."""
     if continuum_centre is not None and continuum is None:
         raise ValueError('continuum_centre needs continuum')
-    if phase_centre is not None or continuum_centre is not None:
-        return _preprocess_shifted(dataset, collector, start_channel, stop_channel,
-                                   polarization_matrices, vis_load, vis_limit, continuum,
-                                   phase_centre, continuum_centre)
-    if continuum is None:
+    if spectral is not None:
+        if spectral.bin > 1 and continuum_centre is not None:
+            raise ValueError('spectral averaging (bin > 1) cannot be combined with continuum_centre')
+        channels_out = spectral.output_channels(stop_channel - start_channel)
+        if collector.num_channels != channels_out:
+            raise ValueError('the spectral filter gives {} channels, the collector was made for {}'.format(
+                channels_out, collector.num_channels))
+    if continuum is None and phase_centre is None and spectral is None:
         try:
             for chunk in data_iter(dataset, vis_limit, vis_load, start_channel, stop_channel):
                 collector.add(chunk['uvw'], chunk['weights'], chunk['vis'],
@@ -207,76 +222,75 @@ def preprocess_visibilities(dataset, collector, start_channel, stop_channel, pol
         finally:
             collector.close()
         return collector
-
-    from . import accel
-    from .continuum import UVContSubTemplate
-    queue = collector.queue
-    context = queue.context
-    subtract = UVContSubTemplate(context, continuum).instantiate(queue, stop_channel - start_channel)
-    try:
-        for chunk in data_iter(dataset, vis_limit, vis_load, start_channel, stop_channel):
-            vis = accel.DeviceArray(context, chunk['vis'].shape, np.complex64, queue=queue)
-            weights = accel.DeviceArray(context, chunk['weights'].shape, np.float32, queue=queue)
-            vis.set(queue, chunk['vis'])
-            weights.set(queue, chunk['weights'])
-            subtract(vis, weights)
-            collector.add(chunk['uvw'], weights, vis,
-                          chunk.get('feed_angle1'), chunk.get('feed_angle2'), *polarization_matrices)
-        collector.continuum_counts = subtract.counts()
-    finally:
-        collector.close()
-    return collector
+    return _preprocess_device(dataset, collector, start_channel, stop_channel, polarization_matrices,
+                              vis_load, vis_limit, continuum, phase_centre, continuum_centre, spectral)
 
 
-def _preprocess_shifted(dataset, collector, start_channel, stop_channel, polarization_matrices,
-                        vis_load, vis_limit, continuum, phase_centre, continuum_centre):
-    """:func:`preprocess_visibilities` with ``phase_centre`` and / or ``continuum_centre``."""
+def _preprocess_device(dataset, collector, start_channel, stop_channel, polarization_matrices,
+                       vis_load, vis_limit, continuum, phase_centre, continuum_centre, spectral):
+    """:func:`preprocess_visibilities` with any of its operators: every block goes to the device
+    once and through them on the collector's queue."""
     from . import accel, phaseshift
     from .continuum import UVContSubTemplate
+    from .spectral import SpectralFilterTemplate
     queue = collector.queue
     context = queue.context
-    origin = tuple(float(x) for x in dataset.phase_centre())
-    target = origin if phase_centre is None else tuple(float(x) for x in phase_centre)
-    inv_wavelength = phaseshift.inverse_wavelengths(
-        [dataset.frequency(channel) for channel in range(start_channel, stop_channel)])
-
-    def shifter(*centres, **kwargs):
-        params = phaseshift.PhaseShiftParameters(*centres, **kwargs)
-        return phaseshift.PhaseShiftTemplate(context, params).instantiate(queue, inv_wavelength)
+    shifted = phase_centre is not None or continuum_centre is not None
+    channels = stop_channel - start_channel
     try:
-        if continuum_centre is not None:
-            source = tuple(float(x) for x in continuum_centre)
-            before = shifter(origin, source)
-            after = shifter(origin, target, from_centre=source)
-        else:
-            before = shifter(origin, target)
-            after = None
+        before = after = None
+        if shifted:
+            origin = tuple(float(x) for x in dataset.phase_centre())
+            target = origin if phase_centre is None else tuple(float(x) for x in phase_centre)
+            inv_wavelength = phaseshift.inverse_wavelengths(
+                [dataset.frequency(channel) for channel in range(start_channel, stop_channel)])
+
+            def shifter(*centres, **kwargs):
+                params = phaseshift.PhaseShiftParameters(*centres, **kwargs)
+                return phaseshift.PhaseShiftTemplate(context, params).instantiate(queue, inv_wavelength)
+            if continuum_centre is not None:
+                source = tuple(float(x) for x in continuum_centre)
+                before = shifter(origin, source)
+                after = shifter(origin, target, from_centre=source)
+            else:
+                before = shifter(origin, target)
+        smooth = None
+        if spectral is not None:
+            smooth = SpectralFilterTemplate(context, spectral).instantiate(queue, channels)
+            channels = smooth.num_channels_out
         subtract = None
         if continuum is not None:
-            subtract = UVContSubTemplate(context, continuum).instantiate(queue, stop_channel - start_channel)
+            subtract = UVContSubTemplate(context, continuum).instantiate(queue, channels)
         for chunk in data_iter(dataset, vis_limit, vis_load, start_channel, stop_channel):
             vis = accel.DeviceArray(context, chunk['vis'].shape, np.complex64, queue=queue)
             weights = accel.DeviceArray(context, chunk['weights'].shape, np.float32, queue=queue)
-            uvw = accel.DeviceArray(context, chunk['uvw'].shape, np.float32, queue=queue)
             vis.set(queue, chunk['vis'])
             weights.set(queue, chunk['weights'])
-            uvw.set(queue, chunk['uvw'])
-            if after is None:
-                uvw = before(vis, uvw)
-                if subtract is not None:
-                    subtract(vis, weights)
-            else:
-                before(vis, uvw, write_uvw=False)
+            uvw = chunk['uvw']
+            if shifted:
+                uvw = accel.DeviceArray(context, chunk['uvw'].shape, np.float32, queue=queue)
+                uvw.set(queue, chunk['uvw'])
+                if after is None:
+                    uvw = before(vis, uvw)
+                else:
+                    before(vis, uvw, write_uvw=False)
+            if smooth is not None:
+                vis, weights = smooth(vis, weights)
+            if subtract is not None:
                 subtract(vis, weights)
+            if after is not None:
                 if after.template.params.writes_uvw:
                     uvw = after(vis, uvw)
                 else:
                     after(vis, uvw, write_uvw=False)
             collector.add(uvw, weights, vis,
                           chunk.get('feed_angle1'), chunk.get('feed_angle2'), *polarization_matrices)
+        if smooth is not None:
+            collector.spectral_counts = smooth.counts()
         if subtract is not None:
             collector.continuum_counts = subtract.counts()
-        collector.phase_centre = target
+        if shifted:
+            collector.phase_centre = target
     finally:
         collector.close()
     return collector
