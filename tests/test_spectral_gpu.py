@@ -9,7 +9,18 @@ is the rounding the contract allows; the second covers float64 sums in another o
 into FMAs, about L 2^-53 S = 8e-15 S at L = 72 (no cancellation in S1: g, w >= 0) -- two orders
 inside the bound, while any float32 step lands near 6e-8 S and fails.  Weights:
 |dev - t| <= 2^-24 |t| (1 + 1e-9).  The kept / flagged set and the two counters are exactly the
-twin's."""
+twin's.
+
+What runs is listed in spectral_cases.py: SHAPES on every plane with the second stream and the
+repeated calls; FORM_SHAPES, which take each of the six kernel forms past one round and one chunk
+(test_spectral_host.py checks, without a device, that the two lists reach every branch of the
+kernels' loops); and ABI_CASES, the (length, offset, step) that only a direct call of
+kimg_spectral_filter can make, against the contract written out a second time.  Measured on an
+MI355X over FORM_SHAPES and ABI_CASES (3.0 million float32 words, lengths up to 72): the largest
+err / bound is 0.9995 for values and 0.99999 for weights, all of it the final float32 rounding, which
+alone may use the whole first term; no error went past 2^-24 |t|, so the 1e-12 S term was not
+drawn on at all, and every word had the bits of the truth rounded once -- the float64 differences
+(L 2^-53 S) are too small to move a word across a float32 rounding boundary in so few samples."""
 import itertools
 
 import numpy as np
@@ -17,40 +28,35 @@ import pytest
 
 import golden_inputs as gi
 from helpers import context_queue, make_params, SENTINELS
+from spectral_cases import (ABI_CASES, ABI_CHANNELS, FORM_PLANES, FORM_SHAPES, HANNING, SHAPES,
+                            contract_double, random_block)
+from spectral_cases import window as _span
 
 pytestmark = pytest.mark.gpu
 
-#: SF_CHUNK of csrc/spectral.hip: output channels per blockIdx.y
-CHUNK = 64
-HANNING = (0.25, 0.5, 0.25)
-FIVE = (0.1, 0.2, 0.4, 0.2, 0.1)
-NINE = (0.02, 0.05, 0.11, 0.17, 0.3, 0.17, 0.11, 0.05, 0.02)
-#: (C_in, taps, bin); the last two: two chunks of output channels and five more, so that windows
-#: straddle both chunk seams
-SHAPES = [
-    (1, HANNING, 1), (2, HANNING, 1), (3, HANNING, 1), (7, (1.0,), 2), (7, HANNING, 2),
-    (64, (1.0,), 64), (9, NINE, 1), (3 * (2 * CHUNK + 5) + 1, HANNING, 3), (2 * CHUNK + 5, FIVE, 1),
-]
 #: (N, Q): one element, partial / whole / whole + 1 waves, every polarization count, partial workgroups
 PLANES = [(1, 1), (63, 1), (64, 1), (65, 1), (257, 2), (257, 3), (1000, 4)]
 
 
 def _window(g, offset, step, o, C_in):
     """(i, c) of the inputs of output o that lie inside the band."""
-    return [(i, o * step - offset + i) for i in range(len(g)) if 0 <= o * step - offset + i < C_in]
+    return _span(len(g), offset, step, o, C_in)
 
 
 def _parameters(C_in, taps, bin):
     """The shape's parameters, with a coverage threshold that some set of inputs meets EXACTLY: the
     default 0.5 where the coefficients allow it (the dyadic ones do), else the coverage of the first
-    half of a window, searched among the neighbours of cov / sum(g) so that the product rounds to cov."""
+    half of the window of the output that _threshold_subset looks at -- of the part of it inside the
+    band, where the band cuts it -- searched among the neighbours of cov / sum(g) so that the product
+    rounds to cov."""
     from katsdpimager_amd.spectral import SpectralParameters
     params = SpectralParameters(taps, bin)
     if _threshold_subset(params, C_in) is not None:
         return params
     g, offset, step = params.coefficients()
+    inside = [i for i, c in _window(g, offset, step, params.output_channels(C_in) // 2, C_in)]
     cov = 0.0
-    for i in range(len(g) // 2 + 1):
+    for i in inside[:len(inside) // 2 + 1]:
         cov += g[i]
     guess = cov / float(g.sum())
     for mc in [guess] + [np.nextafter(guess, d) for d in (0.0, 1.0)]:
@@ -88,9 +94,7 @@ def _inputs(params, C, N, Q, seed):
     whose windows has no usable input at all, and one whose window is exactly at the coverage
     threshold (and so kept)."""
     rng = np.random.default_rng(seed)
-    vis = ((rng.normal(size=(C, N, Q)) + 1j * rng.normal(size=(C, N, Q))) * 3.0).astype(np.complex64)
-    weights = rng.uniform(0.5, 2.0, (C, N, Q)).astype(np.float32)
-    weights[rng.random((C, N, Q)) < 0.2] = 0.0
+    vis, weights = random_block(rng, C, N, Q)
     v2, w2 = vis.reshape(C, N * Q), weights.reshape(C, N * Q)       # (views)
     g, offset, step = params.coefficients()
     marks = {}
@@ -143,19 +147,26 @@ def _bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
-def _check_against_twin(got_vis, got_weights, vis, weights, params):
-    from katsdpimager_amd import spectral
-    want, want_weights, kept = spectral.filter_host_double(vis, weights, params)
+def _worst(err, bound, ratios, key):
+    """Keeps in ratios[key] the largest err / bound seen (an error where the bound is 0 counts as inf)."""
+    if ratios is not None and err.size:
+        with np.errstate(divide='ignore', invalid='ignore'):
+            r = np.where(err > 0, err / bound, 0.0)
+        ratios[key] = max(ratios.get(key, 0.0), float(r.max()))
+
+
+def _check_against_truth(got_vis, got_weights, vis, weights, truth, length, offset, step, ratios=None):
+    """`truth`: (vis complex128, weights float64, kept) before the contract's one rounding."""
+    want, want_weights, kept = truth
     assert got_vis.shape == want.shape and got_weights.shape == want.shape
     assert got_vis.dtype == np.complex64 and got_weights.dtype == np.float32
     # S: the largest |v| among the usable inputs of every output's window
-    g, offset, step = params.coefficients()
     C_in, C_out = vis.shape[0], want.shape[0]
     usable = (weights > 0) & np.isfinite(vis.real) & np.isfinite(vis.imag)
     size = np.where(usable, np.abs(vis.astype(np.complex128)), 0.0)
     S = np.zeros(want.shape)
     for o in range(C_out):
-        for i, c in _window(g, offset, step, o, C_in):
+        for i, c in _span(length, offset, step, o, C_in):
             S[o] = np.maximum(S[o], size[c])
     # the kept set: flagged samples are +0 in all three words, kept ones have a weight above 0
     assert np.array_equal(got_weights > 0, kept)
@@ -165,13 +176,58 @@ def _check_against_twin(got_vis, got_weights, vis, weights, params):
         d = getattr(got_vis, part)[kept].astype(np.float64)
         err = np.abs(d - t)
         bound = 2.0 ** -24 * np.abs(t) + 1e-12 * S[kept]
+        _worst(err, bound, ratios, 'values')
+        # (the rounding alone may use all of the first term; what an error takes of the second one)
+        _worst(np.maximum(err - 2.0 ** -24 * np.abs(t), 0.0), 1e-12 * S[kept], ratios, 'second term')
         assert (err <= bound).all(), 'worst excess {:.3g}'.format(float((err - bound).max()))
     t = want_weights[kept]
     err = np.abs(got_weights[kept].astype(np.float64) - t)
     bound = 2.0 ** -24 * np.abs(t) * (1 + 1e-9)
+    _worst(err, bound, ratios, 'weights')
     assert (err <= bound).all(), 'weights: worst excess {:.3g}'.format(float((err - bound).max()))
     n = int(kept.sum())
+    if ratios is not None:
+        # how many float32 words are not the truth's, rounded once: what the float64 sums in another
+        # order or with another contraction move across a rounding boundary
+        other = int((_bits(got_vis[kept]) != _bits(want[kept].astype(np.complex64))).sum()
+                    + (_bits(got_weights[kept]) != _bits(want_weights[kept].astype(np.float32))).sum())
+        ratios['words of other bits'] = ratios.get('words of other bits', 0) + other
+        ratios['words'] = ratios.get('words', 0) + 3 * n
     return kept, (n, kept.size - n)
+
+
+def _check_against_twin(got_vis, got_weights, vis, weights, params, ratios=None):
+    from katsdpimager_amd import spectral
+    g, offset, step = params.coefficients()
+    return _check_against_truth(got_vis, got_weights, vis, weights,
+                                spectral.filter_host_double(vis, weights, params), len(g), offset, step,
+                                ratios)
+
+
+def _on_padded_blocks(ctx, q, op, vis, weights):
+    """op on padded channel pitches, different for the two arrays: the outputs on the host, after
+    the checks of their shapes and of the inputs and their padding coming back bit for bit."""
+    C_out, (C, N, Q) = op.num_channels_out, vis.shape
+    d_vis = _PaddedBlock(ctx, q, vis, 5)
+    d_weights = _PaddedBlock(ctx, q, weights, 11)
+    out_vis, out_weights = op(d_vis.array, d_weights.array)
+    assert out_vis.shape == (C_out, N, Q) and out_weights.shape == (C_out, N, Q)
+    assert out_vis.tensor.is_contiguous() and out_weights.tensor.is_contiguous()
+    got_vis, got_weights = out_vis.get(q), out_weights.get(q)
+    d_vis.assert_unchanged(q)
+    d_weights.assert_unchanged(q)
+    return got_vis, got_weights
+
+
+def _assert_marks(marks, kept, counts):
+    """The hand-made samples of _inputs came out as they were made to."""
+    if marks:
+        C_out = kept.shape[0]
+        o, j = marks['unusable']
+        assert not kept.reshape(C_out, -1)[o, j]
+        o, j = marks['threshold']
+        assert kept.reshape(C_out, -1)[o, j]
+        assert counts[0] >= 1 and counts[1] >= 1
 
 
 @pytest.mark.parametrize('C,taps,bin', SHAPES)
@@ -186,24 +242,11 @@ def test_device_against_twin(C, taps, bin):
         vis, weights, marks = _inputs(params, C, N, Q, 1000 * C + 10 * bin + i)
         op = template.instantiate(q, C)
         assert op.counts() == (0, 0) and op.num_channels_out == C_out
-        # padded channel pitches, different for the two arrays
-        d_vis = _PaddedBlock(ctx, q, vis, 5)
-        d_weights = _PaddedBlock(ctx, q, weights, 11)
-        out_vis, out_weights = op(d_vis.array, d_weights.array)
-        assert out_vis.shape == (C_out, N, Q) and out_weights.shape == (C_out, N, Q)
-        assert out_vis.tensor.is_contiguous() and out_weights.tensor.is_contiguous()
-        got_vis, got_weights = out_vis.get(q), out_weights.get(q)
-        d_vis.assert_unchanged(q)
-        d_weights.assert_unchanged(q)
+        got_vis, got_weights = _on_padded_blocks(ctx, q, op, vis, weights)
         kept, counts = _check_against_twin(got_vis, got_weights, vis, weights, params)
         assert sum(counts) == C_out * N * Q
         assert op.counts() == counts
-        if marks:
-            o, j = marks['unusable']
-            assert not kept.reshape(C_out, N * Q)[o, j]
-            o, j = marks['threshold']
-            assert kept.reshape(C_out, N * Q)[o, j]
-            assert counts[0] >= 1 and counts[1] >= 1
+        _assert_marks(marks, kept, counts)
         # dense inputs, a side stream, the same operator twice: the same bits, and the counts of an
         # operator add up over its calls; an empty block in between changes nothing
         op2 = template.instantiate(side, C)
@@ -223,6 +266,33 @@ def test_device_against_twin(C, taps, bin):
         assert np.array_equal(_bits(e_weights.get(side)), _bits(weights))
         op2.reset_counts()
         assert op2.counts() == (0, 0)
+
+
+@pytest.mark.parametrize('C,taps,bin', FORM_SHAPES)
+def test_every_form_past_one_round_and_one_chunk(C, taps, bin):
+    """The shapes that take every form of csrc/spectral.hip through all of its control flow (the
+    list says what each is there for; test_spectral_host.py checks that the lists reach it all), under
+    the bounds of the module docstring.  Prints the largest err / bound it met."""
+    from katsdpimager_amd import spectral
+    ctx, q = context_queue()
+    params = _parameters(C, taps, bin)
+    template = spectral.SpectralFilterTemplate(ctx, params)
+    C_out = params.output_channels(C)
+    ratios = {}
+    for i, (N, Q) in enumerate(FORM_PLANES):
+        vis, weights, marks = _inputs(params, C, N, Q, 1000 * C + 10 * bin + len(taps) + i)
+        assert bool(marks) == (N * Q >= 63)
+        op = template.instantiate(q, C)
+        assert op.counts() == (0, 0) and op.num_channels_out == C_out
+        got_vis, got_weights = _on_padded_blocks(ctx, q, op, vis, weights)
+        try:
+            kept, counts = _check_against_twin(got_vis, got_weights, vis, weights, params, ratios)
+        finally:
+            print('C_in {} length {} bin {} plane {}x{}: worst err / bound so far {}'.format(
+                C, len(taps) + bin - 1, bin, N, Q, ratios))
+        assert sum(counts) == C_out * N * Q
+        assert op.counts() == counts
+        _assert_marks(marks, kept, counts)
 
 
 def test_the_entry_point_on_device_pointers():
@@ -266,6 +336,52 @@ def test_the_entry_point_on_device_pointers():
     assert call() == 0
     assert counts.get(q).tolist() == [0, C * N]
     assert not _bits(out_vis.get(q)).any() and not _bits(out_weights.get(q)).any()
+
+
+@pytest.mark.parametrize('length,offset,step', ABI_CASES)
+def test_every_offset_on_device_pointers(length, offset, step):
+    """kimg_spectral_filter takes any 0 <= offset < length and any length at step 1; the Python layer
+    sends len(taps) // 2 and odd tap counts only.  Random coefficients that are not symmetric (a
+    reversed or shifted tap order cannot pass), all four arrays padded, the truth the contract of the
+    header written out in spectral_cases.contract_double (test_spectral_host.py holds it against the
+    twin), the bounds those of the module docstring."""
+    import ctypes
+    from katsdpimager_amd import accel
+    from katsdpimager_amd._lib import lib
+    ctx, q = context_queue()
+    C, N = ABI_CHANNELS, 65
+    C_out = C // step
+    rng = np.random.default_rng(10000 * step + 100 * length + offset)
+    vis, weights = random_block(rng, C, N, 1)
+    g = rng.uniform(0.1, 1.0, length)
+    assert length < 3 or not np.array_equal(g, g[::-1])
+    min_sum = 0.5 * float(g.sum())
+    d_vis = _PaddedBlock(ctx, q, vis, 5)
+    d_weights = _PaddedBlock(ctx, q, weights, 11)
+    out_vis = _PaddedBlock(ctx, q, np.full((C_out, N, 1), SENTINELS[np.dtype(np.complex64)]), 3)
+    out_weights = _PaddedBlock(ctx, q, np.full((C_out, N, 1), SENTINELS[np.dtype(np.float32)]), 7)
+    counts = accel.DeviceArray(ctx, (2,), np.int64)
+    counts.zero(q)
+    assert lib().kimg_spectral_filter(
+        d_vis.whole.ptr, N + 5, d_weights.whole.ptr, N + 11, C, out_vis.whole.ptr, N + 3,
+        out_weights.whole.ptr, N + 7, C_out, N, g.ctypes.data_as(ctypes.c_void_p), length, offset, step,
+        min_sum, counts.ptr, q.handle) == 0
+    got = []
+    for block in (out_vis, out_weights):
+        whole = block.whole.get(q)
+        assert np.array_equal(_bits(whole[:, N:]), _bits(block.host[:, N:])), 'output padding written'
+        got.append(whole[:, :N].reshape(C_out, N, 1))
+    d_vis.assert_unchanged(q)
+    d_weights.assert_unchanged(q)
+    truth = contract_double(vis, weights, g, offset, step, min_sum, C_out)
+    ratios = {}
+    try:
+        kept, expected = _check_against_truth(got[0], got[1], vis, weights, truth, length, offset, step,
+                                              ratios)
+    finally:
+        print('length {} offset {} step {}: worst err / bound {}'.format(length, offset, step, ratios))
+    assert sum(expected) == C_out * N
+    assert tuple(counts.get(q).tolist()) == expected
 
 
 # ---- through the loader into the store --------------------------------------------------------------

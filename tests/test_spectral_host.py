@@ -1,7 +1,10 @@
 """Spectral smoothing and channel averaging without a device: the parameters object, the numpy twin
 (spectral.filter_host, the executable form of the contract in include/kimg.h) against truths that do
 not share its code, the noise it promises, the argument checks of kimg_spectral_filter (they run
-before any HIP call), the ABI surface, and the loader's keyword."""
+before any HIP call), the ABI surface, and the loader's keyword; and, for test_spectral_gpu.py, that
+the contract written out for the entry point's wider parameters (spectral_cases.contract_double) is
+the twin's wherever both apply, and that the shapes it runs reach every form of csrc/spectral.hip and
+every branch of its loops."""
 import ctypes
 import os
 import re
@@ -9,6 +12,8 @@ import re
 import numpy as np
 import pytest
 
+import spectral_cases as cases
+from spectral_cases import contract_double
 from katsdpimager_amd import loader, spectral
 from katsdpimager_amd.spectral import SpectralParameters, filter_host, filter_host_double
 
@@ -231,6 +236,166 @@ def test_noise_of_the_output_is_what_its_weight_says():
     scaled = np.sqrt(w.astype(np.float64)) * out.real
     assert abs(scaled.var() - 1.0) <= 0.05
     assert abs((np.sqrt(w.astype(np.float64)) * out.imag).var() - 1.0) <= 0.05
+
+
+# ---- the contract written out a second time, for the entry point's wider parameters ------------------
+@pytest.mark.parametrize('C,taps,bin', cases.SHAPES + cases.FORM_SHAPES)
+def test_contract_written_out_agrees_with_the_twin(C, taps, bin):
+    """spectral_cases.contract_double (output by output, usable inputs only) against
+    filter_host_double (tap by tap over all outputs, unusable inputs as zeros) wherever
+    SpectralParameters reaches.  Both add the same float64 terms in ascending tap order, and an
+    unusable input's +0.0 changes no bit of a sum, so the twin's own precision is: the same bits."""
+    rng = np.random.default_rng(7 * C + bin)
+    vis, weights = cases.random_block(rng, C, 5, 2)
+    weights[C // 2, 1, 0] = -1.0
+    vis[C // 3, 2, 1] = complex(np.nan, 1.0)
+    vis[0, 3, 0] = complex(2.0, -np.inf)
+    weights[:, 4, 1] = 0.0                              # windows with nothing usable at all
+    params = SpectralParameters(taps, bin)
+    g, offset, step = params.coefficients()
+    want = filter_host_double(vis, weights, params)
+    got = contract_double(vis, weights, g, offset, step, params.min_sum(), params.output_channels(C))
+    assert not want[2][:, 4, 1].any() and want[2].any()
+    for a, b in zip(got, want):
+        assert a.dtype == b.dtype and a.shape == b.shape
+        assert a.tobytes() == b.tobytes()
+
+
+# ---- the shape lists of test_spectral_gpu.py against the dispatch of csrc/spectral.hip ---------------
+def _kernel_constants():
+    """SF_CHUNK, SF_UNROLL, {L: outputs per round} of the sliding instantiations, the longest filter
+    and the largest bin, as csrc/spectral.hip and include/kimg.h state them."""
+    from katsdpimager_amd import build
+    source = open(os.path.join(build.CSRC, 'spectral.hip')).read()
+    header = open(os.path.join(os.path.dirname(build.HERE), 'include', 'kimg.h')).read()
+    const = {name: int(value)
+             for name, value in re.findall(r'^constexpr int (SF_\w+) = (\d+);', source, re.M)}
+    rounds = {int(L): int(L) * int(M) for L, M in re.findall(
+        r'step == 1 && length == (\d+)\)\s*sliding\(integral_constant<int, \1>\{\}, '
+        r'integral_constant<int, (\d+)>\{\}\);', source)}
+    defines = dict(re.findall(r'^#define (KIMG_SPECTRAL_MAX_\w+) (\d+)$', header, re.M))
+    largest_bin = int(defines['KIMG_SPECTRAL_MAX_BIN'])
+    longest = int(defines['KIMG_SPECTRAL_MAX_TAPS']) + largest_bin - 1
+    assert 'SF_MAX_LENGTH = KIMG_SPECTRAL_MAX_TAPS + KIMG_SPECTRAL_MAX_BIN - 1;' in source
+    return const['SF_CHUNK'], const['SF_UNROLL'], rounds, longest, largest_bin
+
+
+def _situations(C_in, length, offset, step, chunk, unroll, rounds, longest, largest_bin):
+    """The dispatch at the end of kimg_spectral_filter and the loops of its kernels, restated: the
+    form that (length, offset, step) selects, and what of that form's control flow C_in channels take
+    it through.  A set of (form, situation)."""
+    C_out = C_in // step
+    assert C_out >= 1 and 0 <= offset < length <= longest
+    if step == 1 and length in rounds:
+        form = 'sliding {}'.format(length)
+    elif offset == 0 and length == step:
+        form = 'disjoint'
+    else:
+        form = 'window'
+    found = set()
+    spans = [(begin, min(C_out, begin + chunk)) for begin in range(0, C_out, chunk)]
+    if len(spans) > 1:
+        found.add('several chunks')
+    for begin, end in spans:
+        if begin > 0:
+            found.add('a chunk that begins past output 0')
+        if form.startswith('sliding'):
+            R = rounds[length]
+            # for (o0 = begin; o0 < end; o0 += R): prefetch if (o0 + R < end); outputs o0 + u < end
+            prefetched = False
+            for o0 in range(begin, end, R):
+                partial = end - o0 < R
+                if partial:
+                    found.add('a partial last round')
+                    if prefetched:
+                        found.add('a partial round after a prefetch')
+                if o0 + R < end:
+                    found.add('a round with the prefetch taken')
+                    prefetched = True
+            if end - begin == R:
+                found.add('a chunk of one exact round')
+    if form != 'disjoint' and C_in < length:
+        found.add('a band shorter than the window')
+    if form != 'disjoint':
+        found.add('offset {}'.format('first' if offset == 0 else 'last' if offset == length - 1
+                                     else 'between'))
+    if form == 'window':
+        found.add('step 1' if step == 1 else 'step above 1')
+    if not form.startswith('sliding'):
+        # for (i0 = 0; i0 < length; i0 += unroll): taps i0 + u < length
+        if length > unroll:
+            found.add('several unroll groups, {}'.format('no remainder' if length % unroll == 0
+                                                         else 'a remainder'))
+        else:
+            found.add('one unroll group')
+        if C_in > C_out * step:
+            found.add('input channels left over')
+    if form == 'window' and length == longest:
+        found.add('the longest filter')
+    if form == 'disjoint' and length == largest_bin:
+        found.add('the largest bin')
+    return {(form, s) for s in found}
+
+
+#: what the shape lists (C_in, taps, bin) have to reach ...
+_LOOPS = ['several chunks', 'a chunk that begins past output 0']
+_SLIDING = _LOOPS + ['a round with the prefetch taken', 'a partial last round',
+                     'a partial round after a prefetch', 'a chunk of one exact round',
+                     'a band shorter than the window']
+_GROUPS = ['one unroll group', 'several unroll groups, no remainder', 'several unroll groups, a remainder',
+           'input channels left over']
+SHAPES_REACH = (
+    [('sliding {}'.format(L), s) for L in (3, 5, 7, 9) for s in _SLIDING]
+    + [('disjoint', s) for s in _LOOPS + _GROUPS + ['the largest bin']]
+    + [('window', s) for s in _LOOPS + _GROUPS + ['a band shorter than the window', 'the longest filter']])
+#: ... and the (length, offset, step) cases of the entry point
+_OFFSETS = ['offset first', 'offset between', 'offset last']
+ABI_REACH = (
+    [('sliding {}'.format(L), s) for L in (3, 5, 7, 9) for s in _OFFSETS]
+    + [('window', s) for s in _OFFSETS + ['step 1', 'step above 1']]
+    + [('disjoint', 'one unroll group')])
+
+
+def test_kernel_constants_are_the_ones_the_lists_were_written_for():
+    chunk, unroll, rounds, longest, largest_bin = _kernel_constants()
+    assert chunk == cases.CHUNK == 64 and unroll == 4 and longest == 72 and largest_bin == 64
+    assert rounds == {3: 6, 5: 5, 7: 7, 9: 9}
+
+
+def test_shape_lists_reach_every_form_and_every_branch_of_its_loops():
+    """Shape lists rot: every (form, situation) of SHAPES_REACH must be met by some shape, and every
+    shape of FORM_SHAPES must be the kind the dispatch takes it for (its place in the list)."""
+    constants = _kernel_constants()
+    reached = {}
+    for C, taps, bin in cases.SHAPES + cases.FORM_SHAPES:
+        g, offset, step = SpectralParameters(taps, bin).coefficients()
+        for situation in _situations(C, len(g), offset, step, *constants):
+            reached.setdefault(situation, []).append((C, len(g), step))
+    missing = [s for s in SHAPES_REACH if s not in reached]
+    assert not missing, 'no shape reaches {}'.format(missing)
+    # the forms, in the order of the list's sections
+    forms = []
+    for C, taps, bin in cases.FORM_SHAPES:
+        g, offset, step = SpectralParameters(taps, bin).coefficients()
+        form = {f for f, s in _situations(C, len(g), offset, step, *constants)}.pop()
+        if not forms or forms[-1] != form:
+            forms.append(form)
+    assert forms == ['sliding 3', 'sliding 5', 'sliding 7', 'sliding 9', 'disjoint', 'window']
+    # a list that loses a shape which alone reaches a situation fails above: such shapes exist
+    sole = {shapes[0] for shapes in reached.values() if len(shapes) == 1}
+    assert (64 * 66 + 3, 72, 64) in sole and (4, 5, 1) in sole and (7, 7, 1) in sole
+
+
+def test_entry_point_cases_reach_every_offset_of_every_form():
+    constants = _kernel_constants()
+    reached = set()
+    for length, offset, step in cases.ABI_CASES:
+        reached |= _situations(cases.ABI_CHANNELS, length, offset, step, *constants)
+    missing = [s for s in ABI_REACH if s not in reached]
+    assert not missing, 'no case reaches {}'.format(missing)
+    assert len(set(cases.ABI_CASES)) == len(cases.ABI_CASES) == 24
+    # lengths that SpectralParameters cannot make: even at step 1
+    assert {(L, 1) for L in (2, 4, 6, 8)} <= {(length, step) for length, _, step in cases.ABI_CASES}
 
 
 # ---- the C entry point, without a device ------------------------------------------------------------
