@@ -8,6 +8,7 @@ store -> imaging weights, PSF, major/minor cycles -> restored image, all on one 
     python examples/image_channel.py --uv-taper 30,20,30 --uv-range 0,3000  (see uv_taper_channel)
     python examples/image_channel.py --primary-beam 0.3     (see primary_beam_channel)
     python examples/image_channel.py --spectral hanning,2   (a band with a one-channel line; see spectral_line)
+    python examples/image_channel.py --statwt 8             (noise that differs between baselines; see statwt_band)
 
 It follows the reference's per-channel flow (frontend.py:31-83 preprocess_visibilities,
 :465-658 process_channel) with the loaders and FITS output left out: the sky is three point
@@ -366,6 +367,65 @@ def spectral_line(args):
     return peaks
 
 
+def statwt_band(args):
+    """--statwt TIME_BIN[:first-last,...]: a synthetic band of 16 channels of pure noise whose sigma
+    differs from baseline to baseline (0.5 to 4) while every weight is 1, through
+    ``loader.preprocess_visibilities`` without and with ``statwt=`` (the listed channels left out of
+    the statistic); prints, for one channel, the image noise the weights predict (``weights_noise``),
+    ``normalized_noise`` and the rms measured in the central half of the dirty image (robust
+    weighting).  With weights that are inverse variances the prediction is the measurement."""
+    import synth
+    from katsdpimager_amd import accel, frontend, imaging, loader, parameters, preprocess, statwt, weight
+    time_bin, _, spans = args.statwt.partition(':')
+    ranges = [(int(a), int(b) + 1) for a, b in (span.split('-') for span in spans.split(','))] if spans else None
+    C = 16
+    params = statwt.StatWtParameters(int(time_bin), line_ranges=ranges)
+    ctx = accel.create_some_context()
+    queue = ctx.create_command_queue()
+    rows = max(args.vis // C, 1000)
+    obs = synth.make_observation(args.pixels, rows, args.w_planes, 1, device='cpu')
+    image_p, grid_p, array_p = synth.make_parameters(obs, 1, args.kernel_width, degrid=True)
+    # (synth's tracks are baseline-major: ceil(rows / baselines) consecutive rows each)
+    num_baselines = synth.baselines_equatorial().shape[0]
+    baseline = (np.arange(rows) // -(-rows // num_baselines)).astype(np.int32)
+    rng = np.random.default_rng(5)
+    sigma = rng.uniform(0.5, 4.0, num_baselines)[baseline]
+    vis = ((rng.normal(size=(rows, C, 1)) + 1j * rng.normal(size=(rows, C, 1)))
+           * sigma[:, None, None]).astype(np.complex64)
+    dataset = loader.LoaderArrays(obs.uvw.numpy(), vis, np.ones((rows, C, 1), np.float32), baseline,
+                                  _frequencies(obs, C), [0])
+    weight_p = parameters.WeightParameters(weight.WeightType.ROBUST, 0.0)
+    # (one minor cycle: the residual is the dirty image but for one component of noise)
+    clean_p = parameters.CleanParameters(1, 0.1, 0.85, 5.0, 0, 0.01, 0.5, 0.02)
+    template = imaging.ImagingTemplate(ctx, array_p, image_p.fixed, weight_p, grid_p.fixed, clean_p)
+    imager = template.instantiate(queue, image_p, grid_p, args.vis_block, 0, 1, streams=2)
+    imager.ensure_all_bound()
+    imager.one_call_major_cycles = False
+    ident = np.ones((1, 1), np.complex64)
+    channel = int(np.flatnonzero(params.mask(C))[0])
+    G = args.pixels
+    results = {}
+    print('{} rows of {} channels, {} baselines with sigma 0.5 to 4, every weight 1; channel {}'.format(
+        rows, C, len(np.unique(baseline)), channel))
+    for label, keyword in (('weights as given', None), ('reweighted', params)):
+        collector = preprocess.VisibilityCollectorDevice(queue, [image_p] * C, [grid_p] * C, args.vis_block)
+        loader.preprocess_visibilities(dataset, collector, 0, C, (ident, None), statwt=keyword)
+        if keyword is not None:
+            print('statwt {}: {} groups kept, {} flagged'.format(params, *collector.statwt_counts))
+        reader = collector.reader()
+        stats = frontend.process_channel(reader, channel, imager, image_p, grid_p, clean_p,
+                                         weight_p.weight_type, args.vis_block, 1, True)
+        dirty = imager.get_buffer('dirty')[0][G // 4:3 * G // 4, G // 4:3 * G // 4]
+        rms = float(np.sqrt(np.mean(np.square(dirty, dtype=np.float64))))
+        results[label] = dict(weights_noise=stats['weights_noise'], normalized_noise=stats['normalized_noise'],
+                              rms=rms)
+        print('{:16s}: weights predict an image noise of {:.6g}, normalized_noise {:.4f}; measured rms '
+              '{:.6g}, {:.3f} of the prediction'.format(
+                  label, stats['weights_noise'], stats['normalized_noise'], rms,
+                  rms / stats['weights_noise']))
+    return results
+
+
 def _frequencies(obs, channels):
     return 299792458.0 / obs.wavelength + 1.0e5 * np.arange(channels)
 
@@ -410,7 +470,13 @@ def main(argv=None):
                     help='instead of the three-source channel: Hanning-smooth (and average N channels to one) a '
                          'synthetic band with a line in one channel, and print the line\'s dirty peak in every '
                          'output channel')
+    ap.add_argument('--statwt', metavar='TIME_BIN[:first-last,...]',
+                    help='instead of the three-source channel: a synthetic band of noise whose sigma differs from '
+                         'baseline to baseline under equal weights, imaged without and with the weights rescaled '
+                         'from the scatter of groups of TIME_BIN rows (the listed channels left out), e.g. --statwt 8')
     args = ap.parse_args(argv)
+    if args.statwt:
+        return statwt_band(args)
     if args.spectral:
         return spectral_line(args)
     if args.primary_beam:

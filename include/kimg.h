@@ -1110,6 +1110,75 @@ int kimg_spectral_filter(const void *vis_in, int64_t vis_in_channel_pitch, const
                          int64_t plane_elements, const double *coeff_host, int length, int offset,
                          int step, double min_sum, uint64_t *counts, void *stream);
 
+/* ---- Statistical reweighting (statwt.hip): the weights of a block of RAW visibilities rescaled so
+ * that they are inverse variances, from the scatter of the visibilities themselves across the
+ * line-free channels (CASA statwt), after kimg_uvcontsub and ahead of kimg_preprocess_convert.  The
+ * reference has none; the semantics are this library's, and katsdpimager_amd/statwt.py holds them once
+ * more as numpy (statwt_host).  The device matches that twin bit for bit.
+ *
+ * vis: complex64 [C][N][P], read only.  weights: float32 [C][N][P], updated in place.  C =
+ *   num_channels, N = num_rows, P = num_pols (1 .. 4), the loader's block layout.  The inner [N][P]
+ *   plane is dense; each array has its own channel pitch in elements of the array, at least N * P.
+ *   Elements of the padding are neither read nor written.  Indices are 64-bit throughout.
+ * fit_mask_host: HOST uint8 [C], nonzero = a line-free channel that enters the statistic.  It is read
+ *   during the call and travels to the kernels by value.
+ * Groups.  A group is up to time_bin (1 .. KIMG_STATWT_MAX_BIN) consecutive rows of ONE baseline
+ *   within the block; the statistic is taken per group and per polarization.  Loader blocks are
+ *   stably sorted by baseline, so a baseline's samples are one contiguous, time-ordered run of rows,
+ *   and the groups are that run cut every time_bin rows; the last group of a run may be shorter.
+ *   Groups never span blocks: a baseline's rows in the next block start new groups.
+ *   group_offsets: DEVICE int32 [G + 1], G = num_groups: group k is the rows g[k] .. g[k + 1] - 1,
+ *     g[0] = 0, g[G] = N, strictly ascending, g[k + 1] - g[k] <= time_bin.
+ *   row_group: DEVICE int32 [N]: the group of every row (g[row_group[r]] <= r < g[row_group[r] + 1]).
+ *   The host makes both (statwt.group_offsets) and answers for them; the kernels clamp what they read
+ *   from them to the arrays' bounds, so wrong tables give wrong weights and nothing else.
+ * A sample (c, r, p) is usable iff fit_mask[c] != 0, its weight w is above 0 and finite, and both
+ *   parts of its visibility v = (re, im) are finite.
+ * Per group and polarization, all in float64, every product and every sum rounded on its own (no
+ * fused multiply-add), in exactly this order:
+ *   1. per row r, over its usable channels in ascending c, starting from 0:
+ *        s0 += w,  sr += w * re,  si += w * im,  m += 1
+ *   2. over the group's rows in ascending r, starting from 0: S0 = sum s0_r, SR, SI, M likewise;
+ *        the mean is mu = (SR / S0, SI / S0)
+ *   3. per row, over its usable channels in ascending c, starting from 0:
+ *        dr = re - mu_r,  di = im - mu_i,  t = dr * dr,  t = t + di * di,  q += w * t
+ *      then Q = sum q_r in ascending r
+ *   4. chi2 = Q / (2.0 * (M - 1)): the weighted scatter per real component about the group's own
+ *      mean.  For equal input weights w, w / chi2 is 1 / variance of the group's samples.
+ *   5. the group is kept iff M >= min_samples (at least 2) and chi2_lo < chi2 < chi2_hi, both
+ *      comparisons false for a NaN.  With the Python defaults (0, inf) constant data (chi2 == 0),
+ *      S0 == 0 and overflow all flag the group; a narrower range is the caller's outlier cut.
+ * For EVERY channel of the group's rows, line channels included:
+ *   kept: weights[c][r][p] = float32((double) w / chi2) where w > 0; a weight that is not above 0
+ *     (or is NaN) stays as it is, bit for bit.  Relative channel weights survive; only the absolute
+ *     scale is measured.
+ *   flagged: weights[c][r][p] = 0.
+ * The visibilities are never written.
+ * counts: DEVICE uint64 [2]: the number of kept and of flagged (group, polarization) pairs of the call
+ *   are ADDED to it (one atomic add per wave and counter); the caller zeroes it.
+ * chi2: DEVICE float64 [G][P], or NULL: chi2 of every pair, NaN where M < 2.
+ * workspace: DEVICE, 8-byte aligned, at least KIMG_STATWT_WORKSPACE_PER_ELEMENT * N * P bytes
+ *   (KIMG_EWORKSPACE otherwise): the per-row partial sums between the three launches.
+ * Returns, before any HIP call: KIMG_EINVAL for a null vis, weights, fit_mask_host, group_offsets,
+ *   row_group, workspace or counts; for C < 1, N < 0, P outside 1 .. 4, time_bin outside
+ *   1 .. KIMG_STATWT_MAX_BIN, min_samples < 2 or a NaN in the chi2 range; KIMG_EUNSUPPORTED for
+ *   N > 2^31 - 1 (rows are 32-bit in the tables); KIMG_EINVAL for a pitch below N * P;
+ *   KIMG_EUNSUPPORTED for C > KIMG_UVCONTSUB_MAX_CHANNELS.  N = 0 is then a successful call that does
+ *   nothing.  Then KIMG_EINVAL for G < 1, G > N or G * time_bin < N, KIMG_EWORKSPACE for a short
+ *   workspace and KIMG_EINVAL for one that is not 8-byte aligned.
+ * Asynchronous on `stream`, no allocation, capturable; equal inputs give equal bits.  Traffic: 12
+ *   bytes per element and fit channel twice over, 8 per element and channel (4 for a flagged group).
+ * Not done here: pooling polarizations, channel bins narrower than the band, groups across block
+ *   boundaries, sliding windows, medians or other robust statistics. */
+#define KIMG_STATWT_MAX_BIN 64
+#define KIMG_STATWT_WORKSPACE_PER_ELEMENT 36
+int kimg_statwt(const void *vis, int64_t vis_channel_pitch, float *weights,
+                int64_t weights_channel_pitch, int num_channels, int64_t num_rows, int num_pols,
+                const uint8_t *fit_mask_host, const int32_t *group_offsets, int64_t num_groups,
+                const int32_t *row_group, int time_bin, int min_samples, double chi2_lo,
+                double chi2_hi, double *chi2, void *workspace, size_t workspace_bytes,
+                uint64_t *counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

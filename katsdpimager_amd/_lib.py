@@ -121,6 +121,9 @@ PROTOTYPES = {
     # spectral filter: (vis_in, pitch, weights_in, pitch, C_in), (vis_out, pitch, weights_out, pitch,
     # C_out), plane_elements, (coeff_host, length, offset, step), min_sum, counts, stream
     'kimg_spectral_filter': (c_int, [P, L, P, L, I, P, L, P, L, I, L, P, I, I, I, D, P, P]),
+    # statistical reweighting: (vis, pitch, weights, pitch, C, N, P), fit_mask_host, (group_offsets, G,
+    # row_group), time_bin, min_samples, (chi2_lo, chi2_hi), chi2, (workspace, bytes), counts, stream
+    'kimg_statwt': (c_int, [P, L, P, L, I, L, I, P, P, L, P, I, I, D, D, P, P, c_size_t, P, P]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),

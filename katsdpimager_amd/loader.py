@@ -166,7 +166,7 @@ def data_iter(dataset, vis_limit, vis_load, start_channel, stop_channel):
 
 def preprocess_visibilities(dataset, collector, start_channel, stop_channel, polarization_matrices,
                             vis_load=32 * 1048576, vis_limit=None, continuum=None,
-                            phase_centre=None, continuum_centre=None, spectral=None):
+                            phase_centre=None, continuum_centre=None, spectral=None, statwt=None):
     """frontend.preprocess_visibilities (frontend.py:40-84): feed every block of the loader, in
     loader order, to ``collector.add`` (a :class:`~.preprocess.VisibilityCollectorDevice`; its
     conversion and compression kernels run asynchronously on its queue, which plays the role of
@@ -204,6 +204,16 @@ def preprocess_visibilities(dataset, collector, start_channel, stop_channel, pol
     coverage) over all blocks.  With ``bin`` above 1 there is no ``continuum_centre``: its second
     shift would need the averaged frequencies.
 
+    ``statwt`` (:class:`~.statwt.StatWtParameters`; new here) rescales the weights of every block to
+    inverse variances measured from the scatter of its visibilities (``statwt.StatWt`` on the
+    collector's queue, fed the block's ``baselines``): per block it runs right after the continuum
+    fit and BEFORE the second shift of ``continuum_centre`` -- a shift puts a per-channel phase ramp
+    on any continuum left over, and a ramp reads as scatter; what the fit leaves is noise, which does
+    not mind the order.  Its mask spans the channels the operator sees, the spectral filter's outputs
+    if there is one (ValueError, before any block is read, if it does not fit them).  Groups never
+    span blocks.  The collector gets ``statwt_counts``: the (group, polarization) pairs (kept,
+    flagged) over all blocks.
+
     With none of the keywords the function is what it was."""
     if continuum_centre is not None and continuum is None:
         raise ValueError('continuum_centre needs continuum')
@@ -214,7 +224,9 @@ def preprocess_visibilities(dataset, collector, start_channel, stop_channel, pol
         if collector.num_channels != channels_out:
             raise ValueError('the spectral filter gives {} channels, the collector was made for {}'.format(
                 channels_out, collector.num_channels))
-    if continuum is None and phase_centre is None and spectral is None:
+    if statwt is not None:
+        statwt.mask(stop_channel - start_channel if spectral is None else channels_out)
+    if continuum is None and phase_centre is None and spectral is None and statwt is None:
         try:
             for chunk in data_iter(dataset, vis_limit, vis_load, start_channel, stop_channel):
                 collector.add(chunk['uvw'], chunk['weights'], chunk['vis'],
@@ -223,16 +235,19 @@ def preprocess_visibilities(dataset, collector, start_channel, stop_channel, pol
             collector.close()
         return collector
     return _preprocess_device(dataset, collector, start_channel, stop_channel, polarization_matrices,
-                              vis_load, vis_limit, continuum, phase_centre, continuum_centre, spectral)
+                              vis_load, vis_limit, continuum, phase_centre, continuum_centre, spectral,
+                              statwt)
 
 
 def _preprocess_device(dataset, collector, start_channel, stop_channel, polarization_matrices,
-                       vis_load, vis_limit, continuum, phase_centre, continuum_centre, spectral):
+                       vis_load, vis_limit, continuum, phase_centre, continuum_centre, spectral,
+                       statwt=None):
     """:func:`preprocess_visibilities` with any of its operators: every block goes to the device
     once and through them on the collector's queue."""
     from . import accel, phaseshift
     from .continuum import UVContSubTemplate
     from .spectral import SpectralFilterTemplate
+    from .statwt import StatWtTemplate
     queue = collector.queue
     context = queue.context
     shifted = phase_centre is not None or continuum_centre is not None
@@ -261,6 +276,9 @@ def _preprocess_device(dataset, collector, start_channel, stop_channel, polariza
         subtract = None
         if continuum is not None:
             subtract = UVContSubTemplate(context, continuum).instantiate(queue, channels)
+        reweight = None
+        if statwt is not None:
+            reweight = StatWtTemplate(context, statwt).instantiate(queue, channels)
         for chunk in data_iter(dataset, vis_limit, vis_load, start_channel, stop_channel):
             vis = accel.DeviceArray(context, chunk['vis'].shape, np.complex64, queue=queue)
             weights = accel.DeviceArray(context, chunk['weights'].shape, np.float32, queue=queue)
@@ -278,6 +296,8 @@ def _preprocess_device(dataset, collector, start_channel, stop_channel, polariza
                 vis, weights = smooth(vis, weights)
             if subtract is not None:
                 subtract(vis, weights)
+            if reweight is not None:
+                reweight(vis, weights, chunk['baselines'])
             if after is not None:
                 if after.template.params.writes_uvw:
                     uvw = after(vis, uvw)
@@ -289,6 +309,8 @@ def _preprocess_device(dataset, collector, start_channel, stop_channel, polariza
             collector.spectral_counts = smooth.counts()
         if subtract is not None:
             collector.continuum_counts = subtract.counts()
+        if reweight is not None:
+            collector.statwt_counts = reweight.counts()
         if shifted:
             collector.phase_centre = target
     finally:
