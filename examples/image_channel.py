@@ -9,6 +9,7 @@ store -> imaging weights, PSF, major/minor cycles -> restored image, all on one 
     python examples/image_channel.py --primary-beam 0.3     (see primary_beam_channel)
     python examples/image_channel.py --spectral hanning,2   (a band with a one-channel line; see spectral_line)
     python examples/image_channel.py --statwt 8             (noise that differs between baselines; see statwt_band)
+    python examples/image_channel.py --rfiflag              (bursts of interference in a band of noise; see rfiflag_band)
 
 It follows the reference's per-channel flow (frontend.py:31-83 preprocess_visibilities,
 :465-658 process_channel) with the loaders and FITS output left out: the sky is three point
@@ -426,6 +427,73 @@ def statwt_band(args):
     return results
 
 
+def rfiflag_band(args):
+    """--rfiflag [THRESHOLD]: a synthetic band of 16 channels of noise of sigma 1 under weights of
+    1 with bursts of interference injected -- one channel x 5 integrations of 30 sigma on every 50th
+    baseline, one integration x all channels of 10 sigma on every 50th other -- through
+    ``loader.preprocess_visibilities`` with ``statwt=`` (groups of 8 rows), without and with
+    ``rfiflag=``; prints, for one channel, the fraction of samples flagged, the image noise statwt's
+    weights predict and the rms measured in the central half of the dirty image."""
+    import synth
+    from katsdpimager_amd import (accel, frontend, imaging, loader, parameters, preprocess, rfiflag, statwt,
+                                  weight)
+    keywords = dict(threshold=float(args.rfiflag)) if args.rfiflag else {}
+    C = 16
+    params = rfiflag.RFIFlagParameters(**keywords)
+    reweight = statwt.StatWtParameters(8)
+    ctx = accel.create_some_context()
+    queue = ctx.create_command_queue()
+    rows = max(args.vis // C, 1000)
+    obs = synth.make_observation(args.pixels, rows, args.w_planes, 1, device='cpu')
+    image_p, grid_p, array_p = synth.make_parameters(obs, 1, args.kernel_width, degrid=True)
+    # (synth's tracks are baseline-major: ceil(rows / baselines) consecutive rows each)
+    num_baselines = synth.baselines_equatorial().shape[0]
+    per_baseline = -(-rows // num_baselines)
+    baseline = (np.arange(rows) // per_baseline).astype(np.int32)
+    rng = np.random.default_rng(6)
+    vis = (rng.normal(size=(rows, C, 1)) + 1j * rng.normal(size=(rows, C, 1))).astype(np.complex64)
+    bursts = 0
+    for b in range(0, int(baseline[-1]) + 1, 25):
+        first = b * per_baseline + int(rng.integers(max(per_baseline - 5, 1)))
+        if b % 50 == 0:
+            vis[first:first + 5, int(rng.integers(C)), 0] += np.complex64(30.0)
+        else:
+            vis[first, :, 0] += np.complex64(10.0)
+        bursts += 1
+    dataset = loader.LoaderArrays(obs.uvw.numpy(), vis, np.ones((rows, C, 1), np.float32), baseline,
+                                  _frequencies(obs, C), [0])
+    weight_p = parameters.WeightParameters(weight.WeightType.ROBUST, 0.0)
+    # (one minor cycle: the residual is the dirty image but for one component of noise)
+    clean_p = parameters.CleanParameters(1, 0.1, 0.85, 5.0, 0, 0.01, 0.5, 0.02)
+    template = imaging.ImagingTemplate(ctx, array_p, image_p.fixed, weight_p, grid_p.fixed, clean_p)
+    imager = template.instantiate(queue, image_p, grid_p, args.vis_block, 0, 1, streams=2)
+    imager.ensure_all_bound()
+    imager.one_call_major_cycles = False
+    ident = np.ones((1, 1), np.complex64)
+    G = args.pixels
+    results = {}
+    print('{} rows of {} channels, {} baselines of {} rows, noise of sigma 1, {} bursts'.format(
+        rows, C, len(np.unique(baseline)), per_baseline, bursts))
+    for label, keyword in (('not flagged', None), ('flagged', params)):
+        collector = preprocess.VisibilityCollectorDevice(queue, [image_p] * C, [grid_p] * C, args.vis_block)
+        loader.preprocess_visibilities(dataset, collector, 0, C, (ident, None), statwt=reweight,
+                                       rfiflag=keyword)
+        fraction = 0.0
+        if keyword is not None:
+            kept, flagged, skipped = collector.rfiflag_counts
+            fraction = flagged / max(kept + flagged, 1)
+            print('rfiflag {}: {} samples kept, {} flagged, {} pairs skipped'.format(params, kept, flagged, skipped))
+        reader = collector.reader()
+        stats = frontend.process_channel(reader, 0, imager, image_p, grid_p, clean_p,
+                                         weight_p.weight_type, args.vis_block, 1, True)
+        dirty = imager.get_buffer('dirty')[0][G // 4:3 * G // 4, G // 4:3 * G // 4]
+        rms = float(np.sqrt(np.mean(np.square(dirty, dtype=np.float64))))
+        results[label] = dict(flagged_fraction=fraction, weights_noise=stats['weights_noise'], rms=rms)
+        print('{:12s}: {:.4f} of the samples flagged; statwt\'s weights predict an image noise of {:.6g}; '
+              'measured rms {:.6g}'.format(label, fraction, stats['weights_noise'], rms))
+    return results
+
+
 def _frequencies(obs, channels):
     return 299792458.0 / obs.wavelength + 1.0e5 * np.arange(channels)
 
@@ -474,7 +542,13 @@ def main(argv=None):
                     help='instead of the three-source channel: a synthetic band of noise whose sigma differs from '
                          'baseline to baseline under equal weights, imaged without and with the weights rescaled '
                          'from the scatter of groups of TIME_BIN rows (the listed channels left out), e.g. --statwt 8')
+    ap.add_argument('--rfiflag', metavar='THRESHOLD', nargs='?', const='',
+                    help='instead of the three-source channel: a synthetic band of noise with bursts of '
+                         'interference, imaged without and with the SumThreshold flagger (its defaults, or this '
+                         'threshold), e.g. --rfiflag 8')
     args = ap.parse_args(argv)
+    if args.rfiflag is not None:
+        return rfiflag_band(args)
     if args.statwt:
         return statwt_band(args)
     if args.spectral:

@@ -1179,6 +1179,85 @@ int kimg_statwt(const void *vis, int64_t vis_channel_pitch, float *weights,
                 double chi2_hi, double *chi2, void *workspace, size_t workspace_bytes,
                 uint64_t *counts, void *stream);
 
+/* ---- RFI flagging (rfiflag.hip): interference found in the time-frequency plane of every baseline of
+ * a block of RAW visibilities by SumThreshold (AOFlagger; CASA flagdata tfcrop / rflag with
+ * extendflags) and taken out by zeroing weights, after kimg_uvcontsub and ahead of kimg_statwt.  The
+ * reference has none; the semantics are this library's, and katsdpimager_amd/rfiflag.py holds them
+ * once more as numpy (rfiflag_host).  The device matches that twin bit for bit.
+ *
+ * vis, weights, the block layout, the pitches, group_offsets / row_group (statwt.group_offsets) and
+ *   time_bin: as for kimg_statwt.  A group is one baseline's time-frequency plane of C channels by
+ *   T <= time_bin rows, taken per polarization.  vis is never written.
+ * mask_host: HOST uint8 [C], nonzero = a mask channel: searched for interference, part of the level.
+ *   The other channels are PROTECTED (line channels: a bright line is constant in time and would be
+ *   flagged): they never enter the level, no window flags them, inside a frequency window they count
+ *   as flagged on entry, and only extension 1 below reaches them.
+ * A sample (c, r, p) is usable iff its weight w is above 0 and finite and both parts of its
+ *   visibility (re, im) are finite -- kimg_statwt's predicate.  An unusable sample keeps its weight
+ *   bit for bit, is never flagged and never counted.
+ * Statistic: z = w * (re * re + im * im) in float64, the sum and then the product rounded (the
+ *   squares of float32 values are exact).
+ * Level, per group and polarization, from the usable samples of mask channels: L0 = Z / M, Z the sum
+ *   of z and M the number of samples; then for j = 1 .. level_iterations (0 ..
+ *   KIMG_RFIFLAG_MAX_LEVEL_ITERATIONS) Lj = Z / M over those of them with z <= level_clip * L(j-1)
+ *   (one product).  Sums in kimg_statwt's order: per row over channels in ascending c from 0, then
+ *   over the group's rows in ascending r from 0; M an integer converted once.  If any of these M is
+ *   0, or any L is not finite or not above 0, the (group, polarization) is SKIPPED: nothing of it is
+ *   flagged by any step below.
+ * SumThreshold: for m = 1, 2, 4, ... <= max_window (a power of two up to KIMG_RFIFLAG_MAX_WINDOW),
+ *   k = log2 m, with chi = factors_host[k] * L and the limit (double) m * chi.  factors_host: HOST
+ *   float64 [log2(max_window) + 1], each above 0 (threshold / rho^k, made by the caller), read
+ *   during the call.  Passes run in ascending m; each reads the flags that entered it and ORs its
+ *   own in afterwards, so within a pass nothing depends on the order of evaluation.  In a pass, for
+ *   each direction of `directions` (KIMG_RFIFLAG_TIME | KIMG_RFIFLAG_FREQ):
+ *     frequency: for every row and every s with s + m <= C, the sum over c = s .. s + m - 1 in
+ *       ascending order from 0.0, to which a usable sample of a mask channel that is not flagged on
+ *       entry adds z - L (one subtraction, rounded) and every other sample adds chi.  If at least
+ *       one sample added its own term and the sum is above the limit, every usable sample of a mask
+ *       channel in the window is flagged.  (z of noise is exponentially distributed, mean and
+ *       scatter both L: z - L has mean 0 and chi counts in sigma, as SumThreshold's factors do.)
+ *     time: the same over the rows t = s .. s + m - 1 of one group, s + m <= the group's end, in one
+ *       mask channel.
+ * Extension, after the last pass, each step on the flags as the previous one left them:
+ *   1. extend_freq in (0, 1], or 0 for none: a (row, polarization) with F of its U usable samples of
+ *      mask channels flagged and (double) F > extend_freq * (double) U has ALL its usable samples
+ *      flagged, protected channels included.
+ *   2. extend_time, likewise: a (group, mask channel, polarization) with F of its U usable rows
+ *      flagged and (double) F > extend_time * (double) U has all its usable rows flagged.
+ *   3. extend_pols != 0: a sample flagged in any polarization is flagged in every polarization in
+ *      which it is usable and whose (group, polarization) is not skipped.
+ * Outputs.  weights: +0.0f where flagged, else untouched.  flags: DEVICE uint8 [C][N][P], dense:
+ *   1 = flagged by this call, else 0.  level: DEVICE float64 [G][P], the final L, NaN where skipped.
+ *   counts: DEVICE uint64 [3]: usable samples kept, usable samples flagged (all channels) and skipped
+ *   (group, polarization) pairs of the call are ADDED to it (one atomic add per wave and counter).
+ * workspace: DEVICE, 8-byte aligned, at least KIMG_RFIFLAG_WORKSPACE_PER_ELEMENT * C * N * P +
+ *   KIMG_RFIFLAG_WORKSPACE_PER_ROW * N * P bytes (KIMG_EWORKSPACE otherwise): z and a byte of flag
+ *   state per sample, two sets of the level's per-row partial sums.
+ * Returns, before any HIP call: KIMG_EINVAL for a null pointer argument; for C < 1, N < 0, P outside
+ *   1 .. 4, time_bin outside 1 .. KIMG_STATWT_MAX_BIN, max_window not a power of two in 1 ..
+ *   KIMG_RFIFLAG_MAX_WINDOW, directions outside 1 .. 3, level_iterations outside its range, a
+ *   level_clip or a factor not above 0 (or NaN), an extension share outside [0, 1];
+ *   KIMG_EUNSUPPORTED for N > 2^31 - 1; KIMG_EINVAL for a pitch below N * P; KIMG_EUNSUPPORTED for
+ *   C > KIMG_UVCONTSUB_MAX_CHANNELS.  N = 0 is then a successful call that does nothing.  Then
+ *   KIMG_EINVAL for G < 1, G > N or G * time_bin < N, KIMG_EWORKSPACE for a short workspace and
+ *   KIMG_EINVAL for one that is not 8-byte aligned.
+ * Asynchronous on `stream`, plain launches, no allocation; equal inputs give equal bits.
+ * Not done here: a surface-fit high-pass, medians, groups across block boundaries, a refit of the
+ *   continuum on the flagged residuals. */
+#define KIMG_RFIFLAG_MAX_WINDOW 32
+#define KIMG_RFIFLAG_MAX_LEVEL_ITERATIONS 4
+#define KIMG_RFIFLAG_WORKSPACE_PER_ELEMENT 9
+#define KIMG_RFIFLAG_WORKSPACE_PER_ROW 24
+#define KIMG_RFIFLAG_TIME 1
+#define KIMG_RFIFLAG_FREQ 2
+int kimg_rfi_flag(const void *vis, int64_t vis_channel_pitch, float *weights,
+                  int64_t weights_channel_pitch, int num_channels, int64_t num_rows, int num_pols,
+                  const uint8_t *mask_host, const int32_t *group_offsets, int64_t num_groups,
+                  const int32_t *row_group, int time_bin, const double *factors_host, int max_window,
+                  int directions, int level_iterations, double level_clip, double extend_freq,
+                  double extend_time, int extend_pols, uint8_t *flags, double *level,
+                  void *workspace, size_t workspace_bytes, uint64_t *counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

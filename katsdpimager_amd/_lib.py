@@ -124,6 +124,11 @@ PROTOTYPES = {
     # statistical reweighting: (vis, pitch, weights, pitch, C, N, P), fit_mask_host, (group_offsets, G,
     # row_group), time_bin, min_samples, (chi2_lo, chi2_hi), chi2, (workspace, bytes), counts, stream
     'kimg_statwt': (c_int, [P, L, P, L, I, L, I, P, P, L, P, I, I, D, D, P, P, c_size_t, P, P]),
+    # RFI flagging: (vis, pitch, weights, pitch, C, N, P), mask_host, (group_offsets, G, row_group),
+    # time_bin, (factors_host, max_window), directions, (level_iterations, level_clip), (extend_freq,
+    # extend_time, extend_pols), flags, level, (workspace, bytes), counts, stream
+    'kimg_rfi_flag': (c_int, [P, L, P, L, I, L, I, P, P, L, P, I, P, I, I, I, D, D, D, I, P, P, P,
+                              c_size_t, P, P]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),

@@ -166,7 +166,8 @@ def data_iter(dataset, vis_limit, vis_load, start_channel, stop_channel):
 
 def preprocess_visibilities(dataset, collector, start_channel, stop_channel, polarization_matrices,
                             vis_load=32 * 1048576, vis_limit=None, continuum=None,
-                            phase_centre=None, continuum_centre=None, spectral=None, statwt=None):
+                            phase_centre=None, continuum_centre=None, spectral=None, statwt=None,
+                            rfiflag=None):
     """frontend.preprocess_visibilities (frontend.py:40-84): feed every block of the loader, in
     loader order, to ``collector.add`` (a :class:`~.preprocess.VisibilityCollectorDevice`; its
     conversion and compression kernels run asynchronously on its queue, which plays the role of
@@ -214,6 +215,16 @@ def preprocess_visibilities(dataset, collector, start_channel, stop_channel, pol
     span blocks.  The collector gets ``statwt_counts``: the (group, polarization) pairs (kept,
     flagged) over all blocks.
 
+    ``rfiflag`` (:class:`~.rfiflag.RFIFlagParameters`; new here) flags interference per sample
+    (``rfiflag.RFIFlag`` on the collector's queue, fed the block's ``baselines``): SumThreshold over
+    every baseline's time-frequency plane of the block, the weights of the flagged samples set to 0.
+    Per block it runs right after the continuum fit, on its residuals, and before ``statwt``, which
+    then measures the scatter of what is left.  Its mask spans the channels the operator sees, as
+    for ``statwt`` (ValueError, before any block is read, if it does not fit them); groups never
+    span blocks.  The collector gets ``rfiflag_counts``: usable samples (kept, flagged) and (group,
+    polarization) pairs skipped, over all blocks.  The continuum is not fitted again on the flagged
+    residuals.
+
     With none of the keywords the function is what it was."""
     if continuum_centre is not None and continuum is None:
         raise ValueError('continuum_centre needs continuum')
@@ -226,7 +237,10 @@ def preprocess_visibilities(dataset, collector, start_channel, stop_channel, pol
                 channels_out, collector.num_channels))
     if statwt is not None:
         statwt.mask(stop_channel - start_channel if spectral is None else channels_out)
-    if continuum is None and phase_centre is None and spectral is None and statwt is None:
+    if rfiflag is not None:
+        rfiflag.mask(stop_channel - start_channel if spectral is None else channels_out)
+    if continuum is None and phase_centre is None and spectral is None and statwt is None \
+            and rfiflag is None:
         try:
             for chunk in data_iter(dataset, vis_limit, vis_load, start_channel, stop_channel):
                 collector.add(chunk['uvw'], chunk['weights'], chunk['vis'],
@@ -236,18 +250,19 @@ def preprocess_visibilities(dataset, collector, start_channel, stop_channel, pol
         return collector
     return _preprocess_device(dataset, collector, start_channel, stop_channel, polarization_matrices,
                               vis_load, vis_limit, continuum, phase_centre, continuum_centre, spectral,
-                              statwt)
+                              statwt, rfiflag)
 
 
 def _preprocess_device(dataset, collector, start_channel, stop_channel, polarization_matrices,
                        vis_load, vis_limit, continuum, phase_centre, continuum_centre, spectral,
-                       statwt=None):
+                       statwt=None, rfiflag=None):
     """:func:`preprocess_visibilities` with any of its operators: every block goes to the device
     once and through them on the collector's queue."""
     from . import accel, phaseshift
     from .continuum import UVContSubTemplate
     from .spectral import SpectralFilterTemplate
     from .statwt import StatWtTemplate
+    from .rfiflag import RFIFlagTemplate
     queue = collector.queue
     context = queue.context
     shifted = phase_centre is not None or continuum_centre is not None
@@ -276,6 +291,9 @@ def _preprocess_device(dataset, collector, start_channel, stop_channel, polariza
         subtract = None
         if continuum is not None:
             subtract = UVContSubTemplate(context, continuum).instantiate(queue, channels)
+        flag = None
+        if rfiflag is not None:
+            flag = RFIFlagTemplate(context, rfiflag).instantiate(queue, channels)
         reweight = None
         if statwt is not None:
             reweight = StatWtTemplate(context, statwt).instantiate(queue, channels)
@@ -296,6 +314,8 @@ def _preprocess_device(dataset, collector, start_channel, stop_channel, polariza
                 vis, weights = smooth(vis, weights)
             if subtract is not None:
                 subtract(vis, weights)
+            if flag is not None:
+                flag(vis, weights, chunk['baselines'])
             if reweight is not None:
                 reweight(vis, weights, chunk['baselines'])
             if after is not None:
@@ -309,6 +329,8 @@ def _preprocess_device(dataset, collector, start_channel, stop_channel, polariza
             collector.spectral_counts = smooth.counts()
         if subtract is not None:
             collector.continuum_counts = subtract.counts()
+        if flag is not None:
+            collector.rfiflag_counts = flag.counts()
         if reweight is not None:
             collector.statwt_counts = reweight.counts()
         if shifted:
