@@ -1258,6 +1258,78 @@ int kimg_rfi_flag(const void *vis, int64_t vis_channel_pitch, float *weights,
                   double extend_time, int extend_pols, uint8_t *flags, double *level,
                   void *workspace, size_t workspace_bytes, uint64_t *counts, void *stream);
 
+/* ---- Moment maps (moments.hip): a spectral cube of images reduced along its channel axis to the
+ * maps a spectral-line user reads (CASA immoments, MIRIAD moment): integrated intensity (moment 0),
+ * intensity-weighted coordinate (1), dispersion (2), peak (8) and coordinate of the peak (9), each
+ * taken over the samples above a per-channel cut.  The reference has none; the semantics are this
+ * library's, and katsdpimager_amd/cube.py holds them once more as numpy (moments_host).
+ *
+ * cube: DEVICE float32 [C][M], read only, never written: C = num_channels (1 ..
+ *   KIMG_MOMENTS_MAX_CHANNELS) planes of M = plane_elements values (for images [P][H][W], dense,
+ *   M = P * H * W), channel_pitch elements apart, channel_pitch >= M.  Elements of the padding are
+ *   neither read nor written.  Indices are 64-bit throughout.
+ * Tables, per channel: x DEVICE float64 [C], the coordinate of every channel (km/s or Hz: the
+ *   library does not care); cut DEVICE float32 [C], made by the caller -- float32(clip_sigma) *
+ *   noise[c] as one float32 product, an absolute cut, or -inf for none; filled_host HOST uint8 [C],
+ *   nonzero = the plane holds an image.  filled_host is read during the call and travels to the
+ *   kernel by value, a bit per channel; x and cut are read by the kernel (scalar loads).
+ * Per element m of the plane on its own, over the channels c = first .. stop - 1 (0 <= first < stop
+ *   <= C) in ascending order, with I = cube[c][m]:
+ *   I is usable iff filled[c] and I is finite.
+ *   Selection value: s = (double) I, or with select_hanning != 0
+ *       s = ((0.25 * a) + (0.5 * I)) + (0.25 * b)    in float64, every product and sum rounded,
+ *     a = cube[c - 1][m] and b = cube[c + 1][m], each replaced by I itself where that channel is
+ *     outside first .. stop - 1, not filled, or not finite at m (the replicate rule).
+ *   The sample ENTERS iff I is usable and s > (double) cut[c] (false for a NaN cut).
+ *   For each sample that enters, in float64, nothing fused:
+ *       n += 1;  d = x[c] - x_ref;  S0 += I;  t = I * d;  S1 += t;  S2 += t * d
+ *     and the peak (float32, starting below everything) is replaced, with its channel, only if
+ *     I > peak: the first channel wins a tie.
+ *   x_ref = x[(first + stop) / 2] (integer division).  width: the caller's, float64: the absolute
+ *     mean spacing |x[stop - 1] - x[first]| / (stop - first - 1) of the range, or the channel width
+ *     on that axis for a range of one channel.
+ * Outputs, float32 [M] each, every value ONE rounding of a float64:
+ *     moment 0   S0 * width
+ *     moment 1   x_ref + r,  r = S1 / S0
+ *     moment 2   sqrt(v),  v = S2 / S0 - r * r (division, product, difference), 0 in place of v < 0
+ *     moment 8   the peak
+ *     moment 9   x of the peak's channel
+ *   and count, int32 [M] = n.  Every moment is NaN where n == 0; moments 1 and 2 are NaN unless
+ *   S0 > 0.  outputs: the KIMG_MOMENT_* bits of what is written; the pointer of a bit that is not set
+ *   is ignored (NULL will do) and nothing is written through it.
+ * Agreement with the twin: bit for bit for moments 0, 1, 8, 9 and count (IEEE additions, products
+ *   and divisions in one fixed order).  Moment 2 too: the float64 sqrt of this build is the
+ *   compiler's expansion of llvm.sqrt.f64 (read in the assembly of moments.hip) -- y = v_rsq_f64(x),
+ *   g = x y, h = y / 2, one Goldschmidt step on both in FMAs, then twice the residual correction
+ *   d = fma(-g, g, x), g = fma(d, h, g), the input scaled by 2^256 below 2^-767 -- whose last FMA
+ *   rounds an estimate already inside an ulp once more against the exact residual: correctly
+ *   rounded, as numpy's sqrt is.  The tests assert equal bits, not a bound.
+ * Kernel forms (the host picks): four consecutive elements per thread with 16-byte loads and stores
+ *   when cube, channel_pitch * 4 and every requested output are 16-byte aligned, for the first
+ *   4 * (M / 4) elements; one element per thread for the tail and for everything else.  One launch
+ *   per form, every voxel of the range read once (never for a channel that is not filled), no LDS,
+ *   no atomics, no workspace.
+ * Returns, before any HIP call: KIMG_EINVAL for a null cube, x, cut or filled_host; for C < 1,
+ *   M < 0, a range outside 0 <= first < stop <= C, a pitch below M, a width that is NaN, outputs
+ *   without any KIMG_MOMENT_* bit or with others, or a requested output that is NULL (or not
+ *   4-byte aligned); KIMG_EUNSUPPORTED for C > KIMG_MOMENTS_MAX_CHANNELS or M beyond the grid limit
+ *   (2^31 - 1 workgroups of 256 elements).  M = 0 is then a successful call that does nothing.
+ * Asynchronous on `stream`, no allocation, capturable; equal inputs give equal bits.
+ * Not done here: a common restoring beam across planes, spatial smoothing of the selection,
+ *   image-plane continuum subtraction, position-velocity cuts, medians (CASA moments 3 to 7, 10,
+ *   11), cubes across several GPUs. */
+#define KIMG_MOMENTS_MAX_CHANNELS 4096
+#define KIMG_MOMENT_0 1
+#define KIMG_MOMENT_1 2
+#define KIMG_MOMENT_2 4
+#define KIMG_MOMENT_8 8
+#define KIMG_MOMENT_9 16
+#define KIMG_MOMENT_COUNT 32
+int kimg_moments(const float *cube, int64_t channel_pitch, int num_channels, int64_t plane_elements,
+                 int first, int stop, const double *x, const float *cut, const uint8_t *filled_host,
+                 double width, int select_hanning, int outputs, float *moment0, float *moment1,
+                 float *moment2, float *moment8, float *moment9, int32_t *count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

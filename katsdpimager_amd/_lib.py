@@ -129,6 +129,9 @@ PROTOTYPES = {
     # extend_time, extend_pols), flags, level, (workspace, bytes), counts, stream
     'kimg_rfi_flag': (c_int, [P, L, P, L, I, L, I, P, P, L, P, I, P, I, I, I, D, D, D, I, P, P, P,
                               c_size_t, P, P]),
+    # moment maps: (cube, pitch, C, M), (first, stop), (x, cut, filled_host), width, select_hanning,
+    # outputs (KIMG_MOMENT_* bits), (moment0, moment1, moment2, moment8, moment9, count), stream
+    'kimg_moments': (c_int, [P, L, I, L, I, I, P, P, P, D, I, I, P, P, P, P, P, P, P]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),

@@ -1,0 +1,303 @@
+// Moment maps (include/kimg.h, "Moment maps"): a cube [C][M] of images reduced along its channel axis
+// to integrated intensity, intensity-weighted coordinate, dispersion, peak and coordinate of the peak
+// over the samples above a per-channel cut.  katsdpimager_amd/cube.py holds the same contract as numpy
+// (moments_host), and the order of every sum below is that contract's: the device has the twin's bits.
+//
+// One kernel, a column reduction: a thread owns V consecutive elements of the plane (V = 4 with
+// 16-byte loads, or 1) for the whole channel loop, so no sum crosses threads and the order of
+// summation is the loop's.  Adjacent lanes take adjacent elements: a wave reads 1 KiB (V = 4) or 256 B
+// of one channel per load.  The channel loop is unrolled by MM_UNROLL with all loads of a round issued
+// before the first is consumed; a thread has 64 bytes in flight at V = 4.  The per-channel tables are
+// uniform across the wave: x and cut come through scalar loads, `filled` as a bit mask by value in the
+// kernel arguments, and a channel that is not filled is skipped by a uniform branch without a load.
+// With select_hanning the three-channel window lives in registers (prev, cur and the round's loads of
+// the NEXT channels), so every voxel is still read once.  A NaN stands for "no neighbour" in that
+// window -- outside the range, not filled or not finite are one case under the replicate rule.
+#include "kimg_common.h"
+
+namespace {
+
+constexpr int MM_THREADS = 256;
+constexpr int MM_UNROLL = 4;                    // channels whose loads are in flight together
+constexpr int MM_MAX_CHANNELS = KIMG_MOMENTS_MAX_CHANNELS;
+constexpr int MM_ALL = KIMG_MOMENT_0 | KIMG_MOMENT_1 | KIMG_MOMENT_2 | KIMG_MOMENT_8 | KIMG_MOMENT_9
+                       | KIMG_MOMENT_COUNT;
+
+// (one word more than the channels need: mm_filled_from reads two adjacent words)
+struct mm_filled {
+    uint32_t bits[MM_MAX_CHANNELS / 32 + 1];
+};
+
+struct mm_out {
+    float *m0, *m1, *m2, *m8, *m9;
+    int32_t *count;
+};
+
+struct mm_acc {
+    double S0, S1, S2;
+    float peak;
+    int n, pc;
+};
+
+__device__ inline float mm_nan() { return __int_as_float(0x7fc00000); }
+
+// Bit u of the result: channel c + u is filled, for u = 0 .. 32 -- one read of two adjacent words per
+// round of the channel loop.  c is clamped so that the index stays in the mask whatever the caller's
+// range; channels at and past `stop` are the caller's to mask out.
+__device__ inline uint64_t mm_filled_from(const mm_filled &f, int c)
+{
+    c = min(max(c, 0), MM_MAX_CHANNELS - 1);
+    const int i = c >> 5;
+    return (((uint64_t) f.bits[i + 1] << 32) | f.bits[i]) >> (c & 31);
+}
+
+template <int V> __device__ inline void mm_load(const float *p, float (&v)[V])
+{
+    if constexpr (V == 4) {
+        const float4 t = *reinterpret_cast<const float4 *>(p);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+        v[0] = *p;
+    }
+}
+
+template <int V, class T> __device__ inline void mm_store(T *p, const T (&v)[V])
+{
+    if constexpr (V == 4) {
+        struct alignas(16) quad { T a, b, c, d; };
+        *reinterpret_cast<quad *>(p) = quad{v[0], v[1], v[2], v[3]};
+    } else {
+        *p = v[0];
+    }
+}
+
+// One sample: I of channel c with selection value s against the cut ct; d = x[c] - x_ref
+template <bool SECOND>
+__device__ inline void mm_add(mm_acc &a, float I, double s, double ct, double d, int c)
+{
+    const bool enter = isfinite(I) && s > ct;
+    const double Id = (double) I;
+    a.n += enter ? 1 : 0;
+    a.S0 = enter ? a.S0 + Id : a.S0;
+    if constexpr (SECOND) {
+        const double t = Id * d;
+        a.S1 = enter ? a.S1 + t : a.S1;
+        a.S2 = enter ? a.S2 + t * d : a.S2;
+    }
+    const bool higher = enter && I > a.peak;
+    a.peak = higher ? I : a.peak;
+    a.pc = higher ? c : a.pc;
+}
+
+// `groups` threads have work: thread t owns the elements t * V .. t * V + V - 1
+template <int V, bool HANNING, bool SECOND>
+__global__ __launch_bounds__(MM_THREADS)
+void moments_kernel(const float *__restrict__ cube, int64_t pitch, int64_t groups, int first, int stop,
+                    const double *__restrict__ x, const float *__restrict__ cut,
+                    const mm_filled filled, double width, mm_out out)
+{
+    const int64_t t = (int64_t) blockIdx.x * MM_THREADS + threadIdx.x;
+    const bool live = t < groups;
+    // (lanes past the plane run along with clamped addresses and store nothing)
+    const int64_t j = (live ? t : 0) * V;
+    const float *p = cube + j;
+    const double x_ref = x[(first + stop) / 2];
+    mm_acc acc[V];
+#pragma unroll
+    for (int e = 0; e < V; e++) {
+        acc[e].S0 = acc[e].S1 = acc[e].S2 = 0.0;
+        acc[e].peak = -INFINITY;
+        acc[e].n = 0;
+        acc[e].pc = first;
+    }
+
+    if constexpr (!HANNING) {
+        for (int c0 = first; c0 < stop; c0 += MM_UNROLL) {
+            float v[MM_UNROLL][V];
+            bool on[MM_UNROLL];
+            const uint64_t have = mm_filled_from(filled, c0);
+#pragma unroll
+            for (int u = 0; u < MM_UNROLL; u++) {
+                const int c = c0 + u;
+                on[u] = c < stop && ((have >> u) & 1);
+#pragma unroll
+                for (int e = 0; e < V; e++)
+                    v[u][e] = mm_nan();
+                if (on[u])
+                    mm_load<V>(p + (int64_t) c * pitch, v[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < MM_UNROLL; u++) {
+                if (on[u]) {
+                    const int c = c0 + u;
+                    const double d = x[c] - x_ref;
+                    const double ct = (double) cut[c];
+#pragma unroll
+                    for (int e = 0; e < V; e++)
+                        mm_add<SECOND>(acc[e], v[u][e], (double) v[u][e], ct, d, c);
+                }
+            }
+        }
+    } else {
+        float prev[V], cur[V];
+#pragma unroll
+        for (int e = 0; e < V; e++)
+            prev[e] = cur[e] = mm_nan();
+        if (mm_filled_from(filled, first) & 1)
+            mm_load<V>(p + (int64_t) first * pitch, cur);
+        for (int c0 = first; c0 < stop; c0 += MM_UNROLL) {
+            float next[MM_UNROLL][V];       // the channels c0 + 1 .. c0 + MM_UNROLL
+            const uint64_t have = mm_filled_from(filled, c0);
+#pragma unroll
+            for (int u = 0; u < MM_UNROLL; u++) {
+                const int c = c0 + u + 1;
+#pragma unroll
+                for (int e = 0; e < V; e++)
+                    next[u][e] = mm_nan();
+                if (c < stop && ((have >> (u + 1)) & 1))
+                    mm_load<V>(p + (int64_t) c * pitch, next[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < MM_UNROLL; u++) {
+                const int c = c0 + u;
+                if (c < stop) {
+                    const double d = x[c] - x_ref;
+                    const double ct = (double) cut[c];
+#pragma unroll
+                    for (int e = 0; e < V; e++) {
+                        const float I = cur[e];
+                        const float a = isfinite(prev[e]) ? prev[e] : I;
+                        const float b = isfinite(next[u][e]) ? next[u][e] : I;
+                        const double s = ((0.25 * (double) a) + (0.5 * (double) I)) + (0.25 * (double) b);
+                        mm_add<SECOND>(acc[e], I, s, ct, d, c);
+                        prev[e] = I;
+                        cur[e] = next[u][e];
+                    }
+                }
+            }
+        }
+    }
+
+    if (!live)
+        return;
+    float m0[V], m1[V], m2[V], m8[V], m9[V];
+    int32_t n[V];
+#pragma unroll
+    for (int e = 0; e < V; e++) {
+        const mm_acc &a = acc[e];
+        const bool any = a.n > 0;
+        const bool positive = any && a.S0 > 0.0;
+        n[e] = a.n;
+        m0[e] = any ? (float) (a.S0 * width) : mm_nan();
+        m8[e] = any ? a.peak : mm_nan();
+        m9[e] = mm_nan();
+        if (out.m9 && any)
+            m9[e] = (float) x[a.pc];
+        m1[e] = m2[e] = mm_nan();
+        if constexpr (SECOND) {
+            const double r = a.S1 / a.S0;
+            const double q = a.S2 / a.S0;
+            double var = q - r * r;
+            var = var < 0.0 ? 0.0 : var;
+            m1[e] = positive ? (float) (x_ref + r) : mm_nan();
+            m2[e] = positive ? (float) sqrt(var) : mm_nan();
+        }
+    }
+    if (out.m0) mm_store<V>(out.m0 + j, m0);
+    if (out.m1) mm_store<V>(out.m1 + j, m1);
+    if (out.m2) mm_store<V>(out.m2 + j, m2);
+    if (out.m8) mm_store<V>(out.m8 + j, m8);
+    if (out.m9) mm_store<V>(out.m9 + j, m9);
+    if (out.count) mm_store<V>(out.count + j, n);
+}
+
+template <int V>
+void mm_launch(const float *cube, int64_t pitch, int64_t groups, int first, int stop, const double *x,
+               const float *cut, const mm_filled &filled, double width, bool hanning, bool second,
+               const mm_out &out, hipStream_t s)
+{
+    const unsigned blocks = (unsigned) kimg_divup(groups, MM_THREADS);
+    auto go = [&](auto h, auto m) {
+        moments_kernel<V, decltype(h)::value, decltype(m)::value><<<blocks, MM_THREADS, 0, s>>>(
+            cube, pitch, groups, first, stop, x, cut, filled, width, out);
+    };
+    using yes = std::true_type;
+    using no = std::false_type;
+    if (hanning)
+        second ? go(yes{}, yes{}) : go(yes{}, no{});
+    else
+        second ? go(no{}, yes{}) : go(no{}, no{});
+}
+
+mm_out mm_offset(const mm_out &o, int64_t by)
+{
+    mm_out r = o;
+    if (r.m0) r.m0 += by;
+    if (r.m1) r.m1 += by;
+    if (r.m2) r.m2 += by;
+    if (r.m8) r.m8 += by;
+    if (r.m9) r.m9 += by;
+    if (r.count) r.count += by;
+    return r;
+}
+
+}  // namespace
+
+extern "C" int kimg_moments(const float *cube, int64_t channel_pitch, int num_channels,
+                            int64_t plane_elements, int first, int stop, const double *x,
+                            const float *cut, const uint8_t *filled_host, double width,
+                            int select_hanning, int outputs, float *moment0, float *moment1,
+                            float *moment2, float *moment8, float *moment9, int32_t *count,
+                            void *stream)
+{
+    KIMG_CHECK_ARG(cube && x && cut && filled_host);
+    KIMG_CHECK_ARG(num_channels >= 1 && plane_elements >= 0);
+    KIMG_CHECK_ARG(first >= 0 && first < stop && stop <= num_channels);
+    KIMG_CHECK_ARG(channel_pitch >= plane_elements);
+    KIMG_CHECK_ARG(width == width);
+    KIMG_CHECK_ARG(outputs != 0 && (outputs & ~MM_ALL) == 0);
+    mm_out out;
+    out.m0 = (outputs & KIMG_MOMENT_0) ? moment0 : nullptr;
+    out.m1 = (outputs & KIMG_MOMENT_1) ? moment1 : nullptr;
+    out.m2 = (outputs & KIMG_MOMENT_2) ? moment2 : nullptr;
+    out.m8 = (outputs & KIMG_MOMENT_8) ? moment8 : nullptr;
+    out.m9 = (outputs & KIMG_MOMENT_9) ? moment9 : nullptr;
+    out.count = (outputs & KIMG_MOMENT_COUNT) ? count : nullptr;
+    const void *ptrs[6] = {out.m0, out.m1, out.m2, out.m8, out.m9, out.count};
+    const int bits[6] = {KIMG_MOMENT_0, KIMG_MOMENT_1, KIMG_MOMENT_2, KIMG_MOMENT_8, KIMG_MOMENT_9,
+                         KIMG_MOMENT_COUNT};
+    uintptr_t alignment = (uintptr_t) cube | ((uintptr_t) channel_pitch * sizeof(float));
+    for (int i = 0; i < 6; i++) {
+        if (outputs & bits[i]) {
+            KIMG_CHECK_ARG(ptrs[i] && ((uintptr_t) ptrs[i] & 3) == 0);
+            alignment |= (uintptr_t) ptrs[i];
+        }
+    }
+    KIMG_CHECK_ARG(((uintptr_t) cube & 3) == 0 && ((uintptr_t) x & 7) == 0 && ((uintptr_t) cut & 3) == 0);
+    if (num_channels > MM_MAX_CHANNELS || plane_elements > (int64_t) 0x7fffffff * MM_THREADS)
+        return KIMG_EUNSUPPORTED;
+    if (plane_elements == 0)
+        return 0;
+
+    mm_filled filled = {};
+    for (int c = 0; c < num_channels; c++)
+        if (filled_host[c])
+            filled.bits[c >> 5] |= 1u << (c & 31);
+    const bool second = outputs & (KIMG_MOMENT_1 | KIMG_MOMENT_2);
+    const bool hanning = select_hanning != 0;
+    hipStream_t s = (hipStream_t) stream;
+    // the form: four elements per thread where every address a thread forms is 16-byte aligned, one
+    // element per thread for the tail and for everything else
+    int64_t done = 0;
+    if ((alignment & 15) == 0 && plane_elements >= 4) {
+        done = plane_elements & ~(int64_t) 3;
+        mm_launch<4>(cube, channel_pitch, done / 4, first, stop, x, cut, filled, width, hanning, second,
+                     out, s);
+    }
+    if (done < plane_elements)
+        mm_launch<1>(cube + done, channel_pitch, plane_elements - done, first, stop, x, cut, filled,
+                     width, hanning, second, mm_offset(out, done), s);
+    return kimg_launch_status();
+}
+
+KIMG_PRELOAD_THIS_UNIT((moments_kernel<1, false, false>))

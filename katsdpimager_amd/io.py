@@ -79,6 +79,45 @@ def write_fits(filename, data, cards):
         f.write(b'\0' * (-len(payload) % _BLOCK))
 
 
+def _sky_cards(image, image_parameters, frequency, frequency_step, phase_centre, beam, bunit, date,
+               ref, step):
+    """The cards both image writers share (io.py:126-181): ``image`` [...][m][l] for DATAMIN and
+    DATAMAX, the FREQ axis starting at ``frequency`` in steps of ``frequency_step``, the STOKES axis
+    at ``ref`` in steps of ``step``."""
+    height, width = image.shape[-2:]
+    if date is None:
+        date = datetime.datetime.utcnow().isoformat(timespec='milliseconds')
+    delt = math.degrees(math.asin(float(image_parameters.pixel_size)))
+    cards = []
+    if bunit is not None:
+        cards.append(('BUNIT', bunit))
+    cards += [
+        ('ORIGIN', 'katsdpimager_amd'), ('HISTORY', 'Created by katsdpimager_amd'),
+        ('TIMESYS', 'UTC'), ('DATE', date),
+        # pixel -> (l, m): the reference point is the image centre; FITS counts from 1 and the
+        # l axis is stored reversed so that RA increases to the left
+        ('CRPIX1', width * 0.5), ('CRPIX2', height * 0.5 + 1.0), ('CRPIX4', 1.0),
+        ('CDELT1', -delt), ('CDELT2', delt), ('CDELT4', float(frequency_step)),
+        ('EQUINOX', 2000.0), ('RADESYS', 'FK5'),
+        ('CUNIT1', 'deg'), ('CUNIT2', 'deg'), ('CUNIT4', 'Hz'),
+        ('CTYPE1', 'RA---SIN'), ('CTYPE2', 'DEC--SIN'), ('CTYPE4', 'FREQ'),
+        ('CRVAL1', math.degrees(float(phase_centre[0]))),
+        ('CRVAL2', math.degrees(float(phase_centre[1]))),
+        ('CRVAL4', float(frequency)),
+    ]
+    if beam is not None:
+        pix = math.degrees(float(image_parameters.pixel_size))
+        cards += [('BMAJ', beam.major * pix), ('BMIN', beam.minor * pix),
+                  ('BPA', math.degrees(float(beam.theta)))]
+    cards += [('CTYPE3', 'STOKES'), ('CRPIX3', 1.0), ('CRVAL3', float(ref)),
+              ('CDELT3', float(step))]
+    datamin = float(np.fmin.reduce(image, axis=None))
+    datamax = float(np.fmax.reduce(image, axis=None))
+    if not math.isnan(datamin):
+        cards += [('DATAMIN', datamin), ('DATAMAX', datamax)]
+    return cards
+
+
 def write_fits_image(image, image_parameters, filename, channel, phase_centre, beam=None,
                      bunit='Jy/beam', extra_fits_headers=None, date=None):
     """io.py:88-204.  ``image`` [polarization][m][l] (phase centre at [M, N] of a 2M x 2N image);
@@ -91,36 +130,8 @@ def write_fits_image(image, image_parameters, filename, channel, phase_centre, b
     ref, step, order = fits_polarization_axis(image_parameters.fixed.polarizations)
     if np.any(order != np.arange(len(order))):
         raise ValueError('polarizations must be in FITS order')
-    if date is None:
-        date = datetime.datetime.utcnow().isoformat(timespec='milliseconds')
-    delt = math.degrees(math.asin(float(image_parameters.pixel_size)))
-    cards = []
-    if bunit is not None:
-        cards.append(('BUNIT', bunit))
-    cards += [
-        ('ORIGIN', 'katsdpimager_amd'), ('HISTORY', 'Created by katsdpimager_amd'),
-        ('TIMESYS', 'UTC'), ('DATE', date),
-        # pixel -> (l, m): the reference point is the image centre; FITS counts from 1 and the
-        # l axis is stored reversed so that RA increases to the left
-        ('CRPIX1', image.shape[2] * 0.5), ('CRPIX2', image.shape[1] * 0.5 + 1.0), ('CRPIX4', 1.0),
-        ('CDELT1', -delt), ('CDELT2', delt), ('CDELT4', 1.0),
-        ('EQUINOX', 2000.0), ('RADESYS', 'FK5'),
-        ('CUNIT1', 'deg'), ('CUNIT2', 'deg'), ('CUNIT4', 'Hz'),
-        ('CTYPE1', 'RA---SIN'), ('CTYPE2', 'DEC--SIN'), ('CTYPE4', 'FREQ'),
-        ('CRVAL1', math.degrees(float(phase_centre[0]))),
-        ('CRVAL2', math.degrees(float(phase_centre[1]))),
-        ('CRVAL4', 299792458.0 / float(image_parameters.wavelength)),
-    ]
-    if beam is not None:
-        pix = math.degrees(float(image_parameters.pixel_size))
-        cards += [('BMAJ', beam.major * pix), ('BMIN', beam.minor * pix),
-                  ('BPA', math.degrees(float(beam.theta)))]
-    cards += [('CTYPE3', 'STOKES'), ('CRPIX3', 1.0), ('CRVAL3', float(ref)),
-              ('CDELT3', float(step))]
-    datamin = float(np.fmin.reduce(image, axis=None))
-    datamax = float(np.fmax.reduce(image, axis=None))
-    if not math.isnan(datamin):
-        cards += [('DATAMIN', datamin), ('DATAMAX', datamax)]
+    cards = _sky_cards(image, image_parameters, 299792458.0 / float(image_parameters.wavelength), 1.0,
+                       phase_centre, beam, bunit, date, ref, step)
     if extra_fits_headers:
         extra = dict(extra_fits_headers)
         cards = [(k, extra.pop(k) if k in extra else v) for k, v in cards] + list(extra.items())
@@ -129,6 +140,40 @@ def write_fits_image(image, image_parameters, filename, channel, phase_centre, b
         filename = filename % channel
     except TypeError:
         pass
+    write_fits(filename, out, cards)
+    return out, cards
+
+
+def write_fits_cube(cube, image_parameters, filename, frequencies, phase_centre, beam=None,
+                    bunit='Jy/beam', rest_frequency=None, date=None):
+    """A spectral cube [channel][polarization][m][l] (``cube.SpectralCube.get()``) as one FITS file:
+    the cards of :func:`write_fits_image` with ``NAXIS4`` = the channels, ``CRVAL4`` =
+    ``frequencies[0]``, ``CDELT4`` their spacing and ``CRPIX4`` = 1; ``RESTFRQ`` when
+    ``rest_frequency`` is given.  A linear FREQ axis cannot describe uneven channels: ValueError if
+    the spacing varies by more than 1e-6 of itself.  One ``beam`` serves every plane (a common
+    restoring beam is the caller's to make).  Returns (the array as written, the header as a list of
+    (key, value))."""
+    cube = np.asarray(cube)
+    if cube.ndim != 4:
+        raise ValueError('cube must be [channel][polarization][m][l]')
+    frequencies = np.asarray(frequencies, np.float64)
+    if frequencies.shape != (cube.shape[0],) or not np.all(np.isfinite(frequencies)):
+        raise ValueError('frequencies must have one finite entry per channel')
+    if len(frequencies) > 1:
+        steps = np.diff(frequencies)
+        step = float((frequencies[-1] - frequencies[0]) / (len(frequencies) - 1))
+        if step == 0.0 or np.max(np.abs(steps - step)) > 1e-6 * abs(step):
+            raise ValueError('the channels are not evenly spaced: a linear FREQ axis cannot describe them')
+    else:
+        step = 1.0
+    ref, pol_step, order = fits_polarization_axis(image_parameters.fixed.polarizations)
+    if len(order) != cube.shape[1] or np.any(order != np.arange(len(order))):
+        raise ValueError('polarizations must be in FITS order, one per plane')
+    cards = _sky_cards(cube, image_parameters, frequencies[0], step, phase_centre, beam, bunit, date,
+                       ref, pol_step)
+    if rest_frequency is not None:
+        cards.append(('RESTFRQ', float(rest_frequency)))
+    out = cube[:, :, :, ::-1]
     write_fits(filename, out, cards)
     return out, cards
 
