@@ -71,12 +71,18 @@ extern "C" {
  *                          room for it (see `workspace` of kimg_grid); without the bit only calls
  *                          long enough for it to pay do.  For comparison and tests.  Together with
  *                          KIMG_ARITH_NO_FOLD it is KIMG_EINVAL.  (0x400, not the next free bit:
- *                          0x200 alone stays an invalid `arith`, as callers have been told.) */
+ *                          0x200 alone stays an invalid `arith`, as callers have been told.)
+ *   KIMG_ARITH_NO_PREFOLD  a bit OR-ed into any of the forms (kimg_grid only): the call does not take
+ *                          the fold pre-pass whatever the number of records -- for a caller that
+ *                          has measured its stream (kimg_fold_plan) and knows that it does not fold.
+ *                          The window kernel still folds the runs it meets.  A fold plan given with
+ *                          it is ignored; together with KIMG_ARITH_PREFOLD it is KIMG_EINVAL. */
 #define KIMG_ARITH_FP32 0
 #define KIMG_ARITH_SPLIT_FP16 1
 #define KIMG_ARITH_FP32_32X32 2
 #define KIMG_ARITH_NO_FOLD 0x100
 #define KIMG_ARITH_PREFOLD 0x400
+#define KIMG_ARITH_NO_PREFOLD 0x800
 
 /* Kernel choice of kimg_grid / kimg_degrid (argument `variant`) */
 #define KIMG_VARIANT_AUTO 0     /* MFMA window kernel when the parameters allow it */
@@ -181,8 +187,9 @@ int kimg_kernel_table(void *table, const double *ws, int w_planes, int kernel_wi
  *                   kimg_fold_runs_workspace_bytes(P, max N / 2) more.  A call on N records takes
  *                   the pre-pass when workspace_bytes is at least kimg_grid_workspace_bytes(0, ...)
  *                   + kimg_fold_runs_workspace_bytes(P, N / 2), uv, w_plane, vis and workspace are
- *                   16-byte aligned, and N >= 8 Mi or KIMG_ARITH_PREFOLD is set; with less -- the
- *                   sizes of before the pre-pass existed, or NULL -- it silently goes without.
+ *                   16-byte aligned, and N >= 8 Mi or KIMG_ARITH_PREFOLD is set or a fold plan is
+ *                   given (kimg_grid_planned); with less -- the sizes of before the pre-pass
+ *                   existed, or NULL -- it silently goes without.
  *   variant         KIMG_VARIANT_*: automatic = MFMA window kernel when supported (kernel_width
  *                   <= 64), else the generic scatter kernel
  *   arith           KIMG_ARITH_* (above); anything else is KIMG_EINVAL
@@ -212,7 +219,7 @@ int kimg_grid_jumps(const int16_t *uv, int64_t num_vis, int kernel_width, uint32
  *                     bytes.  At its start a header: uint32 use_folded, uint32 spans, int64 H (the
  *                     number of heads of runs), then three device pointers into the workspace --
  *                     the compacted uv int16 [H][4], w_plane int16 [H], vis complex64 [H][P] -- and
- *                     int64 capacity.
+ *                     int64 capacity.  (Further words of the first 256 bytes belong to the library.)
  * If 2 H > N (folding would not halve the stream) or H > capacity, use_folded is 0 and no record is
  * written; else use_folded is 1 and the H records are there.
  * KIMG_EINVAL for null or misaligned pointers and N < 1, KIMG_EWORKSPACE for a short workspace. */
@@ -226,6 +233,46 @@ int kimg_grid(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride, int 
               const int16_t *uv, const int16_t *w_plane, const void *vis, int64_t num_vis,
               const void *convolve_kernel, int w_planes, int oversample, int kernel_width,
               void *workspace, size_t workspace_bytes, int variant, int arith, void *stream);
+/* Fold plans: the count launch of the pre-pass run ONCE for a stream that is gridded several times.
+ * The heads of runs depend on uv and w_plane alone, and a slice is gridded with the same coordinates
+ * for the PSF, for the dirty image and in every major cycle; only vis changes.
+ *   kimg_fold_plan_bytes()  size of a plan: a small fixed number of bytes of device memory, 16-byte
+ *                           aligned.  Its first words: uint32 magic, uint32 spans, int64 num_vis,
+ *                           int64 tiles per span, int64 H (the heads of runs kimg_fold_runs would
+ *                           count), so a caller can read H back (32 bytes) and decide.
+ *   kimg_fold_plan          fills `plan` for (uv, w_plane, N >= 1, P): two launches, asynchronous,
+ *                           capturable, no allocation.  The plan depends on P because the spans do.
+ *   kimg_fold_runs_planned  kimg_fold_runs with the counts taken from `fold_plan`: one launch (and
+ *                           a 16-byte memset).  NULL: kimg_fold_runs.
+ *   kimg_grid_planned       kimg_grid with `fold_plan` for the MFMA variant's pre-pass, which is
+ *                           then taken at ANY N (room in the workspace and alignment as always):
+ *                           the plan is the caller's statement that the stream folds, so give one
+ *                           only when 2 H <= N, and KIMG_ARITH_NO_PREFOLD otherwise.  The generic
+ *                           and binned variants, KIMG_ARITH_NO_FOLD and KIMG_ARITH_NO_PREFOLD
+ *                           ignore it.  NULL: kimg_grid.
+ * A STALE PLAN NEVER CHANGES THE RESULT.  A plan is untrusted device data, which the host cannot
+ * read: the pre-pass counts every span's heads again while it compacts, and only if the plan was made
+ * for this N and span layout and every span's count is the plan's does use_folded become 1 -- then
+ * the output is bit for bit what the unplanned call writes.  Otherwise (coordinates rewritten in
+ * place, the plan of another stream, another P-layout, arbitrary bytes) use_folded is 0 and kimg_grid
+ * grids the caller's stream; records may then have been written, but whatever the plan holds nothing
+ * is written outside the workspace.  The decision is taken on the device, without a read-back.  All
+ * the host checks is the pointer: KIMG_EINVAL for a plan that is not 16-byte aligned. */
+size_t kimg_fold_plan_bytes(void);
+int kimg_fold_plan(const int16_t *uv, const int16_t *w_plane, int64_t num_vis, int num_polarizations,
+                   void *plan, void *stream);
+int kimg_fold_runs_planned(const int16_t *uv, const int16_t *w_plane, const void *vis,
+                           int64_t num_vis, int num_polarizations, int64_t capacity, void *workspace,
+                           size_t workspace_bytes, void *stream, const void *fold_plan);
+/* (kimg_grid's arguments in kimg_grid's order -- the four after `grid` and `weights_grid` are its
+ * row and polarization strides, refused alike -- then the plan) */
+int kimg_grid_planned(void *grid, int64_t grid_row, int64_t grid_pol, int grid_size,
+                      int num_polarizations,
+                      const float *weights_grid, int64_t wg_row, int64_t wg_pol,
+                      const int16_t *uv, const int16_t *w_plane, const void *vis, int64_t num_vis,
+                      const void *convolve_kernel, int w_planes, int oversample, int kernel_width,
+                      void *workspace, size_t workspace_bytes, int variant, int arith, void *stream,
+                      const void *fold_plan);
 
 /* ---- degridding: grid.py:985-1029 Degridder.static_run/_run + degrid.mako:77-199
  * vis[r][p] -= weights[r][p] * sum_{j,k} kern[w][sub_v][j]*kern[w][sub_u][k]*grid[p][v0+j][u0+k]

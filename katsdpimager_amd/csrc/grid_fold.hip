@@ -21,6 +21,14 @@
 //    2 H > N or H above the output's capacity the header says use_folded = 0 and no record is
 //    written -- a stream without duplicates costs the count pass only.
 // No allocation, no read-back, no synchronisation: the call is asynchronous and capturable.
+//
+// A fold plan (kimg_fold_plan) is launch 1 run ahead of time and kept by the caller: the counts
+// depend on uv and w_plane alone, which stay the same from one gridding pass over a slice to the
+// next.  A call that is given one issues launch 2 only.  The plan is untrusted: launch 2 counts every
+// span's heads anyway, and the last workgroup to finish -- found by a ticket, nobody waits -- sets
+// use_folded only if every span found the count the plan gave it.  Then the offsets were the right
+// ones and the output is what the two launches write; else the window kernel grids the caller's
+// stream.  Output indices are checked against the capacity whatever the plan holds.
 #include "kimg_common.h"
 
 namespace {
@@ -159,6 +167,30 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_count_kernel(
         counts[blockIdx.x] = (uint32_t) sum;
 }
 
+// A fold plan's fields from the counts that fold_count_kernel left in it (one workgroup)
+__global__ __launch_bounds__(FOLD_THREADS) void fold_plan_finish_kernel(
+    kimg_fold_plan_data *__restrict__ plan, int64_t num_vis, int64_t tiles_per_span, int spans)
+{
+    __shared__ unsigned long long s_red[FOLD_WAVES];
+    unsigned long long all = 0;
+    for (int i = threadIdx.x; i < KIMG_FOLD_MAX_SPANS; i += FOLD_THREADS) {
+        if (i < spans)
+            all += plan->counts[i];
+        else
+            plan->counts[i] = 0;
+    }
+    const unsigned long long H = fold_block_sum(all, s_red);
+    if (threadIdx.x == 0) {
+        plan->magic = KIMG_FOLD_PLAN_MAGIC;
+        plan->spans = (uint32_t) spans;
+        plan->num_vis = num_vis;
+        plan->tiles_per_span = tiles_per_span;
+        plan->count = (int64_t) H;
+    }
+    if (threadIdx.x < 8)
+        plan->reserved[threadIdx.x] = 0;
+}
+
 // What the segmented scan over a tile's threads carries: heads seen, whether any, and the sum of the
 // samples since the last head (of all samples while there was none)
 template <int P>
@@ -227,17 +259,27 @@ __device__ __attribute__((always_inline)) inline void fold_load_samples(
     }
 }
 
-template <int P>
+// PLANNED: `counts` are a fold plan's (`plan`, untrusted device data) and not this call's count
+// launch's.  A plan made for another length or layout is refused by every workgroup alike; counts
+// of any value give offsets in [0, H] with H <= capacity, and every store below checks its index
+// against the capacity.  Each workgroup leaves its own count of heads in `recount` and, with a
+// ticket, whether it was the plan's; the last one to finish writes use_folded.
+template <int P, bool PLANNED>
 __global__ __launch_bounds__(FOLD_THREADS) void fold_compact_kernel(
     const int16_t *__restrict__ uv, const int16_t *__restrict__ w_plane,
     const float2 *__restrict__ vis, int64_t num_vis, int64_t tiles_per_span, int spans,
     const uint32_t *__restrict__ counts, int64_t capacity, kimg_fold_header *__restrict__ header,
-    int2 *__restrict__ out_uv, int16_t *__restrict__ out_w, float2 *__restrict__ out_vis)
+    int2 *__restrict__ out_uv, int16_t *__restrict__ out_w, float2 *__restrict__ out_vis,
+    const kimg_fold_plan_data *__restrict__ plan, uint32_t *__restrict__ recount)
 {
     __shared__ unsigned long long s_red[FOLD_WAVES];
     __shared__ fold_elem<P> s_tot[2][FOLD_WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
+    bool plan_ok = true;
+    if (PLANNED)
+        plan_ok = plan->magic == KIMG_FOLD_PLAN_MAGIC && plan->spans == (uint32_t) spans
+                  && plan->num_vis == num_vis && plan->tiles_per_span == tiles_per_span;
     // the records before this span, and all of them: every workgroup reads the same counts and
     // takes the same decision
     unsigned long long before = 0, all = 0;
@@ -248,9 +290,10 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_compact_kernel(
     }
     const int64_t offset = (int64_t) fold_block_sum(before, s_red);
     const int64_t H = (int64_t) fold_block_sum(all, s_red);
-    const bool use = 2 * H <= num_vis && H <= capacity;
+    const bool use = plan_ok && 2 * H <= num_vis && H <= capacity;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        header->use_folded = use ? 1u : 0u;
+        if (!PLANNED || !use)       // (a plan's verdict comes with the last ticket)
+            header->use_folded = use ? 1u : 0u;
         header->spans = (uint32_t) spans;
         header->count = H;
         header->uv = reinterpret_cast<const int16_t *>(out_uv);
@@ -382,6 +425,15 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_compact_kernel(
 #pragma unroll
         for (int p = 0; p < P; p++)
             out_vis[(run_base - 1) * P + p] = carry[p];
+    if (PLANNED && threadIdx.x == 0) {
+        const int64_t mine = run_base - offset;
+        recount[blockIdx.x] = (uint32_t) mine;
+        const unsigned add = 1u + (mine != (int64_t) counts[blockIdx.x] ? 0x10000u : 0u);
+        const unsigned now = atomicAdd(&header->ticket[0], add) + add;
+        // (the next launch reads the header: no other workgroup of this one does)
+        if ((now & 0xffffu) == (unsigned) spans)
+            header->use_folded = (now >> 16) == 0 ? 1u : 0u;
+    }
 }
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -396,7 +448,8 @@ size_t kimg_fold_workspace_bytes(int P, int64_t capacity)
 }
 
 int kimg_fold_launch(const int16_t *uv, const int16_t *w_plane, const float2 *vis, int64_t num_vis,
-                     int P, int64_t capacity, void *workspace, hipStream_t stream)
+                     int P, int64_t capacity, void *workspace, hipStream_t stream,
+                     const kimg_fold_plan_data *plan_data)
 {
     if (capacity < 0)
         capacity = 0;
@@ -410,12 +463,40 @@ int kimg_fold_launch(const int16_t *uv, const int16_t *w_plane, const float2 *vi
     out += align256((size_t) capacity * P * sizeof(float2));
     int16_t *out_w = reinterpret_cast<int16_t *>(out);
     const fold_plan plan = fold_plan_of(num_vis, P);
+    if (plan_data != nullptr) {
+        // the workspace's counts are free for the spans' own counts
+        KIMG_HIP(hipMemsetAsync(header->ticket, 0, sizeof(header->ticket), stream));
+        kimg_for_pols(P, [&](auto p) {
+            fold_compact_kernel<decltype(p)::value, true><<<plan.spans, FOLD_THREADS, 0, stream>>>(
+                uv, w_plane, vis, num_vis, plan.tiles_per_span, plan.spans, plan_data->counts,
+                capacity, header, out_uv, out_w, out_vis, plan_data, counts); });
+        return kimg_launch_status();
+    }
     fold_count_kernel<<<plan.spans, FOLD_THREADS, 0, stream>>>(uv, w_plane, num_vis,
                                                                plan.tiles_per_span, counts);
     kimg_for_pols(P, [&](auto p) {
-        fold_compact_kernel<decltype(p)::value><<<plan.spans, FOLD_THREADS, 0, stream>>>(
+        fold_compact_kernel<decltype(p)::value, false><<<plan.spans, FOLD_THREADS, 0, stream>>>(
             uv, w_plane, vis, num_vis, plan.tiles_per_span, plan.spans, counts, capacity, header,
-            out_uv, out_w, out_vis); });
+            out_uv, out_w, out_vis, nullptr, nullptr); });
+    return kimg_launch_status();
+}
+
+extern "C" size_t kimg_fold_plan_bytes(void) { return sizeof(kimg_fold_plan_data); }
+
+extern "C" int kimg_fold_plan(const int16_t *uv, const int16_t *w_plane, int64_t num_vis,
+                              int num_polarizations, void *plan, void *stream)
+{
+    KIMG_CHECK_ARG(uv && w_plane && plan && num_vis >= 1);
+    if (num_polarizations < 1 || num_polarizations > 4)
+        return KIMG_EUNSUPPORTED;
+    KIMG_CHECK_ARG(aligned16(uv) && aligned16(w_plane) && aligned16(plan));
+    kimg_fold_plan_data *data = static_cast<kimg_fold_plan_data *>(plan);
+    const fold_plan layout = fold_plan_of(num_vis, num_polarizations);
+    hipStream_t s = (hipStream_t) stream;
+    fold_count_kernel<<<layout.spans, FOLD_THREADS, 0, s>>>(uv, w_plane, num_vis,
+                                                            layout.tiles_per_span, data->counts);
+    fold_plan_finish_kernel<<<1, FOLD_THREADS, 0, s>>>(data, num_vis, layout.tiles_per_span,
+                                                       layout.spans);
     return kimg_launch_status();
 }
 
@@ -426,18 +507,29 @@ extern "C" size_t kimg_fold_runs_workspace_bytes(int num_polarizations, int64_t 
     return kimg_fold_workspace_bytes(num_polarizations, capacity);
 }
 
-extern "C" int kimg_fold_runs(const int16_t *uv, const int16_t *w_plane, const void *vis,
-                              int64_t num_vis, int num_polarizations, int64_t capacity,
-                              void *workspace, size_t workspace_bytes, void *stream)
+extern "C" int kimg_fold_runs_planned(const int16_t *uv, const int16_t *w_plane, const void *vis,
+                                      int64_t num_vis, int num_polarizations, int64_t capacity,
+                                      void *workspace, size_t workspace_bytes, void *stream,
+                                      const void *fold_plan)
 {
     KIMG_CHECK_ARG(uv && w_plane && vis && workspace && num_vis >= 1 && capacity >= 0);
     if (num_polarizations < 1 || num_polarizations > 4)
         return KIMG_EUNSUPPORTED;
-    KIMG_CHECK_ARG(aligned16(uv) && aligned16(w_plane) && aligned16(vis) && aligned16(workspace));
+    KIMG_CHECK_ARG(aligned16(uv) && aligned16(w_plane) && aligned16(vis) && aligned16(workspace)
+                   && aligned16(fold_plan));
     if (workspace_bytes < kimg_fold_workspace_bytes(num_polarizations, capacity))
         return KIMG_EWORKSPACE;
     return kimg_fold_launch(uv, w_plane, static_cast<const float2 *>(vis), num_vis,
-                            num_polarizations, capacity, workspace, (hipStream_t) stream);
+                            num_polarizations, capacity, workspace, (hipStream_t) stream,
+                            static_cast<const kimg_fold_plan_data *>(fold_plan));
+}
+
+extern "C" int kimg_fold_runs(const int16_t *uv, const int16_t *w_plane, const void *vis,
+                              int64_t num_vis, int num_polarizations, int64_t capacity,
+                              void *workspace, size_t workspace_bytes, void *stream)
+{
+    return kimg_fold_runs_planned(uv, w_plane, vis, num_vis, num_polarizations, capacity, workspace,
+                                  workspace_bytes, stream, nullptr);
 }
 
 // (kimg_preload, api.hip)

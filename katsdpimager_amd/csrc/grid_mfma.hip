@@ -1559,7 +1559,8 @@ size_t kimg_grid_mfma_workspace_bytes(int P, int w_planes, int oversample, int k
 // to 0.705-0.716 ms and from 0.725-0.727 to 0.750-0.763 ms per launch (bench.py --full, three runs each
 // way), outside their own spread.  Track streams of 1 and 4 Mi records would gain (0.078 -> 0.065,
 // 0.250 -> 0.124 ms), but nothing cheap tells the two kinds apart before the count pass has run, so
-// the bound lies above the store's slices.  DESIGN 5.1 has the figures.
+// the bound lies above the store's slices.  DESIGN 5.1 has the figures.  A caller that has measured
+// its stream once needs no bound: it brings a fold plan (kimg_grid_planned) or KIMG_ARITH_NO_PREFOLD.
 #ifndef KIMG_PREFOLD_MIN_VIS
 #define KIMG_PREFOLD_MIN_VIS (8 << 20)
 #endif
@@ -1575,11 +1576,14 @@ int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
                    int P, const float *weights_grid, int64_t wg_row_stride, int64_t wg_pol_stride,
                    const int16_t *uv, const int16_t *w_plane, const void *vis, int64_t num_vis,
                    const void *convolve_kernel, int w_planes, int oversample, int kernel_width,
-                   void *workspace, size_t workspace_bytes, int arith, hipStream_t stream)
+                   void *workspace, size_t workspace_bytes, int arith, hipStream_t stream,
+                   const void *fold_plan)
 {
     const bool fold = !(arith & KIMG_ARITH_NO_FOLD);
-    const bool prefold_always = (arith & KIMG_ARITH_PREFOLD) != 0;
-    arith &= ~(KIMG_ARITH_NO_FOLD | KIMG_ARITH_PREFOLD);
+    const bool prefold_never = (arith & KIMG_ARITH_NO_PREFOLD) != 0;
+    // (a fold plan is the caller's statement that the stream folds: the pre-pass at any length)
+    const bool prefold_always = (arith & KIMG_ARITH_PREFOLD) != 0 || fold_plan != nullptr;
+    arith &= ~(KIMG_ARITH_NO_FOLD | KIMG_ARITH_PREFOLD | KIMG_ARITH_NO_PREFOLD);
     const bool in_lds = table_in_lds(P, w_planes, oversample, kernel_width);
     if (!in_lds && (workspace == nullptr
                     || workspace_bytes < kimg_grid_mfma_workspace_bytes(P, w_planes, oversample,
@@ -1592,12 +1596,14 @@ int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
     const kimg_fold_header *folded = nullptr;
     const size_t own_bytes = kimg_grid_mfma_workspace_bytes(P, w_planes, oversample, kernel_width);
     auto aligned16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (fold && (prefold_always || num_vis >= KIMG_PREFOLD_MIN_VIS) && workspace != nullptr
+    if (fold && !prefold_never && (prefold_always || num_vis >= KIMG_PREFOLD_MIN_VIS)
+        && workspace != nullptr
         && workspace_bytes >= own_bytes + kimg_grid_prefold_workspace_bytes(num_vis, P)
         && aligned16(uv) && aligned16(w_plane) && aligned16(vis) && aligned16(workspace)) {
         void *fold_ws = static_cast<unsigned char *>(workspace) + (own_bytes - 256);
         if (const int rc = kimg_fold_launch(uv, w_plane, (const float2 *) vis, num_vis, P, num_vis / 2,
-                                            fold_ws, stream))
+                                            fold_ws, stream,
+                                            static_cast<const kimg_fold_plan_data *>(fold_plan)))
             return rc;
         folded = static_cast<const kimg_fold_header *>(fold_ws);
     }

@@ -72,7 +72,8 @@ int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
                    int P, const float *weights_grid, int64_t wg_row_stride, int64_t wg_pol_stride,
                    const int16_t *uv, const int16_t *w_plane, const void *vis, int64_t num_vis,
                    const void *convolve_kernel, int w_planes, int oversample, int kernel_width,
-                   void *workspace, size_t workspace_bytes, int arith, hipStream_t stream);
+                   void *workspace, size_t workspace_bytes, int arith, hipStream_t stream,
+                   const void *fold_plan = nullptr);
 bool kimg_grid_mfma_supported(int P, int w_planes, int oversample, int kernel_width);
 size_t kimg_grid_mfma_workspace_bytes(int P, int w_planes, int oversample, int kernel_width);
 // What kimg_grid_mfma needs ON TOP of the above to run the fold pre-pass on num_vis records, and the
@@ -97,11 +98,29 @@ struct kimg_fold_header {
     const int16_t *uv, *w_plane;    // the compacted stream: `count` records
     const float2 *vis;              //   [count][P]
     int64_t capacity;
+    uint32_t reserved[4];
+    // calls with a fold plan only: spans that have finished (bits 0-15) and spans whose own count of
+    // heads was not the plan's (bits 16-31); a 16-byte block that the call zeroes ahead of its launch
+    uint32_t ticket[4];
+};
+// A fold plan (kimg_fold_plan, include/kimg.h): what the count launch of the pre-pass finds out about
+// one (uv, w_plane, num_vis, P) stream, kept by the caller in device memory.  Untrusted where it is
+// used: see fold_compact_kernel.
+constexpr int KIMG_FOLD_MAX_SPANS = 1024;
+constexpr uint32_t KIMG_FOLD_PLAN_MAGIC = 0x31504c46u;     // "FLP1"
+struct kimg_fold_plan_data {
+    uint32_t magic, spans;          // the layout the counts belong to: fold_plan_of(num_vis, P)
+    int64_t num_vis, tiles_per_span;
+    int64_t count;                  // H, the sum of the counts
+    uint32_t reserved[8];
+    uint32_t counts[KIMG_FOLD_MAX_SPANS];   // heads of runs per span
 };
 size_t kimg_fold_workspace_bytes(int P, int64_t capacity);
-// (16-byte aligned uv, w_plane, vis and workspace; workspace of at least the size above)
+// (16-byte aligned uv, w_plane, vis and workspace; workspace of at least the size above; `plan`: null
+// or a fold plan in device memory, which replaces the count launch)
 int kimg_fold_launch(const int16_t *uv, const int16_t *w_plane, const float2 *vis, int64_t num_vis,
-                     int P, int64_t capacity, void *workspace, hipStream_t stream);
+                     int P, int64_t capacity, void *workspace, hipStream_t stream,
+                     const kimg_fold_plan_data *plan = nullptr);
 // *out = the bit pattern of the largest |component| among the n floats of a kernel table (ktable.hip):
 // the fp16 hi/lo forms of the window kernels choose their table scale from it when the table is in
 // HBM.  (Hidden: a helper between two units of the library, no part of its dynamic symbol table.)

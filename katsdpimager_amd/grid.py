@@ -220,6 +220,38 @@ GRID_ARITH = {'fp32': 0, 'split_fp16': 1, 'fp32_32x32': 2}
 #: window gridder then gives every record its own update instead of summing the samples of
 #: consecutive records with equal (u, v, sub_u, sub_v, w_plane) first.  For comparison and tests.
 GRID_ARITH_NO_FOLD = 0x100
+#: OR-ed into ``arith`` for kimg_grid when a measurement has shown that the bound stream does not fold
+#: (KIMG_ARITH_NO_PREFOLD): the call skips the fold pre-pass whatever its length.
+GRID_ARITH_NO_PREFOLD = 0x800
+
+
+class FoldPlan:
+    """One measurement of a (uv, w_plane, num_vis) stream for the gridder's fold pre-pass
+    (``kimg_fold_plan``, include/kimg.h): ``heads`` runs among ``num_vis`` records of
+    ``polarizations`` polarizations, and the device buffer ``plan`` that spares every gridding
+    call on that stream the count launch.  It says nothing about any other stream."""
+
+    def __init__(self, plan, heads, num_vis, polarizations):
+        self.plan = plan
+        self.heads = heads
+        self.num_vis = num_vis
+        self.polarizations = polarizations
+
+    @property
+    def foldable(self):
+        """Whether the pre-pass would at least halve the stream (its own criterion)."""
+        return 2 * self.heads <= self.num_vis
+
+
+def measure_fold_plan(queue, uv, w_plane, num_vis, polarizations):
+    """:class:`FoldPlan` of the first ``num_vis`` records of the device arrays ``uv`` and
+    ``w_plane`` (16-byte aligned); synchronises with ``queue`` (one small read-back)."""
+    plan = accel.DeviceArray(queue.context, (int(lib().kimg_fold_plan_bytes()),), np.uint8,
+                             queue=queue)
+    check(lib().kimg_fold_plan(uv.ptr, w_plane.ptr, num_vis, polarizations, plan.ptr, queue.handle),
+          'kimg_fold_plan')
+    heads = int(plan.get(queue)[24:32].view(np.int64)[0])
+    return FoldPlan(plan, heads, num_vis, polarizations)
 
 
 #: `auto` variant: calls smaller than this go straight to the window kernel ...
@@ -359,9 +391,10 @@ class GridDegrid(VisOperation):
                                                 queue=self.command_queue)
         self._init_locality(0 if self._f64 and dims[3] > 32 else binned_bytes(self.max_vis, *dims))
 
-    def _launch(self, name, *head, arith_flags=0):
+    def _launch(self, name, *head, arith_flags=0, tail=()):
         """Call ``name`` (float32) or ``name + '_f64'`` with `head`, then the arguments the four have
-        in common; the float32 functions also take the template's ``arith``."""
+        in common; the float32 functions also take the template's ``arith``.  `tail`: what ``name``
+        takes after the stream."""
         variant = self._choose_variant()
         if variant == GRID_VARIANTS['binned']:
             # gridder 34 + 8 P, degridder 38 + 12 P bytes per visibility of max_vis
@@ -373,7 +406,7 @@ class GridDegrid(VisOperation):
             name += '_f64'
         else:
             args += (self.template.arith | arith_flags,)
-        check(getattr(lib(), name)(*args, self.command_queue.handle), name)
+        check(getattr(lib(), name)(*args, self.command_queue.handle, *tail), name)
         self._note_variant(variant)
 
     # ---- stream order: window kernel as is, or tile-binned first (see GridderTemplate) ----------
@@ -456,13 +489,109 @@ class Gridder(GridDegrid):
         if Gg > 32000 or Gg * Gg * 8 >= 1 << 32:
             self._binned_bytes = 0
 
+    # ---- the fold plan of the bound stream (FoldPlan) -------------------------------------------
+    # It belongs to this operation and the buffers bound to it: unlike `locality_hint` it is never
+    # copied to another operation, and it goes when uv or w_plane is rebound or num_vis changes.
+    # `_fold` is (FoldPlan, key); the key is checked again at every call, because slots can also be
+    # bound through a compound slot of an OperationSequence, which does not come through bind().
+    _fold = None
+
+    def _fold_key(self):
+        uv, w_plane = self.slots['uv'].buffer, self.slots['w_plane'].buffer
+        if uv is None or w_plane is None:
+            return None
+        return (uv.ptr, w_plane.ptr, self.num_vis)
+
+    @property
+    def fold_plan(self):
+        """The :class:`FoldPlan` that the next call will use, or None."""
+        if self._fold is not None and self._fold[1] != self._fold_key():
+            self._fold = None
+        return self._fold[0] if self._fold is not None else None
+
+    def set_fold_plan(self, fold_plan):
+        """Use `fold_plan` (:class:`FoldPlan` of exactly the bound uv, w_plane and num_vis, as the
+        resident store measures it once per slice; None: forget) for the calls on the bound
+        stream.  A plan that cannot be this stream's is ignored; one that is stale all the same
+        costs time, never correctness (include/kimg.h)."""
+        self._fold = None
+        if fold_plan is None or not self._fold_window_route():
+            return
+        if (fold_plan.num_vis != self.num_vis
+                or fold_plan.polarizations != self.slots['grid'].shape[0]):
+            return
+        if fold_plan.foldable:
+            self._fold_workspace()
+        self._fold = (fold_plan, self._fold_key())
+
+    def _fold_window_route(self):
+        """Whether a call on the bound stream takes the float32 window kernel on the stream as it
+        is, with folding on and buffers the pre-pass can read."""
+        if self._f64 or not self.template.fold_runs or self.num_vis < 1:
+            return False
+        variant = self.template.variant
+        if variant == GRID_VARIANTS['auto']:
+            if not self._binned_bytes or self.locality_hint is not True:
+                return False
+        elif variant != GRID_VARIANTS['mfma']:
+            return False
+        return all(self.slots[name].buffer is not None and self.slots[name].buffer.ptr % 16 == 0
+                   for name in ('uv', 'w_plane', 'vis'))
+
+    def _fold_workspace(self):
+        """Room for the pre-pass in the workspace at the bound length (calls without a plan take
+        the pre-pass from 8 Mi records only, and shorter operations were sized without it)."""
+        dims = (self.slots['grid'].shape[0],) + self._kernel_args()[1:]
+        need = int(lib().kimg_grid_workspace_bytes(0, *dims)) \
+            + int(lib().kimg_fold_runs_workspace_bytes(dims[0], self.num_vis // 2))
+        if self._workspace_bytes < need:
+            self._workspace = accel.DeviceArray(self.command_queue.context, (need,), np.uint8,
+                                                queue=self.command_queue)
+            self._workspace_bytes = need
+
+    def bind(self, **kwargs):
+        if 'uv' in kwargs or 'w_plane' in kwargs:
+            self._fold = None
+        super().bind(**kwargs)
+
+    def _set_num_vis(self, n):
+        VisOperation.num_vis.fset(self, n)
+        if self._fold is not None and self._fold[1][2] != n:
+            self._fold = None
+
+    num_vis = property(VisOperation.num_vis.fget, _set_num_vis)
+
+    def measure_locality(self):
+        """:meth:`GridDegrid.measure_locality`, and where the calls on the bound stream will take
+        the window kernel also its :class:`FoldPlan`: every such call then skips the count launch
+        of the fold pre-pass, or the whole pre-pass if the stream does not fold."""
+        f = super().measure_locality()
+        self._fold = None
+        if self._fold_window_route():
+            self.set_fold_plan(measure_fold_plan(
+                self.command_queue, self.buffer('uv'), self.buffer('w_plane'), self.num_vis,
+                self.slots['grid'].shape[0]))
+        return f
+
+    def _fold_call(self):
+        """(function, arith flags, arguments after the stream) of a call on the bound stream."""
+        if not self.template.fold_runs:
+            return 'kimg_grid', GRID_ARITH_NO_FOLD, ()
+        fold_plan = self.fold_plan
+        if fold_plan is None:
+            return 'kimg_grid', 0, ()
+        if not fold_plan.foldable:
+            return 'kimg_grid', GRID_ARITH_NO_PREFOLD, ()
+        return 'kimg_grid_planned', 0, (fold_plan.plan.ptr,)
+
     def _run(self):
         grid = self.buffer('grid')
         wg = self.buffer('weights_grid')
         P, G = grid.shape[0], grid.shape[1]
-        self._launch('kimg_grid', grid.ptr, G, G * G, G, P, wg.ptr, G, G * G,
+        name, arith_flags, tail = self._fold_call()
+        self._launch(name, grid.ptr, G, G * G, G, P, wg.ptr, G, G * G,
                      self.buffer('uv').ptr, self.buffer('w_plane').ptr, self.buffer('vis').ptr,
-                     arith_flags=0 if self.template.fold_runs else GRID_ARITH_NO_FOLD)
+                     arith_flags=arith_flags, tail=tail)
 
 
 class DegridderTemplate:

@@ -392,6 +392,7 @@ class Imaging(accel.OperationSequence):
             # new coordinates from the host: nothing is known about their order
             side_now = self._use_side()
             (self._side.gridder if side_now else self._gridder).locality_hint = None
+            (self._side.gridder if side_now else self._gridder).set_fold_plan(None)
             if self.template.fixed_grid_parameters.degrid:
                 (self._side.predict if side_now else self._predict).locality_hint = None
         if name in ('uv', 'w_plane', 'vis', 'weights') and self._use_side():
@@ -469,6 +470,7 @@ class Imaging(accel.OperationSequence):
         self.num_vis = num_vis
         self.bind(uv=uv, w_plane=w_plane, vis=vis)
         self._gridder.locality_hint = None
+        self._gridder.set_fold_plan(None)
         if self.template.fixed_grid_parameters.degrid:
             self._predict.locality_hint = None
         if weights is not None:
@@ -501,6 +503,7 @@ class Imaging(accel.OperationSequence):
             side.bind_chunk(uv=chunk.uv, w_plane=chunk.w_plane, weights=chunk.weights,
                             vis=side.own['vis'])
             side.gridder.locality_hint = getattr(chunk, 'locality', None)
+            side.gridder.set_fold_plan(getattr(chunk, 'fold_plan', None))
             if self.template.fixed_grid_parameters.degrid:
                 side.predict.locality_hint = getattr(chunk, 'locality', None)
             if field == 'vis':
@@ -517,6 +520,7 @@ class Imaging(accel.OperationSequence):
         self.num_vis = n
         self.bind(uv=chunk.uv, w_plane=chunk.w_plane, weights=chunk.weights)
         self._gridder.locality_hint = getattr(chunk, 'locality', None)
+        self._gridder.set_fold_plan(getattr(chunk, 'fold_plan', None))
         if self.template.fixed_grid_parameters.degrid:
             self._predict.locality_hint = getattr(chunk, 'locality', None)
         own_vis = self.buffer('vis')

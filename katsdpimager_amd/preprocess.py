@@ -44,7 +44,7 @@ class DeviceChunk:
     """A block of one (channel, w_slice) in HBM.  The arrays are views of the store with
     ``block_size`` rows of which the first ``num_vis`` are valid."""
 
-    def __init__(self, num_vis, uv, w_plane, weights, vis, locality=None):
+    def __init__(self, num_vis, uv, w_plane, weights, vis, locality=None, fold_plan=None):
         self.num_vis = num_vis
         self.uv = uv
         self.w_plane = w_plane
@@ -54,6 +54,9 @@ class DeviceChunk:
         #: True = consecutive records stay close (window kernel as is), False = bin them first,
         #: None = unknown (the gridder's `auto` variant measures on every call)
         self.locality = locality
+        #: ``grid.FoldPlan`` of exactly these ``num_vis`` records, or None (unknown; always None
+        #: for a block that is not its whole slice), for ``Gridder.set_fold_plan``
+        self.fold_plan = fold_plan
 
     def __len__(self):
         return self.num_vis
@@ -110,6 +113,9 @@ class _SliceStore:
         self.arrays = None
         #: True once :meth:`reorder` has put the records into the window kernels' order
         self.ordered = False
+        #: ``grid.FoldPlan`` of the whole slice, measured once by the reader (None: not yet, or
+        #: the records have changed since); a reallocation keeps the records and so the plan
+        self.fold_plan = None
         import threading
         self._slack_lock = threading.Lock()     # (readers on several host threads: ensure_slack)
 
@@ -155,6 +161,7 @@ class _SliceStore:
     def append(self, src, start, count):
         """Copy ``count`` rows starting at ``start`` from the dict of arrays ``src``."""
         self.reserve(count)
+        self.fold_plan = None
         for name, dst in self.arrays.items():
             src[name].copy_region(self.queue, dst, np.s_[start:start + count],
                                   np.s_[self.length:self.length + count])
@@ -168,6 +175,7 @@ class _SliceStore:
         if self.length == 0 or self.ordered:
             self.ordered = True
             return self.length
+        self.fold_plan = None
         n = self.length
         try:
             out, kept = reorder_device_arrays(self.queue, self.P, n, self.arrays, kernel_width,
@@ -409,6 +417,9 @@ class VisibilityCollectorDevice:
         if self._closed:
             return
         self._closed = True
+        for stores in self._stores:
+            for store in stores:
+                store.fold_plan = None
         if self.reorder:
             with _trace_range('store_reorder'):
                 for ch, stores in enumerate(self._stores):
@@ -464,10 +475,30 @@ class VisibilityReaderDevice:
             return
         store.ensure_slack(block_size)
         locality = self._locality(channel, w_slice)
+        # (a plan describes the whole slice: only a block that covers it carries one)
+        fold_plan = self._fold_plan(channel, w_slice) if block_size >= store.length else None
         for start in range(0, store.length, block_size):
             v = store.view(start, block_size)
             yield DeviceChunk(min(block_size, store.length - start), v['uv'], v['w_plane'],
-                              v['weights'], v['vis'], locality)
+                              v['weights'], v['vis'], locality, fold_plan)
+
+    def _fold_plan(self, channel, w_slice):
+        """``grid.FoldPlan`` of a stored slice, measured once (``kimg_fold_plan`` + a small
+        read-back) and kept with the slice; None for a merged slice, which has no two adjacent
+        records with equal coordinates, and where there is no window kernel to use it."""
+        store = self._stores[channel][w_slice]
+        if store.ordered and self.collector.merge:
+            return None
+        kernel_width = getattr(self.collector.grid_parameters[channel].fixed, 'kernel_width', None)
+        if kernel_width is None or kernel_width > 64 or self._locality(channel, w_slice) is not True:
+            return None
+        with store._slack_lock:
+            if store.fold_plan is None or store.fold_plan.num_vis != store.length:
+                from . import grid
+                store.fold_plan = grid.measure_fold_plan(
+                    self.collector.queue, store.arrays['uv'], store.arrays['w_plane'],
+                    store.length, store.P)
+            return store.fold_plan
 
     def _locality(self, channel, w_slice):
         """Measured once per stored slice (``kimg_grid_jumps`` + a 4-byte read-back): does the
