@@ -142,3 +142,88 @@ def abi_errors(lib, pointer):
                             a['m1'], a['m2'], a['m8'], a['m9'], a['count'], a['stream']) == 0
     return len(bad) + 1
 
+
+# ---- ranges, unfilled channels and peaks on the seams of the `filled` bit mask -----------------------
+#: bands of two words exactly, of one channel and of one word and a channel more
+SEAM_CHANNELS = (64, 65, 97)
+#: the longest band of kimg_moments and the plane its launch runs on
+LIMIT_CHANNELS = 4096
+LIMIT_PLANE = (1, 3, 5)
+
+
+def seam_ranges(C):
+    """(first, stop): first on either side of the seam at 32, on it and on the seam at 64; stop a
+    seam, a seam - 1, a seam + 1, and C."""
+    stops = sorted({s + d for s in (32, 64, 96) for d in (-1, 0, 1)} | {C})
+    return [(first, stop) for first in (31, 32, 33, 64) for stop in stops if first < stop <= C]
+
+
+def seam_cases(C):
+    """[(first, stop, unfilled channels, select_hanning)]: every range of seam_ranges with the last
+    bit of words 0 and 1 (and of the range) or the first bit of words 1 and 2 (and of the range)
+    unfilled, or the range's two end channels alone."""
+    out = []
+    for first, stop in seam_ranges(C):
+        for unfilled in ((31, 63, stop - 1), (32, 64, first), (first, stop - 1)):
+            for hanning in (False, True):
+                out.append((first, stop, tuple(sorted({c for c in unfilled if c < C})), hanning))
+    return out
+
+
+def seam_filled(C, unfilled):
+    filled = np.ones(C, np.uint8)
+    filled[list(unfilled)] = 0
+    return filled
+
+
+def seam_cube(C, plane, seed):
+    """(cube, x, cut): random_cube without its unfilled channel, and
+      voxel 2 k      the peak of range k of seam_ranges, 64, in that range's last channel,
+      voxel 2 k + 1  in its first channel,
+      the last 8 voxels  a NaN in channel 31, 32, 63 or 64 between finite neighbours, and in each of
+                     the two channels next to it between finite neighbours."""
+    cube, x, _, cut = random_cube(C, plane, seed)
+    flat = cube.reshape(C, -1)
+    M = flat.shape[1]
+    ranges = seam_ranges(C)
+    assert M >= 2 * len(ranges) + 8 and np.shares_memory(flat, cube)
+    for k, (first, stop) in enumerate(ranges):
+        flat[stop - 1, 2 * k] = 64.0
+        flat[first, 2 * k + 1] = 64.0
+    for k, c in enumerate((31, 32, 63, 64, 30, 33, 62, 65)):
+        c = min(c, C - 2)
+        flat[c - 1:c + 2, M - 1 - k] = [0.75, np.nan, 1.25]
+    return cube, x, cut
+
+
+def assert_seam_peaks(C, case, moment9, x):
+    """The twin's moment 9 says of the hand-made voxels of seam_cube what they were made for."""
+    first, stop, unfilled, _ = case
+    k = seam_ranges(C).index((first, stop))
+    flat = moment9.reshape(-1)
+    if stop - 1 not in unfilled:
+        assert flat[2 * k] == np.float32(x[stop - 1])
+    if first not in unfilled:
+        assert flat[2 * k + 1] == np.float32(x[first])
+
+
+def limit_cases():
+    """[(first, stop, unfilled, select_hanning)] of the launch at LIMIT_CHANNELS: the upper half from
+    one channel past the middle seam, and the whole band; channels 2047 and 2048 and one of the last
+    word unfilled, and in the half band the last channel too -- the round of the channel loop that
+    starts there reads the last word of the mask and the spare word behind it."""
+    C = LIMIT_CHANNELS
+    return [(first, stop, unfilled, hanning)
+            for first, stop, unfilled in ((C // 2 + 1, C, (C // 2 - 1, C // 2, C - 9, C - 1)),
+                                          (0, C, (C // 2 - 1, C // 2, C - 9)))
+            for hanning in (False, True)]
+
+
+def limit_cube(seed):
+    """(cube, x, cut) of LIMIT_CHANNELS x LIMIT_PLANE: voxel 0 has its peak in the band's last channel,
+    voxel 1 in the channel before it."""
+    cube, x, _, cut = random_cube(LIMIT_CHANNELS, LIMIT_PLANE, seed)
+    flat = cube.reshape(LIMIT_CHANNELS, -1)
+    flat[-1, 0] = 64.0
+    flat[-2, 1] = 64.0
+    return cube, x, cut

@@ -87,6 +87,46 @@ def inputs(C, N, P, seed, protect=True):
     return vis, weights, ids, mask
 
 
+#: the hot run of band_inputs: 32 channels that straddle the seam between words 1 and 2 of the mask
+HOT = (48, 80)
+BRIGHT = 32
+
+
+def band_inputs(C, N, P, seed, mask):
+    """(vis, weights, ids, mask) for a band of more than 80 channels: the noise and the embedded
+    features of :func:`inputs` with the protected channels of ``mask`` (0 = protected; band_cases.py)
+    instead of the middle of the band; channel 32, the first of word 1, protected as well, bright and
+    constant; and in one row of polarization 0 a run of 32 usable samples, channels 48 to 79, at
+    z = 12, about five times the noise's level (1.25 x 2): the windows that hold them lie across the
+    seam between words 1 and 2 of the mask at channel 64, the one window of 32 that holds them all
+    among them.  The row is the middle one of the longest run of one baseline; it and the two rows on
+    either side of it (its group at time_bin 3, whichever that is) are plain noise without zero
+    weights in polarization 0, so that no burst of :func:`inputs` lifts the group's level over the run."""
+    vis, weights, ids, _ = inputs(C, N, P, seed, protect=False)
+    mask = np.array(mask, np.uint8)
+    mask[BRIGHT] = 0
+    vis[BRIGHT] = 40.0 - 30.0j
+    row = hot_row(ids)
+    rng = np.random.default_rng(seed + 1)
+    near = slice(max(row - 2, 0), min(row + 3, N))
+    shape = vis[:, near, 0].shape
+    vis[:, near, 0] = (rng.normal(size=shape) + 1j * rng.normal(size=shape)).astype(np.complex64)
+    weights[:, near, 0] = rng.uniform(0.5, 2.0, shape).astype(np.float32)
+    vis[BRIGHT] = 40.0 - 30.0j
+    vis[HOT[0]:HOT[1], row, 0] = np.complex64(np.sqrt(12.0))
+    weights[HOT[0]:HOT[1], row, 0] = 1.0
+    return vis, weights, ids, mask
+
+
+def hot_row(ids):
+    """The row that holds the hot run of band_inputs: the middle of the longest run of one id."""
+    edges = np.flatnonzero(np.diff(ids)) + 1
+    starts = np.concatenate(([0], edges))
+    stops = np.concatenate((edges, [len(ids)]))
+    g = int(np.argmax(stops - starts))
+    return int(starts[g] + stops[g]) // 2
+
+
 def by_loops(vis, weights, ids, params):
     """``kimg_rfi_flag`` as include/kimg.h words it, one sample at a time in Python floats (IEEE
     float64, like the contract): (weights, flags, level, counts).  For small blocks."""

@@ -108,6 +108,76 @@ def test_device_against_twin(C):
     assert seen == set(COMBINATIONS)
 
 
+#: a plane whose element count is a multiple of four and one whose is not, each of two workgroups in
+#: its widest form: with LAYOUTS they give all three kernel forms
+SEAM_PLANES = ((2, 16, 36), (1, 5, 257))
+
+
+def _on_every_layout(ctx, q, data, x, cut, the_cases, check):
+    """Every case (first, stop, unfilled, select_hanning) through the twin once and through the device
+    on every layout of LAYOUTS: bit equality.  Returns the kernel forms that ran."""
+    from katsdpimager_amd import cube
+    C, plane = data.shape[0], data.shape[1:]
+    devices = [(_PaddedCube(ctx, q, data, pad, offset), pad, offset) for pad, offset in LAYOUTS]
+    forms = set()
+    for turn, case in enumerate(the_cases):
+        first, stop, unfilled, hanning = case
+        filled = cases.seam_filled(C, unfilled)
+        params = cube.MomentParameters(SUBSETS[-1 - turn % 2], channels=(first, stop), select_hanning=hanning)
+        want = cube.moments_host(data, x, cut, filled, params, channel_width=2.5)
+        check(case, want)
+        op = cube.MomentsTemplate(ctx, params).instantiate(q, data.shape)
+        for device, pad, offset in devices:
+            got = op(device.array, coordinates=x, cut=cut, filled=filled, channel_width=2.5)
+            where = (C, plane, pad, offset) + case
+            assert set(got) == set(params.moments) | {'count'}, where
+            for key in want:
+                cases.assert_same_bits(got[key].get(q), want[key], where + (key,))
+            forms.add(_form(device.M, pad, offset))
+    for device, _, _ in devices:
+        device.assert_unchanged(q)
+    return forms
+
+
+@pytest.mark.parametrize('C', cases.SEAM_CHANNELS)
+def test_device_against_twin_at_the_mask_seams(C):
+    """Ranges whose first channel lies on either side of the seam at 32, on it and on the seam at 64
+    and whose stop is a seam, next to one, or C; the channels on the seams and the range's ends
+    unfilled; NaN neighbours of the seam channels under select_hanning; peaks in the range's first and
+    last channel (moments_cases.seam_cases, seam_cube)."""
+    ctx, q = context_queue()
+    forms, seen = set(), set()
+
+    def check(case, want):
+        cases.assert_seam_peaks(C, case, want[9], x)
+        seen.add(case)
+    for i, plane in enumerate(SEAM_PLANES):
+        data, x, cut = cases.seam_cube(C, plane, 2000 * C + i)
+        forms |= _on_every_layout(ctx, q, data, x, cut, cases.seam_cases(C), check)
+    assert forms == {'scalar', 'vector', 'vector+tail'}
+    # (two of a range's unfilled sets coincide where its end is the channel on the seam)
+    assert seen == set(cases.seam_cases(C)) and len(seen) >= 6 * len(cases.seam_ranges(C)) - 8
+    assert {case[0] for case in seen} >= {31, 32, 33} and {case[1] for case in seen} >= {63, 64, C}
+
+
+def test_one_launch_at_the_longest_band():
+    """4096 channels, 129 words of mask by value: the upper half of the band and all of it, the last
+    channel unfilled in one and holding a peak in the other."""
+    ctx, q = context_queue()
+    data, x, cut = cases.limit_cube(4096)
+    C = cases.LIMIT_CHANNELS
+    seen = []
+
+    def check(case, want):
+        first, stop, unfilled, _ = case
+        flat = want[9].reshape(-1)
+        assert flat[1] == np.float32(x[C - 2])
+        assert C - 1 in unfilled or flat[0] == np.float32(x[C - 1])
+        seen.append(case)
+    forms = _on_every_layout(ctx, q, data, x, cut, cases.limit_cases(), check)
+    assert forms == {'scalar'} and len(seen) == 4
+
+
 def test_spectral_cube_put_and_moments_on_another_queue():
     """The cube: NaN until filled, planes put from a device array of another queue and from the host,
     refusals before anything is copied; then the moments of the cube itself with clip_sigma, launched

@@ -57,6 +57,42 @@ def test_twin_against_the_restatement(C, plane, channels, hanning):
         assert ((flat == flat.max(axis=0)).sum(axis=0) > 1).any()
 
 
+@pytest.mark.parametrize('C', cases.SEAM_CHANNELS)
+def test_twin_against_the_restatement_at_the_mask_seams(C):
+    """The cases of test_moments_gpu.test_device_against_twin_at_the_mask_seams on a plane small
+    enough for the loops: ranges that start and stop on and next to the seams of the device's `filled`
+    bit mask, unfilled channels there, peaks in the range's end channels."""
+    data, x, cut = cases.seam_cube(C, (2, 5, 6), 300 + C)
+    for case in cases.seam_cases(C):
+        first, stop, unfilled, hanning = case
+        filled = cases.seam_filled(C, unfilled)
+        params = cube.MomentParameters(ALL, channels=(first, stop), select_hanning=hanning)
+        got = cube.moments_host(data, x, cut, filled, params, channel_width=2.5)
+        width = cube.range_width(x, first, stop, 2.5)
+        want = cases.restate(data, x, cut, filled, first, stop, hanning, width)
+        for key in want:
+            cases.assert_same_bits(got[key], want[key], (key, C) + case)
+        cases.assert_seam_peaks(C, case, got[9], x)
+        if stop - first > 2:
+            assert got['count'].max() > 1 and (got['count'] < stop - first - len(unfilled) + 2).any()
+
+
+def test_twin_against_the_restatement_at_the_longest_band():
+    data, x, cut = cases.limit_cube(4096)
+    C = cases.LIMIT_CHANNELS
+    assert C == cube.MAX_CHANNELS
+    for first, stop, unfilled, hanning in cases.limit_cases():
+        filled = cases.seam_filled(C, unfilled)
+        params = cube.MomentParameters(ALL, channels=(first, stop), select_hanning=hanning)
+        got = cube.moments_host(data, x, cut, filled, params)
+        want = cases.restate(data, x, cut, filled, first, stop, hanning, cube.range_width(x, first, stop))
+        for key in want:
+            cases.assert_same_bits(got[key], want[key], (key, first, stop, hanning))
+        flat = got[9].reshape(-1)
+        assert C - 1 in unfilled or flat[0] == np.float32(x[C - 1])
+        assert flat[1] == np.float32(x[C - 2])
+
+
 def test_restatement_width():
     x = np.array([10.0, 7.0, 5.0, 1.0])
     assert cube.range_width(x, 0, 4) == 3.0 and cube.range_width(x, 1, 3) == 2.0

@@ -29,6 +29,9 @@ O = (0.93, -0.52)
 T = (0.93 + 0.031, -0.52 + 0.021)       # about 2 degrees away: delay 0.034, 1200 turns at 8 km
 SHAPES = [(1, 1), (5, 4), (33, 2), (7, 3)]
 ROWS = [1, 63, 64, 65, 257, 4003]
+#: bands past 64 channels and past 1024, at a partial second wave and a second workgroup
+LONG_SHAPES = [(65, 2), (1025, 1)]
+LONG_ROWS = [65, 257]
 
 
 def _inputs(C, N, Q, seed):
@@ -102,6 +105,15 @@ class _Embedded:
 
 @pytest.mark.parametrize('C,Q', SHAPES)
 def test_device_against_twin(C, Q):
+    _device_against_twin(C, Q, ROWS)
+
+
+@pytest.mark.parametrize('C,Q', LONG_SHAPES)
+def test_device_against_twin_on_long_bands(C, Q):
+    _device_against_twin(C, Q, LONG_ROWS)
+
+
+def _device_against_twin(C, Q, rows):
     from katsdpimager_amd import accel, phaseshift
     from katsdpimager_amd._lib import lib
     ctx, q = context_queue()
@@ -110,7 +122,7 @@ def test_device_against_twin(C, Q):
     template = phaseshift.PhaseShiftTemplate(ctx, params)
     p12 = params.params12()
     worst = 0.0
-    for i, N in enumerate(ROWS):
+    for i, N in enumerate(rows):
         vis, uvw, inv_wl = _inputs(C, N, Q, 100 * C + i)
         if N >= 63:
             turns = np.abs(inv_wl[:, None] * (uvw[[11]].astype(np.float64) @ params.delay)[None])

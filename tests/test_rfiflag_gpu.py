@@ -15,6 +15,7 @@ spikes, runs, bursts and rows without weight embedded in it."""
 import numpy as np
 import pytest
 
+import band_cases as bands
 import golden_inputs as gi
 import rfiflag_cases as cases
 from helpers import context_queue, make_params, SENTINELS
@@ -86,6 +87,54 @@ def test_device_against_twin(max_window):
     assert len(seen) == 4 * 3 + 3 * 3 + 3
     # the blocks held something of everything: samples kept, samples flagged, pairs skipped
     assert total.min() > 0
+
+
+@pytest.mark.parametrize('N,P', bands.PLANES)
+@pytest.mark.parametrize('C', [97, 1025])
+def test_device_against_twin_past_one_mask_word(C, N, P):
+    """Windows of up to 32 samples in both directions over bands of four and of 33 mask words, the
+    protected channels those of every mask of band_cases (rfiflag_cases.band_inputs): a bright
+    protected channel at the start of word 1, a hot run under a window of 32 across the seam at 64."""
+    from katsdpimager_amd import rfiflag
+    ctx, q = context_queue()
+    total = np.zeros(3, np.int64)
+    names = set()
+    for i, (name, mask) in enumerate(bands.masks(C)):
+        time_bin = cases.TIME_BINS[i % 3]
+        vis, weights, ids, mask = cases.band_inputs(C, N, P, 100 * C + 10 * N + i, mask)
+        params = rfiflag.RFIFlagParameters(time_bin, max_window=32, directions='both',
+                                           level_iterations=cases.LEVEL_ITERATIONS[i % 3], fit_mask=mask,
+                                           extend_pols=bool(i % 2))
+        want = rfiflag.rfiflag_host(vis, weights, ids, params)
+        op = rfiflag.RFIFlagTemplate(ctx, params).instantiate(q, C)
+        got = _run(ctx, q, op, vis, weights, ids)
+        try:
+            cases.assert_same(got + (op.counts(),), want)
+        except AssertionError as e:
+            raise AssertionError('{} at {}'.format(e, (C, N, P, name, params))) from None
+        total += want[3]
+        names.add(name)
+    assert len(names) == len(bands.MASKS)
+    # the blocks held something of everything: samples kept, samples flagged, pairs skipped
+    assert total.min() > 0
+
+
+def test_one_launch_at_the_longest_band():
+    """16384 channels, 512 words of mask by value in the kernel arguments: the only protected channels
+    are 32, 8191, 8192 and two of the last word; the workspace is the one workspace_bytes states."""
+    from katsdpimager_amd import continuum, rfiflag
+    ctx, q = context_queue()
+    C, N, P = continuum.MAX_CHANNELS, 6, 2
+    assert C == 16384
+    vis, weights, ids, mask = cases.band_inputs(C, N, P, 16384, bands.limit_mask(C))
+    weights[:, 2, 1] = 0.0                          # (a row without weight: time_bin 1 skips it)
+    params = rfiflag.RFIFlagParameters(1, max_window=32, directions='both', fit_mask=mask)
+    want = rfiflag.rfiflag_host(vis, weights, ids, params)
+    assert min(want[3]) > 0
+    op = rfiflag.RFIFlagTemplate(ctx, params).instantiate(q, C)
+    got = _run(ctx, q, op, vis, weights, ids)
+    cases.assert_same(got + (op.counts(),), want)
+    assert op._workspace.shape[0] == op.workspace_bytes(C, N, P) == 9 * C * N * P + 24 * N * P
 
 
 def test_the_longest_window_along_time_in_a_group_that_holds_it():
@@ -178,16 +227,15 @@ def _assert_same_store(a, b, channels):
     assert records > 20
 
 
-@pytest.fixture(scope='module')
-def band():
-    """Two blocks of 8 channels: 4 baselines x 6 times in time order, two polarizations, noise of a
+def _make_band(C):
+    """Two blocks of C channels: 4 baselines x 6 times in time order, two polarizations, noise of a
     different sigma on every baseline about a continuum, weights U(0.5, 1.5) with some zeros,
     spikes in both blocks and one baseline whose first block has no weight at all."""
     from katsdpimager_amd import loader
     ctx, q = context_queue()
     c = gi.E2E_CONFIGS['degrid']
     ip, gp, ap = make_params(c)
-    C, baselines, times, P = 8, 4, 6, 2
+    baselines, times, P = 4, 6, 2
     R = baselines * times
     rng = np.random.default_rng(45)
     uvw = gi.e2e_raw(c)[0][:R]
@@ -205,6 +253,17 @@ def band():
                                   longest_baseline=c['longest_baseline'])
     return dict(ctx=ctx, q=q, ip=ip, gp=gp, C=C, dataset=dataset, vis_load=C * R // 2,
                 stokes=np.array([[0.5, 0.5]], np.complex64))
+
+
+@pytest.fixture(scope='module')
+def band():
+    return _make_band(8)
+
+
+@pytest.fixture(scope='module')
+def long_band():
+    """70 channels: three words of the operators' channel masks."""
+    return _make_band(70)
 
 
 def _collector(band, channels):
@@ -265,6 +324,32 @@ def test_between_the_continuum_fit_and_statwt_after_the_spectral_filter(band):
     assert through.rfiflag_counts == flagged and through.statwt_counts == reweighted
     # per block 4 baselines of 3 rows, one group each, two polarizations; one pair without weight
     assert flagged[1] > 0 and flagged[2] >= 1 and sum(reweighted) == 2 * 4 * 2
+    assert not hasattr(by_hand, 'rfiflag_counts')
+
+
+def test_between_the_continuum_fit_and_statwt_with_line_ranges_on_the_mask_seams(long_band):
+    """70 channels with the line ranges (30, 34) and (62, 66), across the seams at 32 and 64 of the
+    three operators' masks alike: the store byte for byte the twins' chained by hand, and the three
+    sets of counts."""
+    from katsdpimager_amd import continuum, rfiflag, statwt
+    band = long_band
+    C = band['C']
+    ranges = [(30, 34), (62, 66)]
+    cont = continuum.UVContSubParameters(1, line_ranges=ranges)
+    params = rfiflag.RFIFlagParameters(3, max_window=32, line_ranges=ranges)
+    reweight = statwt.StatWtParameters(3, line_ranges=ranges, min_samples=4)
+    through, by_hand, flagged, reweighted = _through_and_by_hand(
+        band, params, reweight, C,
+        [lambda: continuum.UVContSubTemplate(band['ctx'], cont).instantiate(band['q'], C)], continuum=cont)
+    _assert_same_store(through, by_hand, C)
+    assert through.rfiflag_counts == flagged and through.statwt_counts == reweighted
+    from katsdpimager_amd import loader
+    fitted = np.zeros(2, np.int64)
+    for chunk in loader.data_iter(band['dataset'], None, band['vis_load'], 0, C):
+        fitted += continuum.uvcontsub_host(chunk['vis'], chunk['weights'], cont)[2]
+    # (the baseline without weight in the first block: three rows of one polarization)
+    assert through.continuum_counts == tuple(fitted) == (2 * 12 * 2 - 3, 3)
+    assert flagged[0] > 0 and flagged[1] > 0 and flagged[2] >= 1 and sum(reweighted) == 2 * 4 * 2
     assert not hasattr(by_hand, 'rfiflag_counts')
 
 

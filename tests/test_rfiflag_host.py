@@ -14,6 +14,7 @@ import re
 import numpy as np
 import pytest
 
+import band_cases as bands
 import rfiflag_cases as cases
 from katsdpimager_amd import loader, rfiflag
 from katsdpimager_amd.rfiflag import RFIFlagParameters, rfiflag_host
@@ -225,6 +226,49 @@ def test_twin_against_the_loops_on_noisy_blocks(seed):
         flags, _, counts = _run(vis, weights, ids, params)
         flagged += counts[1]
     assert flagged > 0
+
+
+@pytest.mark.parametrize('make', [bands.straddle, bands.alternate_words, bands.word0_empty])
+def test_twin_against_the_loops_past_one_mask_word(make):
+    """97 channels, four words of the device's mask, windows of up to 32 in both directions, on a
+    block small enough for the loops: the twin the device is compared with."""
+    C, N, P = 97, 10, 2
+    vis, weights, ids, mask = cases.band_inputs(C, N, P, 97, make(C))
+    ids = np.repeat(np.array([3, 1], np.int32), 5)
+    params = RFIFlagParameters(4, max_window=32, directions='both', fit_mask=mask)
+    flags, level, counts = _run(vis, weights, ids, params)
+    assert counts[0] > 0 and counts[1] > 0
+
+
+@pytest.mark.parametrize('C', [97, 1025])
+def test_long_band_cases_hold_what_they_were_made_for(C):
+    """The blocks of test_rfiflag_gpu.test_device_against_twin_past_one_mask_word, with the twin
+    alone: every plane's blocks together have samples kept, samples flagged and pairs skipped; the
+    bright channel at 32 is protected and never flagged, the searched samples of the hot run are
+    flagged, and (looked at in the band of 97) the windows of 32 flag what the shorter ones leave."""
+    longest = False
+    for N, P in bands.PLANES:
+        total = np.zeros(3, np.int64)
+        for i, (name, mask) in enumerate(bands.masks(C)):
+            time_bin = cases.TIME_BINS[i % 3]
+            vis, weights, ids, mask = cases.band_inputs(C, N, P, 100 * C + 10 * N + i, mask)
+            assert not mask[cases.BRIGHT] and mask.any()
+            params = RFIFlagParameters(time_bin, max_window=32, directions='both',
+                                       level_iterations=cases.LEVEL_ITERATIONS[i % 3], fit_mask=mask,
+                                       extend_pols=bool(i % 2))
+            _, flags, level, counts = rfiflag_host(vis, weights, ids, params)
+            total += counts
+            run = slice(*cases.HOT)
+            searched = mask[run].astype(bool)
+            if searched.any():
+                assert flags[run, cases.hot_row(ids), 0][searched].all(), (C, N, P, name)
+            if C == 97:
+                shorter = RFIFlagParameters(time_bin, max_window=16, directions='both',
+                                            level_iterations=cases.LEVEL_ITERATIONS[i % 3], fit_mask=mask,
+                                            extend_pols=bool(i % 2))
+                longest |= not np.array_equal(rfiflag_host(vis, weights, ids, shorter)[1], flags)
+        assert total.min() > 0
+    assert longest or C != 97
 
 
 # ---- pure noise -------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@ cannot reach two samples and holds no kept group at all."""
 import numpy as np
 import pytest
 
+import band_cases as bands
 import golden_inputs as gi
 import statwt_cases as cases
 from helpers import context_queue, make_params, SENTINELS
@@ -92,6 +93,52 @@ def test_device_against_twin(shape):
                 _assert_chi2(chi2, want_chi2)
                 assert op.counts() == counts, where
     assert {'exact', 'empty', 'constant', 'samples'} <= seen
+
+
+def _against_twin(ctx, q, C, mask, N, P, time_bin, seed):
+    """One block of statwt_cases.inputs through the twin (whose answer for the hand-made groups is
+    checked) and the device: bit equality; the marks it held."""
+    from katsdpimager_amd import statwt
+    vis, weights, ids, params, marks = cases.inputs(C, mask, N, P, time_bin, seed)
+    _, offsets, _, most = cases.parameters(C, mask, time_bin, ids)
+    want, want_chi2, counts = statwt.statwt_host(vis, weights, ids, params)
+    cases.assert_marks(marks, want, want_chi2, counts, weights, offsets, most, N, P)
+    op = statwt.StatWtTemplate(ctx, params).instantiate(q, C)
+    got, chi2 = _run(ctx, q, op, vis, weights, ids)
+    where = (C, N, P, time_bin)
+    assert np.array_equal(_bits(got), _bits(want)), where
+    _assert_chi2(chi2, want_chi2)
+    assert op.counts() == counts, where
+    return set(marks)
+
+
+@pytest.mark.parametrize('C', bands.CHANNELS)
+def test_device_against_twin_past_one_mask_word(C):
+    """Every mask of band_cases with a fit channel, on both planes, time_bin 1, 3 and 64 in turn."""
+    ctx, q = context_queue()
+    seen, bins = set(), set()
+    turn = 0
+    for i, (name, mask) in enumerate(bands.masks(C)):
+        for N, P in bands.PLANES:
+            time_bin = cases.TIME_BINS[turn % 3]
+            turn += 1
+            try:
+                seen |= _against_twin(ctx, q, C, mask, N, P, time_bin, 9000 * i + 10 * N + P + C)
+            except AssertionError as e:
+                raise AssertionError('{} at {}'.format(e, (C, name, N, P, time_bin))) from None
+            bins.add(time_bin)
+    assert turn >= 8 and bins == set(cases.TIME_BINS)
+    assert {'exact', 'empty', 'constant'} <= seen
+
+
+def test_one_launch_at_the_longest_band():
+    """16384 channels, 512 words of mask by value in the kernel arguments of three launches: the only
+    line channels are 8191, 8192 and two of the last word."""
+    from katsdpimager_amd import continuum
+    ctx, q = context_queue()
+    C = continuum.MAX_CHANNELS
+    assert C == 16384
+    assert {'exact', 'empty', 'constant'} <= _against_twin(ctx, q, C, bands.limit_mask(C), 65, 2, 3, 16384)
 
 
 def test_repeated_calls_and_a_growing_workspace():

@@ -10,6 +10,7 @@ import re
 import numpy as np
 import pytest
 
+import band_cases as bands
 import statwt_cases as cases
 from katsdpimager_amd import loader, statwt
 from katsdpimager_amd.statwt import StatWtParameters, group_offsets, statwt_host
@@ -288,6 +289,96 @@ def test_device_cases_hold_their_hand_made_groups(shape):
                     assert {'low', 'high'} <= set(marks)
     assert {'empty', 'constant', 'samples'} <= seen
     assert ('exact' in seen) and ('low' in seen or C == 1)
+
+
+@pytest.mark.parametrize('C', bands.CHANNELS)
+def test_long_band_cases_hold_their_hand_made_groups(C):
+    """The blocks of test_statwt_gpu.test_device_against_twin_past_one_mask_word, with the twin alone."""
+    seen = set()
+    turn = 0
+    for i, (name, mask) in enumerate(bands.masks(C)):
+        for N, P in bands.PLANES:
+            time_bin = cases.TIME_BINS[turn % 3]
+            turn += 1
+            vis, weights, ids, params, marks = cases.inputs(C, mask, N, P, time_bin, 9000 * i + 10 * N + P + C)
+            _, offsets, _, most = cases.parameters(C, mask, time_bin, ids)
+            new, chi2, counts = statwt_host(vis, weights, ids, params)
+            cases.assert_marks(marks, new, chi2, counts, weights, offsets, most, N, P)
+            seen |= set(marks)
+    assert {'exact', 'empty', 'constant'} <= seen
+
+
+def _per_sample(vis, weights, ids, params):
+    """The contract of kimg_statwt once more, one sample at a time in Python floats: (weights, chi2,
+    counts).  It shares no line with the vectorised twin.  For small blocks."""
+    C, N, P = vis.shape
+    mask = params.mask(C)
+    offsets = group_offsets(ids, params.time_bin)
+    G = len(offsets) - 1
+    lo, hi = params.chi2_range
+    new = weights.copy()
+    chi2 = np.full((G, P), np.nan)
+    kept_groups = 0
+    for g in range(G):
+        rows = range(offsets[g], offsets[g + 1])
+        for p in range(P):
+            def usable(c, r):
+                w, v = float(weights[c, r, p]), vis[c, r, p]
+                return mask[c] and w > 0 and np.isfinite(w) and np.isfinite(v.real) and np.isfinite(v.imag)
+            S0 = SR = SI = 0.0
+            M = 0
+            for r in rows:
+                s0 = sr = si = 0.0
+                for c in range(C):
+                    if usable(c, r):
+                        w = float(weights[c, r, p])
+                        s0 += w
+                        sr += w * float(vis[c, r, p].real)
+                        si += w * float(vis[c, r, p].imag)
+                        M += 1
+                S0, SR, SI = S0 + s0, SR + sr, SI + si
+            Q = 0.0
+            if S0 > 0:
+                mur, mui = SR / S0, SI / S0
+                for r in rows:
+                    q = 0.0
+                    for c in range(C):
+                        if usable(c, r):
+                            dr = float(vis[c, r, p].real) - mur
+                            di = float(vis[c, r, p].imag) - mui
+                            t = dr * dr
+                            t = t + di * di
+                            q += float(weights[c, r, p]) * t
+                    Q += q
+            value = Q / (2.0 * (M - 1)) if M >= 2 else np.nan
+            chi2[g, p] = value
+            kept = M >= params.min_samples and lo < value < hi
+            kept_groups += kept
+            for r in rows:
+                for c in range(C):
+                    if not kept:
+                        new[c, r, p] = 0.0
+                    elif weights[c, r, p] > 0:
+                        with np.errstate(over='ignore'):
+                            new[c, r, p] = np.float32(float(weights[c, r, p]) / value)
+    return new, chi2, (kept_groups, G * P - kept_groups)
+
+
+@pytest.mark.parametrize('make', [bands.straddle, bands.word0_empty])
+@pytest.mark.parametrize('time_bin', [1, 3])
+def test_twin_against_the_per_sample_restatement_past_one_mask_word(make, time_bin):
+    """65 channels, three words of the device's mask: the twin the device is compared with, bit for
+    bit against the loops."""
+    C, N, P = 65, 40, 2
+    mask = make(C)
+    vis, weights, ids, params, marks = cases.inputs(C, mask, N, P, time_bin, 65 + time_bin)
+    got = statwt_host(vis, weights, ids, params)
+    want = _per_sample(vis, weights, ids, params)
+    assert np.array_equal(_bits(got[0]), _bits(want[0]))
+    nan = np.isnan(want[1])
+    assert np.array_equal(np.isnan(got[1]), nan)
+    assert np.array_equal(got[1][~nan].view(np.uint64), want[1][~nan].view(np.uint64))
+    assert got[2] == want[2] and got[2][0] >= 1 and got[2][1] >= 1
 
 
 # ---- the C entry point, without a device ------------------------------------------------------------

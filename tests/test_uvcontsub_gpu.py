@@ -11,6 +11,7 @@ asserted below) -- three orders inside the bound, while any float32 step in the 
 import numpy as np
 import pytest
 
+import band_cases as bands
 import golden_inputs as gi
 from helpers import context_queue, make_params, SENTINELS
 
@@ -29,11 +30,13 @@ SHAPES = [
 PLANES = [(1, 1), (63, 1), (64, 1), (65, 1), (1000, 1), (1000, 2), (1000 * 4 + 3, 1)]
 
 
-def _inputs(C, order, mask, N, Q, seed):
+def _inputs(C, order, mask, N, Q, seed, pool=None):
     """Weights U(0.5, 2) with 20 % zeros, and, where the plane has room, hand-made samples: one that
     cannot be fitted (m = K - 1), one with m == K exactly on well-spread channels (the others
     knocked out by a zero weight, a negative weight or a NaN in turn), a NaN and a negative weight
-    in a fit channel, a NaN in a line channel."""
+    in a fit channel, a NaN in a line channel.  ``pool``: the fit channels that the surviving
+    channels of the first two, and the NaN and the negative weight, are taken from (all of them by
+    default)."""
     rng = np.random.default_rng(seed)
     K = order + 1
     vis = ((rng.normal(size=(C, N, Q)) + 1j * rng.normal(size=(C, N, Q))) * 3.0).astype(np.complex64)
@@ -41,6 +44,7 @@ def _inputs(C, order, mask, N, Q, seed):
     weights[rng.random((C, N, Q)) < 0.2] = 0.0
     fit = np.flatnonzero(mask)
     line = np.flatnonzero(np.asarray(mask) == 0)
+    pool = fit if pool is None else np.asarray(pool)
     v2, w2 = vis.reshape(C, N * Q), weights.reshape(C, N * Q)       # (views)
 
     def keep_only(j, channels):
@@ -53,23 +57,23 @@ def _inputs(C, order, mask, N, Q, seed):
             else:
                 v2[c, j] = complex(np.nan, 2.0) if i % 2 else complex(-1.0, np.inf)
     if N * Q >= 63:
-        spread = fit[np.round(np.linspace(0, len(fit) - 1, K)).astype(int)]
+        spread = pool[np.round(np.linspace(0, len(pool) - 1, K)).astype(int)]
         keep_only(3, spread[:K - 1])            # m = K - 1: flagged
         keep_only(5, spread)                    # m == K
         keep_only(40, fit)                      # every fit channel usable ...
         keep_only(41, fit)
-        v2[fit[len(fit) // 2], 40] = np.nan     # ... but one NaN
-        w2[fit[0], 41] = -0.75                  # ... but one negative weight
+        v2[pool[len(pool) // 2], 40] = np.nan   # ... but one NaN
+        w2[pool[0], 41] = -0.75                 # ... but one negative weight
         if len(line):
             w2[:, 42] = rng.uniform(0.5, 2.0, C)
             v2[line[0], 42] = complex(3.0, np.nan)
     return vis, weights
 
 
-def _cond(weights, vis, C, order, mask):
+def _cond(weights, vis, C, order, mask, frequencies=None):
     """The largest cond(A) over the samples that are fitted."""
     from katsdpimager_amd.continuum import legendre_basis
-    B = legendre_basis(order, C)
+    B = legendre_basis(order, C, frequencies)
     usable = (np.asarray(mask, bool)[:, None, None] & (weights > 0)
               & np.isfinite(vis.real) & np.isfinite(vis.imag))
     w = np.where(usable, weights.astype(np.float64), 0.0)
@@ -167,6 +171,82 @@ def test_device_against_twin(C, order, mask):
             assert op2.counts() == (call * counts[0], call * counts[1])
         op2.reset_counts()
         assert op2.counts() == (0, 0)
+
+
+# ---- bands longer than one word of the fit mask (band_cases.py) --------------------------------------
+def seam_case(C, order, mask):
+    """(pool, frequencies) of a long-band case.  ``pool``: the fit channels outside word 0 of the mask
+    (all fit channels where fewer than K lie there), from which the hand-made samples of _inputs take
+    their surviving channels.  ``frequencies``: the step into a channel of the pool is 1 MHz, into any
+    other channel 1/256 MHz, so that the pool lies evenly over x in [-1, 1] whatever the mask: with a
+    mask that confines the fit channels to the last 33 of 1025, evenly spaced channels would put them
+    on x in [0.94, 1], where cond(A) of an order-1 fit is already 1e4 by geometry alone and the bound
+    of this file does not apply."""
+    fit = np.flatnonzero(mask)
+    pool = fit[fit >= bands.WORD]
+    if len(pool) < order + 1:
+        pool = fit
+    step = np.full(C, 1.0 / 256.0)
+    step[pool] = 1.0
+    return pool, 1.4e9 + 1.0e6 * np.cumsum(step)
+
+
+def seam_inputs(C, order, mask, N, Q, seed):
+    """(vis, weights, params, pool) of a long-band case."""
+    from katsdpimager_amd import continuum
+    pool, frequencies = seam_case(C, order, mask)
+    params = continuum.UVContSubParameters(order, fit_mask=mask, frequencies=frequencies)
+    vis, weights = _inputs(C, order, mask, N, Q, seed, pool=pool)
+    return vis, weights, params, pool
+
+
+def _run_padded(ctx, q, params, vis, weights):
+    """The operator on padded channel pitches, different for the two arrays (the padding is checked
+    to come back unchanged): (vis, weights, counts)."""
+    from katsdpimager_amd import continuum
+    op = continuum.UVContSubTemplate(ctx, params).instantiate(q, vis.shape[0])
+    d_vis = _PaddedBlock(ctx, q, vis, 5)
+    d_weights = _PaddedBlock(ctx, q, weights, 11)
+    op(d_vis.array, d_weights.array)
+    return d_vis.get(q), d_weights.get(q), op.counts()
+
+
+@pytest.mark.parametrize('order', [0, 1, 2, 3])
+@pytest.mark.parametrize('C', bands.CHANNELS)
+def test_device_against_twin_past_one_mask_word(C, order):
+    """Every mask of band_cases that leaves order + 1 fit channels, on both planes: the bound and the
+    condition of test_device_against_twin, unchanged.  (A different summation order over C terms
+    costs about C 2^-53 cond(A) S, 1e-10 S at 1025 channels and cond(A) = 1e3.)"""
+    ctx, q = context_queue()
+    ran = 0
+    for i, (name, mask) in enumerate(bands.masks(C, least=order + 1)):
+        for k, (N, Q) in enumerate(bands.PLANES):
+            vis, weights, params, pool = seam_inputs(C, order, mask, N, Q, 7000 * C + 10 * i + k)
+            assert _cond(weights, vis, C, order, mask, params.frequencies) <= 1e3, (name, N, Q)
+            got_vis, got_weights, counts = _run_padded(ctx, q, params, vis, weights)
+            try:
+                want = _check_against_twin(got_vis, got_weights, vis, weights, params)
+            except AssertionError as e:
+                raise AssertionError('{} at {}'.format(e, (C, order, name, N, Q))) from None
+            assert counts == want and sum(counts) == N * Q
+            assert counts[0] >= 1 and counts[1] >= 1
+            ran += 1
+    assert ran == 2 * len(bands.masks(C, least=order + 1)) and ran >= 6
+
+
+def test_one_launch_at_the_longest_band():
+    """MAX_CHANNELS channels, 512 words of mask by value in the kernel arguments, order 3: the only
+    line channels are 8191, 8192 and two of the last word."""
+    from katsdpimager_amd import continuum
+    ctx, q = context_queue()
+    C, N, Q, order = continuum.MAX_CHANNELS, 65, 2, 3
+    assert C == 16384
+    mask = bands.limit_mask(C)
+    vis, weights, params, pool = seam_inputs(C, order, mask, N, Q, 16384)
+    assert _cond(weights, vis, C, order, mask, params.frequencies) <= 1e3
+    got_vis, got_weights, counts = _run_padded(ctx, q, params, vis, weights)
+    want = _check_against_twin(got_vis, got_weights, vis, weights, params)
+    assert counts == want and counts[0] >= 1 and counts[1] >= 1 and sum(counts) == N * Q
 
 
 def test_refusals_on_the_device():

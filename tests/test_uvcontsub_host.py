@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import band_cases as bands
 from katsdpimager_amd import continuum
 from katsdpimager_amd.continuum import UVContSubParameters, legendre_basis, uvcontsub_host
 
@@ -113,7 +114,9 @@ def _random_block(rng, C, N, Q, zero_fraction=0.2):
 
 @pytest.mark.parametrize('C,order,mask', [
     (24, 3, [1] * 9 + [0] * 6 + [1] * 9), (5, 3, [1] * 5), (16, 1, [1] * 6 + [0] * 4 + [1] * 6),
-    (7, 2, [1, 1, 0, 0, 0, 1, 1]), (1, 0, [1]), (12, 0, [0, 1] * 6)])
+    (7, 2, [1, 1, 0, 0, 0, 1, 1]), (1, 0, [1]), (12, 0, [0, 1] * 6),
+    # past one word of the device's bit mask (band_cases.py)
+    (65, 3, bands.straddle(65)), (65, 2, bands.word0_empty(65))])
 def test_twin_against_an_independent_solve(C, order, mask):
     """For every sample the model of the twin (input - output, in float64) against numpy's lstsq
     on the sqrt(w)-scaled system, to 1e-10 of the sample's largest |v|."""
@@ -214,3 +217,42 @@ def test_samples_that_cannot_be_fitted_are_flagged():
     assert np.abs(out[0, 1, 0]) > 1e-3          # (an unusable fit channel is still subtracted from)
     assert np.isnan(out[6, 1, 0].real)          # IEEE: NaN in, NaN out
     assert np.isnan(out[4, 4, 0].real) and np.isfinite(out[[0, 1, 2, 3, 5, 6, 7, 8], 4, 0]).all()
+
+
+# ---- the long-band blocks of test_uvcontsub_gpu.py hold what they were made for ----------------------
+def test_band_masks_reach_every_seam():
+    for C in bands.CHANNELS:
+        bands.self_check(C)
+    C = continuum.MAX_CHANNELS
+    mask = bands.limit_mask(C)
+    assert np.flatnonzero(mask == 0).tolist() == [8191, 8192, C - 7, C - 1]
+    assert bands.packed(mask)[[255, 256, 511]].tolist() == [0x7fffffff, 0xfffffffe, 0x7dffffff]
+
+
+@pytest.mark.parametrize('C', bands.CHANNELS)
+def test_long_band_cases_are_well_conditioned_and_hold_their_samples(C):
+    """What test_uvcontsub_gpu.test_device_against_twin_past_one_mask_word asserts of its inputs, with
+    the twin alone: cond(A) <= 1e3, a sample that is fitted and one that is not, and the hand-made
+    samples' surviving channels outside word 0 of the mask wherever K fit channels lie there."""
+    import test_uvcontsub_gpu as device_cases
+    for order in range(4):
+        K = order + 1
+        cases = bands.masks(C, least=K)
+        assert len(cases) >= 4 and all(mask.sum() >= K for _, mask in cases)
+        for i, (name, mask) in enumerate(cases):
+            N, Q = bands.PLANES[i % 2]
+            vis, weights, params, pool = device_cases.seam_inputs(C, order, mask, N, Q, 7000 * C + 10 * i)
+            assert device_cases._cond(weights, vis, C, order, mask, params.frequencies) <= 1e3
+            x = continuum.legendre_basis(1, C, params.frequencies)[1]
+            assert x[0] == -1.0 and x[-1] == 1.0 and (np.diff(x) > 0).all()
+            _, new_weights, fitted = continuum.uvcontsub_host_double(vis, weights, params)
+            fitted, v, w = fitted.reshape(-1), vis.reshape(C, -1), weights.reshape(C, -1)
+            usable = mask.astype(bool)[:, None] & (w > 0) & np.isfinite(v.real) & np.isfinite(v.imag)
+            assert not fitted[3] and usable[:, 3].sum() == K - 1
+            assert fitted[5] and usable[:, 5].sum() == K
+            assert usable[:, 40].sum() == usable[:, 41].sum() == mask.sum() - 1
+            assert fitted[40] == fitted[41] == (mask.sum() - 1 >= K)
+            if (np.flatnonzero(mask) >= bands.WORD).sum() >= K:
+                assert pool.min() >= bands.WORD
+                assert np.flatnonzero(usable[:, 5]).min() >= bands.WORD
+                assert K == 1 or np.flatnonzero(usable[:, 3]).min() >= bands.WORD
