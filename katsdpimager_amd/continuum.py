@@ -16,11 +16,12 @@ import numpy as np
 
 from . import accel
 from ._lib import lib, check
+from .channel_block import MAX_CHANNELS                                           # noqa: F401
+from .channel_block import (ChannelOperator, ChannelSelection, OperatorTemplate, channel_count,
+                            channel_pitch, check_block)
 
 #: KIMG_UVCONTSUB_MAX_ORDER
 MAX_ORDER = 3
-#: KIMG_UVCONTSUB_MAX_CHANNELS
-MAX_CHANNELS = 16384
 
 
 class UVContSubParameters:
@@ -38,24 +39,10 @@ class UVContSubParameters:
             raise ValueError('order must be an integer') from None
         if as_int != order or not 0 <= as_int <= MAX_ORDER:
             raise ValueError('order must be an integer from 0 to {}'.format(MAX_ORDER))
-        if (fit_mask is None) == (line_ranges is None):
-            raise ValueError('exactly one of fit_mask and line_ranges must be given')
+        self._selection = ChannelSelection(fit_mask, line_ranges, order=as_int)
         self.order = as_int
-        self.fit_mask = None
-        self.line_ranges = None
-        if fit_mask is not None:
-            fit_mask = np.asarray(fit_mask)
-            if fit_mask.ndim != 1:
-                raise ValueError('fit_mask must have one entry per channel')
-            self.fit_mask = (fit_mask != 0).astype(np.uint8)
-        else:
-            ranges = []
-            for r in line_ranges:
-                first, stop = (int(x) for x in r)
-                if first < 0 or stop < first:
-                    raise ValueError('bad line range {!r}'.format(r))
-                ranges.append((first, stop))
-            self.line_ranges = ranges
+        self.fit_mask = self._selection.fit_mask
+        self.line_ranges = self._selection.line_ranges
         self.frequencies = None
         if frequencies is not None:
             frequencies = np.asarray(frequencies, np.float64)
@@ -69,33 +56,15 @@ class UVContSubParameters:
 
     def mask(self, num_channels):
         """The fit mask of ``num_channels`` channels, uint8 (1 = enters the fit)."""
-        num_channels = int(num_channels)
-        if num_channels < 1:
-            raise ValueError('no channels')
+        num_channels = channel_count(num_channels)
         if self.frequencies is not None and len(self.frequencies) != num_channels:
             raise ValueError('{} frequencies for {} channels'.format(len(self.frequencies), num_channels))
-        if self.fit_mask is not None:
-            if len(self.fit_mask) != num_channels:
-                raise ValueError('fit_mask has {} entries for {} channels'.format(
-                    len(self.fit_mask), num_channels))
-            mask = self.fit_mask.copy()
-        else:
-            mask = np.ones(num_channels, np.uint8)
-            for first, stop in self.line_ranges:
-                if stop > num_channels:
-                    raise ValueError('line range ({}, {}) beyond the {} channels'.format(
-                        first, stop, num_channels))
-                mask[first:stop] = 0
-        if int(mask.sum()) < self.order + 1:
-            raise ValueError('order {} needs {} line-free channels, {} remain'.format(
-                self.order, self.order + 1, int(mask.sum())))
-        return mask
+        return self._selection.mask(num_channels)
 
     def __repr__(self):
-        which = 'fit_mask={!r}'.format(self.fit_mask.tolist()) if self.fit_mask is not None \
-            else 'line_ranges={!r}'.format(self.line_ranges)
         return 'UVContSubParameters({!r}, {}{})'.format(
-            self.order, which, '' if self.frequencies is None else ', frequencies=...')
+            self.order, self._selection.spelling(),
+            '' if self.frequencies is None else ', frequencies=...')
 
 
 def legendre_basis(order, num_channels, frequencies=None):
@@ -131,10 +100,7 @@ def uvcontsub_host_double(vis, weights, params):
     and the weights 0."""
     vis = np.asarray(vis)
     weights = np.asarray(weights)
-    if vis.dtype != np.complex64 or weights.dtype != np.float32:
-        raise TypeError('vis must be complex64 and weights float32')
-    if vis.ndim != 3 or vis.shape != weights.shape:
-        raise ValueError('vis and weights must both be [channel][row][polarization]')
+    check_block(vis, weights)
     C = vis.shape[0]
     K = params.order + 1
     mask = params.mask(C)
@@ -198,19 +164,7 @@ def uvcontsub_host(vis, weights, params):
     return rounded, new_weights, (n_fitted, int(fitted.size) - n_fitted)
 
 
-class UVContSubTemplate:
-    def __init__(self, context, params, tuning=None):
-        if not isinstance(params, UVContSubParameters):
-            raise TypeError('params must be UVContSubParameters')
-        lib()
-        self.context = context
-        self.params = params
-
-    def instantiate(self, *args, **kwargs):
-        return UVContSub(self, *args, **kwargs)
-
-
-class UVContSub:
+class UVContSub(ChannelOperator):
     """``kimg_uvcontsub`` for blocks of ``num_channels`` channels.  ``op(vis, weights)`` works in
     place on two :class:`accel.DeviceArray` of shape [C][N][Q] (complex64 / float32) whose inner
     [N][Q] plane is dense; the channel axis may have any pitch (a view of a larger tensor).  The
@@ -218,59 +172,28 @@ class UVContSub:
     fitted and flagged since construction or :meth:`reset_counts`."""
 
     def __init__(self, template, command_queue, num_channels):
+        super().__init__(template, command_queue, num_channels, masked=True)
         params = template.params
-        self.template = template
-        self.command_queue = command_queue
-        self.num_channels = int(num_channels)
         self.order = params.order
-        if self.num_channels > MAX_CHANNELS:
-            raise ValueError('at most {} channels'.format(MAX_CHANNELS))
-        self._mask = np.ascontiguousarray(params.mask(self.num_channels), np.uint8)
         basis = legendre_basis(params.order, self.num_channels, params.frequencies)
-        context = command_queue.context
-        self._basis = accel.DeviceArray(context, basis.shape, np.float64, queue=command_queue)
+        self._basis = accel.DeviceArray(command_queue.context, basis.shape, np.float64,
+                                        queue=command_queue)
         self._basis.set(command_queue, basis)
-        self._counts = accel.DeviceArray(context, (2,), np.int64, queue=command_queue)
-        self._counts.zero(command_queue)
-
-    @staticmethod
-    def _channel_pitch(array, what):
-        t = array.tensor
-        C, N, Q = array.shape
-        if N * Q == 0:
-            return 0
-        strides = t.stride()
-        if (Q > 1 and strides[2] != 1) or (N > 1 and strides[1] != Q):
-            raise ValueError('{}: the [row][polarization] plane must be dense'.format(what))
-        if C == 1:
-            return N * Q
-        if strides[0] < N * Q:
-            raise ValueError('{}: channels overlap'.format(what))
-        return int(strides[0])
 
     def __call__(self, vis, weights):
-        if vis.dtype != np.complex64 or weights.dtype != np.float32:
-            raise TypeError('vis must be complex64 and weights float32')
-        if len(vis.shape) != 3 or vis.shape != weights.shape:
-            raise ValueError('vis and weights must both be [channel][row][polarization]')
-        if vis.shape[0] != self.num_channels:
-            raise ValueError('the operator was made for {} channels, the block has {}'.format(
-                self.num_channels, vis.shape[0]))
+        self._check_block(vis, weights)
         plane = vis.shape[1] * vis.shape[2]
         if plane == 0:
             return
         vis.used_on(self.command_queue)
         weights.used_on(self.command_queue)
         check(lib().kimg_uvcontsub(
-            vis.ptr, self._channel_pitch(vis, 'vis'), weights.ptr,
-            self._channel_pitch(weights, 'weights'), self.num_channels, plane,
+            vis.ptr, channel_pitch(vis, 'vis'), weights.ptr,
+            channel_pitch(weights, 'weights'), self.num_channels, plane,
             self._mask.ctypes.data_as(ctypes.c_void_p), self._basis.ptr, self.order,
             self._counts.ptr, self.command_queue.handle), 'kimg_uvcontsub')
 
-    def counts(self):
-        """(fitted, flagged) samples so far; waits for the queue."""
-        host = self._counts.get(self.command_queue)
-        return int(host[0]), int(host[1])
 
-    def reset_counts(self):
-        self._counts.zero(self.command_queue)
+class UVContSubTemplate(OperatorTemplate):
+    params_type = UVContSubParameters
+    operator = UVContSub

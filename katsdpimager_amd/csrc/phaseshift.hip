@@ -3,22 +3,18 @@
 // rotated into that direction's frame.  katsdpimager_amd/phaseshift.py holds the same contract as
 // numpy (phase_shift_host).
 //
-// One thread owns one element j of the dense [row][pol] plane, so a wave reads and writes 64
-// consecutive complex64 (512 B) per channel.  The thread reads its row's three coordinates once and
+// The thread layout is kimg_channel_block.h's.  The thread reads its row's three coordinates once and
 // forms d = delay . uvw in float64; per channel the turn count d / lambda_c is formed and reduced to
 // [-0.5, 0.5] in float64 (it runs to thousands of turns; float32 has lost the phase long before), and
 // only the reduced angle goes to float32: sincospif of its float32 value, corrected to first order by
 // the float32 remainder of the rounding.  1 / lambda_c is the same for every lane and comes through
-// the scalar cache.  The channels are walked PS_UNROLL at a time, the loads of all of them issued
+// the scalar cache.  The channels are walked CB_UNROLL at a time, the loads of all of them issued
 // before the first is used.  The thread of a row's first polarization writes the rotated
 // coordinates; other waves may still be reading that row, which is why uvw_out may not overlap uvw_in.
 // No LDS, no atomics.  Traffic: 16 bytes per element and channel, 12 (+ 12) per row.
-#include "kimg_common.h"
+#include "kimg_channel_block.h"
 
 namespace {
-
-constexpr int PS_THREADS = 256;
-constexpr int PS_UNROLL = 4;                    // channels whose loads are in flight together
 
 struct ps_params {
     double rotation[9];                         // row-major: uvw' = rotation . uvw
@@ -27,12 +23,12 @@ struct ps_params {
 
 // Q_T: the number of polarizations, or 0 for "use the runtime value"
 template <int Q_T>
-__global__ __launch_bounds__(PS_THREADS)
+__global__ __launch_bounds__(CB_THREADS)
 void phase_shift_kernel(float2 *__restrict__ vis, int64_t vis_pitch, int C, int64_t plane, int Q,
                         const float *__restrict__ uvw_in, float *__restrict__ uvw_out,
                         const double *__restrict__ inv_wavelength, const ps_params p)
 {
-    const int64_t j = (int64_t) blockIdx.x * PS_THREADS + threadIdx.x;
+    const int64_t j = cb_element();
     if (j >= plane)
         return;
     const int64_t n = Q_T ? j / Q_T : j / Q;
@@ -46,14 +42,14 @@ void phase_shift_kernel(float2 *__restrict__ vis, int64_t vis_pitch, int C, int6
     const double d = (p.delay[0] * u + p.delay[1] * v) + p.delay[2] * w;
     float2 *v_ptr = vis + j;
 
-    for (int c0 = 0; c0 < C; c0 += PS_UNROLL) {
-        float2 x[PS_UNROLL];
+    for (int c0 = 0; c0 < C; c0 += CB_UNROLL) {
+        float2 x[CB_UNROLL];
 #pragma unroll
-        for (int k = 0; k < PS_UNROLL; k++)
+        for (int k = 0; k < CB_UNROLL; k++)
             if (c0 + k < C)
                 x[k] = v_ptr[(int64_t) (c0 + k) * vis_pitch];
 #pragma unroll
-        for (int k = 0; k < PS_UNROLL; k++) {
+        for (int k = 0; k < CB_UNROLL; k++) {
             const int c = c0 + k;
             if (c >= C)
                 continue;
@@ -91,7 +87,7 @@ extern "C" int kimg_phase_shift(void *vis, int64_t vis_channel_pitch, int num_ch
         const uintptr_t bytes = (uintptr_t) num_rows * 3 * sizeof(float);
         KIMG_CHECK_ARG(in + bytes <= out || out + bytes <= in);
     }
-    if (plane > (int64_t) 0x7fffffff * PS_THREADS)
+    if (!cb_plane_fits(plane))
         return KIMG_EUNSUPPORTED;
     if (num_rows == 0)
         return 0;
@@ -101,9 +97,9 @@ extern "C" int kimg_phase_shift(void *vis, int64_t vis_channel_pitch, int num_ch
     for (int i = 0; i < 3; i++)
         p.delay[i] = params12_host[9 + i];
     hipStream_t s = (hipStream_t) stream;
-    const unsigned blocks = (unsigned) kimg_divup(plane, PS_THREADS);
+    const unsigned blocks = cb_blocks(plane);
     auto launch = [&](auto q) {
-        phase_shift_kernel<decltype(q)::value><<<blocks, PS_THREADS, 0, s>>>(
+        phase_shift_kernel<decltype(q)::value><<<blocks, CB_THREADS, 0, s>>>(
             (float2 *) vis, vis_channel_pitch, num_channels, plane, num_polarizations, uvw_in, uvw_out,
             inv_wavelength, p);
     };

@@ -4,9 +4,8 @@
 // holds the same contract as numpy (rfiflag_host), and the order of every sum below is that
 // contract's: the device has the twin's bits.
 //
-// The thread layout is contsub.hip's and statwt.hip's: one thread owns one element j of the dense
-// [row][pol] plane and walks channels, so every channel step of a wave is one coalesced access.  All
-// launches are plain, there is no LDS and no atomic but the three counters'.
+// The thread layout, the channel mask, the load round and the group tables are kimg_channel_block.h's.
+// All launches are plain, there is no LDS and no atomic but the three counters'.
 //
 // Between the launches the workspace holds, per sample,
 //   zs     float64: z = w (re^2 + im^2) of a usable sample of a mask channel, -1 for every other
@@ -32,30 +31,13 @@
 //   time: the thread of row s evaluates the window that STARTS at s, the m - 1 later rows of the same
 //     channel read through the caches (P elements apart, never past the group's end); on a hit it
 //     stamps the window's rows itself.
-#include "kimg_common.h"
+#include "kimg_channel_block.h"
 
 namespace {
 
-constexpr int RF_THREADS = 256;
-constexpr int RF_UNROLL = 4;                    // channels whose loads are in flight together
-constexpr int RF_MAX_CHANNELS = KIMG_UVCONTSUB_MAX_CHANNELS;
-constexpr int RF_MAX_BIN = KIMG_STATWT_MAX_BIN;
 constexpr int RF_MAX_PASSES = 6;                // window lengths 1 .. KIMG_RFIFLAG_MAX_WINDOW
 constexpr uint8_t STAMP_FREQ = RF_MAX_PASSES + 1;
 constexpr uint8_t STAMP_TIME = RF_MAX_PASSES + 2;
-
-struct rf_mask {
-    uint32_t bits[RF_MAX_CHANNELS / 32];
-    __device__ bool operator[](int c) const { return (bits[c >> 5] >> (c & 31)) & 1u; }
-};
-
-struct rf_groups {
-    const int32_t *offsets;     // [G + 1]
-    const int32_t *row_group;   // [N]
-    int G;
-    int N;
-    int P;
-};
 
 // The workspace: zs and stamp [C][plane], the partials [plane]
 struct rf_state {
@@ -66,31 +48,8 @@ struct rf_state {
     int64_t plane;
 };
 
-__device__ inline bool rf_usable(float w, float2 v)
-{
-    return w > 0.0f && isfinite(w) && isfinite(v.x) && isfinite(v.y);
-}
-
-// Row and polarization of plane element j; the rows [r0, r1) of its group, and the group.  Whatever the
-// tables hold, 0 <= g < G and 0 <= r0 <= r1 <= N with at most RF_MAX_BIN rows: nothing past the arrays
-// is ever touched.
-struct rf_place {
-    int r, p, g, r0, r1;
-};
-
-__device__ inline rf_place rf_place_of(const rf_groups &t, int64_t j)
-{
-    rf_place at;
-    at.r = (int) (j / t.P);
-    at.p = (int) (j - (int64_t) at.r * t.P);
-    at.g = min(max(t.row_group[at.r], 0), t.G - 1);
-    at.r0 = min(max(t.offsets[at.g], 0), t.N);
-    at.r1 = min(min(max(t.offsets[at.g + 1], at.r0), t.N), at.r0 + RF_MAX_BIN);
-    return at;
-}
-
 // (Z, M) of the group from the rows' partials in ascending row order; the level, and whether it is one
-__device__ inline bool rf_group_level(const rf_state &st, int set, const rf_groups &t, const rf_place &at,
+__device__ inline bool rf_group_level(const rf_state &st, int set, const cb_groups &t, const cb_place &at,
                                       double &L)
 {
     double Z = 0.0;
@@ -104,38 +63,30 @@ __device__ inline bool rf_group_level(const rf_state &st, int set, const rf_grou
     return M > 0 && isfinite(L) && L > 0.0;
 }
 
-__global__ __launch_bounds__(RF_THREADS)
+__global__ __launch_bounds__(CB_THREADS)
 void rfi_prepare_kernel(const float2 *__restrict__ vis, int64_t vis_pitch,
                         const float *__restrict__ weights, int64_t weights_pitch, int C,
-                        const rf_mask mask, rf_state st)
+                        const cb_mask mask, rf_state st)
 {
-    const int64_t j = (int64_t) blockIdx.x * RF_THREADS + threadIdx.x;
+    const int64_t j = cb_element();
     if (j >= st.plane)
         return;
     const float2 *v_ptr = vis + j;
     const float *w_ptr = weights + j;
     double Z = 0.0;
     int M = 0;
-    for (int c0 = 0; c0 < C; c0 += RF_UNROLL) {
-        float2 v[RF_UNROLL];
-        float w[RF_UNROLL];
+    for (int c0 = 0; c0 < C; c0 += CB_UNROLL) {
+        float2 v[CB_UNROLL];
+        float w[CB_UNROLL];
+        bool fit[CB_UNROLL];
+        cb_load_round(v_ptr, vis_pitch, w_ptr, weights_pitch, C, mask, c0, v, w, fit);
 #pragma unroll
-        for (int u = 0; u < RF_UNROLL; u++) {
-            const int c = c0 + u;
-            v[u] = make_float2(0.0f, 0.0f);
-            w[u] = 0.0f;
-            if (c < C && mask[c]) {
-                v[u] = v_ptr[(int64_t) c * vis_pitch];
-                w[u] = w_ptr[(int64_t) c * weights_pitch];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < RF_UNROLL; u++) {
+        for (int u = 0; u < CB_UNROLL; u++) {
             const int c = c0 + u;
             if (c >= C)
                 continue;
             double z = -1.0;
-            if (mask[c] && rf_usable(w[u], v[u])) {
+            if (fit[u] && cb_usable_finite_weight(w[u], v[u])) {
                 double t = (double) v[u].x * (double) v[u].x;
                 t = t + (double) v[u].y * (double) v[u].y;
                 z = (double) w[u] * t;
@@ -152,13 +103,13 @@ void rfi_prepare_kernel(const float2 *__restrict__ vis, int64_t vis_pitch,
 
 // One level iteration: the mean of the samples not above clip times the level of partials `set`, as
 // partials `set ^ 1`.  A group without a level leaves partials of nothing, and so stays without one.
-__global__ __launch_bounds__(RF_THREADS)
-void rfi_level_kernel(int C, rf_groups groups, rf_state st, int set, double clip)
+__global__ __launch_bounds__(CB_THREADS)
+void rfi_level_kernel(int C, cb_groups groups, rf_state st, int set, double clip)
 {
-    const int64_t j = (int64_t) blockIdx.x * RF_THREADS + threadIdx.x;
+    const int64_t j = cb_element();
     if (j >= st.plane)
         return;
-    const rf_place at = rf_place_of(groups, j);
+    const cb_place at = cb_place_of(groups, j);
     double L;
     const bool ok = rf_group_level(st, set, groups, at, L);
     const double limit = clip * L;
@@ -166,13 +117,13 @@ void rfi_level_kernel(int C, rf_groups groups, rf_state st, int set, double clip
     double Z = 0.0;
     int M = 0;
     if (ok) {
-        for (int c0 = 0; c0 < C; c0 += RF_UNROLL) {
-            double z[RF_UNROLL];
+        for (int c0 = 0; c0 < C; c0 += CB_UNROLL) {
+            double z[CB_UNROLL];
 #pragma unroll
-            for (int u = 0; u < RF_UNROLL; u++)
+            for (int u = 0; u < CB_UNROLL; u++)
                 z[u] = c0 + u < C ? z_ptr[(int64_t) (c0 + u) * st.plane] : -1.0;
 #pragma unroll
-            for (int u = 0; u < RF_UNROLL; u++) {
+            for (int u = 0; u < CB_UNROLL; u++) {
                 if (z[u] >= 0.0 && z[u] <= limit) {
                     Z += z[u];
                     M++;
@@ -185,13 +136,13 @@ void rfi_level_kernel(int C, rf_groups groups, rf_state st, int set, double clip
 }
 
 // The level of every (group, polarization), NaN where there is none, written by the group's first row
-__global__ __launch_bounds__(RF_THREADS)
-void rfi_level_out_kernel(rf_groups groups, rf_state st, int set, double *__restrict__ level,
+__global__ __launch_bounds__(CB_THREADS)
+void rfi_level_out_kernel(cb_groups groups, rf_state st, int set, double *__restrict__ level,
                           unsigned long long *__restrict__ counts)
 {
-    const int64_t j = (int64_t) blockIdx.x * RF_THREADS + threadIdx.x;
-    const bool live = j < st.plane;
-    const rf_place at = rf_place_of(groups, live ? j : 0);
+    const cb_lane t = cb_lane_of(st.plane);
+    const bool live = t.live;
+    const cb_place at = cb_place_of(groups, t.jj);
     double L;
     const bool ok = rf_group_level(st, set, groups, at, L);
     const bool first = live && at.r == at.r0;
@@ -206,14 +157,14 @@ void rfi_level_out_kernel(rf_groups groups, rf_state st, int set, double *__rest
 // channel c + i adds to a window (z - L, or chi), good bit i whether that is its own z, open bit i whether the sample
 // may be stamped (a usable sample of a mask channel that nothing has flagged).
 template <int M>
-__global__ __launch_bounds__(RF_THREADS)
-void rfi_freq_kernel(int C, rf_groups groups, rf_state st, const double *__restrict__ level,
+__global__ __launch_bounds__(CB_THREADS)
+void rfi_freq_kernel(int C, cb_groups groups, rf_state st, const double *__restrict__ level,
                      double factor, uint8_t mine)
 {
-    const int64_t j = (int64_t) blockIdx.x * RF_THREADS + threadIdx.x;
+    const int64_t j = cb_element();
     if (j >= st.plane)
         return;
-    const rf_place at = rf_place_of(groups, j);
+    const cb_place at = cb_place_of(groups, j);
     const double L = level[(int64_t) at.g * groups.P + at.p];
     if (!(L == L))
         return;
@@ -250,11 +201,11 @@ void rfi_freq_kernel(int C, rf_groups groups, rf_state st, const double *__restr
             take(z_ptr[(int64_t) i * st.plane], s_ptr[(int64_t) i * st.plane]);
     }
     int through = -1;                               // flag through this channel
-    for (int c0 = 0; c0 < C; c0 += RF_UNROLL) {
-        double z[RF_UNROLL];
-        uint8_t s[RF_UNROLL];
+    for (int c0 = 0; c0 < C; c0 += CB_UNROLL) {
+        double z[CB_UNROLL];
+        uint8_t s[CB_UNROLL];
 #pragma unroll
-        for (int u = 0; u < RF_UNROLL; u++) {
+        for (int u = 0; u < CB_UNROLL; u++) {
             const int c = c0 + u + M - 1;
             z[u] = -1.0;
             s[u] = 0;
@@ -264,7 +215,7 @@ void rfi_freq_kernel(int C, rf_groups groups, rf_state st, const double *__restr
             }
         }
 #pragma unroll
-        for (int u = 0; u < RF_UNROLL; u++) {
+        for (int u = 0; u < CB_UNROLL; u++) {
             const int c = c0 + u;
             shift();
             if (c + M - 1 < C)
@@ -285,14 +236,14 @@ void rfi_freq_kernel(int C, rf_groups groups, rf_state st, const double *__restr
 
 // A window pass along time, windows of m rows of one group in one mask channel.  The thread of row s
 // has the window s .. s + m - 1.
-__global__ __launch_bounds__(RF_THREADS)
-void rfi_time_kernel(int C, const rf_mask mask, rf_groups groups, rf_state st,
+__global__ __launch_bounds__(CB_THREADS)
+void rfi_time_kernel(int C, const cb_mask mask, cb_groups groups, rf_state st,
                      const double *__restrict__ level, double factor, int m, uint8_t mine)
 {
-    const int64_t j = (int64_t) blockIdx.x * RF_THREADS + threadIdx.x;
+    const int64_t j = cb_element();
     if (j >= st.plane)
         return;
-    const rf_place at = rf_place_of(groups, j);
+    const cb_place at = cb_place_of(groups, j);
     if (at.r + m > at.r1)
         return;
     const double L = level[(int64_t) at.g * groups.P + at.p];
@@ -326,25 +277,25 @@ void rfi_time_kernel(int C, const rf_mask mask, rf_groups groups, rf_state st,
 
 // Extension over a row: with more than `share` of its usable samples of mask channels flagged, all its
 // usable samples are, those of protected channels (which zs knows nothing of) included
-__global__ __launch_bounds__(RF_THREADS)
+__global__ __launch_bounds__(CB_THREADS)
 void rfi_extend_freq_kernel(const float2 *__restrict__ vis, int64_t vis_pitch,
                             const float *__restrict__ weights, int64_t weights_pitch, int C,
-                            const rf_mask mask, rf_groups groups, rf_state st,
+                            const cb_mask mask, cb_groups groups, rf_state st,
                             const double *__restrict__ level, double share)
 {
-    const int64_t j = (int64_t) blockIdx.x * RF_THREADS + threadIdx.x;
+    const int64_t j = cb_element();
     if (j >= st.plane)
         return;
-    const rf_place at = rf_place_of(groups, j);
+    const cb_place at = cb_place_of(groups, j);
     const double L = level[(int64_t) at.g * groups.P + at.p];
     if (!(L == L))
         return;
     int have = 0, hit = 0;
-    for (int c0 = 0; c0 < C; c0 += RF_UNROLL) {
-        double z[RF_UNROLL];
-        uint8_t s[RF_UNROLL];
+    for (int c0 = 0; c0 < C; c0 += CB_UNROLL) {
+        double z[CB_UNROLL];
+        uint8_t s[CB_UNROLL];
 #pragma unroll
-        for (int u = 0; u < RF_UNROLL; u++) {
+        for (int u = 0; u < CB_UNROLL; u++) {
             const int c = c0 + u;
             z[u] = -1.0;
             s[u] = 0;
@@ -354,7 +305,7 @@ void rfi_extend_freq_kernel(const float2 *__restrict__ vis, int64_t vis_pitch,
             }
         }
 #pragma unroll
-        for (int u = 0; u < RF_UNROLL; u++) {
+        for (int u = 0; u < CB_UNROLL; u++) {
             have += z[u] >= 0.0;
             hit += z[u] >= 0.0 && s[u] != 0;
         }
@@ -367,7 +318,7 @@ void rfi_extend_freq_kernel(const float2 *__restrict__ vis, int64_t vis_pitch,
         if (mask[c])
             open = st.zs[(int64_t) c * st.plane + j] >= 0.0 && *s_ptr == 0;
         else
-            open = rf_usable(weights[(int64_t) c * weights_pitch + j], vis[(int64_t) c * vis_pitch + j]);
+            open = cb_usable_finite_weight(weights[(int64_t) c * weights_pitch + j], vis[(int64_t) c * vis_pitch + j]);
         if (open)
             *s_ptr = STAMP_FREQ;
     }
@@ -376,13 +327,13 @@ void rfi_extend_freq_kernel(const float2 *__restrict__ vis, int64_t vis_pitch,
 // Extension over a channel of a group: with more than `share` of its usable rows flagged (by anything
 // before this step), all its usable rows are.  Every row of the group counts for itself, reads the
 // others through the caches, and stamps its own sample only.
-__global__ __launch_bounds__(RF_THREADS)
-void rfi_extend_time_kernel(int C, const rf_mask mask, rf_groups groups, rf_state st, double share)
+__global__ __launch_bounds__(CB_THREADS)
+void rfi_extend_time_kernel(int C, const cb_mask mask, cb_groups groups, rf_state st, double share)
 {
-    const int64_t j = (int64_t) blockIdx.x * RF_THREADS + threadIdx.x;
+    const int64_t j = cb_element();
     if (j >= st.plane)
         return;
-    const rf_place at = rf_place_of(groups, j);
+    const cb_place at = cb_place_of(groups, j);
     const int64_t first = (int64_t) at.r0 * groups.P + at.p;
     const int rows = at.r1 - at.r0;
     for (int c = 0; c < C; c++) {
@@ -403,35 +354,28 @@ void rfi_extend_time_kernel(int C, const rf_mask mask, rf_groups groups, rf_stat
     }
 }
 
-__device__ inline unsigned long long rf_wave_sum(int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_xor(v, off, WAVE);
-    return (unsigned long long) v;
-}
-
 // Extension over polarizations; the flags, the weights, the counts of usable samples kept and flagged
-__global__ __launch_bounds__(RF_THREADS)
+__global__ __launch_bounds__(CB_THREADS)
 void rfi_finish_kernel(const float2 *__restrict__ vis, int64_t vis_pitch, float *__restrict__ weights,
-                       int64_t weights_pitch, int C, rf_groups groups, rf_state st,
+                       int64_t weights_pitch, int C, cb_groups groups, rf_state st,
                        const double *__restrict__ level, int extend_pols,
                        uint8_t *__restrict__ flags, unsigned long long *__restrict__ counts)
 {
-    const int64_t j = (int64_t) blockIdx.x * RF_THREADS + threadIdx.x;
-    const bool live = j < st.plane;
+    const cb_lane t = cb_lane_of(st.plane);
+    const int64_t j = t.j;
+    const bool live = t.live;
     int kept = 0, flagged = 0;
     if (live) {
-        const rf_place at = rf_place_of(groups, j);
+        const cb_place at = cb_place_of(groups, j);
         const double L = level[(int64_t) at.g * groups.P + at.p];
         const bool spread = extend_pols && L == L;
         const int64_t row = j - at.p;
-        for (int c0 = 0; c0 < C; c0 += RF_UNROLL) {
-            float2 v[RF_UNROLL];
-            float w[RF_UNROLL];
-            bool own[RF_UNROLL], any[RF_UNROLL];
+        for (int c0 = 0; c0 < C; c0 += CB_UNROLL) {
+            float2 v[CB_UNROLL];
+            float w[CB_UNROLL];
+            bool own[CB_UNROLL], any[CB_UNROLL];
 #pragma unroll
-            for (int u = 0; u < RF_UNROLL; u++) {
+            for (int u = 0; u < CB_UNROLL; u++) {
                 const int c = c0 + u;
                 v[u] = make_float2(0.0f, 0.0f);
                 w[u] = 0.0f;
@@ -446,11 +390,11 @@ void rfi_finish_kernel(const float2 *__restrict__ vis, int64_t vis_pitch, float 
                 }
             }
 #pragma unroll
-            for (int u = 0; u < RF_UNROLL; u++) {
+            for (int u = 0; u < CB_UNROLL; u++) {
                 const int c = c0 + u;
                 if (c >= C)
                     continue;
-                const bool usable = rf_usable(w[u], v[u]);
+                const bool usable = cb_usable_finite_weight(w[u], v[u]);
                 const bool flag = own[u] || (any[u] && usable);
                 flags[(int64_t) c * st.plane + j] = flag;
                 if (flag)
@@ -460,13 +404,7 @@ void rfi_finish_kernel(const float2 *__restrict__ vis, int64_t vis_pitch, float 
             }
         }
     }
-    const unsigned long long n_kept = rf_wave_sum(kept), n_flagged = rf_wave_sum(flagged);
-    if ((threadIdx.x & (WAVE - 1)) == 0) {
-        if (n_kept)
-            atomicAdd(&counts[0], n_kept);
-        if (n_flagged)
-            atomicAdd(&counts[1], n_flagged);
-    }
+    cb_count_sums(kept, flagged, counts);
 }
 
 }  // namespace
@@ -480,11 +418,7 @@ extern "C" int kimg_rfi_flag(const void *vis, int64_t vis_channel_pitch, float *
                              double extend_time, int extend_pols, uint8_t *flags, double *level,
                              void *workspace, size_t workspace_bytes, uint64_t *counts, void *stream)
 {
-    KIMG_CHECK_ARG(vis && weights && mask_host && group_offsets && row_group && factors_host);
-    KIMG_CHECK_ARG(flags && level && workspace && counts);
-    KIMG_CHECK_ARG(num_channels >= 1 && num_rows >= 0);
-    KIMG_CHECK_ARG(num_pols >= 1 && num_pols <= 4);
-    KIMG_CHECK_ARG(time_bin >= 1 && time_bin <= RF_MAX_BIN);
+    KIMG_CHECK_ARG(factors_host && flags && level);
     KIMG_CHECK_ARG(max_window >= 1 && max_window <= KIMG_RFIFLAG_MAX_WINDOW
                    && (max_window & (max_window - 1)) == 0);
     KIMG_CHECK_ARG(directions >= 1 && directions <= (KIMG_RFIFLAG_TIME | KIMG_RFIFLAG_FREQ));
@@ -496,26 +430,17 @@ extern "C" int kimg_rfi_flag(const void *vis, int64_t vis_channel_pitch, float *
         passes++;
     for (int k = 0; k < passes; k++)
         KIMG_CHECK_ARG(factors_host[k] > 0.0);
-    // (rows are 32-bit in the group tables; the plane then stays far inside the grid limit)
-    if (num_rows > 0x7fffffff)
-        return KIMG_EUNSUPPORTED;
-    const int64_t plane = num_rows * num_pols;
-    KIMG_CHECK_ARG(vis_channel_pitch >= plane && weights_channel_pitch >= plane);
-    if (num_channels > RF_MAX_CHANNELS)
-        return KIMG_EUNSUPPORTED;
-    if (plane == 0)
-        return 0;
-    KIMG_CHECK_ARG(num_groups >= 1 && num_groups <= num_rows && num_groups * time_bin >= num_rows);
+    int64_t plane;
+    const int rc = cb_check_block(vis, vis_channel_pitch, weights, weights_channel_pitch, num_channels,
+                                  num_rows, num_pols, mask_host, group_offsets, num_groups, row_group,
+                                  time_bin, workspace, workspace_bytes, KIMG_RFIFLAG_WORKSPACE_PER_ROW,
+                                  KIMG_RFIFLAG_WORKSPACE_PER_ELEMENT, counts, plane);
+    if (rc != 0 || plane == 0)
+        return rc;
     const size_t samples = (size_t) plane * num_channels;
-    if (workspace_bytes < samples * KIMG_RFIFLAG_WORKSPACE_PER_ELEMENT
-                          + (size_t) plane * KIMG_RFIFLAG_WORKSPACE_PER_ROW)
-        return KIMG_EWORKSPACE;
-    KIMG_CHECK_ARG(((uintptr_t) workspace & 7) == 0);
 
-    rf_mask mask = {};
-    for (int c = 0; c < num_channels; c++)
-        if (mask_host[c])
-            mask.bits[c >> 5] |= 1u << (c & 31);
+    cb_mask mask;
+    cb_pack_mask(mask_host, num_channels, mask);
     rf_state st;
     st.plane = plane;
     st.zs = (double *) workspace;
@@ -524,25 +449,25 @@ extern "C" int kimg_rfi_flag(const void *vis, int64_t vis_channel_pitch, float *
     st.M[0] = (int *) (st.Z[1] + plane);
     st.M[1] = st.M[0] + plane;
     st.stamp = (uint8_t *) (st.M[1] + plane);
-    const rf_groups groups = {group_offsets, row_group, (int) num_groups, (int) num_rows, num_pols};
+    const cb_groups groups = {group_offsets, row_group, (int) num_groups, (int) num_rows, num_pols};
     const float2 *v = (const float2 *) vis;
     hipStream_t s = (hipStream_t) stream;
-    const unsigned blocks = (unsigned) kimg_divup(plane, RF_THREADS);
+    const unsigned blocks = cb_blocks(plane);
     unsigned long long *n = (unsigned long long *) counts;
 
-    rfi_prepare_kernel<<<blocks, RF_THREADS, 0, s>>>(
+    rfi_prepare_kernel<<<blocks, CB_THREADS, 0, s>>>(
         v, vis_channel_pitch, weights, weights_channel_pitch, num_channels, mask, st);
     int set = 0;
     for (int i = 0; i < level_iterations; i++, set ^= 1)
-        rfi_level_kernel<<<blocks, RF_THREADS, 0, s>>>(num_channels, groups, st, set, level_clip);
-    rfi_level_out_kernel<<<blocks, RF_THREADS, 0, s>>>(groups, st, set, level, n);
+        rfi_level_kernel<<<blocks, CB_THREADS, 0, s>>>(num_channels, groups, st, set, level_clip);
+    rfi_level_out_kernel<<<blocks, CB_THREADS, 0, s>>>(groups, st, set, level, n);
     for (int k = 0; k < passes; k++) {
         const int m = 1 << k;
         const uint8_t mine = (uint8_t) (1 + k);
         const double factor = factors_host[k];
         if ((directions & KIMG_RFIFLAG_FREQ) && m <= num_channels) {
             auto launch = [&](auto length) {
-                rfi_freq_kernel<decltype(length)::value><<<blocks, RF_THREADS, 0, s>>>(
+                rfi_freq_kernel<decltype(length)::value><<<blocks, CB_THREADS, 0, s>>>(
                     num_channels, groups, st, level, factor, mine);
             };
             switch (m) {
@@ -558,16 +483,16 @@ extern "C" int kimg_rfi_flag(const void *vis, int64_t vis_channel_pitch, float *
                 continue;
         }
         if ((directions & KIMG_RFIFLAG_TIME) && m <= time_bin)
-            rfi_time_kernel<<<blocks, RF_THREADS, 0, s>>>(num_channels, mask, groups, st, level, factor,
+            rfi_time_kernel<<<blocks, CB_THREADS, 0, s>>>(num_channels, mask, groups, st, level, factor,
                                                          m, mine);
     }
     if (extend_freq > 0.0)
-        rfi_extend_freq_kernel<<<blocks, RF_THREADS, 0, s>>>(
+        rfi_extend_freq_kernel<<<blocks, CB_THREADS, 0, s>>>(
             v, vis_channel_pitch, weights, weights_channel_pitch, num_channels, mask, groups, st, level,
             extend_freq);
     if (extend_time > 0.0)
-        rfi_extend_time_kernel<<<blocks, RF_THREADS, 0, s>>>(num_channels, mask, groups, st, extend_time);
-    rfi_finish_kernel<<<blocks, RF_THREADS, 0, s>>>(
+        rfi_extend_time_kernel<<<blocks, CB_THREADS, 0, s>>>(num_channels, mask, groups, st, extend_time);
+    rfi_finish_kernel<<<blocks, CB_THREADS, 0, s>>>(
         v, vis_channel_pitch, weights, weights_channel_pitch, num_channels, groups, st, level,
         extend_pols, flags, n);
     return kimg_launch_status();

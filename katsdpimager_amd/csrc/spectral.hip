@@ -3,9 +3,7 @@
 // integer decimation, weighted and aware of flags; new dense vis and weights arrays come out.
 // katsdpimager_amd/spectral.py holds the same contract as numpy (filter_host).
 //
-// The access pattern is contsub.hip's: one thread owns one element j of the dense [row][pol] plane, so
-// a wave reads 64 consecutive complex64 (512 B) and 64 consecutive weights (256 B) per channel.  The
-// combined coefficients g (taps convolved with the box of the bin, at most 72 doubles) are a kernel
+// The thread layout is kimg_channel_block.h's.  The combined coefficients g (taps convolved with the box of the bin, at most 72 doubles) are a kernel
 // argument: the same for every lane, they come through the scalar cache.  The channel axis is split
 // over blockIdx.y in chunks of SF_CHUNK output channels, so that a block of few rows and thousands of
 // channels still fills the device; a chunk starts its window afresh and re-reads its halo.
@@ -19,12 +17,11 @@
 //   window   (everything else): each output walks its own L inputs; the overlap of neighbouring
 //            windows (K - 1 of K + n - 1 channels) is re-read, through the cache.
 // No LDS, no atomics on data; the two counters take one atomic add per wave each.
-#include "kimg_common.h"
+#include "kimg_channel_block.h"
 
 namespace {
 
-constexpr int SF_THREADS = 256;
-constexpr int SF_UNROLL = 4;                    // channels whose loads are in flight together
+constexpr int SF_UNROLL = 4;                    // inputs of a window whose loads are in flight together
 constexpr int SF_CHUNK = 64;                    // output channels per blockIdx.y
 constexpr int SF_MAX_LENGTH = KIMG_SPECTRAL_MAX_TAPS + KIMG_SPECTRAL_MAX_BIN - 1;
 
@@ -44,7 +41,7 @@ struct sf_sums {
 
 __device__ inline sf_sample sf_make(float2 v, float w)
 {
-    const bool usable = w > 0.0f && isfinite(v.x) && isfinite(v.y);
+    const bool usable = cb_usable(w, v);
     sf_sample s;
     s.w = usable ? (double) w : 0.0;
     s.wr = usable ? (double) w * (double) v.x : 0.0;
@@ -86,8 +83,7 @@ __device__ inline unsigned sf_finish(const sf_sums &a, double min_sum, bool live
     return (unsigned) __popcll(__ballot(live && keep));
 }
 
-// The addressing every form shares.  Lanes past the plane run along with clamped addresses and store
-// nothing: the wave's branches stay uniform and its counters are reduced over all 64 lanes.
+// The addressing every form shares.  Lanes past the plane run along (cb_lane_of): sf_finish ballots.
 struct sf_lane {
     const float2 *v_in;
     const float *w_in;
@@ -113,14 +109,13 @@ struct sf_arrays {
 
 __device__ inline sf_lane sf_lane_of(const sf_arrays &a)
 {
-    const int64_t j = (int64_t) blockIdx.x * SF_THREADS + threadIdx.x;
+    const cb_lane at = cb_lane_of(a.plane);
     sf_lane t;
-    t.live = j < a.plane;
-    const int64_t jj = t.live ? j : 0;
-    t.v_in = a.vis_in + jj;
-    t.w_in = a.weights_in + jj;
-    t.v_out = a.vis_out + jj;
-    t.w_out = a.weights_out + jj;
+    t.live = at.live;
+    t.v_in = a.vis_in + at.jj;
+    t.w_in = a.weights_in + at.jj;
+    t.v_out = a.vis_out + at.jj;
+    t.w_out = a.weights_out + at.jj;
     t.o_begin = (int) blockIdx.y * SF_CHUNK;
     t.o_end = min(a.C_out, t.o_begin + SF_CHUNK);
     return t;
@@ -131,13 +126,9 @@ __device__ inline void sf_count(const sf_lane &t, unsigned long long kept, int64
 {
     if ((threadIdx.x & (WAVE - 1)) == 0) {
         // (the wave's live lanes: its first lane's element up to the end of the plane)
-        const int64_t first = (int64_t) blockIdx.x * SF_THREADS + threadIdx.x;
+        const int64_t first = cb_element();
         const int64_t lanes = max((int64_t) 0, min((int64_t) WAVE, plane - first));
-        const unsigned long long flagged = (unsigned long long) lanes * (t.o_end - t.o_begin) - kept;
-        if (kept)
-            atomicAdd(&counts[0], kept);
-        if (flagged)
-            atomicAdd(&counts[1], flagged);
+        cb_add_nonzero(counts, kept, (unsigned long long) lanes * (t.o_end - t.o_begin) - kept);
     }
 }
 
@@ -170,7 +161,7 @@ __device__ inline sf_sample sf_make(const sf_raw &r, bool wanted)
 // next round are issued before the arithmetic and the stores of this one: in the wave's memory
 // counter they are then older than the stores, and waiting for them never waits for a store.
 template <int L, int M>
-__global__ __launch_bounds__(SF_THREADS)
+__global__ __launch_bounds__(CB_THREADS)
 void spectral_sliding_kernel(const sf_arrays a, const sf_coeff coeff, int offset, double min_sum,
                              unsigned long long *__restrict__ counts)
 {
@@ -225,7 +216,7 @@ void spectral_sliding_kernel(const sf_arrays a, const sf_coeff coeff, int offset
 // Output o takes the inputs o * step - offset + i, i = 0 .. length - 1, SF_UNROLL of them in flight.
 // DISJOINT: offset == 0 and length == step, so that all of them lie inside the band.
 template <bool DISJOINT>
-__global__ __launch_bounds__(SF_THREADS)
+__global__ __launch_bounds__(CB_THREADS)
 void spectral_window_kernel(const sf_arrays a, const sf_coeff coeff, int length, int offset, int step,
                             double min_sum, unsigned long long *__restrict__ counts)
 {
@@ -286,7 +277,7 @@ extern "C" int kimg_spectral_filter(const void *vis_in, int64_t vis_in_channel_p
                    && vis_out_channel_pitch >= plane_elements
                    && weights_out_channel_pitch >= plane_elements);
     const int chunks = kimg_divup(num_channels_out, SF_CHUNK);
-    if (plane_elements > (int64_t) 0x7fffffff * SF_THREADS || chunks > 65535)
+    if (!cb_plane_fits(plane_elements) || chunks > 65535)
         return KIMG_EUNSUPPORTED;
     // out of place: an output that starts inside an input would be written while still being read
     const uint64_t vis_in_bytes =
@@ -304,10 +295,10 @@ extern "C" int kimg_spectral_filter(const void *vis_in, int64_t vis_in_channel_p
                          vis_out_channel_pitch, weights_out, weights_out_channel_pitch,
                          num_channels_out, plane_elements};
     hipStream_t s = (hipStream_t) stream;
-    const dim3 blocks((unsigned) kimg_divup(plane_elements, SF_THREADS), (unsigned) chunks);
+    const dim3 blocks(cb_blocks(plane_elements), (unsigned) chunks);
     unsigned long long *c = (unsigned long long *) counts;
     auto sliding = [&](auto l, auto m) {
-        spectral_sliding_kernel<decltype(l)::value, decltype(m)::value><<<blocks, SF_THREADS, 0, s>>>(
+        spectral_sliding_kernel<decltype(l)::value, decltype(m)::value><<<blocks, CB_THREADS, 0, s>>>(
             a, coeff, offset, min_sum, c);
     };
     using std::integral_constant;
@@ -320,10 +311,10 @@ extern "C" int kimg_spectral_filter(const void *vis_in, int64_t vis_in_channel_p
     else if (step == 1 && length == 9)
         sliding(integral_constant<int, 9>{}, integral_constant<int, 1>{});
     else if (offset == 0 && length == step)
-        spectral_window_kernel<true><<<blocks, SF_THREADS, 0, s>>>(a, coeff, length, offset, step,
+        spectral_window_kernel<true><<<blocks, CB_THREADS, 0, s>>>(a, coeff, length, offset, step,
                                                                    min_sum, c);
     else
-        spectral_window_kernel<false><<<blocks, SF_THREADS, 0, s>>>(a, coeff, length, offset, step,
+        spectral_window_kernel<false><<<blocks, CB_THREADS, 0, s>>>(a, coeff, length, offset, step,
                                                                     min_sum, c);
     return kimg_launch_status();
 }

@@ -39,6 +39,7 @@ import numpy as np
 
 from . import accel
 from ._lib import lib, check
+from .channel_block import integer
 
 #: KIMG_MOMENTS_MAX_CHANNELS
 MAX_CHANNELS = 4096
@@ -113,8 +114,8 @@ class MomentParameters:
                 first, stop = channels
             except (TypeError, ValueError):
                 raise ValueError('channels must be (first, stop)') from None
-            first = self._integer(first, 'first channel', 0, MAX_CHANNELS - 1)
-            stop = self._integer(stop, 'stop channel', first + 1, MAX_CHANNELS)
+            first = integer(first, 'first channel', 0, MAX_CHANNELS - 1)
+            stop = integer(stop, 'stop channel', first + 1, MAX_CHANNELS)
             self.channels = (first, stop)
         if clip_sigma is not None and cut is not None:
             raise ValueError('at most one of clip_sigma and cut may be given')
@@ -123,16 +124,6 @@ class MomentParameters:
         if not isinstance(select_hanning, (bool, np.bool_)):
             raise ValueError('select_hanning must be a bool')
         self.select_hanning = bool(select_hanning)
-
-    @staticmethod
-    def _integer(value, name, low, high):
-        try:
-            as_int = int(value)
-        except (TypeError, ValueError, OverflowError):
-            raise ValueError('{} must be an integer'.format(name)) from None
-        if as_int != value or not low <= as_int <= high:
-            raise ValueError('{} must be an integer from {} to {}'.format(name, low, high))
-        return as_int
 
     @staticmethod
     def _number(value, name):

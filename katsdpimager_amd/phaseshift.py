@@ -19,6 +19,7 @@ import numpy as np
 
 from . import accel
 from ._lib import lib, check
+from .channel_block import ChannelOperator, OperatorTemplate, channel_pitch
 
 LIGHTSPEED = 299792458.0
 
@@ -152,19 +153,7 @@ def phase_shift_host(vis, uvw, inv_wavelength, params):
         return out.astype(np.complex64), new_uvw.astype(np.float32)
 
 
-class PhaseShiftTemplate:
-    def __init__(self, context, params, tuning=None):
-        if not isinstance(params, PhaseShiftParameters):
-            raise TypeError('params must be PhaseShiftParameters')
-        lib()
-        self.context = context
-        self.params = params
-
-    def instantiate(self, *args, **kwargs):
-        return PhaseShift(self, *args, **kwargs)
-
-
-class PhaseShift:
+class PhaseShift(ChannelOperator):
     """``kimg_phase_shift`` for blocks whose channels have the inverse wavelengths
     ``inv_wavelength`` (float64, 1 / metres; :func:`inverse_wavelengths`).  ``op(vis, uvw)`` rotates
     the visibilities of a :class:`accel.DeviceArray` [C][N][Q] (complex64; the [N][Q] plane dense,
@@ -173,41 +162,24 @@ class PhaseShift:
     ``write_uvw=False``, rotates the visibilities only and returns None.  Asynchronous on
     ``command_queue``."""
 
+    COUNTERS = 0
+
     def __init__(self, template, command_queue, inv_wavelength):
-        self.template = template
-        self.command_queue = command_queue
         inv_wavelength = np.ascontiguousarray(np.atleast_1d(inv_wavelength), np.float64)
         if inv_wavelength.ndim != 1 or len(inv_wavelength) < 1 or not np.all(np.isfinite(inv_wavelength)):
             raise ValueError('inv_wavelength must be finite, one per channel')
-        self.num_channels = len(inv_wavelength)
+        super().__init__(template, command_queue, len(inv_wavelength))
         self._params12 = np.ascontiguousarray(template.params.params12())
         self._inv_wavelength = accel.DeviceArray(command_queue.context, inv_wavelength.shape, np.float64,
                                                  queue=command_queue)
         self._inv_wavelength.set(command_queue, inv_wavelength)
-
-    @staticmethod
-    def _channel_pitch(array, what):
-        t = array.tensor
-        C, N, Q = array.shape
-        if N * Q == 0:
-            return 0
-        strides = t.stride()
-        if (Q > 1 and strides[2] != 1) or (N > 1 and strides[1] != Q):
-            raise ValueError('{}: the [row][polarization] plane must be dense'.format(what))
-        if C == 1:
-            return N * Q
-        if strides[0] < N * Q:
-            raise ValueError('{}: channels overlap'.format(what))
-        return int(strides[0])
 
     def __call__(self, vis, uvw, write_uvw=True):
         if vis.dtype != np.complex64 or uvw.dtype != np.float32:
             raise TypeError('vis must be complex64 and uvw float32')
         if len(vis.shape) != 3 or tuple(uvw.shape) != (vis.shape[1], 3):
             raise ValueError('vis must be [channel][row][polarization] and uvw [row][3]')
-        if vis.shape[0] != self.num_channels:
-            raise ValueError('the operator was made for {} channels, the block has {}'.format(
-                self.num_channels, vis.shape[0]))
+        self._check_channels(vis)
         if vis.shape[2] < 1:
             raise ValueError('no polarizations')
         if not uvw.tensor.is_contiguous():
@@ -222,7 +194,12 @@ class PhaseShift:
         vis.used_on(queue)
         uvw.used_on(queue)
         check(lib().kimg_phase_shift(
-            vis.ptr, self._channel_pitch(vis, 'vis'), self.num_channels, N, vis.shape[2], uvw.ptr,
+            vis.ptr, channel_pitch(vis, 'vis'), self.num_channels, N, vis.shape[2], uvw.ptr,
             new_uvw.ptr if write_uvw else None, self._inv_wavelength.ptr,
             self._params12.ctypes.data_as(ctypes.c_void_p), queue.handle), 'kimg_phase_shift')
         return new_uvw
+
+
+class PhaseShiftTemplate(OperatorTemplate):
+    params_type = PhaseShiftParameters
+    operator = PhaseShift

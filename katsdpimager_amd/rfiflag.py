@@ -30,8 +30,9 @@ import numpy as np
 
 from . import accel
 from ._lib import lib, check
-from .continuum import MAX_CHANNELS
-from .statwt import MAX_BIN, StatWtParameters, group_offsets, _row_groups, _sum_over_groups
+from .channel_block import (MAX_BIN, ChannelOperator, ChannelSelection, OperatorTemplate,
+                            channel_pitch, check_block, group_offsets, group_tables,
+                            grown_workspace, integer, _row_groups, _sum_over_groups)
 
 #: KIMG_RFIFLAG_MAX_WINDOW
 MAX_WINDOW = 32
@@ -61,7 +62,6 @@ class RFIFlagParameters:
     def __init__(self, time_bin=64, threshold=6.0, rho=1.5, max_window=16, directions='both',
                  level_iterations=2, level_clip=4.0, extend_freq=0.5, extend_time=0.5,
                  extend_pols=True, fit_mask=None, line_ranges=None):
-        integer = StatWtParameters._integer
         self.time_bin = integer(time_bin, 'time_bin', 1, MAX_BIN)
         self.max_window = integer(max_window, 'max_window', 1, MAX_WINDOW)
         if self.max_window & (self.max_window - 1):
@@ -84,11 +84,11 @@ class RFIFlagParameters:
         if not isinstance(extend_pols, (bool, np.bool_)):
             raise ValueError('extend_pols must be True or False')
         self.extend_pols = bool(extend_pols)
-        # the channel mask in statwt's two spellings, validated there
-        spelled = StatWtParameters(1, fit_mask=fit_mask, line_ranges=line_ranges)
-        self.fit_mask = spelled.fit_mask
-        self.line_ranges = spelled.line_ranges
-        self._spelled = spelled
+        self._selection = ChannelSelection(fit_mask, line_ranges)
+        self.fit_mask = self._selection.fit_mask
+        self.line_ranges = self._selection.line_ranges
+        if self.fit_mask is not None:
+            self.mask(len(self.fit_mask))
 
     @staticmethod
     def _number(value, name):
@@ -111,7 +111,7 @@ class RFIFlagParameters:
     def mask(self, num_channels):
         """The channel mask of ``num_channels`` channels, uint8 (1 = searched for interference and
         part of the level, 0 = protected)."""
-        return self._spelled.mask(num_channels)
+        return self._selection.mask(num_channels)
 
     def factors(self):
         """float64 [log2(max_window) + 1]: ``threshold / rho**k``, the threshold of a window of
@@ -120,17 +120,12 @@ class RFIFlagParameters:
         return np.float64(self.threshold) / np.float64(self.rho) ** k
 
     def __repr__(self):
-        which = ''
-        if self.fit_mask is not None:
-            which = ', fit_mask={!r}'.format(self.fit_mask.tolist())
-        elif self.line_ranges is not None:
-            which = ', line_ranges={!r}'.format(self.line_ranges)
         return ('RFIFlagParameters({}, threshold={!r}, rho={!r}, max_window={}, directions={!r}, '
                 'level_iterations={}, level_clip={!r}, extend_freq={!r}, extend_time={!r}, '
                 'extend_pols={!r}{})').format(
                     self.time_bin, self.threshold, self.rho, self.max_window, self.directions,
                     self.level_iterations, self.level_clip, self.extend_freq, self.extend_time,
-                    self.extend_pols, which)
+                    self.extend_pols, self._selection.spelling(', '))
 
 
 def rfiflag_host(vis, weights, baselines, params):
@@ -141,10 +136,7 @@ def rfiflag_host(vis, weights, baselines, params):
     samples kept and flagged, and skipped (group, polarization) pairs."""
     vis = np.asarray(vis)
     weights = np.asarray(weights)
-    if vis.dtype != np.complex64 or weights.dtype != np.float32:
-        raise TypeError('vis must be complex64 and weights float32')
-    if vis.ndim != 3 or vis.shape != weights.shape:
-        raise ValueError('vis and weights must both be [channel][row][polarization]')
+    check_block(vis, weights)
     C, N, P = vis.shape
     if len(baselines) != N:
         raise ValueError('{} baselines for {} rows'.format(len(baselines), N))
@@ -241,19 +233,7 @@ def rfiflag_host(vis, weights, baselines, params):
     return new_weights, flags.astype(np.uint8), level, counts
 
 
-class RFIFlagTemplate:
-    def __init__(self, context, params, tuning=None):
-        if not isinstance(params, RFIFlagParameters):
-            raise TypeError('params must be RFIFlagParameters')
-        lib()
-        self.context = context
-        self.params = params
-
-    def instantiate(self, *args, **kwargs):
-        return RFIFlag(self, *args, **kwargs)
-
-
-class RFIFlag:
+class RFIFlag(ChannelOperator):
     """``kimg_rfi_flag`` for blocks of ``num_channels`` channels.  ``op(vis, weights, baselines)``
     zeroes the weights of the samples it flags and leaves ``vis`` alone: two
     :class:`accel.DeviceArray` of shape [C][N][P] (complex64 / float32) whose inner [N][P] plane is
@@ -265,19 +245,14 @@ class RFIFlag:
     flagged and the (group, polarization) pairs skipped since construction or :meth:`reset_counts`.
     The workspace is the operator's and grows on demand."""
 
+    COUNTERS = 3
+
     def __init__(self, template, command_queue, num_channels):
+        super().__init__(template, command_queue, num_channels, masked=True)
         params = template.params
-        self.template = template
-        self.command_queue = command_queue
-        self.num_channels = int(num_channels)
-        if self.num_channels > MAX_CHANNELS:
-            raise ValueError('at most {} channels'.format(MAX_CHANNELS))
         self.params = params
         self.time_bin = params.time_bin
-        self._mask = np.ascontiguousarray(params.mask(self.num_channels), np.uint8)
         self._factors = np.ascontiguousarray(params.factors(), np.float64)
-        self._counts = accel.DeviceArray(command_queue.context, (3,), np.int64, queue=command_queue)
-        self._counts.zero(command_queue)
         self._workspace = None
         self._tables = None
         self.flags = None
@@ -288,44 +263,25 @@ class RFIFlag:
         return WORKSPACE_PER_ELEMENT * C * N * P + WORKSPACE_PER_ROW * N * P
 
     def __call__(self, vis, weights, baselines):
-        from .statwt import StatWt
-        if vis.dtype != np.complex64 or weights.dtype != np.float32:
-            raise TypeError('vis must be complex64 and weights float32')
-        if len(vis.shape) != 3 or vis.shape != weights.shape:
-            raise ValueError('vis and weights must both be [channel][row][polarization]')
-        if vis.shape[0] != self.num_channels:
-            raise ValueError('the operator was made for {} channels, the block has {}'.format(
-                self.num_channels, vis.shape[0]))
+        self._check_block(vis, weights)
         C, N, P = vis.shape
         if not 1 <= P <= 4:
             raise ValueError('1 to 4 polarizations')
-        baselines = np.asarray(baselines)
-        if baselines.shape != (N,) or baselines.dtype.kind not in 'iu':
-            raise ValueError('baselines must be an integer array with one entry per row')
         queue = self.command_queue
         context = queue.context
-        offsets = group_offsets(baselines, self.time_bin)
-        G = len(offsets) - 1
+        tables, G = group_tables(queue, baselines, N, self.time_bin)
         self.flags = accel.DeviceArray(context, (C, N, P), np.uint8, queue=queue)
         self.level = accel.DeviceArray(context, (G, P), np.float64, queue=queue)
         if N == 0:
             return
-        sizes = np.diff(offsets)
-        if offsets[0] != 0 or offsets[-1] != N or sizes.min() < 1 or sizes.max() > self.time_bin:
-            raise ValueError('bad group offsets')
-        # one upload: the offsets, then the group of every row
-        tables = np.concatenate((offsets, _row_groups(offsets)))
-        self._tables = accel.DeviceArray(context, tables.shape, np.int32, queue=queue)
-        self._tables.set(queue, tables)
-        need = self.workspace_bytes(C, N, P)
-        if self._workspace is None or self._workspace.shape[0] < need:
-            self._workspace = accel.DeviceArray(context, (need,), np.uint8, queue=queue)
+        self._tables = tables
+        self._workspace = grown_workspace(queue, self._workspace, self.workspace_bytes(C, N, P))
         vis.used_on(queue)
         weights.used_on(queue)
         params = self.params
         check(lib().kimg_rfi_flag(
-            vis.ptr, StatWt._channel_pitch(vis, 'vis'), weights.ptr,
-            StatWt._channel_pitch(weights, 'weights'), C, N, P,
+            vis.ptr, channel_pitch(vis, 'vis'), weights.ptr,
+            channel_pitch(weights, 'weights'), C, N, P,
             self._mask.ctypes.data_as(ctypes.c_void_p), self._tables.ptr, G,
             self._tables.ptr + 4 * (G + 1), self.time_bin,
             self._factors.ctypes.data_as(ctypes.c_void_p), params.max_window,
@@ -335,11 +291,7 @@ class RFIFlag:
             int(params.extend_pols), self.flags.ptr, self.level.ptr, self._workspace.ptr,
             self._workspace.shape[0], self._counts.ptr, queue.handle), 'kimg_rfi_flag')
 
-    def counts(self):
-        """(kept, flagged, skipped) so far: usable samples kept, usable samples flagged, (group,
-        polarization) pairs without a level; waits for the queue."""
-        host = self._counts.get(self.command_queue)
-        return int(host[0]), int(host[1]), int(host[2])
 
-    def reset_counts(self):
-        self._counts.zero(self.command_queue)
+class RFIFlagTemplate(OperatorTemplate):
+    params_type = RFIFlagParameters
+    operator = RFIFlag

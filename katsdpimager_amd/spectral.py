@@ -16,6 +16,7 @@ import numpy as np
 
 from . import accel
 from ._lib import lib, check
+from .channel_block import ChannelOperator, OperatorTemplate, channel_pitch, check_block
 
 #: KIMG_SPECTRAL_MAX_TAPS
 MAX_TAPS = 9
@@ -102,10 +103,7 @@ def filter_host_double(vis, weights, params):
     False both are 0."""
     vis = np.asarray(vis)
     weights = np.asarray(weights)
-    if vis.dtype != np.complex64 or weights.dtype != np.float32:
-        raise TypeError('vis must be complex64 and weights float32')
-    if vis.ndim != 3 or vis.shape != weights.shape:
-        raise ValueError('vis and weights must both be [channel][row][polarization]')
+    check_block(vis, weights)
     C_in = vis.shape[0]
     g, offset, step = params.coefficients()
     min_sum = params.min_sum()
@@ -154,19 +152,7 @@ def filter_host(vis, weights, params):
     return out, new_weights, (n_kept, int(kept.size) - n_kept)
 
 
-class SpectralFilterTemplate:
-    def __init__(self, context, params, tuning=None):
-        if not isinstance(params, SpectralParameters):
-            raise TypeError('params must be SpectralParameters')
-        lib()
-        self.context = context
-        self.params = params
-
-    def instantiate(self, *args, **kwargs):
-        return SpectralFilter(self, *args, **kwargs)
-
-
-class SpectralFilter:
+class SpectralFilter(ChannelOperator):
     """``kimg_spectral_filter`` for blocks of ``num_channels_in`` channels.  ``op(vis, weights)``
     reads two :class:`accel.DeviceArray` of shape [C_in][N][Q] (complex64 / float32) whose inner
     [N][Q] plane is dense -- the channel axis may have any pitch (a view of a larger tensor) -- and
@@ -176,39 +162,15 @@ class SpectralFilter:
 
     def __init__(self, template, command_queue, num_channels_in):
         params = template.params
-        self.template = template
-        self.command_queue = command_queue
-        self.num_channels_in = int(num_channels_in)
-        self.num_channels_out = params.output_channels(self.num_channels_in)
+        self.num_channels_out = params.output_channels(num_channels_in)
+        super().__init__(template, command_queue, num_channels_in)
+        self.num_channels_in = self.num_channels
         g, self._offset, self._step = params.coefficients()
         self._coeff = np.ascontiguousarray(g, np.float64)
         self._min_sum = params.min_sum()
-        self._counts = accel.DeviceArray(command_queue.context, (2,), np.int64, queue=command_queue)
-        self._counts.zero(command_queue)
-
-    @staticmethod
-    def _channel_pitch(array, what):
-        t = array.tensor
-        C, N, Q = array.shape
-        if N * Q == 0:
-            return 0
-        strides = t.stride()
-        if (Q > 1 and strides[2] != 1) or (N > 1 and strides[1] != Q):
-            raise ValueError('{}: the [row][polarization] plane must be dense'.format(what))
-        if C == 1:
-            return N * Q
-        if strides[0] < N * Q:
-            raise ValueError('{}: channels overlap'.format(what))
-        return int(strides[0])
 
     def __call__(self, vis, weights):
-        if vis.dtype != np.complex64 or weights.dtype != np.float32:
-            raise TypeError('vis must be complex64 and weights float32')
-        if len(vis.shape) != 3 or vis.shape != weights.shape:
-            raise ValueError('vis and weights must both be [channel][row][polarization]')
-        if vis.shape[0] != self.num_channels_in:
-            raise ValueError('the operator was made for {} channels, the block has {}'.format(
-                self.num_channels_in, vis.shape[0]))
+        self._check_block(vis, weights)
         queue = self.command_queue
         shape = (self.num_channels_out,) + tuple(vis.shape[1:])
         out_vis = accel.DeviceArray(queue.context, shape, np.complex64, queue=queue)
@@ -219,17 +181,14 @@ class SpectralFilter:
         vis.used_on(queue)
         weights.used_on(queue)
         check(lib().kimg_spectral_filter(
-            vis.ptr, self._channel_pitch(vis, 'vis'), weights.ptr,
-            self._channel_pitch(weights, 'weights'), self.num_channels_in,
+            vis.ptr, channel_pitch(vis, 'vis'), weights.ptr,
+            channel_pitch(weights, 'weights'), self.num_channels_in,
             out_vis.ptr, plane, out_weights.ptr, plane, self.num_channels_out, plane,
             self._coeff.ctypes.data_as(ctypes.c_void_p), len(self._coeff), self._offset, self._step,
             self._min_sum, self._counts.ptr, queue.handle), 'kimg_spectral_filter')
         return out_vis, out_weights
 
-    def counts(self):
-        """(kept, flagged) output samples so far; waits for the queue."""
-        host = self._counts.get(self.command_queue)
-        return int(host[0]), int(host[1])
 
-    def reset_counts(self):
-        self._counts.zero(self.command_queue)
+class SpectralFilterTemplate(OperatorTemplate):
+    params_type = SpectralParameters
+    operator = SpectralFilter

@@ -24,10 +24,10 @@ import numpy as np
 
 from . import accel
 from ._lib import lib, check
-from .continuum import MAX_CHANNELS
+from .channel_block import (MAX_BIN, ChannelOperator, ChannelSelection, OperatorTemplate,
+                            channel_pitch, check_block, group_offsets, group_tables,
+                            grown_workspace, integer, _row_groups, _sum_over_groups)
 
-#: KIMG_STATWT_MAX_BIN
-MAX_BIN = 64
 #: KIMG_STATWT_WORKSPACE_PER_ELEMENT
 WORKSPACE_PER_ELEMENT = 36
 
@@ -42,26 +42,13 @@ class StatWtParameters:
     ``wtrange``, stated on the variance)."""
 
     def __init__(self, time_bin=1, fit_mask=None, line_ranges=None, min_samples=8, chi2_range=None):
-        self.time_bin = self._integer(time_bin, 'time_bin', 1, MAX_BIN)
-        self.min_samples = self._integer(min_samples, 'min_samples', 2, 2 ** 31 - 1)
-        if fit_mask is not None and line_ranges is not None:
-            raise ValueError('at most one of fit_mask and line_ranges may be given')
-        self.fit_mask = None
-        self.line_ranges = None
-        if fit_mask is not None:
-            fit_mask = np.asarray(fit_mask)
-            if fit_mask.ndim != 1 or not len(fit_mask):
-                raise ValueError('fit_mask must have one entry per channel')
-            self.fit_mask = (fit_mask != 0).astype(np.uint8)
+        self.time_bin = integer(time_bin, 'time_bin', 1, MAX_BIN)
+        self.min_samples = integer(min_samples, 'min_samples', 2, 2 ** 31 - 1)
+        self._selection = ChannelSelection(fit_mask, line_ranges)
+        self.fit_mask = self._selection.fit_mask
+        self.line_ranges = self._selection.line_ranges
+        if self.fit_mask is not None:
             self.mask(len(self.fit_mask))
-        elif line_ranges is not None:
-            ranges = []
-            for r in line_ranges:
-                first, stop = (int(x) for x in r)
-                if first < 0 or stop < first:
-                    raise ValueError('bad line range {!r}'.format(r))
-                ranges.append((first, stop))
-            self.line_ranges = ranges
         if chi2_range is None:
             chi2_range = (0.0, np.inf)
         try:
@@ -72,84 +59,13 @@ class StatWtParameters:
             raise ValueError('chi2_range must be (lo, hi) with 0 <= lo < hi')
         self.chi2_range = (lo, hi)
 
-    @staticmethod
-    def _integer(value, name, low, high):
-        try:
-            as_int = int(value)
-        except (TypeError, ValueError, OverflowError):
-            raise ValueError('{} must be an integer'.format(name)) from None
-        if as_int != value or not low <= as_int <= high:
-            raise ValueError('{} must be an integer from {} to {}'.format(name, low, high))
-        return as_int
-
     def mask(self, num_channels):
         """The fit mask of ``num_channels`` channels, uint8 (1 = enters the statistic)."""
-        num_channels = int(num_channels)
-        if num_channels < 1:
-            raise ValueError('no channels')
-        if self.fit_mask is not None:
-            if len(self.fit_mask) != num_channels:
-                raise ValueError('fit_mask has {} entries for {} channels'.format(
-                    len(self.fit_mask), num_channels))
-            mask = self.fit_mask.copy()
-        else:
-            mask = np.ones(num_channels, np.uint8)
-            for first, stop in self.line_ranges or ():
-                if stop > num_channels:
-                    raise ValueError('line range ({}, {}) beyond the {} channels'.format(
-                        first, stop, num_channels))
-                mask[first:stop] = 0
-        if not mask.any():
-            raise ValueError('no line-free channel remains')
-        return mask
+        return self._selection.mask(num_channels)
 
     def __repr__(self):
-        which = ''
-        if self.fit_mask is not None:
-            which = ', fit_mask={!r}'.format(self.fit_mask.tolist())
-        elif self.line_ranges is not None:
-            which = ', line_ranges={!r}'.format(self.line_ranges)
         return 'StatWtParameters({}{}, min_samples={}, chi2_range={!r})'.format(
-            self.time_bin, which, self.min_samples, self.chi2_range)
-
-
-def group_offsets(baselines, time_bin):
-    """int32 [G + 1]: the first row of every group of a block whose rows carry the baseline ids
-    ``baselines`` [N], and N at the end.  Equal consecutive ids form a run (an id that returns later
-    in the block starts a new run); each run is cut every ``time_bin`` rows, its last group taking
-    what is left."""
-    baselines = np.asarray(baselines)
-    if baselines.ndim != 1:
-        raise ValueError('baselines must have one entry per row')
-    time_bin = int(time_bin)
-    if not 1 <= time_bin <= MAX_BIN:
-        raise ValueError('time_bin must lie in 1 to {}'.format(MAX_BIN))
-    N = len(baselines)
-    if N > 2 ** 31 - 1:
-        raise ValueError('too many rows')
-    if N == 0:
-        return np.zeros(1, np.int32)
-    starts = np.flatnonzero(np.concatenate(([True], baselines[1:] != baselines[:-1])))
-    lengths = np.diff(np.concatenate((starts, [N])))
-    groups = (lengths + time_bin - 1) // time_bin           # per run
-    run = np.repeat(np.arange(len(starts)), groups)         # per group
-    within = np.arange(int(groups.sum())) - (np.cumsum(groups) - groups)[run]
-    return np.concatenate((starts[run] + within * time_bin, [N])).astype(np.int32)
-
-
-def _row_groups(offsets):
-    """int32 [N]: the group of every row."""
-    return np.repeat(np.arange(len(offsets) - 1, dtype=np.int32), np.diff(offsets))
-
-
-def _sum_over_groups(per_row, offsets, time_bin):
-    """[G][P]: the rows of every group added up in ascending row order, starting from 0."""
-    first, stop = offsets[:-1].astype(np.int64), offsets[1:].astype(np.int64)
-    total = np.zeros((len(first),) + per_row.shape[1:], per_row.dtype)
-    for i in range(time_bin):
-        has = first + i < stop
-        total[has] = total[has] + per_row[first[has] + i]
-    return total
+            self.time_bin, self._selection.spelling(', '), self.min_samples, self.chi2_range)
 
 
 def statwt_host(vis, weights, baselines, params):
@@ -160,10 +76,7 @@ def statwt_host(vis, weights, baselines, params):
     has fewer than 2 usable samples) and the counts in units of group x polarization."""
     vis = np.asarray(vis)
     weights = np.asarray(weights)
-    if vis.dtype != np.complex64 or weights.dtype != np.float32:
-        raise TypeError('vis must be complex64 and weights float32')
-    if vis.ndim != 3 or vis.shape != weights.shape:
-        raise ValueError('vis and weights must both be [channel][row][polarization]')
+    check_block(vis, weights)
     C, N, P = vis.shape
     if len(baselines) != N:
         raise ValueError('{} baselines for {} rows'.format(len(baselines), N))
@@ -217,19 +130,7 @@ def statwt_host(vis, weights, baselines, params):
     return new_weights, np.where(M < 2, np.nan, chi2), (n_kept, int(kept.size) - n_kept)
 
 
-class StatWtTemplate:
-    def __init__(self, context, params, tuning=None):
-        if not isinstance(params, StatWtParameters):
-            raise TypeError('params must be StatWtParameters')
-        lib()
-        self.context = context
-        self.params = params
-
-    def instantiate(self, *args, **kwargs):
-        return StatWt(self, *args, **kwargs)
-
-
-class StatWt:
+class StatWt(ChannelOperator):
     """``kimg_statwt`` for blocks of ``num_channels`` channels.  ``op(vis, weights, baselines)``
     rescales ``weights`` in place and leaves ``vis`` alone: two :class:`accel.DeviceArray` of shape
     [C][N][P] (complex64 / float32) whose inner [N][P] plane is dense -- the channel axis may have
@@ -241,82 +142,38 @@ class StatWt:
     the first call).  The workspace is the operator's and grows on demand."""
 
     def __init__(self, template, command_queue, num_channels):
+        super().__init__(template, command_queue, num_channels, masked=True)
         params = template.params
-        self.template = template
-        self.command_queue = command_queue
-        self.num_channels = int(num_channels)
-        if self.num_channels > MAX_CHANNELS:
-            raise ValueError('at most {} channels'.format(MAX_CHANNELS))
         self.time_bin = params.time_bin
         self.min_samples = params.min_samples
         self.chi2_range = params.chi2_range
-        self._mask = np.ascontiguousarray(params.mask(self.num_channels), np.uint8)
-        self._counts = accel.DeviceArray(command_queue.context, (2,), np.int64, queue=command_queue)
-        self._counts.zero(command_queue)
         self._workspace = None
         self._tables = None
         self.chi2 = None
 
-    @staticmethod
-    def _channel_pitch(array, what):
-        t = array.tensor
-        C, N, Q = array.shape
-        if N * Q == 0:
-            return 0
-        strides = t.stride()
-        if (Q > 1 and strides[2] != 1) or (N > 1 and strides[1] != Q):
-            raise ValueError('{}: the [row][polarization] plane must be dense'.format(what))
-        if C == 1:
-            return N * Q
-        if strides[0] < N * Q:
-            raise ValueError('{}: channels overlap'.format(what))
-        return int(strides[0])
-
     def __call__(self, vis, weights, baselines):
-        if vis.dtype != np.complex64 or weights.dtype != np.float32:
-            raise TypeError('vis must be complex64 and weights float32')
-        if len(vis.shape) != 3 or vis.shape != weights.shape:
-            raise ValueError('vis and weights must both be [channel][row][polarization]')
-        if vis.shape[0] != self.num_channels:
-            raise ValueError('the operator was made for {} channels, the block has {}'.format(
-                self.num_channels, vis.shape[0]))
+        self._check_block(vis, weights)
         C, N, P = vis.shape
         if not 1 <= P <= 4:
             raise ValueError('1 to 4 polarizations')
-        baselines = np.asarray(baselines)
-        if baselines.shape != (N,) or baselines.dtype.kind not in 'iu':
-            raise ValueError('baselines must be an integer array with one entry per row')
         queue = self.command_queue
-        context = queue.context
-        offsets = group_offsets(baselines, self.time_bin)
-        G = len(offsets) - 1
-        self.chi2 = accel.DeviceArray(context, (G, P), np.float64, queue=queue)
+        tables, G = group_tables(queue, baselines, N, self.time_bin)
+        self.chi2 = accel.DeviceArray(queue.context, (G, P), np.float64, queue=queue)
         if N == 0:
             return
-        sizes = np.diff(offsets)
-        if offsets[0] != 0 or offsets[-1] != N or sizes.min() < 1 or sizes.max() > self.time_bin:
-            raise ValueError('bad group offsets')
-        # one upload: the offsets, then the group of every row
-        tables = np.concatenate((offsets, _row_groups(offsets)))
-        self._tables = accel.DeviceArray(context, tables.shape, np.int32, queue=queue)
-        self._tables.set(queue, tables)
-        need = WORKSPACE_PER_ELEMENT * N * P
-        if self._workspace is None or self._workspace.shape[0] < need:
-            self._workspace = accel.DeviceArray(context, (need,), np.uint8, queue=queue)
+        self._tables = tables
+        self._workspace = grown_workspace(queue, self._workspace, WORKSPACE_PER_ELEMENT * N * P)
         vis.used_on(queue)
         weights.used_on(queue)
         check(lib().kimg_statwt(
-            vis.ptr, self._channel_pitch(vis, 'vis'), weights.ptr,
-            self._channel_pitch(weights, 'weights'), C, N, P,
+            vis.ptr, channel_pitch(vis, 'vis'), weights.ptr,
+            channel_pitch(weights, 'weights'), C, N, P,
             self._mask.ctypes.data_as(ctypes.c_void_p), self._tables.ptr, G,
             self._tables.ptr + 4 * (G + 1), self.time_bin, self.min_samples,
             self.chi2_range[0], self.chi2_range[1], self.chi2.ptr, self._workspace.ptr,
             self._workspace.shape[0], self._counts.ptr, queue.handle), 'kimg_statwt')
 
-    def counts(self):
-        """(kept, flagged) group x polarization pairs so far; waits for the queue."""
-        host = self._counts.get(self.command_queue)
-        return int(host[0]), int(host[1])
 
-    def reset_counts(self):
-        self._counts.zero(self.command_queue)
+class StatWtTemplate(OperatorTemplate):
+    params_type = StatWtParameters
+    operator = StatWt
