@@ -15,20 +15,10 @@
 //   4. the unchanged window kernel over the sorted copies.
 // Results equal the direct path's up to the order of float additions.
 // kimg_grid_jumps counts the records that would force a window jump, so that callers can choose.
-#include "kimg_common.h"
-#include <hipcub/hipcub.hpp>
+#include "kimg_record_stream.h"
+#include "kimg_window_plan.h"
 
 namespace {
-
-constexpr int WIN = 32;
-
-// Window slack (cells a footprint origin may move without a flush) of the launches that grid a
-// K-tap kernel: K itself up to 32 taps, (K+1)/2-tap blocks above.
-__host__ __device__ inline int window_slack(int K)
-{
-    const int taps = K > WIN ? (K + 1) / 2 : K;
-    return WIN - taps;
-}
 
 struct bin_geometry {
     int half;           // grid_size / 2: u + half is a non-negative cell index
@@ -58,26 +48,9 @@ __global__ __launch_bounds__(256) void bin_key_kernel(
     index[i] = (unsigned) i;
 }
 
-template <int P>
+// The stream in tile order; WEIGHTS: the degridder's (it also needs the statistical weights) ...
+template <int P, bool WEIGHTS>
 __global__ __launch_bounds__(256) void gather_kernel(
-    const unsigned *__restrict__ index, int64_t n, const int2 *__restrict__ uv,
-    const int16_t *__restrict__ w_plane, const float2 *__restrict__ vis,
-    int2 *__restrict__ uv_out, int16_t *__restrict__ wp_out, float2 *__restrict__ vis_out)
-{
-    const int64_t i = blockIdx.x * (int64_t) blockDim.x + threadIdx.x;
-    if (i >= n)
-        return;
-    const unsigned src = index[i];
-    uv_out[i] = uv[src];
-    wp_out[i] = w_plane[src];
-#pragma unroll
-    for (int p = 0; p < P; p++)
-        vis_out[i * P + p] = vis[(int64_t) src * P + p];
-}
-
-// the degridder's inputs in tile order (it also needs the statistical weights) ...
-template <int P>
-__global__ __launch_bounds__(256) void gather_degrid_kernel(
     const unsigned *__restrict__ index, int64_t n, const int2 *__restrict__ uv,
     const int16_t *__restrict__ w_plane, const float *__restrict__ weights,
     const float2 *__restrict__ vis, int2 *__restrict__ uv_out, int16_t *__restrict__ wp_out,
@@ -87,16 +60,10 @@ __global__ __launch_bounds__(256) void gather_degrid_kernel(
     if (i >= n)
         return;
     const int64_t src = index[i];
-    uv_out[i] = uv[src];
-    wp_out[i] = w_plane[src];
-#pragma unroll
-    for (int p = 0; p < P; p++) {
-        w_out[i * P + p] = weights[src * P + p];
-        vis_out[i * P + p] = vis[src * P + p];
-    }
+    copy_record<P, WEIGHTS>(i, src, uv, w_plane, weights, vis, uv_out, wp_out, w_out, vis_out);
 }
 
-// ... and its results back in the caller's order
+// ... and the degridder's results back in the caller's order
 template <int P>
 __global__ __launch_bounds__(256) void scatter_vis_kernel(
     const unsigned *__restrict__ index, int64_t n, const float2 *__restrict__ vis_sorted,
@@ -129,39 +96,31 @@ __global__ __launch_bounds__(256) void jump_count_kernel(
 }
 
 struct binned_ws {
-    size_t table;       // the window kernel's own scratch (padded table copy), first
-    size_t keys[2], index[2], uv, wp, vis, weights, cub, cub_bytes, total;
+    void *table;        // the window kernel's own scratch (padded table copy), first
+    index_sort<unsigned> sort;
+    int2 *uv;
+    int16_t *wp;
+    float2 *vis;
+    float *weights;     // degridders only
+    void *cub;
+    size_t table_bytes, cub_bytes, total;
 };
 
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
-hipError_t layout(int64_t n, int P, int W, int OV, int K, bool degrid, binned_ws &ws)
+// (`workspace` null: the size only)
+hipError_t carve(int64_t n, int P, int W, int OV, int K, bool degrid, void *workspace, binned_ws &ws)
 {
-    size_t off = align256(degrid ? kimg_degrid_mfma_workspace_bytes(P, W, OV, K)
-                                 : kimg_grid_mfma_workspace_bytes(P, W, OV, K));
-    ws.table = 0;
-    for (int i = 0; i < 2; i++) {
-        ws.keys[i] = off;
-        off += align256((size_t) n * sizeof(unsigned));
-        ws.index[i] = off;
-        off += align256((size_t) n * sizeof(unsigned));
-    }
-    ws.uv = off;
-    off += align256((size_t) n * sizeof(int2));
-    ws.wp = off;
-    off += align256((size_t) n * sizeof(int16_t));
-    ws.vis = off;
-    off += align256((size_t) n * P * sizeof(float2));
-    ws.weights = off;
-    if (degrid)
-        off += align256((size_t) n * P * sizeof(float));
-    ws.cub_bytes = 0;
-    hipcub::DoubleBuffer<unsigned> k(nullptr, nullptr), v(nullptr, nullptr);
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, ws.cub_bytes, k, v, (int) n, 0, 32,
-                                                      (hipStream_t) 0);
-    ws.cub = off;
-    off += align256(ws.cub_bytes);
-    ws.total = off;
+    ws_carver c(workspace);
+    ws.table = c.take<unsigned char>(degrid ? kimg_degrid_mfma_workspace_bytes(P, W, OV, K)
+                                            : kimg_grid_mfma_workspace_bytes(P, W, OV, K));
+    ws.table_bytes = c.total();
+    ws.sort.carve(c, n);
+    ws.uv = c.take<int2>((size_t) n);
+    ws.wp = c.take<int16_t>((size_t) n);
+    ws.vis = c.take<float2>((size_t) n * P);
+    ws.weights = degrid ? c.take<float>((size_t) n * P) : nullptr;
+    const hipError_t e = ws.sort.temp_bytes(n, ws.cub_bytes);
+    ws.cub = c.take<unsigned char>(ws.cub_bytes);
+    ws.total = c.total();
     return e;
 }
 
@@ -171,7 +130,7 @@ size_t binned_workspace_bytes(int64_t n, int P, int W, int OV, int K, bool degri
         || !(degrid ? kimg_degrid_mfma_supported(P, W, OV, K) : kimg_grid_mfma_supported(P, W, OV, K)))
         return 0;
     binned_ws ws;
-    if (layout(n, P, W, OV, K, degrid, ws) != hipSuccess)
+    if (carve(n, P, W, OV, K, degrid, nullptr, ws) != hipSuccess)
         return 0;
     return ws.total;
 }
@@ -186,53 +145,40 @@ int kimg_bin_stream(const int16_t *uv, const int16_t *w_plane, const float *weig
     if (num_vis >= ((int64_t) 1 << 31))
         return KIMG_EUNSUPPORTED;
     binned_ws ws;
-    hipError_t e = layout(num_vis, P, w_planes, oversample, kernel_width, weights != nullptr, ws);
+    hipError_t e = carve(num_vis, P, w_planes, oversample, kernel_width, weights != nullptr, workspace, ws);
     if (e != hipSuccess)
         return -(int) e;
     if (workspace == nullptr || workspace_bytes < ws.total)
         return KIMG_EWORKSPACE;
-    unsigned char *base = static_cast<unsigned char *>(workspace);
-    hipcub::DoubleBuffer<unsigned> keys(reinterpret_cast<unsigned *>(base + ws.keys[0]),
-                                        reinterpret_cast<unsigned *>(base + ws.keys[1]));
-    hipcub::DoubleBuffer<unsigned> index(reinterpret_cast<unsigned *>(base + ws.index[0]),
-                                         reinterpret_cast<unsigned *>(base + ws.index[1]));
-    // keys of the footprint-origin bins, sorted; index.Current() = the caller's record of sorted place i
+    // keys of the footprint-origin bins, sorted; out.index = the caller's record of sorted place i
     bin_geometry g;
     g.half = grid_size / 2;
     g.bin = window_slack(kernel_width) + 1;
     g.nbu = (grid_size + g.bin - 1) / g.bin;
     const int nbv = g.nbu;
     g.last_key = (unsigned) g.nbu * (unsigned) nbv;
-    int bits = 1;
-    while (bits < 32 && (g.last_key >> bits) != 0)
-        bits++;
     const int blocks = kimg_divup(num_vis, 256);
-    bin_key_kernel<<<blocks, 256, 0, stream>>>(uv, num_vis, g, grid_size, keys.Current(),
-                                               index.Current());
-    size_t cub_bytes = ws.cub_bytes;
-    KIMG_HIP(hipcub::DeviceRadixSort::SortPairs(base + ws.cub, cub_bytes, keys, index, (int) num_vis,
-                                                0, bits, stream));
+    bin_key_kernel<<<blocks, 256, 0, stream>>>(uv, num_vis, g, grid_size, ws.sort.keys[0],
+                                               ws.sort.index[0]);
+    KIMG_HIP(ws.sort.sort(ws.cub, ws.cub_bytes, num_vis, sort_bits(g.last_key), stream, out.index));
     int rc = kimg_launch_status();
     if (rc)
         return rc;
-    int2 *uv_s = reinterpret_cast<int2 *>(base + ws.uv);
-    int16_t *wp_s = reinterpret_cast<int16_t *>(base + ws.wp);
-    out.uv = reinterpret_cast<const int16_t *>(uv_s);
-    out.w_plane = wp_s;
-    out.vis = reinterpret_cast<float2 *>(base + ws.vis);
-    out.weights = reinterpret_cast<float *>(base + ws.weights);
-    out.index = index.Current();
-    out.table = base + ws.table;
-    out.table_bytes = ws.keys[0];
+    out.uv = reinterpret_cast<const int16_t *>(ws.uv);
+    out.w_plane = ws.wp;
+    out.vis = ws.vis;
+    out.weights = ws.weights;
+    out.table = ws.table;
+    out.table_bytes = ws.table_bytes;
     const int2 *uv2 = reinterpret_cast<const int2 *>(uv);
     const float2 *vis2 = static_cast<const float2 *>(vis);
     kimg_for_pols(P, [&](auto p) {
         if (weights)
-            gather_degrid_kernel<decltype(p)::value><<<blocks, 256, 0, stream>>>(
-                out.index, num_vis, uv2, w_plane, weights, vis2, uv_s, wp_s, out.weights, out.vis);
+            gather_kernel<decltype(p)::value, true><<<blocks, 256, 0, stream>>>(
+                out.index, num_vis, uv2, w_plane, weights, vis2, ws.uv, ws.wp, ws.weights, ws.vis);
         else
-            gather_kernel<decltype(p)::value><<<blocks, 256, 0, stream>>>(
-                out.index, num_vis, uv2, w_plane, vis2, uv_s, wp_s, out.vis); });
+            gather_kernel<decltype(p)::value, false><<<blocks, 256, 0, stream>>>(
+                out.index, num_vis, uv2, w_plane, nullptr, vis2, ws.uv, ws.wp, nullptr, ws.vis); });
     return kimg_launch_status();
 }
 

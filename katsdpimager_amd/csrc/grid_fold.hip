@@ -29,7 +29,7 @@
 // use_folded only if every span found the count the plan gave it.  Then the offsets were the right
 // ones and the output is what the two launches write; else the window kernel grids the caller's
 // stream.  Output indices are checked against the capacity whatever the plan holds.
-#include "kimg_common.h"
+#include "kimg_record_stream.h"
 
 namespace {
 
@@ -39,11 +39,35 @@ constexpr int FOLD_TILE = FOLD_THREADS * FOLD_RECORDS;
 constexpr int FOLD_MAX_SPANS = 1024;                        // (what the counts' array holds)
 constexpr int FOLD_WAVES = FOLD_THREADS / WAVE;
 
-// workspace layout (bytes): header, the spans' counts, then the compacted uv, vis and w_plane
+// workspace layout: header, the spans' counts, then the compacted uv, vis and w_plane
 constexpr size_t FOLD_HEADER_BYTES = 256;
 constexpr size_t FOLD_COUNTS_BYTES = FOLD_MAX_SPANS * sizeof(uint32_t);
+static_assert(sizeof(kimg_fold_header) <= FOLD_HEADER_BYTES && FOLD_COUNTS_BYTES % 256 == 0,
+              "the header and the counts are the workspace's first two sections, at 0 and 256");
 
-inline size_t align256(size_t n) { return (n + 255) / 256 * 256; }
+struct fold_ws {
+    kimg_fold_header *header;
+    uint32_t *counts;
+    int2 *uv;
+    float2 *vis;
+    int16_t *w_plane;
+    size_t total;
+};
+
+// (`workspace` null: the size only)
+inline fold_ws fold_carve(int P, int64_t capacity, void *workspace)
+{
+    const size_t cap = capacity > 0 ? (size_t) capacity : 0;
+    ws_carver c(workspace);
+    fold_ws ws;
+    ws.header = reinterpret_cast<kimg_fold_header *>(c.take<unsigned char>(FOLD_HEADER_BYTES));
+    ws.counts = c.take<uint32_t>(FOLD_COUNTS_BYTES / sizeof(uint32_t));
+    ws.uv = c.take<int2>(cap);
+    ws.vis = c.take<float2>(cap * P);
+    ws.w_plane = c.take<int16_t>(cap);
+    ws.total = c.total();
+    return ws;
+}
 
 struct fold_plan {
     int spans;
@@ -442,9 +466,7 @@ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 
 size_t kimg_fold_workspace_bytes(int P, int64_t capacity)
 {
-    const size_t cap = capacity > 0 ? (size_t) capacity : 0;
-    return FOLD_HEADER_BYTES + FOLD_COUNTS_BYTES + align256(cap * sizeof(int2))
-           + align256(cap * P * sizeof(float2)) + align256(cap * sizeof(int16_t));
+    return fold_carve(P, capacity, nullptr).total;
 }
 
 int kimg_fold_launch(const int16_t *uv, const int16_t *w_plane, const float2 *vis, int64_t num_vis,
@@ -453,31 +475,23 @@ int kimg_fold_launch(const int16_t *uv, const int16_t *w_plane, const float2 *vi
 {
     if (capacity < 0)
         capacity = 0;
-    unsigned char *base = static_cast<unsigned char *>(workspace);
-    kimg_fold_header *header = reinterpret_cast<kimg_fold_header *>(base);
-    uint32_t *counts = reinterpret_cast<uint32_t *>(base + FOLD_HEADER_BYTES);
-    unsigned char *out = base + FOLD_HEADER_BYTES + FOLD_COUNTS_BYTES;
-    int2 *out_uv = reinterpret_cast<int2 *>(out);
-    out += align256((size_t) capacity * sizeof(int2));
-    float2 *out_vis = reinterpret_cast<float2 *>(out);
-    out += align256((size_t) capacity * P * sizeof(float2));
-    int16_t *out_w = reinterpret_cast<int16_t *>(out);
+    const fold_ws ws = fold_carve(P, capacity, workspace);
     const fold_plan plan = fold_plan_of(num_vis, P);
     if (plan_data != nullptr) {
         // the workspace's counts are free for the spans' own counts
-        KIMG_HIP(hipMemsetAsync(header->ticket, 0, sizeof(header->ticket), stream));
+        KIMG_HIP(hipMemsetAsync(ws.header->ticket, 0, sizeof(ws.header->ticket), stream));
         kimg_for_pols(P, [&](auto p) {
             fold_compact_kernel<decltype(p)::value, true><<<plan.spans, FOLD_THREADS, 0, stream>>>(
                 uv, w_plane, vis, num_vis, plan.tiles_per_span, plan.spans, plan_data->counts,
-                capacity, header, out_uv, out_w, out_vis, plan_data, counts); });
+                capacity, ws.header, ws.uv, ws.w_plane, ws.vis, plan_data, ws.counts); });
         return kimg_launch_status();
     }
     fold_count_kernel<<<plan.spans, FOLD_THREADS, 0, stream>>>(uv, w_plane, num_vis,
-                                                               plan.tiles_per_span, counts);
+                                                               plan.tiles_per_span, ws.counts);
     kimg_for_pols(P, [&](auto p) {
         fold_compact_kernel<decltype(p)::value, false><<<plan.spans, FOLD_THREADS, 0, stream>>>(
-            uv, w_plane, vis, num_vis, plan.tiles_per_span, plan.spans, counts, capacity, header,
-            out_uv, out_w, out_vis, nullptr, nullptr); });
+            uv, w_plane, vis, num_vis, plan.tiles_per_span, plan.spans, ws.counts, capacity,
+            ws.header, ws.uv, ws.w_plane, ws.vis, nullptr, nullptr); });
     return kimg_launch_status();
 }
 

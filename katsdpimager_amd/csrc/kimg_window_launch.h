@@ -9,7 +9,6 @@
 // Private to the including unit, like the kernels it serves (tap_split is a kernel parameter).
 namespace {
 
-constexpr int WIN = 32;                         // the window: 32 x 32 grid points
 constexpr size_t LDS_LIMIT = 160 * 1024;        // LDS a workgroup may have on gfx950
 
 // Kernel widths above 32 are (de)gridded as 2 x 2 blocks of taps, one launch per block: the
@@ -29,7 +28,7 @@ struct tap_split {
 template <class F> inline int kimg_for_tap_blocks(int K, F &&f)
 {
     const bool wide = K > WIN;
-    const int Kh = wide ? (K + 1) / 2 : K;              // taps per block along one axis
+    const int Kh = window_taps_of(K);                   // taps per block along one axis
     const int nblk = wide ? 2 : 1;
     for (int jb = 0; jb < nblk; jb++)
         for (int kb = 0; kb < nblk; kb++) {

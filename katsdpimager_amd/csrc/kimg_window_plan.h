@@ -1,7 +1,8 @@
 // How a window kernel's launch divides a stream of num_vis records, as functions of the record
 // count that the host (window_partition_of, kimg_window_launch.h) and the device (the prologue of
-// grid_mfma_kernel, when the fold pre-pass has shortened the stream) evaluate alike.  Nothing here
-// needs the HIP runtime: the host test of these helpers compiles this file alone.
+// grid_mfma_kernel, when the fold pre-pass has shortened the stream) evaluate alike; and the window's
+// geometry as a function of the kernel width.  Nothing here needs the HIP runtime: the host test of
+// these helpers compiles this file alone.
 #pragma once
 #include <stdint.h>
 
@@ -10,6 +11,18 @@
 #else
 #define KIMG_HD
 #endif
+
+// The window and what a K-tap kernel leaves of it.  The launches (kimg_for_tap_blocks,
+// kimg_window_launch.h), the strips of the resident store (store.hip) and the bins of the tile-binned
+// variant (grid_binned.hip) all take it from here: an order laid out for another slack than the
+// kernels' is an order the window does not follow.
+constexpr int WIN = 32;                         // the window: 32 x 32 grid points
+
+// Taps of one launch along one axis: K itself up to 32 taps, (K + 1) / 2-tap blocks above
+KIMG_HD inline int window_taps_of(int K) { return K > WIN ? (K + 1) / 2 : K; }
+
+// Cells a footprint origin may move without the window moving
+KIMG_HD inline int window_slack(int K) { return WIN - window_taps_of(K); }
 
 // Records per workgroup when every workgroup streams one contiguous span: a multiple of 64, at
 // least one batch per wave.  `blocks` workgroups of that span cover the stream.

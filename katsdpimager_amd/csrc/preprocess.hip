@@ -10,8 +10,7 @@
 // The merge keeps the reference's arithmetic: a run of adjacent equal keys is summed left to
 // right in float32 by the thread that owns the head of the run, so sums are bit-identical to
 // the sequential host loop.
-#include "kimg_common.h"
-#include <hipcub/hipcub.hpp>
+#include "kimg_record_stream.h"
 
 namespace {
 
@@ -210,15 +209,9 @@ __global__ __launch_bounds__(256) void pp_gather_stream_kernel(
     const int m = ipos[n - 1];
     if (t >= m)
         return;
-    int64_t s = perm[t];
-    const int2 uv = *reinterpret_cast<const int2 *>(m_uv + 4 * s);
-    *reinterpret_cast<int2 *>(out_uv + 4 * t) = uv;
-    out_wplane[t] = m_wplane[s];
-#pragma unroll
-    for (int p = 0; p < P; p++) {
-        out_w[t * P + p] = m_w[s * P + p];
-        out_vis[t * P + p] = m_vis[s * P + p];
-    }
+    const int64_t s = perm[t];
+    copy_record<P, true>(t, s, reinterpret_cast<const int2 *>(m_uv), m_wplane, m_w, m_vis,
+                         reinterpret_cast<int2 *>(out_uv), out_wplane, out_w, out_vis);
 }
 
 __global__ __launch_bounds__(256) void pp_real_to_complex_kernel(
@@ -383,8 +376,6 @@ __global__ __launch_bounds__(256) void pp_sort_init_kernel(
     sval[i] = (int) i;
 }
 
-inline size_t align_up(size_t x) { return (x + 255) & ~(size_t) 255; }
-
 struct pp_workspace {
     int *valid, *pos, *hidx, *sval_in, *sval_out;   // valid = pv (last valid index), pos = ipos (heads so far)
     unsigned short *skey_in, *skey_out;
@@ -395,15 +386,8 @@ struct pp_workspace {
     size_t cub_bytes, total;
 };
 
-int slice_bits(int w_slices)
-{
-    int bits = 1;
-    while ((1 << bits) <= w_slices)     // keys 0..w_slices (sentinel) must fit
-        bits++;
-    return bits;
-}
-
-hipError_t layout_workspace(int64_t n, int P, char *base, pp_workspace &ws)
+// (`workspace` null: the size only)
+hipError_t layout_workspace(int64_t n, int P, void *workspace, pp_workspace &ws)
 {
     size_t scan_bytes = 0, sort_bytes = 0, scan2_bytes = 0;
     hipError_t e = hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (int *) nullptr,
@@ -421,52 +405,23 @@ hipError_t layout_workspace(int64_t n, int P, char *base, pp_workspace &ws)
                                            (int *) nullptr, (int) n, 0, 16);
     if (e != hipSuccess)
         return e;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off += align_up(bytes);
-        return p;
-    };
-    size_t ni = (size_t) n * sizeof(int);
-    ws.valid = (int *) take(ni);
-    ws.pos = (int *) take(ni);
-    ws.hidx = (int *) take(ni);
-    ws.sval_in = (int *) take(ni);
-    ws.sval_out = (int *) take(ni);
-    ws.skey_in = (unsigned short *) take((size_t) n * 2);
-    ws.skey_out = (unsigned short *) take((size_t) n * 2);
-    ws.m_uv = (short *) take((size_t) n * 8);
-    ws.m_wplane = (short *) take((size_t) n * 2);
-    ws.m_w = (float *) take((size_t) n * P * 4);
-    ws.m_vis = (float2 *) take((size_t) n * P * 8);
+    ws_carver c(workspace);
+    const size_t count = (size_t) n;
+    ws.valid = c.take<int>(count);
+    ws.pos = c.take<int>(count);
+    ws.hidx = c.take<int>(count);
+    ws.sval_in = c.take<int>(count);
+    ws.sval_out = c.take<int>(count);
+    ws.skey_in = c.take<unsigned short>(count);
+    ws.skey_out = c.take<unsigned short>(count);
+    ws.m_uv = c.take<short>(count * 4);
+    ws.m_wplane = c.take<short>(count);
+    ws.m_w = c.take<float>(count * P);
+    ws.m_vis = c.take<float2>(count * P);
     ws.cub_bytes = scan_bytes > sort_bytes ? scan_bytes : sort_bytes;
-    ws.cub = take(ws.cub_bytes);
-    ws.total = off;
+    ws.cub = c.take<unsigned char>(ws.cub_bytes);
+    ws.total = c.total();
     return hipSuccess;
-}
-
-template <int P, int Q>
-int convert_launch(int64_t n, const float *uvw, const float *weights, const float2 *vis,
-                   const float *fa1, const float *fa2, const pp_matrices &mat,
-                   const pp_channel &ch, short *key, float *out_w, float2 *out_vis,
-                   hipStream_t stream)
-{
-    pp_convert_kernel<P, Q><<<kimg_divup(n, 256), 256, 0, stream>>>(
-        n, uvw, weights, vis, fa1, fa2, mat, ch, key, out_w, out_vis);
-    return kimg_launch_status();
-}
-
-template <int P>
-int convert_q(int Q, int64_t n, const float *uvw, const float *weights, const float2 *vis,
-              const float *fa1, const float *fa2, const pp_matrices &mat, const pp_channel &ch,
-              short *key, float *out_w, float2 *out_vis, hipStream_t stream)
-{
-    switch (Q) {
-    case 1: return convert_launch<P, 1>(n, uvw, weights, vis, fa1, fa2, mat, ch, key, out_w, out_vis, stream);
-    case 2: return convert_launch<P, 2>(n, uvw, weights, vis, fa1, fa2, mat, ch, key, out_w, out_vis, stream);
-    case 3: return convert_launch<P, 3>(n, uvw, weights, vis, fa1, fa2, mat, ch, key, out_w, out_vis, stream);
-    default: return convert_launch<P, 4>(n, uvw, weights, vis, fa1, fa2, mat, ch, key, out_w, out_vis, stream);
-    }
 }
 
 template <int P>
@@ -497,7 +452,8 @@ int compress_impl(int64_t n, int w_slices, int window, const short *key, const f
     if (!single) {
         cb = ws.cub_bytes;
         KIMG_HIP(hipcub::DeviceRadixSort::SortPairs(ws.cub, cb, ws.skey_in, ws.skey_out, ws.sval_in,
-                                                    ws.sval_out, (int) n, 0, slice_bits(w_slices),
+                                                    ws.sval_out, (int) n, 0,
+                                                    sort_bits((unsigned) w_slices) /* the sentinel */,
                                                     stream));
         pp_slice_counts_kernel<<<kimg_divup(w_slices, 64), 64, 0, stream>>>(n, ws.skey_out, w_slices,
                                                                            counts);
@@ -545,12 +501,12 @@ extern "C" int kimg_preprocess_convert(
     ch.max_slice_plane = w_slices * w_planes - 1;                          // :430
     const float2 *v = static_cast<const float2 *>(vis);
     float2 *ov = static_cast<float2 *>(out_vis);
-    switch (num_pols) {
-    case 1: return convert_q<1>(num_in_pols, num_vis, uvw, weights, v, feed_angle1, feed_angle2, mat, ch, key, out_weights, ov, stream);
-    case 2: return convert_q<2>(num_in_pols, num_vis, uvw, weights, v, feed_angle1, feed_angle2, mat, ch, key, out_weights, ov, stream);
-    case 3: return convert_q<3>(num_in_pols, num_vis, uvw, weights, v, feed_angle1, feed_angle2, mat, ch, key, out_weights, ov, stream);
-    default: return convert_q<4>(num_in_pols, num_vis, uvw, weights, v, feed_angle1, feed_angle2, mat, ch, key, out_weights, ov, stream);
-    }
+    kimg_for_pols(num_pols, [&](auto p) {
+        kimg_for_pols(num_in_pols, [&](auto q) {
+            pp_convert_kernel<decltype(p)::value, decltype(q)::value>
+                <<<kimg_divup(num_vis, 256), 256, 0, stream>>>(
+                    num_vis, uvw, weights, v, feed_angle1, feed_angle2, mat, ch, key, out_weights, ov); }); });
+    return kimg_launch_status();
 }
 
 extern "C" size_t kimg_preprocess_workspace_bytes(int64_t num_vis, int num_pols)
@@ -581,18 +537,17 @@ extern "C" int kimg_preprocess_compress(
     }
     KIMG_CHECK_ARG(key && weights && vis && out_uv && out_w_plane && out_weights && out_vis);
     pp_workspace ws;
-    KIMG_HIP(layout_workspace(num_vis, num_pols, static_cast<char *>(workspace), ws));
+    KIMG_HIP(layout_workspace(num_vis, num_pols, workspace, ws));
     if (workspace == nullptr || workspace_bytes < ws.total)
         return KIMG_EWORKSPACE;
     const float2 *v = static_cast<const float2 *>(vis);
     float2 *ov = static_cast<float2 *>(out_vis);
     unsigned long long *c = reinterpret_cast<unsigned long long *>(counts);
-    switch (num_pols) {
-    case 1: return compress_impl<1>(num_vis, w_slices, window, key, weights, v, out_uv, out_w_plane, out_weights, ov, c, ws, stream);
-    case 2: return compress_impl<2>(num_vis, w_slices, window, key, weights, v, out_uv, out_w_plane, out_weights, ov, c, ws, stream);
-    case 3: return compress_impl<3>(num_vis, w_slices, window, key, weights, v, out_uv, out_w_plane, out_weights, ov, c, ws, stream);
-    default: return compress_impl<4>(num_vis, w_slices, window, key, weights, v, out_uv, out_w_plane, out_weights, ov, c, ws, stream);
-    }
+    int rc = 0;
+    kimg_for_pols(num_pols, [&](auto p) {
+        rc = compress_impl<decltype(p)::value>(num_vis, w_slices, window, key, weights, v, out_uv,
+                                               out_w_plane, out_weights, ov, c, ws, stream); });
+    return rc;
 }
 
 extern "C" int kimg_real_to_complex(void *dst, const float *src, int64_t count, void *stream_)

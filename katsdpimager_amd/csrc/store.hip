@@ -22,26 +22,13 @@
 // (the sort is stable), exactly like compress() sums an arrival run (preprocess.cpp:334-372).
 // Gridding, weights and degridding are linear in (vis, weights) for equal coordinates, so the
 // results differ from the unmerged store's only by the order of float additions.
-#include "kimg_common.h"
-#include <hipcub/hipcub.hpp>
+#include "kimg_record_stream.h"
+#include "kimg_window_plan.h"
 
 namespace {
 
-constexpr int WIN = 32;
-
-__host__ __device__ inline int strip_width(int K)
-{
-    const int taps = K > WIN ? (K + 1) / 2 : K;
-    return WIN - taps + 1;              // window slack + 1
-}
-
-inline int bits_for(unsigned values)      // bits needed for 0 .. values - 1
-{
-    int b = 0;
-    while (b < 32 && ((uint64_t) 1 << b) < values)
-        b++;
-    return b;
-}
+// Bits of a key field of `values` values, 0 .. values - 1: none for a field of one value
+inline int bits_for(unsigned values) { return values > 1 ? sort_bits(values - 1) : 0; }
 
 struct key_layout {
     int width;              // columns per strip
@@ -52,7 +39,7 @@ struct key_layout {
 key_layout make_layout(int kernel_width, int oversample, int w_planes, bool merge)
 {
     key_layout k;
-    k.width = strip_width(kernel_width);
+    k.width = window_slack(kernel_width) + 1;
     k.wp_bits = merge ? bits_for((unsigned) w_planes) : 0;
     k.sub_bits = merge ? bits_for((unsigned) oversample) : 0;
     k.in_bits = merge ? bits_for((unsigned) k.width) : 0;
@@ -98,13 +85,7 @@ __global__ __launch_bounds__(256) void store_gather_kernel(
     if (i == 0)
         *count = (unsigned long long) n;
     const int64_t src = index[i];
-    uv_out[i] = uv[src];
-    wp_out[i] = w_plane[src];
-#pragma unroll
-    for (int p = 0; p < P; p++) {
-        w_out[i * P + p] = weights[src * P + p];
-        vis_out[i * P + p] = vis[src * P + p];
-    }
+    copy_record<P, true>(i, src, uv, w_plane, weights, vis, uv_out, wp_out, w_out, vis_out);
 }
 
 // head[i] = 1 when sorted record i starts a run of equal coordinates.  Out-of-range sub-pixel or
@@ -127,6 +108,7 @@ struct head_flag {
             return 1u;
         const unsigned a = index[i - 1], b = index[i];
         const int2 ra = uv[a], rb = uv[b];
+        // (the planes are loaded only where the cells are equal)
         return (ra.x != rb.x || ra.y != rb.y || w_plane[a] != w_plane[b]) ? 1u : 0u;
     }
 };
@@ -168,37 +150,25 @@ __global__ __launch_bounds__(256) void store_merge_kernel(
         }
     }
     const int64_t o = (int64_t) run - 1;
-    uv_out[o] = uv[first];
-    wp_out[o] = w_plane[first];
-#pragma unroll
-    for (int p = 0; p < P; p++) {
-        w_out[o * P + p] = w[p];
-        vis_out[o * P + p] = s[p];
-    }
+    copy_coords(o, first, uv, w_plane, uv_out, wp_out);
+    copy_samples<P, true>(o, 0, w, s, w_out, vis_out);     // (the sums are the one record of w, s)
 }
 
 struct reorder_ws {
-    size_t keys[2], index[2], runs, cub, cub_bytes, total;
+    index_sort<unsigned long long> sort;
+    unsigned *runs;
+    void *cub;
+    size_t cub_bytes, total;
 };
 
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
-hipError_t layout(int64_t n, reorder_ws &ws)
+// (`workspace` null: the size only)
+hipError_t carve(int64_t n, void *workspace, reorder_ws &ws)
 {
-    size_t off = 0;
-    for (int i = 0; i < 2; i++) {
-        ws.keys[i] = off;
-        off += align256((size_t) n * sizeof(unsigned long long));
-        ws.index[i] = off;
-        off += align256((size_t) n * sizeof(unsigned));
-    }
-    ws.runs = off;
-    off += align256((size_t) n * sizeof(unsigned));
-    hipcub::DoubleBuffer<unsigned long long> k(nullptr, nullptr);
-    hipcub::DoubleBuffer<unsigned> v(nullptr, nullptr);
+    ws_carver c(workspace);
+    ws.sort.carve(c, n);
+    ws.runs = c.take<unsigned>((size_t) n);
     size_t sort_bytes = 0, scan_bytes = 0;
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, k, v, (int) n, 0, 64,
-                                                      (hipStream_t) 0);
+    hipError_t e = ws.sort.temp_bytes(n, sort_bytes);
     if (e != hipSuccess)
         return e;
     head_flag hf{nullptr, nullptr, nullptr};
@@ -208,9 +178,8 @@ hipError_t layout(int64_t n, reorder_ws &ws)
     e = hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, heads, (unsigned *) nullptr, (int) n,
                                          (hipStream_t) 0);
     ws.cub_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-    ws.cub = off;
-    off += align256(ws.cub_bytes);
-    ws.total = off;
+    ws.cub = c.take<unsigned char>(ws.cub_bytes);
+    ws.total = c.total();
     return e;
 }
 
@@ -221,7 +190,7 @@ extern "C" size_t kimg_store_reorder_workspace_bytes(int64_t num_vis)
     if (num_vis <= 0 || num_vis >= ((int64_t) 1 << 31))
         return 0;
     reorder_ws ws;
-    if (layout(num_vis, ws) != hipSuccess)
+    if (carve(num_vis, nullptr, ws) != hipSuccess)
         return 0;
     return ws.total;
 }
@@ -243,7 +212,7 @@ extern "C" int kimg_store_reorder(int num_polarizations, int64_t num_vis, int ke
     }
     KIMG_CHECK_ARG(uv && w_plane && weights && vis && out_uv && out_w_plane && out_weights && out_vis);
     reorder_ws ws;
-    hipError_t e = layout(num_vis, ws);
+    hipError_t e = carve(num_vis, workspace, ws);
     if (e != hipSuccess)
         return -(int) e;
     if (workspace == nullptr || workspace_bytes < ws.total)
@@ -251,38 +220,30 @@ extern "C" int kimg_store_reorder(int num_polarizations, int64_t num_vis, int ke
     const key_layout k = make_layout(kernel_width, oversample, w_planes, merge != 0);
     if (k.total_bits > 64)
         return KIMG_EUNSUPPORTED;
-    unsigned char *base = static_cast<unsigned char *>(workspace);
-    hipcub::DoubleBuffer<unsigned long long> keys(
-        reinterpret_cast<unsigned long long *>(base + ws.keys[0]),
-        reinterpret_cast<unsigned long long *>(base + ws.keys[1]));
-    hipcub::DoubleBuffer<unsigned> index(reinterpret_cast<unsigned *>(base + ws.index[0]),
-                                         reinterpret_cast<unsigned *>(base + ws.index[1]));
     const int blocks = kimg_divup(num_vis, 256);
     const int2 *uv2 = reinterpret_cast<const int2 *>(uv);
-    strip_key_kernel<<<blocks, 256, 0, s>>>(uv2, w_plane, num_vis, k, keys.Current(), index.Current());
-    size_t cub_bytes = ws.cub_bytes;
-    KIMG_HIP(hipcub::DeviceRadixSort::SortPairs(base + ws.cub, cub_bytes, keys, index, (int) num_vis,
-                                                0, k.total_bits, s));
+    strip_key_kernel<<<blocks, 256, 0, s>>>(uv2, w_plane, num_vis, k, ws.sort.keys[0], ws.sort.index[0]);
+    const unsigned *index;
+    KIMG_HIP(ws.sort.sort(ws.cub, ws.cub_bytes, num_vis, k.total_bits, s, index));
     int2 *uv_o = reinterpret_cast<int2 *>(out_uv);
     const float2 *vis2 = static_cast<const float2 *>(vis);
     float2 *vis_o = static_cast<float2 *>(out_vis);
     if (!merge) {
         kimg_for_pols(num_polarizations, [&](auto p) {
             store_gather_kernel<decltype(p)::value><<<blocks, 256, 0, s>>>(
-                index.Current(), num_vis, uv2, w_plane, weights, vis2, uv_o, out_w_plane, out_weights,
+                index, num_vis, uv2, w_plane, weights, vis2, uv_o, out_w_plane, out_weights,
                 vis_o, reinterpret_cast<unsigned long long *>(out_count)); });
         return kimg_launch_status();
     }
-    unsigned *runs = reinterpret_cast<unsigned *>(base + ws.runs);
-    head_flag hf{index.Current(), uv2, w_plane};
+    head_flag hf{index, uv2, w_plane};
     hipcub::CountingInputIterator<int64_t> counting(0);
     hipcub::TransformInputIterator<unsigned, head_flag, hipcub::CountingInputIterator<int64_t>> heads(
         counting, hf);
-    cub_bytes = ws.cub_bytes;
-    KIMG_HIP(hipcub::DeviceScan::InclusiveSum(base + ws.cub, cub_bytes, heads, runs, (int) num_vis, s));
+    size_t cub_bytes = ws.cub_bytes;
+    KIMG_HIP(hipcub::DeviceScan::InclusiveSum(ws.cub, cub_bytes, heads, ws.runs, (int) num_vis, s));
     kimg_for_pols(num_polarizations, [&](auto p) {
         store_merge_kernel<decltype(p)::value><<<blocks, 256, 0, s>>>(
-            index.Current(), runs, num_vis, uv2, w_plane, weights, vis2, uv_o, out_w_plane,
+            index, ws.runs, num_vis, uv2, w_plane, weights, vis2, uv_o, out_w_plane,
             out_weights, vis_o, reinterpret_cast<unsigned long long *>(out_count)); });
     return kimg_launch_status();
 }
