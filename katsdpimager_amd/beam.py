@@ -14,6 +14,7 @@ import numpy as np
 
 from . import accel, types
 from ._lib import lib, check
+from .image_plane import ImageTemplate, plane2d_args
 
 
 class _Param(float):
@@ -108,18 +109,6 @@ def beam_covariance_sqrt(beam):
     return Q @ D @ Q.T
 
 
-class FourierBeamTemplate:
-    """beam.py:204-233."""
-
-    def __init__(self, context, dtype, tuning=None):
-        types.require_float32(dtype, 'FourierBeamTemplate')
-        self.context = context
-        self.dtype = np.dtype(dtype)
-
-    def instantiate(self, *args, **kwargs):
-        return FourierBeam(self, *args, **kwargs)
-
-
 class FourierBeam(accel.Operation):
     """beam.py:236-311.  Slot **data**: complex (height, width // 2 + 1), transformed in place.
     ``beam`` must be set before the operation is run."""
@@ -149,9 +138,19 @@ class FourierBeam(accel.Operation):
             raise ValueError('Must set beam')
         amplitude, a, b, c = self.coefficients()
         data = self.buffer('data')
-        check(lib().kimg_fourier_beam(data.ptr, data.shape[1], data.shape[1], data.shape[0],
+        check(lib().kimg_fourier_beam(*plane2d_args(data), data.shape[1], data.shape[0],
                                       amplitude, a, b, c, self.command_queue.handle),
               'kimg_fourier_beam')
+
+
+class FourierBeamTemplate(ImageTemplate):
+    """beam.py:204-233.  One plane: no polarizations."""
+    operator = FourierBeam
+
+    def __init__(self, context, dtype, tuning=None):
+        types.require_float32(dtype, 'FourierBeamTemplate')
+        self.context = context
+        self.dtype = np.dtype(dtype)
 
 
 class _RfftPlan:

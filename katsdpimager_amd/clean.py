@@ -15,6 +15,8 @@ import numpy as np
 
 from . import accel, types
 from ._lib import lib, check
+from .image_plane import (ImageTemplate, border_pixels, check_polarizations, masked_call,
+                          plane_args, plane_pitches, psf_args)
 from .parameters import CLEAN_I, CLEAN_SUMSQ  # noqa: F401
 
 #: median(|x|) -> sigma for a zero-mean Gaussian (clean.py:34)
@@ -52,31 +54,12 @@ def noise_threshold_scale(mode, threshold, num_polarizations):
     raise ValueError('Invalid mode {}'.format(mode))
 
 
-def _image_args(array):
-    P, H, W = array.shape
-    return array.ptr, W, H * W, W, H, P
-
-
-class PsfPatchTemplate:
-    """clean.py:37-69."""
-    def __init__(self, context, dtype, num_polarizations, tuning=None):
-        types.require_float32(dtype, 'PsfPatchTemplate')
-        lib()
-        self.context = context
-        self.num_polarizations = num_polarizations
-        self.dtype = np.dtype(dtype)
-
-    def instantiate(self, *args, **kwargs):
-        return PsfPatch(self, *args, **kwargs)
-
-
 class PsfPatch(accel.Operation):
     """Size of the central PSF box holding every |psf| >= threshold (clean.py:72-163).
     Slots: **psf** [P][H][W]; **bound** int32 [2]."""
 
     def __init__(self, template, command_queue, shape, allocator=None):
-        if shape[0] != template.num_polarizations:
-            raise ValueError('Mismatch in number of polarizations')
+        check_polarizations(template, shape)
         super().__init__(command_queue, allocator)
         self.template = template
         self.slots['psf'] = accel.IOSlot(shape, template.dtype)
@@ -112,23 +95,15 @@ class PsfPatch(accel.Operation):
             min_y = max(min_y, mid_y - hlimit)
             max_x = min(max_x, mid_x + hlimit)
             max_y = min(max_y, mid_y + hlimit)
-        rc = lib().kimg_psf_patch(psf.ptr, W, H * W, P, min_x, min_y, max_x, max_y, mid_x, mid_y,
-                                  threshold, bound.ptr, self.command_queue.handle)
+        rc = lib().kimg_psf_patch(psf.ptr, *plane_pitches(psf), P, min_x, min_y, max_x, max_y,
+                                  mid_x, mid_y, threshold, bound.ptr, self.command_queue.handle)
         check(rc, 'kimg_psf_patch')
         return True
 
 
-class NoiseEstTemplate:
-    """clean.py:206-244."""
-    def __init__(self, context, dtype, num_polarizations, tuning=None):
-        types.require_float32(dtype, 'NoiseEstTemplate')
-        lib()
-        self.context = context
-        self.dtype = np.dtype(dtype)
-        self.num_polarizations = num_polarizations
-
-    def instantiate(self, *args, **kwargs):
-        return NoiseEst(self, *args, **kwargs)
+class PsfPatchTemplate(ImageTemplate):
+    """clean.py:37-69."""
+    operator = PsfPatch
 
 
 class NoiseEst(accel.Operation):
@@ -141,13 +116,10 @@ class NoiseEst(accel.Operation):
     """
 
     def __init__(self, template, command_queue, image_shape, border, allocator=None):
-        if image_shape[0] != template.num_polarizations:
-            raise ValueError('Mismatch in number of polarizations')
-        if border >= 0.5:
-            raise ValueError('Border must be less than half the image size')
+        check_polarizations(template, image_shape)
+        self.border_pixels = border_pixels(border, image_shape)
         super().__init__(command_queue, allocator)
         self.template = template
-        self.border_pixels = round(border * min(image_shape[1], image_shape[2]))
         self.slots['dirty'] = accel.IOSlot(image_shape, template.dtype)
         self.slots['rank'] = accel.IOSlot((256,), np.uint32)
         self._scratch = None
@@ -161,7 +133,7 @@ class NoiseEst(accel.Operation):
         dirty, hist = self.buffer('dirty'), self.buffer('rank')
         prefix = 0
         for p in (3, 2, 1, 0):
-            rc = lib().kimg_abs_histogram(*_image_args(dirty), self.border_pixels, p, prefix,
+            rc = lib().kimg_abs_histogram(*plane_args(dirty), self.border_pixels, p, prefix,
                                           hist.ptr, self.command_queue.handle)
             check(rc, 'kimg_abs_histogram')
             h = hist.get(self.command_queue).astype(np.int64)
@@ -182,7 +154,7 @@ class NoiseEst(accel.Operation):
             self._scratch = accel.DeviceArray(
                 ctx, (lib().kimg_noise_est_scratch_bytes() // 4,), np.uint32, queue=self.command_queue)
             self._result = accel.DeviceArray(ctx, (1,), np.float32, queue=self.command_queue)
-        rc = lib().kimg_noise_est(*_image_args(dirty), self.border_pixels,
+        rc = lib().kimg_noise_est(*plane_args(dirty), self.border_pixels,
                                   float(np.float32(_MEDIAN_TO_RMS)), self._scratch.ptr,
                                   self._result.ptr, self.command_queue.handle)
         check(rc, 'kimg_noise_est')
@@ -201,7 +173,7 @@ class NoiseEst(accel.Operation):
         hi = lo
         if n % 2 == 0:
             out = self.buffer('rank')
-            rc = lib().kimg_abs_count_le(*_image_args(dirty), bp, float(lo), out.ptr,
+            rc = lib().kimg_abs_count_le(*plane_args(dirty), bp, float(lo), out.ptr,
                                          self.command_queue.handle)
             check(rc, 'kimg_abs_count_le')
             res = out.get(self.command_queue)
@@ -211,29 +183,14 @@ class NoiseEst(accel.Operation):
         return median * np.float32(_MEDIAN_TO_RMS)
 
 
-class _CleanStepTemplate:
-    def __init__(self, context, dtype, num_polarizations, tuning=None):
-        types.require_float32(dtype, type(self).__name__)
-        lib()
-        self.context = context
-        self.dtype = np.dtype(dtype)
-        self.num_polarizations = num_polarizations
+class NoiseEstTemplate(ImageTemplate):
+    """clean.py:206-244."""
+    operator = NoiseEst
 
 
 def _tile_shape(image_shape, border_pixels):
     return (accel.divup(image_shape[1] - 2 * border_pixels, TILE),
             accel.divup(image_shape[2] - 2 * border_pixels, TILE))
-
-
-class _UpdateTilesTemplate(_CleanStepTemplate):
-    """clean.py:356-395."""
-    def __init__(self, context, dtype, num_polarizations, mode, tuning=None):
-        super().__init__(context, dtype, num_polarizations, tuning)
-        self.mode = mode
-        self.tilex = self.tiley = TILE
-
-    def instantiate(self, *args, **kwargs):
-        return _UpdateTiles(self, *args, **kwargs)
 
 
 class _UpdateTiles(accel.Operation):
@@ -242,13 +199,10 @@ class _UpdateTiles(accel.Operation):
     optional **mask** uint8 [H][W] (see :class:`Clean`)."""
 
     def __init__(self, template, command_queue, image_shape, border, allocator=None):
-        if image_shape[0] != template.num_polarizations:
-            raise ValueError('Mismatch in number of polarizations')
-        if border >= 0.5:
-            raise ValueError('Border must be less than half the image size')
+        check_polarizations(template, image_shape)
+        self.border_pixels = border_pixels(border, image_shape)
         super().__init__(command_queue, allocator)
         self.template = template
-        self.border_pixels = round(border * min(image_shape[1], image_shape[2]))
         ty, tx = _tile_shape(image_shape, self.border_pixels)
         self.slots['dirty'] = accel.IOSlot(image_shape, template.dtype)
         self.slots['tile_max'] = accel.IOSlot((ty, tx), template.dtype)
@@ -268,26 +222,21 @@ class _UpdateTiles(accel.Operation):
         y0 = max((y0 - bp) // TILE, 0)
         x1 = min(accel.divup(x1 - bp, TILE), tile_max.shape[1])
         y1 = min(accel.divup(y1 - bp, TILE), tile_max.shape[0])
-        mask = self.buffer('mask')
-        if x0 < x1 and y0 < y1 and mask is not None:
-            mask.used_on(self.command_queue)
-            rc = lib().kimg_update_tiles_masked(
-                *_image_args(self.buffer('dirty')), bp, self.template.mode,
-                tile_max.ptr, tile_pos.ptr, tile_max.shape[1], tile_max.shape[0],
-                x0, y0, x1, y1, self.command_queue.handle, mask.ptr, mask.shape[1])
-            check(rc, 'kimg_update_tiles_masked')
-        elif x0 < x1 and y0 < y1:
-            rc = lib().kimg_update_tiles(
-                *_image_args(self.buffer('dirty')), bp, self.template.mode,
-                tile_max.ptr, tile_pos.ptr, tile_max.shape[1], tile_max.shape[0],
-                x0, y0, x1, y1, self.command_queue.handle)
-            check(rc, 'kimg_update_tiles')
+        if x0 < x1 and y0 < y1:
+            masked_call('kimg_update_tiles', self.buffer('mask'), self.command_queue,
+                        *plane_args(self.buffer('dirty')), bp, self.template.mode,
+                        tile_max.ptr, tile_pos.ptr, tile_max.shape[1], tile_max.shape[0],
+                        x0, y0, x1, y1, self.command_queue.handle)
 
 
-class _FindPeakTemplate(_CleanStepTemplate):
-    """clean.py:483-513."""
-    def instantiate(self, *args, **kwargs):
-        return _FindPeak(self, *args, **kwargs)
+class _UpdateTilesTemplate(ImageTemplate):
+    """clean.py:356-395."""
+    operator = _UpdateTiles
+
+    def __init__(self, context, dtype, num_polarizations, mode, tuning=None):
+        super().__init__(context, dtype, num_polarizations, tuning)
+        self.mode = mode
+        self.tilex = self.tiley = TILE
 
 
 class _FindPeak(accel.Operation):
@@ -295,8 +244,7 @@ class _FindPeak(accel.Operation):
     bound, a best metric of exactly 0 is reported as position (-1, -1): no allowed pixel is left."""
 
     def __init__(self, template, command_queue, image_shape, tile_shape, allocator=None):
-        if image_shape[0] != template.num_polarizations:
-            raise ValueError('Mismatch in number of polarizations')
+        check_polarizations(template, image_shape)
         super().__init__(command_queue, allocator)
         self.template = template
         pair = accel.Dimension(2, exact=True)
@@ -311,29 +259,16 @@ class _FindPeak(accel.Operation):
     def _run(self):
         dirty = self.buffer('dirty')
         tile_max = self.buffer('tile_max')
-        P, H, W = dirty.shape
-        mask = self.buffer('mask')
-        if mask is not None:
-            mask.used_on(self.command_queue)
-            rc = lib().kimg_find_peak_masked(
-                dirty.ptr, W, H * W, P, tile_max.ptr, self.buffer('tile_pos').ptr,
-                tile_max.shape[1], tile_max.shape[0], self.buffer('peak_value').ptr,
-                self.buffer('peak_pos').ptr, self.buffer('peak_pixel').ptr,
-                self.command_queue.handle, mask.ptr, mask.shape[1])
-            check(rc, 'kimg_find_peak_masked')
-            return
-        rc = lib().kimg_find_peak(
-            dirty.ptr, W, H * W, P, tile_max.ptr, self.buffer('tile_pos').ptr,
-            tile_max.shape[1], tile_max.shape[0], self.buffer('peak_value').ptr,
-            self.buffer('peak_pos').ptr, self.buffer('peak_pixel').ptr,
-            self.command_queue.handle)
-        check(rc, 'kimg_find_peak')
+        masked_call('kimg_find_peak', self.buffer('mask'), self.command_queue,
+                    dirty.ptr, *plane_pitches(dirty), dirty.shape[0], tile_max.ptr,
+                    self.buffer('tile_pos').ptr, tile_max.shape[1], tile_max.shape[0],
+                    self.buffer('peak_value').ptr, self.buffer('peak_pos').ptr,
+                    self.buffer('peak_pixel').ptr, self.command_queue.handle)
 
 
-class _SubtractPsfTemplate(_CleanStepTemplate):
-    """clean.py:590-622."""
-    def instantiate(self, *args, **kwargs):
-        return _SubtractPsf(self, *args, **kwargs)
+class _FindPeakTemplate(ImageTemplate):
+    """clean.py:483-513."""
+    operator = _FindPeak
 
 
 class _SubtractPsf(accel.Operation):
@@ -343,10 +278,7 @@ class _SubtractPsf(accel.Operation):
     def __init__(self, template, command_queue, loop_gain, image_shape, psf_shape,
                  allocator=None):
         super().__init__(command_queue, allocator)
-        if image_shape[0] != template.num_polarizations:
-            raise ValueError('Mismatch in number of polarizations')
-        if psf_shape[0] != template.num_polarizations:
-            raise ValueError('Mismatch in number of polarizations')
+        check_polarizations(template, image_shape, psf_shape)
         self.slots['dirty'] = accel.IOSlot(image_shape, template.dtype)
         self.slots['model'] = accel.IOSlot(image_shape, template.dtype)
         self.slots['psf'] = accel.IOSlot(psf_shape, template.dtype)
@@ -360,14 +292,18 @@ class _SubtractPsf(accel.Operation):
     def __call__(self, pos, psf_patch, **kwargs):
         self.bind(**kwargs)
         self.ensure_all_bound()
-        dirty, psf = self.buffer('dirty'), self.buffer('psf')
-        P, H, W = dirty.shape
+        dirty = self.buffer('dirty')
         rc = lib().kimg_subtract_psf(
-            dirty.ptr, self.buffer('model').ptr, W, H * W, W, H, P,
-            psf.ptr, psf.shape[2], psf.shape[1] * psf.shape[2], psf.shape[2], psf.shape[1],
+            dirty.ptr, self.buffer('model').ptr, *plane_args(dirty)[1:],
+            *psf_args(self.buffer('psf')),
             psf_patch[2], psf_patch[1], self.buffer('peak_pixel').ptr,
             pos[1], pos[0], self.loop_gain, self.command_queue.handle)
         check(rc, 'kimg_subtract_psf')
+
+
+class _SubtractPsfTemplate(ImageTemplate):
+    """clean.py:590-622."""
+    operator = _SubtractPsf
 
 
 # KIMG_CLEAN_FORM_* ('persistent' and 'one_workgroup' are retired: they run as 'one_launch')
@@ -500,31 +436,17 @@ class Clean(accel.OperationSequence):
         self.ensure_all_bound()
         if max_cycles <= 0:
             return []
-        dirty, psf = self.buffer('dirty'), self.buffer('psf')
-        P, H, W = dirty.shape
+        dirty = self.buffer('dirty')
         cp = self.template.clean_parameters
         self._ensure_log(max_cycles)
         tile_max = self.buffer('tile_max')
-        mask = self.buffer('mask')
-        if mask is not None:
-            mask.used_on(self.command_queue)
-            rc = lib().kimg_clean_cycles_masked(
-                dirty.ptr, self.buffer('model').ptr, W, H * W, W, H, P,
-                psf.ptr, psf.shape[2], psf.shape[1] * psf.shape[2], psf.shape[2], psf.shape[1],
-                psf_patch[2], psf_patch[1], self._update_tiles.border_pixels, cp.mode,
-                cp.loop_gain, threshold, tile_max.ptr, self.buffer('tile_pos').ptr,
-                tile_max.shape[1], tile_max.shape[0], max_cycles, self.template.form,
-                self._state.ptr, self._log.ptr, self.command_queue.handle, mask.ptr, mask.shape[1])
-            check(rc, 'kimg_clean_cycles_masked')
-            return self._collect_cycles() if collect else None
-        rc = lib().kimg_clean_cycles(
-            dirty.ptr, self.buffer('model').ptr, W, H * W, W, H, P,
-            psf.ptr, psf.shape[2], psf.shape[1] * psf.shape[2], psf.shape[2], psf.shape[1],
-            psf_patch[2], psf_patch[1], self._update_tiles.border_pixels, cp.mode,
-            cp.loop_gain, threshold, tile_max.ptr, self.buffer('tile_pos').ptr,
-            tile_max.shape[1], tile_max.shape[0], max_cycles, self.template.form,
-            self._state.ptr, self._log.ptr, self.command_queue.handle)
-        check(rc, 'kimg_clean_cycles')
+        masked_call('kimg_clean_cycles', self.buffer('mask'), self.command_queue,
+                    dirty.ptr, self.buffer('model').ptr, *plane_args(dirty)[1:],
+                    *psf_args(self.buffer('psf')),
+                    psf_patch[2], psf_patch[1], self._update_tiles.border_pixels, cp.mode,
+                    cp.loop_gain, threshold, tile_max.ptr, self.buffer('tile_pos').ptr,
+                    tile_max.shape[1], tile_max.shape[0], max_cycles, self.template.form,
+                    self._state.ptr, self._log.ptr, self.command_queue.handle)
         return self._collect_cycles() if collect else None
 
     def run_major_cycles(self, psf_patch, noise_threshold, left_for_next, max_cycles):
@@ -544,15 +466,14 @@ class Clean(accel.OperationSequence):
             return False
         if self.buffer('mask') is not None:     # (the multi-component form has no masked kernels)
             return False
-        dirty, psf = self.buffer('dirty'), self.buffer('psf')
-        P, H, W = dirty.shape
+        dirty = self.buffer('dirty')
         cp = self.template.clean_parameters
         self._ensure_log(max_cycles)
         tile_max = self.buffer('tile_max')
         done, first = ctypes.c_int(0), ctypes.c_float(0.0)
         rc = lib().kimg_clean_major_cycles(
-            dirty.ptr, self.buffer('model').ptr, W, H * W, W, H, P,
-            psf.ptr, psf.shape[2], psf.shape[1] * psf.shape[2], psf.shape[2], psf.shape[1],
+            dirty.ptr, self.buffer('model').ptr, *plane_args(dirty)[1:],
+            *psf_args(self.buffer('psf')),
             psf_patch[2], psf_patch[1], self._update_tiles.border_pixels, cp.mode,
             cp.loop_gain, float(noise_threshold), float(left_for_next), tile_max.ptr,
             self.buffer('tile_pos').ptr, tile_max.shape[1], tile_max.shape[0], max_cycles,
@@ -748,11 +669,10 @@ def enqueue_cycles_batch(cleans, psf_patches, thresholds, max_cycles, command_qu
             q.stream.wait_event(ev)
     first = cleans[0]
     dirty, psf, tile_max = first.buffer('dirty'), first.buffer('psf'), first.buffer('tile_max')
-    P, H, W = dirty.shape
     cp = first.template.clean_parameters
     rc = lib().kimg_clean_cycles_batch(
-        table, len(cleans), W, H * W, W, H, P, psf.shape[2], psf.shape[1] * psf.shape[2],
-        psf.shape[2], psf.shape[1], first._update_tiles.border_pixels, cp.mode, cp.loop_gain,
+        table, len(cleans), *plane_args(dirty)[1:], *psf_args(psf)[1:],
+        first._update_tiles.border_pixels, cp.mode, cp.loop_gain,
         tile_max.shape[1], tile_max.shape[0], q.handle)
     check(rc, 'kimg_clean_cycles_batch')
     return q

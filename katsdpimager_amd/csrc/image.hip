@@ -249,18 +249,110 @@ __global__ __launch_bounds__(256) void apply_primary_beam_kernel(
         image[addr] = beam < threshold ? replacement : image[addr] / beam;
 }
 
+// One thread per pixel of a row, one row of blocks per row: what every launch below but the
+// reductions at the end of the file looks like.
+template <typename... Params, typename... Args>
+int launch_rows(void (*kernel)(Params...), int width, int height, void *stream, Args... args)
+{
+    kernel<<<dim3(kimg_divup(width, 256), height), 256, 0, (hipStream_t) stream>>>(args...);
+    return kimg_launch_status();
+}
+
+// The checks and the launch of the operations that exist in both precisions: T = float behind the
+// plain name, double behind *_f64 (the reference's --precision double; always the plain route:
+// the own transforms of transform.hip and the w = 0 real route of this file are float32 only).
+template <typename T>
+int grid_to_layer_call(void *layer, int layer_size, const void *grid, int64_t grid_row_stride,
+                       int grid_size, void *stream)
+{
+    KIMG_CHECK_ARG(layer && grid && layer_size > 0 && grid_size > 0 && grid_size <= layer_size);
+    KIMG_CHECK_ARG(layer_size % 2 == 0 && grid_size % 2 == 0 && grid_row_stride >= grid_size);
+    return launch_rows(grid_to_layer_kernel<T>, layer_size, layer_size, stream, (cplx<T> *) layer,
+                       layer_size, (const cplx<T> *) grid, grid_row_stride, grid_size);
+}
+
+template <typename T>
+int layer_to_grid_call(void *grid, int64_t grid_row_stride, int grid_size, const void *layer,
+                       int layer_size, void *stream)
+{
+    KIMG_CHECK_ARG(layer && grid && layer_size > 0 && grid_size > 0 && grid_size <= layer_size);
+    KIMG_CHECK_ARG(layer_size % 2 == 0 && grid_size % 2 == 0 && grid_row_stride >= grid_size);
+    return launch_rows(layer_to_grid_kernel<T>, grid_size, grid_size, stream, (cplx<T> *) grid,
+                       grid_row_stride, grid_size, (const cplx<T> *) layer, layer_size);
+}
+
+template <typename T>
+int layer_to_image_call(T *image, int64_t image_row_stride, const void *layer, int size,
+                        const T *kernel1d, T lm_scale, T lm_bias, T w, void *stream)
+{
+    KIMG_CHECK_ARG(image && layer && kernel1d && size > 0 && size % 2 == 0
+                   && image_row_stride >= size);
+    return launch_rows(layer_to_image_kernel<T>, size, size, stream, image, image_row_stride,
+                       (const cplx<T> *) layer, size, kernel1d, lm_scale, lm_bias, w);
+}
+
+template <typename T>
+int image_to_layer_call(void *layer, const T *image, int64_t image_row_stride, int size,
+                        const T *kernel1d, T lm_scale, T lm_bias, T w, void *stream)
+{
+    KIMG_CHECK_ARG(image && layer && kernel1d && size > 0 && size % 2 == 0
+                   && image_row_stride >= size);
+    return launch_rows(image_to_layer_kernel<T>, size, size, stream, (cplx<T> *) layer, image,
+                       image_row_stride, size, kernel1d, lm_scale, lm_bias, w);
+}
+
+// (P outside 1..4: KIMG_EUNSUPPORTED here, the factors travel in a scale_t; add_image and
+// apply_primary_beam loop over P, refuse P <= 0 with KIMG_EINVAL and take any P above)
+template <typename T>
+int scale_call(T *image, int64_t row_stride, int64_t pol_stride, int width, int height,
+               int num_polarizations, const T *scale_host, void *stream)
+{
+    KIMG_CHECK_ARG(image && scale_host && width > 0 && height > 0);
+    KIMG_CHECK_ARG(row_stride >= width);
+    if (num_polarizations < 1 || num_polarizations > 4)
+        return KIMG_EUNSUPPORTED;
+    scale_t<T> sc = {};
+    for (int p = 0; p < num_polarizations; p++)
+        sc.v[p] = scale_host[p];
+    return launch_rows(scale_kernel<T>, width, height, stream, image, row_stride, pol_stride,
+                       width, num_polarizations, sc);
+}
+
+template <typename T>
+int add_image_call(T *dest, int64_t dest_row_stride, int64_t dest_pol_stride, const T *src,
+                   int64_t src_row_stride, int64_t src_pol_stride, int width, int height,
+                   int num_polarizations, void *stream)
+{
+    KIMG_CHECK_ARG(dest && src && width > 0 && height > 0 && num_polarizations > 0);
+    KIMG_CHECK_ARG(dest_row_stride >= width && src_row_stride >= width);
+    return launch_rows(add_image_kernel<T>, width, height, stream, dest, dest_row_stride,
+                       dest_pol_stride, src, src_row_stride, src_pol_stride, width,
+                       num_polarizations);
+}
+
+template <typename T>
+int apply_primary_beam_call(T *image, int64_t row_stride, int64_t pol_stride, const T *beam_power,
+                            int64_t beam_row_stride, int width, int height,
+                            int num_polarizations, T threshold, T replacement, void *stream)
+{
+    KIMG_CHECK_ARG(image && beam_power && width > 0 && height > 0 && num_polarizations > 0);
+    KIMG_CHECK_ARG(row_stride >= width && beam_row_stride >= width);
+    return launch_rows(apply_primary_beam_kernel<T>, width, height, stream, image, row_stride,
+                       pol_stride, beam_power, beam_row_stride, width, num_polarizations,
+                       threshold, replacement);
+}
+
 } // namespace
 
 extern "C" int kimg_grid_to_layer(void *layer, int layer_size, const void *grid,
                                   int64_t grid_row_stride, int grid_size, void *stream)
 {
-    KIMG_CHECK_ARG(layer && grid && layer_size > 0 && grid_size > 0 && grid_size <= layer_size);
-    KIMG_CHECK_ARG(layer_size % 2 == 0 && grid_size % 2 == 0);      // image.py:655-656
-    KIMG_CHECK_ARG(grid_row_stride >= grid_size);
-    dim3 g(kimg_divup(layer_size, 256), layer_size);
-    grid_to_layer_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
-        (float2 *) layer, layer_size, (const float2 *) grid, grid_row_stride, grid_size);
-    return kimg_launch_status();
+    return grid_to_layer_call<float>(layer, layer_size, grid, grid_row_stride, grid_size, stream);
+}
+extern "C" int kimg_grid_to_layer_f64(void *layer, int layer_size, const void *grid,
+                                      int64_t grid_row_stride, int grid_size, void *stream)
+{
+    return grid_to_layer_call<double>(layer, layer_size, grid, grid_row_stride, grid_size, stream);
 }
 
 extern "C" int kimg_grid_to_half_layer(void *half_layer, int layer_size, const void *grid,
@@ -268,11 +360,9 @@ extern "C" int kimg_grid_to_half_layer(void *half_layer, int layer_size, const v
 {
     KIMG_CHECK_ARG(half_layer && grid && layer_size > 0 && layer_size % 2 == 0 && grid_size > 0
                    && grid_size % 2 == 0 && grid_size <= layer_size && grid_row_stride >= grid_size);
-    const dim3 blocks(kimg_divup(layer_size / 2 + 1, 256), layer_size);
-    grid_to_half_layer_kernel<<<blocks, 256, 0, (hipStream_t) stream>>>(
-        static_cast<float2 *>(half_layer), layer_size, static_cast<const float2 *>(grid),
-        grid_row_stride, grid_size);
-    return kimg_launch_status();
+    return launch_rows(grid_to_half_layer_kernel, layer_size / 2 + 1, layer_size, stream,
+                       static_cast<float2 *>(half_layer), layer_size,
+                       static_cast<const float2 *>(grid), grid_row_stride, grid_size);
 }
 
 extern "C" int kimg_real_layer_to_image(float *image, int64_t image_row_stride, const float *layer,
@@ -281,10 +371,8 @@ extern "C" int kimg_real_layer_to_image(float *image, int64_t image_row_stride, 
 {
     KIMG_CHECK_ARG(image && layer && kernel1d && size > 0 && size % 2 == 0
                    && image_row_stride >= size && layer_row_stride >= size);
-    const dim3 blocks(kimg_divup(size, 256), size);
-    real_layer_to_image_kernel<<<blocks, 256, 0, (hipStream_t) stream>>>(
-        image, image_row_stride, layer, layer_row_stride, size, kernel1d, lm_scale, lm_bias);
-    return kimg_launch_status();
+    return launch_rows(real_layer_to_image_kernel, size, size, stream, image, image_row_stride,
+                       layer, layer_row_stride, size, kernel1d, lm_scale, lm_bias);
 }
 
 extern "C" int kimg_image_to_real_layer(float *layer, int64_t layer_row_stride, const float *image,
@@ -293,10 +381,8 @@ extern "C" int kimg_image_to_real_layer(float *layer, int64_t layer_row_stride, 
 {
     KIMG_CHECK_ARG(image && layer && kernel1d && size > 0 && size % 2 == 0
                    && image_row_stride >= size && layer_row_stride >= size);
-    const dim3 blocks(kimg_divup(size, 256), size);
-    image_to_real_layer_kernel<<<blocks, 256, 0, (hipStream_t) stream>>>(
-        layer, layer_row_stride, image, image_row_stride, size, kernel1d, lm_scale, lm_bias);
-    return kimg_launch_status();
+    return launch_rows(image_to_real_layer_kernel, size, size, stream, layer, layer_row_stride,
+                       image, image_row_stride, size, kernel1d, lm_scale, lm_bias);
 }
 
 extern "C" int kimg_half_layer_to_grid(void *grid, int64_t grid_row_stride, int grid_size,
@@ -304,62 +390,64 @@ extern "C" int kimg_half_layer_to_grid(void *grid, int64_t grid_row_stride, int 
 {
     KIMG_CHECK_ARG(half_layer && grid && layer_size > 0 && layer_size % 2 == 0 && grid_size > 0
                    && grid_size % 2 == 0 && grid_size <= layer_size && grid_row_stride >= grid_size);
-    const dim3 blocks(kimg_divup(grid_size, 256), grid_size);
-    half_layer_to_grid_kernel<<<blocks, 256, 0, (hipStream_t) stream>>>(
-        static_cast<float2 *>(grid), grid_row_stride, grid_size,
-        static_cast<const float2 *>(half_layer), layer_size);
-    return kimg_launch_status();
+    return launch_rows(half_layer_to_grid_kernel, grid_size, grid_size, stream,
+                       static_cast<float2 *>(grid), grid_row_stride, grid_size,
+                       static_cast<const float2 *>(half_layer), layer_size);
 }
 
 extern "C" int kimg_layer_to_grid(void *grid, int64_t grid_row_stride, int grid_size,
                                   const void *layer, int layer_size, void *stream)
 {
-    KIMG_CHECK_ARG(layer && grid && layer_size > 0 && grid_size > 0 && grid_size <= layer_size);
-    KIMG_CHECK_ARG(layer_size % 2 == 0 && grid_size % 2 == 0 && grid_row_stride >= grid_size);
-    dim3 g(kimg_divup(grid_size, 256), grid_size);
-    layer_to_grid_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
-        (float2 *) grid, grid_row_stride, grid_size, (const float2 *) layer, layer_size);
-    return kimg_launch_status();
+    return layer_to_grid_call<float>(grid, grid_row_stride, grid_size, layer, layer_size, stream);
+}
+extern "C" int kimg_layer_to_grid_f64(void *grid, int64_t grid_row_stride, int grid_size,
+                                      const void *layer, int layer_size, void *stream)
+{
+    return layer_to_grid_call<double>(grid, grid_row_stride, grid_size, layer, layer_size, stream);
 }
 
 extern "C" int kimg_layer_to_image(float *image, int64_t image_row_stride, const void *layer,
                                    int size, const float *kernel1d, float lm_scale,
                                    float lm_bias, float w, void *stream)
 {
-    KIMG_CHECK_ARG(image && layer && kernel1d && size > 0 && size % 2 == 0);   // image.py:127-128
-    KIMG_CHECK_ARG(image_row_stride >= size);
-    dim3 g(kimg_divup(size, 256), size);
-    layer_to_image_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
-        image, image_row_stride, (const float2 *) layer, size, kernel1d, lm_scale, lm_bias, w);
-    return kimg_launch_status();
+    return layer_to_image_call<float>(image, image_row_stride, layer, size, kernel1d, lm_scale,
+                                      lm_bias, w, stream);
+}
+extern "C" int kimg_layer_to_image_f64(double *image, int64_t image_row_stride, const void *layer,
+                                       int size, const double *kernel1d, double lm_scale,
+                                       double lm_bias, double w, void *stream)
+{
+    return layer_to_image_call<double>(image, image_row_stride, layer, size, kernel1d, lm_scale,
+                                       lm_bias, w, stream);
 }
 
 extern "C" int kimg_image_to_layer(void *layer, const float *image, int64_t image_row_stride,
                                    int size, const float *kernel1d, float lm_scale,
                                    float lm_bias, float w, void *stream)
 {
-    KIMG_CHECK_ARG(image && layer && kernel1d && size > 0 && size % 2 == 0
-                   && image_row_stride >= size);
-    dim3 g(kimg_divup(size, 256), size);
-    image_to_layer_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
-        (float2 *) layer, image, image_row_stride, size, kernel1d, lm_scale, lm_bias, w);
-    return kimg_launch_status();
+    return image_to_layer_call<float>(layer, image, image_row_stride, size, kernel1d, lm_scale,
+                                      lm_bias, w, stream);
+}
+extern "C" int kimg_image_to_layer_f64(void *layer, const double *image, int64_t image_row_stride,
+                                       int size, const double *kernel1d, double lm_scale,
+                                       double lm_bias, double w, void *stream)
+{
+    return image_to_layer_call<double>(layer, image, image_row_stride, size, kernel1d, lm_scale,
+                                       lm_bias, w, stream);
 }
 
 extern "C" int kimg_scale(float *image, int64_t row_stride, int64_t pol_stride, int width,
                           int height, int num_polarizations, const float *scale_host, void *stream)
 {
-    KIMG_CHECK_ARG(image && scale_host && width > 0 && height > 0);
-    KIMG_CHECK_ARG(row_stride >= width);
-    if (num_polarizations < 1 || num_polarizations > 4)
-        return KIMG_EUNSUPPORTED;
-    scale_t<float> sc = {};
-    for (int p = 0; p < num_polarizations; p++)
-        sc.v[p] = scale_host[p];
-    dim3 g(kimg_divup(width, 256), height);
-    scale_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(image, row_stride, pol_stride, width,
-                                                             num_polarizations, sc);
-    return kimg_launch_status();
+    return scale_call<float>(image, row_stride, pol_stride, width, height, num_polarizations,
+                             scale_host, stream);
+}
+extern "C" int kimg_scale_f64(double *image, int64_t row_stride, int64_t pol_stride, int width,
+                              int height, int num_polarizations, const double *scale_host,
+                              void *stream)
+{
+    return scale_call<double>(image, row_stride, pol_stride, width, height, num_polarizations,
+                              scale_host, stream);
 }
 
 extern "C" int kimg_pixel_reciprocal(const float *image, int64_t row_stride, int64_t pol_stride,
@@ -382,23 +470,24 @@ extern "C" int kimg_scale_device(float *image, int64_t row_stride, int64_t pol_s
     KIMG_CHECK_ARG(row_stride >= width);
     if (num_polarizations < 1 || num_polarizations > 4)
         return KIMG_EUNSUPPORTED;
-    dim3 g(kimg_divup(width, 256), height);
-    scale_device_kernel<<<g, 256, 0, (hipStream_t) stream>>>(image, row_stride, pol_stride, width,
-                                                             num_polarizations, scale);
-    return kimg_launch_status();
+    return launch_rows(scale_device_kernel, width, height, stream, image, row_stride, pol_stride,
+                       width, num_polarizations, scale);
 }
 
 extern "C" int kimg_add_image(float *dest, int64_t dest_row_stride, int64_t dest_pol_stride,
                               const float *src, int64_t src_row_stride, int64_t src_pol_stride,
                               int width, int height, int num_polarizations, void *stream)
 {
-    KIMG_CHECK_ARG(dest && src && width > 0 && height > 0 && num_polarizations > 0);
-    KIMG_CHECK_ARG(dest_row_stride >= width && src_row_stride >= width);
-    dim3 g(kimg_divup(width, 256), height);
-    add_image_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
-        dest, dest_row_stride, dest_pol_stride, src, src_row_stride, src_pol_stride, width,
-        num_polarizations);
-    return kimg_launch_status();
+    return add_image_call<float>(dest, dest_row_stride, dest_pol_stride, src, src_row_stride,
+                                 src_pol_stride, width, height, num_polarizations, stream);
+}
+extern "C" int kimg_add_image_f64(double *dest, int64_t dest_row_stride, int64_t dest_pol_stride,
+                                  const double *src, int64_t src_row_stride,
+                                  int64_t src_pol_stride, int width, int height,
+                                  int num_polarizations, void *stream)
+{
+    return add_image_call<double>(dest, dest_row_stride, dest_pol_stride, src, src_row_stride,
+                                  src_pol_stride, width, height, num_polarizations, stream);
 }
 
 extern "C" int kimg_apply_primary_beam(float *image, int64_t row_stride, int64_t pol_stride,
@@ -406,108 +495,18 @@ extern "C" int kimg_apply_primary_beam(float *image, int64_t row_stride, int64_t
                                        int width, int height, int num_polarizations,
                                        float threshold, float replacement, void *stream)
 {
-    KIMG_CHECK_ARG(image && beam_power && width > 0 && height > 0 && num_polarizations > 0);
-    KIMG_CHECK_ARG(row_stride >= width && beam_row_stride >= width);
-    dim3 g(kimg_divup(width, 256), height);
-    apply_primary_beam_kernel<float><<<g, 256, 0, (hipStream_t) stream>>>(
-        image, row_stride, pol_stride, beam_power, beam_row_stride, width, num_polarizations,
-        threshold, replacement);
-    return kimg_launch_status();
+    return apply_primary_beam_call<float>(image, row_stride, pol_stride, beam_power,
+                                          beam_row_stride, width, height, num_polarizations,
+                                          threshold, replacement, stream);
 }
-
-// ---- float64 (the reference's --precision double): the same plain kernels on complex128 /
-// float64 arrays; the phase comes from double sincospi after the same range reduction.
-// Float64 always takes the plain route (copy, C2C transform, layer -> image): the library's own
-// transforms (transform.hip) and the w = 0 real route of this file are float32 only.
-extern "C" int kimg_grid_to_layer_f64(void *layer, int layer_size, const void *grid,
-                                      int64_t grid_row_stride, int grid_size, void *stream)
-{
-    KIMG_CHECK_ARG(layer && grid && layer_size > 0 && grid_size > 0 && grid_size <= layer_size);
-    KIMG_CHECK_ARG(layer_size % 2 == 0 && grid_size % 2 == 0 && grid_row_stride >= grid_size);
-    const dim3 g(kimg_divup(layer_size, 256), layer_size);
-    grid_to_layer_kernel<double><<<g, 256, 0, (hipStream_t) stream>>>(
-        (double2 *) layer, layer_size, (const double2 *) grid, grid_row_stride, grid_size);
-    return kimg_launch_status();
-}
-
-extern "C" int kimg_layer_to_grid_f64(void *grid, int64_t grid_row_stride, int grid_size,
-                                      const void *layer, int layer_size, void *stream)
-{
-    KIMG_CHECK_ARG(layer && grid && layer_size > 0 && grid_size > 0 && grid_size <= layer_size);
-    KIMG_CHECK_ARG(layer_size % 2 == 0 && grid_size % 2 == 0 && grid_row_stride >= grid_size);
-    const dim3 g(kimg_divup(grid_size, 256), grid_size);
-    layer_to_grid_kernel<double><<<g, 256, 0, (hipStream_t) stream>>>(
-        (double2 *) grid, grid_row_stride, grid_size, (const double2 *) layer, layer_size);
-    return kimg_launch_status();
-}
-
-extern "C" int kimg_layer_to_image_f64(double *image, int64_t image_row_stride, const void *layer,
-                                       int size, const double *kernel1d, double lm_scale,
-                                       double lm_bias, double w, void *stream)
-{
-    KIMG_CHECK_ARG(image && layer && kernel1d && size > 0 && size % 2 == 0
-                   && image_row_stride >= size);
-    const dim3 g(kimg_divup(size, 256), size);
-    layer_to_image_kernel<double><<<g, 256, 0, (hipStream_t) stream>>>(
-        image, image_row_stride, (const double2 *) layer, size, kernel1d, lm_scale, lm_bias, w);
-    return kimg_launch_status();
-}
-
-extern "C" int kimg_image_to_layer_f64(void *layer, const double *image, int64_t image_row_stride,
-                                       int size, const double *kernel1d, double lm_scale,
-                                       double lm_bias, double w, void *stream)
-{
-    KIMG_CHECK_ARG(image && layer && kernel1d && size > 0 && size % 2 == 0
-                   && image_row_stride >= size);
-    const dim3 g(kimg_divup(size, 256), size);
-    image_to_layer_kernel<double><<<g, 256, 0, (hipStream_t) stream>>>(
-        (double2 *) layer, image, image_row_stride, size, kernel1d, lm_scale, lm_bias, w);
-    return kimg_launch_status();
-}
-
-extern "C" int kimg_scale_f64(double *image, int64_t row_stride, int64_t pol_stride, int width,
-                              int height, int num_polarizations, const double *scale_host,
-                              void *stream)
-{
-    KIMG_CHECK_ARG(image && scale_host && width > 0 && height > 0);
-    KIMG_CHECK_ARG(row_stride >= width);
-    if (num_polarizations < 1 || num_polarizations > 4)
-        return KIMG_EUNSUPPORTED;
-    scale_t<double> sc = {};
-    for (int p = 0; p < num_polarizations; p++)
-        sc.v[p] = scale_host[p];
-    const dim3 g(kimg_divup(width, 256), height);
-    scale_kernel<double><<<g, 256, 0, (hipStream_t) stream>>>(image, row_stride, pol_stride, width,
-                                                              num_polarizations, sc);
-    return kimg_launch_status();
-}
-
-extern "C" int kimg_add_image_f64(double *dest, int64_t dest_row_stride, int64_t dest_pol_stride,
-                                  const double *src, int64_t src_row_stride,
-                                  int64_t src_pol_stride, int width, int height,
-                                  int num_polarizations, void *stream)
-{
-    KIMG_CHECK_ARG(dest && src && width > 0 && height > 0 && num_polarizations > 0);
-    KIMG_CHECK_ARG(dest_row_stride >= width && src_row_stride >= width);
-    const dim3 g(kimg_divup(width, 256), height);
-    add_image_kernel<double><<<g, 256, 0, (hipStream_t) stream>>>(
-        dest, dest_row_stride, dest_pol_stride, src, src_row_stride, src_pol_stride, width,
-        num_polarizations);
-    return kimg_launch_status();
-}
-
 extern "C" int kimg_apply_primary_beam_f64(double *image, int64_t row_stride, int64_t pol_stride,
                                            const double *beam_power, int64_t beam_row_stride,
                                            int width, int height, int num_polarizations,
                                            double threshold, double replacement, void *stream)
 {
-    KIMG_CHECK_ARG(image && beam_power && width > 0 && height > 0 && num_polarizations > 0);
-    KIMG_CHECK_ARG(row_stride >= width && beam_row_stride >= width);
-    const dim3 g(kimg_divup(width, 256), height);
-    apply_primary_beam_kernel<double><<<g, 256, 0, (hipStream_t) stream>>>(
-        image, row_stride, pol_stride, beam_power, beam_row_stride, width, num_polarizations,
-        threshold, replacement);
-    return kimg_launch_status();
+    return apply_primary_beam_call<double>(image, row_stride, pol_stride, beam_power,
+                                           beam_row_stride, width, height, num_polarizations,
+                                           threshold, replacement, stream);
 }
 
 // ---- restoring beam in the Fourier domain: beam.py:283-311 + fourier_beam.mako ----------
@@ -539,10 +538,8 @@ extern "C" int kimg_fourier_beam(void *data, int64_t row_stride, int width, int 
     if (width == 0 || height == 0)
         return 0;
     KIMG_CHECK_ARG(data != nullptr && height <= 65535);
-    dim3 grid(kimg_divup(width, 256), height);
-    fourier_beam_kernel<<<grid, 256, 0, (hipStream_t) stream>>>(
-        static_cast<float2 *>(data), row_stride, amplitude, a, b, c, width, height);
-    return kimg_launch_status();
+    return launch_rows(fourier_beam_kernel, width, height, stream, static_cast<float2 *>(data),
+                       row_stride, amplitude, a, b, c, width, height);
 }
 
 // ---- output statistics of the restore step: frontend.py:171-209 -------------------------------

@@ -421,10 +421,11 @@ def find_peak(queue, image, pbeam, noise):
     shape (height, width) or None (no primary-beam correction)."""
     from . import accel
     from ._lib import lib, check
-    P, H, W = image.shape
+    from .image_plane import plane_args
+    ptr, row_pitch, pol_pitch, W, H, P = plane_args(image)
     out = accel.DeviceArray(queue.context, (1,), np.float32, queue=queue)
-    check(lib().kimg_image_peak(image.ptr, W, H * W, pbeam.ptr if pbeam is not None else None, W,
-                                W, H, P, float(noise), out.ptr, queue.handle), 'kimg_image_peak')
+    check(lib().kimg_image_peak(ptr, row_pitch, pol_pitch, pbeam.ptr if pbeam is not None else None,
+                                W, W, H, P, float(noise), out.ptr, queue.handle), 'kimg_image_peak')
     peak = float(out.get(queue)[0])
     return peak if peak != 0.0 else float('nan')
 
@@ -435,9 +436,9 @@ def get_totals(queue, image, restoring_beam):
     import math
     from . import accel
     from ._lib import lib, check
-    P, H, W = image.shape
-    sums = accel.DeviceArray(queue.context, (P,), np.float64, queue=queue)
-    check(lib().kimg_image_nansum(image.ptr, W, H * W, W, H, P, sums.ptr, queue.handle),
+    from .image_plane import plane_args
+    sums = accel.DeviceArray(queue.context, (image.shape[0],), np.float64, queue=queue)
+    check(lib().kimg_image_nansum(*plane_args(image), sums.ptr, queue.handle),
           'kimg_image_nansum')
     beam_area = 2 * math.pi * restoring_beam.major * restoring_beam.minor / (8 * math.log(2))
     return [float(x) / beam_area for x in sums.get(queue)]

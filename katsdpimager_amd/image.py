@@ -11,24 +11,17 @@ import numpy as np
 
 from . import accel, types
 from ._lib import lib, check
+from .image_plane import (ImageTemplate, check_image_shape, plane2d_args, plane_args,
+                          plane_pitches, pol_ptr, precision_call)
 
 
-def _pol_ptr(array, pol):
-    """Device address of polarization `pol` of a [P][H][W] array."""
-    return array.ptr + pol * array.shape[1] * array.shape[2] * array.dtype.itemsize
-
-
-def _is_f64(dtype):
-    return np.dtype(dtype) == np.float64
-
-
-class _LayerImageTemplate:
+class _LayerImageTemplate(ImageTemplate):
     """image.py:15-86.  float32 or float64 (the ``kimg_*_f64`` calls)."""
+    float64 = True
+
     def __init__(self, context, real_dtype, tuning=None):
-        types.require_float32_or_64(real_dtype, type(self).__name__)
-        lib()
-        self.context = context
-        self.real_dtype = np.dtype(real_dtype)
+        super().__init__(context, real_dtype, None, tuning)
+        self.real_dtype = self.dtype
 
 
 class _LayerImage(accel.Operation):
@@ -60,10 +53,10 @@ class _LayerImage(accel.Operation):
             raise IndexError('polarization index out of range')
         self.polarization = polarization
 
-
-class LayerToImageTemplate(_LayerImageTemplate):
-    def instantiate(self, *args, **kwargs):
-        return LayerToImage(self, *args, **kwargs)
+    def _tail(self):
+        """What both directions end their argument list with."""
+        return (self.buffer('kernel1d').ptr, self.lm_scale, self.lm_bias, self.w,
+                self.command_queue.handle)
 
 
 class LayerToImage(_LayerImage):
@@ -71,17 +64,13 @@ class LayerToImage(_LayerImage):
     def _run(self):
         image = self.buffer('image')
         size = image.shape[-1]
-        fn = 'kimg_layer_to_image_f64' if _is_f64(self.template.real_dtype) else 'kimg_layer_to_image'
-        rc = getattr(lib(), fn)(
-            _pol_ptr(image, self.polarization), size, self.buffer('layer').ptr, size,
-            self.buffer('kernel1d').ptr, self.lm_scale, self.lm_bias, self.w,
-            self.command_queue.handle)
-        check(rc, fn)
+        fn, name = precision_call('kimg_layer_to_image', self.template.real_dtype)
+        check(fn(pol_ptr(image, self.polarization), size, self.buffer('layer').ptr, size,
+                 *self._tail()), name)
 
 
-class ImageToLayerTemplate(_LayerImageTemplate):
-    def instantiate(self, *args, **kwargs):
-        return ImageToLayer(self, *args, **kwargs)
+class LayerToImageTemplate(_LayerImageTemplate):
+    operator = LayerToImage
 
 
 class ImageToLayer(_LayerImage):
@@ -89,35 +78,18 @@ class ImageToLayer(_LayerImage):
     def _run(self):
         image = self.buffer('image')
         size = image.shape[-1]
-        fn = 'kimg_image_to_layer_f64' if _is_f64(self.template.real_dtype) else 'kimg_image_to_layer'
-        rc = getattr(lib(), fn)(
-            self.buffer('layer').ptr, _pol_ptr(image, self.polarization), size, size,
-            self.buffer('kernel1d').ptr, self.lm_scale, self.lm_bias, self.w,
-            self.command_queue.handle)
-        check(rc, fn)
+        fn, name = precision_call('kimg_image_to_layer', self.template.real_dtype)
+        check(fn(self.buffer('layer').ptr, pol_ptr(image, self.polarization), size, size,
+                 *self._tail()), name)
 
 
-class _ImageTemplate:
+class ImageToLayerTemplate(_LayerImageTemplate):
+    operator = ImageToLayer
+
+
+class _ImageTemplate(ImageTemplate):
     """float32 or float64 (the ``kimg_*_f64`` calls)."""
-    def __init__(self, context, dtype, num_polarizations, tuning=None):
-        types.require_float32_or_64(dtype, type(self).__name__)
-        lib()
-        self.context = context
-        self.dtype = np.dtype(dtype)
-        self.num_polarizations = num_polarizations
-
-
-def _check_image_shape(template, shape):
-    if len(shape) != 3:
-        raise ValueError('Wrong number of dimensions in shape')
-    if shape[0] != template.num_polarizations:
-        raise ValueError('Mismatch in number of polarizations')
-
-
-class ScaleTemplate(_ImageTemplate):
-    """image.py:281-314."""
-    def instantiate(self, *args, **kwargs):
-        return Scale(self, *args, **kwargs)
+    float64 = True
 
 
 class Scale(accel.Operation):
@@ -125,7 +97,7 @@ class Scale(accel.Operation):
     def __init__(self, template, command_queue, shape, allocator=None):
         super().__init__(command_queue, allocator)
         self.template = template
-        _check_image_shape(template, shape)
+        check_image_shape(template, shape)
         self.slots['data'] = accel.IOSlot(shape, template.dtype)
         self.scale_factor = np.zeros((shape[0],), template.dtype)
 
@@ -133,26 +105,17 @@ class Scale(accel.Operation):
         self.scale_factor[:] = scale_factor
 
     def _run(self):
-        data = self.buffer('data')
-        P, H, W = data.shape
-        if _is_f64(self.template.dtype):
-            sf = np.ascontiguousarray(self.scale_factor, np.float64)
-            rc = lib().kimg_scale_f64(data.ptr, W, H * W, W, H, P,
-                                      sf.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                      self.command_queue.handle)
-            check(rc, 'kimg_scale_f64')
-            return
-        sf = np.ascontiguousarray(self.scale_factor, np.float32)
-        rc = lib().kimg_scale(data.ptr, W, H * W, W, H, P,
-                              sf.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                              self.command_queue.handle)
-        check(rc, 'kimg_scale')
+        dtype = self.template.dtype
+        fn, name = precision_call('kimg_scale', dtype)
+        sf = np.ascontiguousarray(self.scale_factor, dtype)
+        c_type = ctypes.c_double if dtype == np.float64 else ctypes.c_float
+        check(fn(*plane_args(self.buffer('data')), sf.ctypes.data_as(ctypes.POINTER(c_type)),
+                 self.command_queue.handle), name)
 
 
-class AddImageTemplate(_ImageTemplate):
-    """image.py:370-403."""
-    def instantiate(self, *args, **kwargs):
-        return AddImage(self, *args, **kwargs)
+class ScaleTemplate(_ImageTemplate):
+    """image.py:281-314."""
+    operator = Scale
 
 
 class AddImage(accel.Operation):
@@ -160,23 +123,20 @@ class AddImage(accel.Operation):
     def __init__(self, template, command_queue, shape, allocator=None):
         super().__init__(command_queue, allocator)
         self.template = template
-        _check_image_shape(template, shape)
+        check_image_shape(template, shape)
         self.slots['src'] = accel.IOSlot(shape, template.dtype)
         self.slots['dest'] = accel.IOSlot(shape, template.dtype)
 
     def _run(self):
         src, dest = self.buffer('src'), self.buffer('dest')
-        P, H, W = src.shape
-        fn = 'kimg_add_image_f64' if _is_f64(self.template.dtype) else 'kimg_add_image'
-        rc = getattr(lib(), fn)(dest.ptr, W, H * W, src.ptr, W, H * W, W, H, P,
-                                self.command_queue.handle)
-        check(rc, fn)
+        fn, name = precision_call('kimg_add_image', self.template.dtype)
+        check(fn(dest.ptr, *plane_pitches(dest), *plane_args(src), self.command_queue.handle),
+              name)
 
 
-class ApplyPrimaryBeamTemplate(_ImageTemplate):
-    """image.py:461-494."""
-    def instantiate(self, *args, **kwargs):
-        return ApplyPrimaryBeam(self, *args, **kwargs)
+class AddImageTemplate(_ImageTemplate):
+    """image.py:370-403."""
+    operator = AddImage
 
 
 class ApplyPrimaryBeam(accel.Operation):
@@ -184,20 +144,22 @@ class ApplyPrimaryBeam(accel.Operation):
     def __init__(self, template, command_queue, shape, threshold, replacement, allocator=None):
         super().__init__(command_queue, allocator)
         self.template = template
-        _check_image_shape(template, shape)
+        check_image_shape(template, shape)
         self.slots['data'] = accel.IOSlot(shape, template.dtype)
         self.slots['beam_power'] = accel.IOSlot(shape[1:], template.dtype)
         self.threshold = threshold
         self.replacement = replacement
 
     def _run(self):
-        data = self.buffer('data')
-        P, H, W = data.shape
-        fn = 'kimg_apply_primary_beam_f64' if _is_f64(self.template.dtype) else 'kimg_apply_primary_beam'
-        rc = getattr(lib(), fn)(
-            data.ptr, W, H * W, self.buffer('beam_power').ptr, W, W, H, P,
-            self.threshold, self.replacement, self.command_queue.handle)
-        check(rc, fn)
+        ptr, row_pitch, pol_pitch, W, H, P = plane_args(self.buffer('data'))
+        fn, name = precision_call('kimg_apply_primary_beam', self.template.dtype)
+        check(fn(ptr, row_pitch, pol_pitch, *plane2d_args(self.buffer('beam_power')), W, H, P,
+                 self.threshold, self.replacement, self.command_queue.handle), name)
+
+
+class ApplyPrimaryBeamTemplate(_ImageTemplate):
+    """image.py:461-494."""
+    operator = ApplyPrimaryBeam
 
 
 class _PlanPool:
@@ -334,7 +296,7 @@ class GridImageTemplate:
 
     def make_fft_plan(self, shape_layer, padded_shape_layer=None):
         plan = FftPlan(shape_layer, types.real_to_complex(self.real_dtype))
-        if self.real_transform and not _is_f64(self.real_dtype):
+        if self.real_transform and self.real_dtype != np.float64:
             plan.real_plan()        # (plan creation costs milliseconds of host time: not in the loop)
         return plan
 
@@ -358,7 +320,7 @@ class _GridImage(accel.Operation):
             self.slots[name] = self._layer_image.slots[name]
         self.slots['grid'] = accel.IOSlot(shape_grid, types.real_to_complex(template.real_dtype))
         #: float64: the plain route for every w (see GridImageTemplate)
-        self._plain = _is_f64(template.real_dtype)
+        self._plain = template.real_dtype == np.float64
         if shape_grid[1] != shape_grid[2] or shape_grid[1] % 2:
             raise ValueError('grid must be square with even size')     # image.py:655-656
 
@@ -371,6 +333,32 @@ class _GridImage(accel.Operation):
         Gg = self.buffer('grid').shape[1]
         return (not self._plain and self.template.real_transform and self.template.own_transform
                 and bool(lib().kimg_grid_image_real_supported(G, Gg)))
+
+    def _route(self):
+        """Which way the next call goes: ``'float64'`` (plain, in double precision);
+        ``'own_real'`` / ``'own_w'``: the library's own transforms, at w = 0 the real one;
+        ``'plan_real'``: w = 0 on the FFT library's complex-to-real plan; ``'plain'``: grid <->
+        layer copy, C2C plan, layer <-> image."""
+        if self._plain:
+            return 'float64'
+        real = self._layer_image.w == 0 and self.template.real_transform
+        if self._own_transform():
+            return 'own_real' if real else 'own_w'
+        return 'plan_real' if real else 'plain'
+
+    def _run_own(self, route, stem, dest, src, *flags):
+        """The two own-transform routes, a call per polarization: ``stem + '_real'``, or
+        ``stem + '_w'`` with w behind the lm factors; `flags` stand before the workspace."""
+        name = stem + ('_real' if route == 'own_real' else '_w')
+        li, layer = self._layer_image, self.buffer('layer')
+        w = () if route == 'own_real' else (float(li.w),)
+        for pol in range(dest.shape[0]):
+            check(getattr(lib(), name)(
+                pol_ptr(dest, pol), dest.shape[2], dest.shape[1],
+                pol_ptr(src, pol), src.shape[2], src.shape[1],
+                self.buffer('kernel1d').ptr, li.lm_scale, li.lm_bias, *w, *flags, layer.ptr,
+                layer.tensor.numel() * layer.tensor.element_size(), self.command_queue.handle),
+                name)
 
 
 class GridToImage(_GridImage):
@@ -394,57 +382,32 @@ class GridToImage(_GridImage):
         P, Gg, _ = grid.shape
         G = layer.shape[0]
         q = self.command_queue
-        if self._plain:
-            for pol in range(P):
-                check(lib().kimg_grid_to_layer_f64(layer.ptr, G, _pol_ptr(grid, pol), Gg, Gg,
-                                                   q.handle), 'kimg_grid_to_layer_f64')
-                self._fft.execute(q, layer, inverse=True)
-                self._layer_image.set_polarization(pol)
-                self._layer_image()
-            return
-        if self._layer_image.w == 0 and self.template.real_transform:
+        route = self._route()
+        if route in ('own_real', 'own_w'):
+            overwrite, self.overwrite_next = self.overwrite_next, False
+            self._run_own(route, 'kimg_grid_to_image', self.buffer('image'), grid,
+                          0 if overwrite else 1)
+        elif route == 'plan_real':
             # w = 0: the phase factor is 1 and only the real part of the transform is used, which
             # is the transform of the grid's Hermitian part: half the layer, a complex-to-real
             # transform in place (real rows of G + 2 floats), half the traffic all the way
             image = self.buffer('image')
             li = self._layer_image
-            if self._own_transform():
-                overwrite, self.overwrite_next = self.overwrite_next, False
-                for pol in range(P):
-                    check(lib().kimg_grid_to_image_real(
-                        _pol_ptr(image, pol), G, G, _pol_ptr(grid, pol), Gg, Gg,
-                        self.buffer('kernel1d').ptr, li.lm_scale, li.lm_bias,
-                        0 if overwrite else 1, layer.ptr,
-                        layer.tensor.numel() * layer.tensor.element_size(), q.handle),
-                        'kimg_grid_to_image_real')
-                return
             self._real_plan = self._fft.real_plan()
             for pol in range(P):
-                check(lib().kimg_grid_to_half_layer(layer.ptr, G, _pol_ptr(grid, pol), Gg, Gg,
+                check(lib().kimg_grid_to_half_layer(layer.ptr, G, pol_ptr(grid, pol), Gg, Gg,
                                                     q.handle), 'kimg_grid_to_half_layer')
                 self._real_plan.execute_in_place(q, layer)
                 check(lib().kimg_real_layer_to_image(
-                    _pol_ptr(image, pol), G, layer.ptr, G + 2, G, self.buffer('kernel1d').ptr,
+                    pol_ptr(image, pol), G, layer.ptr, G + 2, G, self.buffer('kernel1d').ptr,
                     li.lm_scale, li.lm_bias, q.handle), 'kimg_real_layer_to_image')
-            return
-        if self._own_transform():
-            overwrite, self.overwrite_next = self.overwrite_next, False
-            image = self.buffer('image')
-            li = self._layer_image
+        else:       # 'plain', 'float64'
+            fn, name = precision_call('kimg_grid_to_layer', self.template.real_dtype)
             for pol in range(P):
-                check(lib().kimg_grid_to_image_w(
-                    _pol_ptr(image, pol), G, G, _pol_ptr(grid, pol), Gg, Gg,
-                    self.buffer('kernel1d').ptr, li.lm_scale, li.lm_bias, float(li.w),
-                    0 if overwrite else 1, layer.ptr,
-                    layer.tensor.numel() * layer.tensor.element_size(), q.handle),
-                    'kimg_grid_to_image_w')
-            return
-        for pol in range(P):
-            check(lib().kimg_grid_to_layer(layer.ptr, G, _pol_ptr(grid, pol), Gg, Gg,
-                                           q.handle), 'kimg_grid_to_layer')
-            self._fft.execute(q, layer, inverse=True)
-            self._layer_image.set_polarization(pol)
-            self._layer_image()
+                check(fn(layer.ptr, G, pol_ptr(grid, pol), Gg, Gg, q.handle), name)
+                self._fft.execute(q, layer, inverse=True)
+                self._layer_image.set_polarization(pol)
+                self._layer_image()
 
 
 class ImageToGrid(_GridImage):
@@ -460,52 +423,27 @@ class ImageToGrid(_GridImage):
         grid, layer = self.buffer('grid'), self.buffer('layer')
         P, Gg, _ = grid.shape
         G = layer.shape[0]
-        if self._plain:
-            for pol in range(P):
-                self._layer_image.set_polarization(pol)
-                self._layer_image()
-                self._fft.execute(self.command_queue, layer, inverse=False)
-                check(lib().kimg_layer_to_grid_f64(_pol_ptr(grid, pol), Gg, Gg, layer.ptr, G,
-                                                   self.command_queue.handle),
-                      'kimg_layer_to_grid_f64')
-            return
-        if self._layer_image.w == 0 and self.template.real_transform:
+        q = self.command_queue
+        route = self._route()
+        if route in ('own_real', 'own_w'):
+            self._run_own(route, 'kimg_image_to_grid', grid, self.buffer('image'))
+        elif route == 'plan_real':
             # w = 0: the layer is real; real-to-complex transform in place, the grid's other half
             # from F(-k) = conj F(k)
-            q = self.command_queue
             image = self.buffer('image')
             li = self._layer_image
-            if self._own_transform():
-                for pol in range(P):
-                    check(lib().kimg_image_to_grid_real(
-                        _pol_ptr(grid, pol), Gg, Gg, _pol_ptr(image, pol), G, G,
-                        self.buffer('kernel1d').ptr, li.lm_scale, li.lm_bias, layer.ptr,
-                        layer.tensor.numel() * layer.tensor.element_size(), q.handle),
-                        'kimg_image_to_grid_real')
-                return
             self._real_plan = self._fft.real_plan()
             for pol in range(P):
                 check(lib().kimg_image_to_real_layer(
-                    layer.ptr, G + 2, _pol_ptr(image, pol), G, G, self.buffer('kernel1d').ptr,
+                    layer.ptr, G + 2, pol_ptr(image, pol), G, G, self.buffer('kernel1d').ptr,
                     li.lm_scale, li.lm_bias, q.handle), 'kimg_image_to_real_layer')
                 self._real_plan.execute_in_place(q, layer, inverse=False)
-                check(lib().kimg_half_layer_to_grid(_pol_ptr(grid, pol), Gg, Gg, layer.ptr, G,
+                check(lib().kimg_half_layer_to_grid(pol_ptr(grid, pol), Gg, Gg, layer.ptr, G,
                                                     q.handle), 'kimg_half_layer_to_grid')
-            return
-        if self._own_transform():
-            q = self.command_queue
-            image = self.buffer('image')
-            li = self._layer_image
+        else:       # 'plain', 'float64'
+            fn, name = precision_call('kimg_layer_to_grid', self.template.real_dtype)
             for pol in range(P):
-                check(lib().kimg_image_to_grid_w(
-                    _pol_ptr(grid, pol), Gg, Gg, _pol_ptr(image, pol), G, G,
-                    self.buffer('kernel1d').ptr, li.lm_scale, li.lm_bias, float(li.w), layer.ptr,
-                    layer.tensor.numel() * layer.tensor.element_size(), q.handle),
-                    'kimg_image_to_grid_w')
-            return
-        for pol in range(P):
-            self._layer_image.set_polarization(pol)
-            self._layer_image()
-            self._fft.execute(self.command_queue, layer, inverse=False)
-            check(lib().kimg_layer_to_grid(_pol_ptr(grid, pol), Gg, Gg, layer.ptr, G,
-                                           self.command_queue.handle), 'kimg_layer_to_grid')
+                self._layer_image.set_polarization(pol)
+                self._layer_image()
+                self._fft.execute(q, layer, inverse=False)
+                check(fn(pol_ptr(grid, pol), Gg, Gg, layer.ptr, G, q.handle), name)

@@ -17,6 +17,7 @@ import functools
 import numpy as np
 
 from . import accel, clean, grid, image, mask, multiscale, predict, primary_beam, types, weight
+from .image_plane import plane_args
 
 
 class ImagingTemplate:
@@ -704,7 +705,7 @@ class Imaging(accel.OperationSequence):
             self._kept_scale = accel.DeviceArray(self.command_queue.context, (P,), np.float32,
                                                  queue=self.command_queue)
         centre = H // 2             # (frontend.py:541: one index for both axes)
-        check(lib().kimg_pixel_reciprocal(dirty.ptr, W, H * W, W, H, P, centre, centre,
+        check(lib().kimg_pixel_reciprocal(*plane_args(dirty), centre, centre,
                                           self._kept_scale.ptr, self.command_queue.handle),
               'kimg_pixel_reciprocal')
         self.scale_dirty_by_kept()
@@ -713,9 +714,7 @@ class Imaging(accel.OperationSequence):
     def scale_dirty_by_kept(self):
         from ._lib import lib, check
         self._ready()
-        dirty = self.buffer('dirty')
-        P, H, W = dirty.shape
-        check(lib().kimg_scale_device(dirty.ptr, W, H * W, W, H, P, self._kept_scale.ptr,
+        check(lib().kimg_scale_device(*plane_args(self.buffer('dirty')), self._kept_scale.ptr,
                                       self.command_queue.handle), 'kimg_scale_device')
 
     @_serial

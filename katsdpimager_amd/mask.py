@@ -12,8 +12,10 @@ after every major cycle's noise estimate.
 """
 import numpy as np
 
-from . import accel, types
+from . import accel
 from ._lib import lib, check
+from .image_plane import (ImageTemplate, border_pixels, check_polarizations, plane2d_args,
+                          plane_args)
 from .parameters import CLEAN_I, CLEAN_SUMSQ  # noqa: F401
 
 #: KIMG_MASK_MAX_RADIUS
@@ -46,33 +48,15 @@ class AutoMaskParameters:
             self.sigma, self.radius, self.cumulative)
 
 
-class MaskThresholdTemplate:
-    def __init__(self, context, dtype, num_polarizations, mode, tuning=None):
-        types.require_float32(dtype, 'MaskThresholdTemplate')
-        if mode not in (CLEAN_I, CLEAN_SUMSQ):
-            raise ValueError('Invalid mode {}'.format(mode))
-        lib()
-        self.context = context
-        self.dtype = np.dtype(dtype)
-        self.num_polarizations = num_polarizations
-        self.mode = mode
-
-    def instantiate(self, *args, **kwargs):
-        return MaskThreshold(self, *args, **kwargs)
-
-
 class MaskThreshold(accel.Operation):
     """mask = 1 where the pixel is inside the border and its CLEAN metric > threshold, else 0
     (kimg_mask_threshold).  Slots: **image** [P][H][W]; **mask** uint8 [H][W]."""
 
     def __init__(self, template, command_queue, image_shape, border, allocator=None):
-        if image_shape[0] != template.num_polarizations:
-            raise ValueError('Mismatch in number of polarizations')
-        if border >= 0.5:
-            raise ValueError('Border must be less than half the image size')
+        check_polarizations(template, image_shape)
+        self.border_pixels = border_pixels(border, image_shape)
         super().__init__(command_queue, allocator)
         self.template = template
-        self.border_pixels = round(border * min(image_shape[1], image_shape[2]))
         self.slots['image'] = accel.IOSlot(image_shape, template.dtype)
         self.slots['mask'] = accel.IOSlot(image_shape[1:], np.uint8)
 
@@ -84,20 +68,20 @@ class MaskThreshold(accel.Operation):
         self.bind(**kwargs)
         self.ensure_all_bound()
         image, mask = self.buffer('image'), self.buffer('mask')
-        P, H, W = image.shape
-        rc = lib().kimg_mask_threshold(image.ptr, W, H * W, W, H, P, self.border_pixels,
-                                       self.template.mode, float(threshold), mask.ptr, W,
+        rc = lib().kimg_mask_threshold(*plane_args(image), self.border_pixels,
+                                       self.template.mode, float(threshold), *plane2d_args(mask),
                                        self.command_queue.handle)
         check(rc, 'kimg_mask_threshold')
 
 
-class MaskDilateTemplate:
-    def __init__(self, context, tuning=None):
-        lib()
-        self.context = context
+class MaskThresholdTemplate(ImageTemplate):
+    operator = MaskThreshold
 
-    def instantiate(self, *args, **kwargs):
-        return MaskDilate(self, *args, **kwargs)
+    def __init__(self, context, dtype, num_polarizations, mode, tuning=None):
+        super().__init__(context, dtype, num_polarizations, tuning)
+        if mode not in (CLEAN_I, CLEAN_SUMSQ):
+            raise ValueError('Invalid mode {}'.format(mode))
+        self.mode = mode
 
 
 class MaskDilate(accel.Operation):
@@ -133,3 +117,12 @@ class MaskDilate(accel.Operation):
             restrict.ptr if restrict is not None else None, W,
             count.ptr + 4 * index, self.command_queue.handle)
         check(rc, 'kimg_mask_dilate')
+
+
+class MaskDilateTemplate(ImageTemplate):
+    """Masks have no dtype and no polarizations: only the context."""
+    operator = MaskDilate
+
+    def __init__(self, context, tuning=None):
+        lib()
+        self.context = context

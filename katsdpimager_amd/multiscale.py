@@ -15,6 +15,8 @@ import numpy as np
 
 from . import accel, types
 from ._lib import lib, check
+from .image_plane import (ImageTemplate, border_pixels, check_polarizations, plane_args,
+                          plane_pitches)
 from .parameters import CLEAN_I
 
 TILE = 32
@@ -143,7 +145,7 @@ class MultiScaleCleanHost:
         self.loop_gain = np.float32(loop_gain)
         self.image, self.psf, self.model = image, psf, model
         self.mask = None if mask is None else np.asarray(mask) != 0
-        self.border_pixels = round(border * min(H, W))
+        self.border_pixels = border_pixels(border, image.shape, checked=False)
         bp = self.border_pixels
         K = len(params)
         self.tiles = (-(-(H - 2 * bp) // TILE), -(-(W - 2 * bp) // TILE))
@@ -271,25 +273,6 @@ class MultiScaleCleanHost:
 
 # ---- the device operator --------------------------------------------------------------------
 
-class MultiScaleCleanTemplate:
-    """The constructor shape of :class:`clean.CleanTemplate` plus the scales."""
-
-    def __init__(self, context, clean_parameters, multiscale_parameters, dtype, num_polarizations,
-                 tuning=None):
-        types.require_float32(dtype, 'MultiScaleCleanTemplate')
-        if clean_parameters.mode != CLEAN_I:
-            raise ValueError('multi-scale CLEAN runs in mode CLEAN_I only')
-        lib()
-        self.context = context
-        self.clean_parameters = clean_parameters
-        self.multiscale_parameters = multiscale_parameters
-        self.dtype = np.dtype(dtype)
-        self.num_polarizations = num_polarizations
-
-    def instantiate(self, *args, **kwargs):
-        return MultiScaleClean(self, *args, **kwargs)
-
-
 class MultiScaleClean(accel.Operation):
     """Multi-scale minor cycles on the device.  Slots: **dirty** (the residual of scale 0),
     **model**, **psf** (all [P][H][W]) and the optional **mask** (uint8 [H][W], as for
@@ -302,14 +285,10 @@ class MultiScaleClean(accel.Operation):
             raise ValueError('dtype mismatch')
         super().__init__(command_queue, allocator)
         self.template = template
-        P = len(image_parameters.fixed.polarizations)
-        if P != template.num_polarizations:
-            raise ValueError('Mismatch in number of polarizations')
-        shape = (P, image_parameters.pixels, image_parameters.pixels)
-        border = template.clean_parameters.border
-        if border >= 0.5:
-            raise ValueError('Border must be less than half the image size')
-        self.border_pixels = round(border * min(shape[1], shape[2]))
+        shape = (len(image_parameters.fixed.polarizations),
+                 image_parameters.pixels, image_parameters.pixels)
+        check_polarizations(template, shape)
+        self.border_pixels = border_pixels(template.clean_parameters.border, shape)
         self.tiles = (accel.divup(shape[1] - 2 * self.border_pixels, TILE),
                       accel.divup(shape[2] - 2 * self.border_pixels, TILE))
         self.slots['dirty'] = accel.IOSlot(shape, template.dtype)
@@ -343,14 +322,9 @@ class MultiScaleClean(accel.Operation):
     def _run(self):
         raise NotImplementedError('use reset() and run_cycles()')
 
-    def _image_args(self):
-        dirty = self.buffer('dirty')
-        P, H, W = dirty.shape
-        return W, H, P
-
     def _make_layout(self, psf_patch):
         """The sections of the workspace (include/kimg.h), in floats."""
-        W, H, P = self._image_args()
+        P, H, W = self.buffer('dirty').shape
         K = len(self._radii)
         r64 = lambda n: (n + 63) // 64 * 64     # noqa: E731
         tile_pitch = r64(self.tiles[0] * self.tiles[1])
@@ -395,7 +369,7 @@ class MultiScaleClean(accel.Operation):
         """Enqueue whatever set-up is pending for this patch."""
         self.ensure_all_bound()
         patch = tuple(int(x) for x in psf_patch)
-        W, H, P = self._image_args()
+        P, H, W = self.buffer('dirty').shape
         if patch != self._patch:
             self._pending |= _SETUP_PSF | _SETUP_RESIDUALS
             nbytes = lib().kimg_clean_scales_workspace_bytes(
@@ -414,7 +388,7 @@ class MultiScaleClean(accel.Operation):
         dirty, psf = self.buffer('dirty'), self.buffer('psf')
         mask_ptr, mask_row = self._mask_args()
         rc = lib().kimg_clean_scales_setup(
-            dirty.ptr, W, H * W, psf.ptr, W, H * W, W, H, P, patch[2], patch[1],
+            dirty.ptr, *plane_pitches(dirty), *plane_args(psf), patch[2], patch[1],
             self.border_pixels, len(self._radii), self._radii,
             self._taps.ctypes.data, self._cross_taps.ctypes.data, self._pending,
             mask_ptr, mask_row, self._workspace.ptr, self._workspace.shape[0] * 4,
@@ -431,7 +405,7 @@ class MultiScaleClean(accel.Operation):
         """Up to ``max_cycles`` cycles on the device, the host looking at the device once per 64
         of them; the log (:func:`log_dtype`) is read back once."""
         self.prepare(psf_patch)
-        W, H, P = self._image_args()
+        P, H, W = self.buffer('dirty').shape
         self.cycles_done = 0
         if max_cycles <= 0:
             return np.zeros(0, log_dtype(P))
@@ -443,7 +417,7 @@ class MultiScaleClean(accel.Operation):
         mask_ptr, mask_row = self._mask_args()
         done = ctypes.c_int(0)
         rc = lib().kimg_clean_scales_cycles(
-            dirty.ptr, model.ptr, W, H * W, W, H, P, self._patch[2], self._patch[1],
+            dirty.ptr, model.ptr, *plane_args(dirty)[1:], self._patch[2], self._patch[1],
             self.border_pixels, cp.mode, cp.loop_gain, threshold, len(self._radii), self._radii,
             self._biases, max_cycles, mask_ptr, mask_row, self._workspace.ptr,
             self._workspace.shape[0] * 4, self._log.ptr, ctypes.byref(done),
@@ -475,7 +449,7 @@ class MultiScaleClean(accel.Operation):
     def residual(self, k):
         if k == 0:
             return self.buffer('dirty').get(self.command_queue)
-        W, H, P = self._image_args()
+        P, H, W = self.buffer('dirty').shape
         return self._section(self._layout['res'][k], P * H * W).reshape(P, H, W)
 
     def cross_patch(self, j, k):
@@ -492,6 +466,19 @@ class MultiScaleClean(accel.Operation):
         return tmax.reshape((K,) + self.tiles).copy(), tpos.reshape((K,) + self.tiles + (2,)).copy()
 
 
+class MultiScaleCleanTemplate(ImageTemplate):
+    """The constructor shape of :class:`clean.CleanTemplate` plus the scales."""
+    operator = MultiScaleClean
+
+    def __init__(self, context, clean_parameters, multiscale_parameters, dtype, num_polarizations,
+                 tuning=None):
+        super().__init__(context, dtype, num_polarizations, tuning)
+        if clean_parameters.mode != CLEAN_I:
+            raise ValueError('multi-scale CLEAN runs in mode CLEAN_I only')
+        self.clean_parameters = clean_parameters
+        self.multiscale_parameters = multiscale_parameters
+
+
 def convolve_separable(command_queue, src, dest, taps, tmp=None):
     """``dest = conv(src, taps)`` on device arrays [P][H][W] (kimg_image_convolve_separable);
     ``taps``: host float32 [2 R + 1]."""
@@ -502,13 +489,13 @@ def convolve_separable(command_queue, src, dest, taps, tmp=None):
         raise ValueError('an odd number of taps')
     if R > MAX_RADIUS:
         raise ValueError('radius {} exceeds {}'.format(R, MAX_RADIUS))
-    P, H, W = src.shape
     ctx = command_queue.context
     if tmp is None:
         tmp = accel.DeviceArray(ctx, src.shape, np.float32, queue=command_queue)
     dtaps = accel.DeviceArray(ctx, taps.shape, np.float32, queue=command_queue)
     dtaps.set(command_queue, taps)
     rc = lib().kimg_image_convolve_separable(
-        src.ptr, W, H * W, dest.ptr, W, H * W, tmp.ptr, W, H * W, W, H, P, dtaps.ptr, R,
+        src.ptr, *plane_pitches(src), dest.ptr, *plane_pitches(src), tmp.ptr,
+        *plane_args(src)[1:], dtaps.ptr, R,
         command_queue.handle)
     check(rc, 'kimg_image_convolve_separable')

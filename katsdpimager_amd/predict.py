@@ -9,8 +9,9 @@ scope for the hot path).
 """
 import numpy as np
 
-from . import accel, grid, types
+from . import accel, grid
 from ._lib import lib, check
+from .image_plane import ImageTemplate, check_polarizations
 
 
 def extract_sky_image(image_parameters, grid_parameters, components):
@@ -61,23 +62,6 @@ def uvw_scale_bias(image_parameters, grid_parameters):
     return uv_scale, w_scale, w_bias
 
 
-class PredictTemplate:
-    """predict.py:152-287 (no autotuning: one thread per visibility, 256-wide groups)."""
-
-    def __init__(self, context, real_dtype, num_polarizations, tuning=None):
-        # The kernel accumulates in float32 only; the reference takes real_dtype as the
-        # accumulation type, so float64 is refused rather than silently run in float32.
-        types.require_float32(real_dtype, 'PredictTemplate')
-        lib()
-        self.context = context
-        self.real_dtype = np.dtype(real_dtype)
-        self.num_polarizations = num_polarizations
-        self.wgs = 256
-
-    def instantiate(self, *args, **kwargs):
-        return Predict(self, *args, **kwargs)
-
-
 class Predict(grid.VisOperation):
     """Instantiation of :class:`PredictTemplate` (predict.py:289-416).
 
@@ -87,8 +71,7 @@ class Predict(grid.VisOperation):
 
     def __init__(self, template, command_queue, image_parameters, grid_parameters,
                  max_vis, max_sources, allocator=None):
-        if len(image_parameters.fixed.polarizations) != template.num_polarizations:
-            raise ValueError('Mismatch in number of polarizations')
+        check_polarizations(template, (len(image_parameters.fixed.polarizations),))
         super().__init__(command_queue, template.num_polarizations, max_vis, allocator)
         self.template = template
         pol_dim = accel.Dimension(template.num_polarizations, exact=True)
@@ -150,3 +133,15 @@ class Predict(grid.VisOperation):
             self.grid_parameters.fixed.oversample, uv_scale, w_scale, w_bias,
             self.command_queue.handle)
         check(rc, 'kimg_predict')
+
+
+class PredictTemplate(ImageTemplate):
+    """predict.py:152-287 (no autotuning: one thread per visibility, 256-wide groups)."""
+    operator = Predict
+
+    def __init__(self, context, real_dtype, num_polarizations, tuning=None):
+        # The kernel accumulates in float32 only; the reference takes real_dtype as the
+        # accumulation type, so float64 is refused rather than silently run in float32.
+        super().__init__(context, real_dtype, num_polarizations, tuning)
+        self.real_dtype = self.dtype
+        self.wgs = 256

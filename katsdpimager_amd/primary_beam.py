@@ -14,8 +14,9 @@ contract costs.
 """
 import numpy as np
 
-from . import accel, types
+from . import accel
 from ._lib import lib, check, PRIMARY_BEAM_MAX_SAMPLES
+from .image_plane import ImageTemplate, check_image_shape, plane2d_args
 
 SPEED_OF_LIGHT = 299792458.0        # m / s
 
@@ -223,21 +224,6 @@ def correct_host(power, model, dirty, threshold):
     return keep
 
 
-class PrimaryBeamTemplate:
-    """float32 only."""
-    def __init__(self, context, dtype, num_polarizations, tuning=None):
-        types.require_float32(dtype, type(self).__name__)
-        if not 1 <= num_polarizations <= 4:
-            raise ValueError('1 to 4 polarizations, not {}'.format(num_polarizations))
-        lib()
-        self.context = context
-        self.dtype = np.dtype(dtype)
-        self.num_polarizations = num_polarizations
-
-    def instantiate(self, *args, **kwargs):
-        return PrimaryBeam(self, *args, **kwargs)
-
-
 class PrimaryBeam(accel.Operation):
     """Sample the beam model's row on the pixel grid and correct model and dirty by its power
     (``kimg_primary_beam``).  Slots: **beam_power** [H][W], **model** and **dirty** [P][H][W].
@@ -247,10 +233,7 @@ class PrimaryBeam(accel.Operation):
 
     def __init__(self, template, command_queue, image_shape, allocator=None):
         super().__init__(command_queue, allocator)
-        if len(image_shape) != 3:
-            raise ValueError('Wrong number of dimensions in shape')
-        if image_shape[0] != template.num_polarizations:
-            raise ValueError('Mismatch in number of polarizations')
+        check_image_shape(template, image_shape)
         self.template = template
         self.slots['beam_power'] = accel.IOSlot(image_shape[1:], template.dtype)
         self.slots['model'] = accel.IOSlot(image_shape, template.dtype)
@@ -283,7 +266,7 @@ class PrimaryBeam(accel.Operation):
         model = self.buffer('model').ptr if images else None
         dirty = self.buffer('dirty').ptr if images else None
         rc = lib().kimg_primary_beam(
-            beam.ptr, W, model, dirty, W, H * W, W, H, self.template.num_polarizations,
+            *plane2d_args(beam), model, dirty, W, H * W, W, H, self.template.num_polarizations,
             self.row.ptr, self.row.shape[0], float(inv_step32(self.step)), self.lm_scale,
             self.lm_bias, self.threshold, self.command_queue.handle)
         check(rc, 'kimg_primary_beam')
@@ -295,3 +278,13 @@ class PrimaryBeam(accel.Operation):
         """Fill **beam_power** only; the images are not touched (and need not be bound)."""
         self.ensure_bound('beam_power')
         self._launch(False)
+
+
+class PrimaryBeamTemplate(ImageTemplate):
+    """float32 only."""
+    operator = PrimaryBeam
+
+    def __init__(self, context, dtype, num_polarizations, tuning=None):
+        super().__init__(context, dtype, num_polarizations, tuning)
+        if not 1 <= num_polarizations <= 4:
+            raise ValueError('1 to 4 polarizations, not {}'.format(num_polarizations))

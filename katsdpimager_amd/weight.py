@@ -13,6 +13,7 @@ import numpy as np
 
 from . import accel
 from ._lib import lib, check, UVTaper
+from .image_plane import ImageTemplate, check_polarizations, plane_args
 
 
 class WeightType(enum.Enum):
@@ -137,15 +138,12 @@ def uv_taper_host(shape, image_size, params):
     return np.where((r < min_uv) | (r > max_uv), 0.0, t)
 
 
-class GridWeightsTemplate:
-    """weight.py:61-87."""
+class _WeightsStepTemplate(ImageTemplate):
+    """The weights grid is float32 whatever the image is: no dtype."""
     def __init__(self, context, num_polarizations, tuning=None):
         lib()
         self.context = context
         self.num_polarizations = num_polarizations
-
-    def instantiate(self, *args, **kwargs):
-        return GridWeights(self, *args, **kwargs)
 
 
 class GridWeights(accel.Operation):
@@ -156,8 +154,7 @@ class GridWeights(accel.Operation):
     def __init__(self, template, command_queue, grid_shape, max_vis, allocator=None):
         super().__init__(command_queue, allocator)
         self.template = template
-        if grid_shape[0] != template.num_polarizations:
-            raise ValueError('Mismatch in number of polarizations')
+        check_polarizations(template, grid_shape)
         if grid_shape[1] % 2 or grid_shape[2] % 2:
             raise ValueError('Odd-sized grid not currently supported')
         self.max_vis = max_vis
@@ -179,23 +176,15 @@ class GridWeights(accel.Operation):
         self._num_vis = n
 
     def _run(self):
-        grid = self.buffer('grid')
-        P, H, W = grid.shape
-        rc = lib().kimg_grid_weights(grid.ptr, W, H * W, W, H, P, self.buffer('uv').ptr,
+        rc = lib().kimg_grid_weights(*plane_args(self.buffer('grid')), self.buffer('uv').ptr,
                                      self.buffer('weights').ptr, self._num_vis,
                                      self.command_queue.handle)
         check(rc, 'kimg_grid_weights')
 
 
-class DensityWeightsTemplate:
-    """weight.py:186-214."""
-    def __init__(self, context, num_polarizations, tuning=None):
-        lib()
-        self.context = context
-        self.num_polarizations = num_polarizations
-
-    def instantiate(self, *args, **kwargs):
-        return DensityWeights(self, *args, **kwargs)
+class GridWeightsTemplate(_WeightsStepTemplate):
+    """weight.py:61-87."""
+    operator = GridWeights
 
 
 class DensityWeights(accel.Operation):
@@ -210,8 +199,7 @@ class DensityWeights(accel.Operation):
                  image_size=None):
         super().__init__(command_queue, allocator)
         self.template = template
-        if grid_shape[0] != template.num_polarizations:
-            raise ValueError('Mismatch in number of polarizations')
+        check_polarizations(template, grid_shape)
         self.a = 1.0
         self.b = 0.0
         self.taper = taper
@@ -230,23 +218,22 @@ class DensityWeights(accel.Operation):
     def _run(self, mean_sums=None, robust=None):
         """``mean_sums`` (device float64 [2] as :class:`MeanWeight` leaves it) and ``robust``: a =
         robust / (mean weight) worked out on the device instead of ``self.a``."""
-        grid = self.buffer('grid')
         sums = self.buffer('sums')
-        P, H, W = grid.shape
+        grid = plane_args(self.buffer('grid'))
         if self._taper_struct is not None:
             step = 1.0 / self.image_size
             rc = lib().kimg_density_weights_taper(
-                sums.ptr, grid.ptr, W, H * W, W, H, P, self.a, self.b,
+                sums.ptr, *grid, self.a, self.b,
                 mean_sums.ptr if mean_sums is not None else None,
                 float(robust) if mean_sums is not None else 0.0, step, step,
                 ctypes.byref(self._taper_struct), self.command_queue.handle)
             check(rc, 'kimg_density_weights_taper')
         elif mean_sums is not None:
-            rc = lib().kimg_density_weights_robust(sums.ptr, grid.ptr, W, H * W, W, H, P, mean_sums.ptr,
-                                                   float(robust), self.b, self.command_queue.handle)
+            rc = lib().kimg_density_weights_robust(sums.ptr, *grid, mean_sums.ptr, float(robust),
+                                                   self.b, self.command_queue.handle)
             check(rc, 'kimg_density_weights_robust')
         else:
-            rc = lib().kimg_density_weights(sums.ptr, grid.ptr, W, H * W, W, H, P, self.a, self.b,
+            rc = lib().kimg_density_weights(sums.ptr, *grid, self.a, self.b,
                                             self.command_queue.handle)
             check(rc, 'kimg_density_weights')
         s = sums.get(self.command_queue)
@@ -257,14 +244,9 @@ class DensityWeights(accel.Operation):
         return rms, rms * np.sqrt(s[0])
 
 
-class MeanWeightTemplate:
-    """weight.py:296-324."""
-    def __init__(self, context, tuning=None):
-        lib()
-        self.context = context
-
-    def instantiate(self, *args, **kwargs):
-        return MeanWeight(self, *args, **kwargs)
+class DensityWeightsTemplate(_WeightsStepTemplate):
+    """weight.py:186-214."""
+    operator = DensityWeights
 
 
 class MeanWeight(accel.Operation):
@@ -288,6 +270,15 @@ class MeanWeight(accel.Operation):
         rc = lib().kimg_mean_weight(sums.ptr, grid.ptr, W, W, H, self.command_queue.handle)
         check(rc, 'kimg_mean_weight')
         return sums
+
+
+class MeanWeightTemplate(ImageTemplate):
+    """weight.py:296-324.  Only the context: the first polarization of a float32 grid."""
+    operator = MeanWeight
+
+    def __init__(self, context, tuning=None):
+        lib()
+        self.context = context
 
 
 class WeightsTemplate:
