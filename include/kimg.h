@@ -273,6 +273,50 @@ int kimg_grid_planned(void *grid, int64_t grid_row, int64_t grid_pol, int grid_s
                       const void *convolve_kernel, int w_planes, int oversample, int kernel_width,
                       void *workspace, size_t workspace_bytes, int variant, int arith, void *stream,
                       const void *fold_plan);
+/* Fold maps: everything the pre-pass derives from uv and w_plane, kept across calls.  Besides the
+ * counts that is which records head a run and the compacted coordinates; a call that is given a
+ * map reads the samples and one bit per record and writes the sums -- no key is read or compared,
+ * no coordinate written.  A map costs N / 8 + 10 H bytes of device memory (plus 4160).
+ *   kimg_fold_map_bytes     size of a map of N records with room for `heads` runs (0 for arguments
+ *                           out of range).  Take `heads` from the plan's H.
+ *   kimg_fold_map           fills `map` (device memory, 16-byte aligned, map_bytes long) from the
+ *                           stream and its `fold_plan`: one launch (and a 16-byte memset),
+ *                           asynchronous, capturable, no read-back.  The layout is private.  The
+ *                           launch counts every span's heads again; the map is marked valid only
+ *                           if the plan was made for this N and layout, every span found the
+ *                           plan's count and H fits map_bytes -- a stale plan makes a map that
+ *                           every call refuses.  KIMG_EWORKSPACE: map_bytes below
+ *                           kimg_fold_map_bytes(N, P, 0).
+ *   kimg_fold_runs_mapped   kimg_fold_runs with `fold_map`: one launch.  The header's uv and
+ *                           w_plane then point INTO THE MAP, vis into the workspace.  The sums are
+ *                           bit for bit those of kimg_fold_runs_planned, for any samples: the same
+ *                           additions in the same order.  NULL: kimg_fold_runs.
+ *   kimg_grid_mapped        kimg_grid with `fold_map` for the MFMA variant's pre-pass, at any N,
+ *                           under the conditions of kimg_grid_planned.  NULL: kimg_grid.
+ * UNLIKE A PLAN, A MAP IS BELIEVED.  It belongs to the exact bytes of uv[0..N) and w_plane[0..N) it
+ * was made from, and the calls do not look at them again:
+ *   - a map of another N or span layout (another P may be one), one that was never valid, one
+ *     whose H exceeds the capacity (N / 2 for kimg_grid_mapped) and arbitrary bytes are refused on
+ *     the device: use_folded is 0 and kimg_grid grids the caller's stream.  That costs time only.
+ *   - a valid map whose coordinates have since been rewritten in place gives a WRONG grid: make a
+ *     new plan and map after changing uv or w_plane.
+ *   - in no case, junk included, does a map cause a write outside the workspace or the grid: every
+ *     sum's index is checked against the capacity, and the window kernel range-checks the
+ *     compacted coordinates like any caller's.
+ * KIMG_EINVAL for a map that is not 16-byte aligned. */
+size_t kimg_fold_map_bytes(int64_t num_vis, int num_polarizations, int64_t heads);
+int kimg_fold_map(const int16_t *uv, const int16_t *w_plane, int64_t num_vis, int num_polarizations,
+                  const void *fold_plan, void *map, size_t map_bytes, void *stream);
+int kimg_fold_runs_mapped(const int16_t *uv, const int16_t *w_plane, const void *vis,
+                          int64_t num_vis, int num_polarizations, int64_t capacity, void *workspace,
+                          size_t workspace_bytes, void *stream, const void *fold_map);
+int kimg_grid_mapped(void *grid, int64_t grid_row, int64_t grid_pol, int grid_size,
+                     int num_polarizations,
+                     const float *weights_grid, int64_t wg_row, int64_t wg_pol,
+                     const int16_t *uv, const int16_t *w_plane, const void *vis, int64_t num_vis,
+                     const void *convolve_kernel, int w_planes, int oversample, int kernel_width,
+                     void *workspace, size_t workspace_bytes, int variant, int arith, void *stream,
+                     const void *fold_map);
 
 /* ---- degridding: grid.py:985-1029 Degridder.static_run/_run + degrid.mako:77-199
  * vis[r][p] -= weights[r][p] * sum_{j,k} kern[w][sub_v][j]*kern[w][sub_u][k]*grid[p][v0+j][u0+k]

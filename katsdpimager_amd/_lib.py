@@ -37,6 +37,12 @@ PROTOTYPES = {
     'kimg_fold_plan': (c_int, [P, P, L, I, P, P]),
     'kimg_fold_runs_planned': (c_int, [P, P, P, L, I, L, P, c_size_t, P, P]),
     'kimg_grid_planned': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, I, P, P]),
+    # fold maps: (num_vis, P, heads); (uv, w_plane, num_vis, P, plan, map, map_bytes, stream); the
+    # unplanned argument lists plus the map
+    'kimg_fold_map_bytes': (c_size_t, [L, I, L]),
+    'kimg_fold_map': (c_int, [P, P, L, I, P, P, c_size_t, P]),
+    'kimg_fold_runs_mapped': (c_int, [P, P, P, L, I, L, P, c_size_t, P, P]),
+    'kimg_grid_mapped': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, I, P, P]),
     'kimg_degrid': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, I, P]),
     'kimg_degrid_workspace_bytes': (c_size_t, [I, I, I, I]),
     'kimg_degrid_binned_workspace_bytes': (c_size_t, [L, I, I, I, I]),

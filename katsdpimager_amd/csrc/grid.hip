@@ -233,18 +233,21 @@ extern "C" size_t kimg_grid_workspace_bytes(int64_t max_vis, int num_polarizatio
 }
 
 // fold_plan: null, or a fold plan of (uv, w_plane, num_vis, P) for the MFMA variant's pre-pass; the
-// other variants have no use for it (the binned one grids a re-ordered copy of the stream)
-extern "C" int kimg_grid_planned(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
-                                 int grid_size, int num_polarizations, const float *weights_grid,
-                                 int64_t wg_row_stride, int64_t wg_pol_stride, const int16_t *uv,
-                                 const int16_t *w_plane, const void *vis, int64_t num_vis,
-                                 const void *convolve_kernel, int w_planes, int oversample,
-                                 int kernel_width, void *workspace, size_t workspace_bytes,
-                                 int variant, int arith, void *stream, const void *fold_plan)
+// other variants have no use for it (the binned one grids a re-ordered copy of the stream).
+// fold_map: null, or a fold map of the same stream, which comes before a plan.
+static int grid_any(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
+                    int grid_size, int num_polarizations, const float *weights_grid,
+                    int64_t wg_row_stride, int64_t wg_pol_stride, const int16_t *uv,
+                    const int16_t *w_plane, const void *vis, int64_t num_vis,
+                    const void *convolve_kernel, int w_planes, int oversample,
+                    int kernel_width, void *workspace, size_t workspace_bytes,
+                    int variant, int arith, void *stream, const void *fold_plan,
+                    const void *fold_map)
 {
     KIMG_CHECK_ARG(grid && weights_grid && uv && w_plane && vis && convolve_kernel);
     KIMG_CHECK_ARG(grid_row_stride >= grid_size && wg_row_stride >= grid_size);
     KIMG_CHECK_ARG((reinterpret_cast<uintptr_t>(fold_plan) & 15) == 0);
+    KIMG_CHECK_ARG((reinterpret_cast<uintptr_t>(fold_map) & 15) == 0);
     // (the window kernels take the three bits themselves)
     const int form = arith & ~(KIMG_ARITH_NO_FOLD | KIMG_ARITH_PREFOLD | KIMG_ARITH_NO_PREFOLD);
     KIMG_CHECK_ARG(!((arith & KIMG_ARITH_NO_FOLD) && (arith & KIMG_ARITH_PREFOLD)));
@@ -286,7 +289,8 @@ extern "C" int kimg_grid_planned(void *grid, int64_t grid_row_stride, int64_t gr
         return kimg_grid_mfma(grid, grid_row_stride, grid_pol_stride, grid_size,
                               num_polarizations, weights_grid, wg_row_stride, wg_pol_stride, uv,
                               w_plane, vis, num_vis, convolve_kernel, w_planes, oversample,
-                              kernel_width, workspace, workspace_bytes, arith, s, fold_plan);
+                              kernel_width, workspace, workspace_bytes, arith, s, fold_plan,
+                              fold_map);
     int blocks = kimg_divup(num_vis, 4);
     if (blocks > 8192)
         blocks = 8192;
@@ -296,6 +300,34 @@ extern "C" int kimg_grid_planned(void *grid, int64_t grid_row_stride, int64_t gr
             wg_pol_stride, uv, w_plane, (const float2 *) vis, num_vis,
             (const float2 *) convolve_kernel, oversample, kernel_width); });
     return kimg_launch_status();
+}
+
+extern "C" int kimg_grid_planned(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
+                                 int grid_size, int num_polarizations, const float *weights_grid,
+                                 int64_t wg_row_stride, int64_t wg_pol_stride, const int16_t *uv,
+                                 const int16_t *w_plane, const void *vis, int64_t num_vis,
+                                 const void *convolve_kernel, int w_planes, int oversample,
+                                 int kernel_width, void *workspace, size_t workspace_bytes,
+                                 int variant, int arith, void *stream, const void *fold_plan)
+{
+    return grid_any(grid, grid_row_stride, grid_pol_stride, grid_size, num_polarizations,
+                    weights_grid, wg_row_stride, wg_pol_stride, uv, w_plane, vis, num_vis,
+                    convolve_kernel, w_planes, oversample, kernel_width, workspace, workspace_bytes,
+                    variant, arith, stream, fold_plan, nullptr);
+}
+
+extern "C" int kimg_grid_mapped(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
+                                int grid_size, int num_polarizations, const float *weights_grid,
+                                int64_t wg_row_stride, int64_t wg_pol_stride, const int16_t *uv,
+                                const int16_t *w_plane, const void *vis, int64_t num_vis,
+                                const void *convolve_kernel, int w_planes, int oversample,
+                                int kernel_width, void *workspace, size_t workspace_bytes,
+                                int variant, int arith, void *stream, const void *fold_map)
+{
+    return grid_any(grid, grid_row_stride, grid_pol_stride, grid_size, num_polarizations,
+                    weights_grid, wg_row_stride, wg_pol_stride, uv, w_plane, vis, num_vis,
+                    convolve_kernel, w_planes, oversample, kernel_width, workspace, workspace_bytes,
+                    variant, arith, stream, nullptr, fold_map);
 }
 
 extern "C" int kimg_grid(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,

@@ -29,6 +29,12 @@
 // use_folded only if every span found the count the plan gave it.  Then the offsets were the right
 // ones and the output is what the two launches write; else the window kernel grids the caller's
 // stream.  Output indices are checked against the capacity whatever the plan holds.
+//
+// A fold map (kimg_fold_map) keeps the rest of what uv and w_plane decide: every thread's heads, one
+// byte per 8 records, and the compacted coordinates.  A call that is given one reads the samples
+// and the head bits and writes the sums -- launch 2 with its key loads, comparisons and coordinate
+// stores compiled out, so the sums are added in the same order.  The map is checked when it is made,
+// span by span like a plan, and believed afterwards: it belongs to the bytes it was made from.
 #include "kimg_record_stream.h"
 
 namespace {
@@ -88,12 +94,45 @@ inline fold_plan fold_plan_of(int64_t num_vis, int P)
     return p;
 }
 
+// A fold map's sections behind its kimg_fold_map_data: the head bits, one byte per thread and tile,
+// then the compacted uv and w_plane.  Where w_plane begins depends on H alone, which both the launch
+// that fills a map and the pass that uses it sum from the same counts.
+__host__ __device__ inline size_t fold_map_bits_bytes(int64_t num_vis)
+{
+    return ((size_t) (num_vis + FOLD_RECORDS - 1) / FOLD_RECORDS + 15) & ~(size_t) 15;
+}
+
+__host__ __device__ inline int64_t fold_map_round(int64_t heads) { return (heads + 7) & ~(int64_t) 7; }
+
+__host__ __device__ inline const uint8_t *fold_map_bits(const kimg_fold_map_data *map)
+{
+    return reinterpret_cast<const uint8_t *>(map + 1);
+}
+
+__host__ __device__ inline const int2 *fold_map_uv(const kimg_fold_map_data *map, int64_t num_vis)
+{
+    return reinterpret_cast<const int2 *>(fold_map_bits(map) + fold_map_bits_bytes(num_vis));
+}
+
+__host__ __device__ inline const int16_t *fold_map_w(const kimg_fold_map_data *map, int64_t num_vis,
+                                                     int64_t H)
+{
+    return reinterpret_cast<const int16_t *>(fold_map_uv(map, num_vis) + fold_map_round(H));
+}
+
+inline size_t fold_map_bytes(int64_t num_vis, int64_t heads)
+{
+    return sizeof(kimg_fold_map_data) + fold_map_bits_bytes(num_vis)
+           + (size_t) fold_map_round(heads) * (sizeof(int2) + sizeof(int16_t));
+}
+
 // The keys of a thread's 8 records [i0, i0 + 8) and of the record before them
 struct fold_keys {
     int2 uv[FOLD_RECORDS];
     int wp[FOLD_RECORDS];
     int2 prev_uv;
     int prev_wp;
+    unsigned heads;                 // (a fold map's pass: fold_heads as the map keeps it, no keys)
 };
 
 // (uv, w_plane 16-byte aligned; i0 a multiple of 8: whole 16-byte words while the thread's records
@@ -288,14 +327,24 @@ __device__ __attribute__((always_inline)) inline void fold_load_samples(
 // of any value give offsets in [0, H] with H <= capacity, and every store below checks its index
 // against the capacity.  Each workgroup leaves its own count of heads in `recount` and, with a
 // ticket, whether it was the plan's; the last one to finish writes use_folded.
-template <int P, bool PLANNED>
+//
+// MAPPED: `counts` are a fold map's (`map`, untrusted device data as well), and so are the heads: no
+// key is loaded or compared and no coordinate stored -- the header points at the map's.  All else is
+// the one body: the sums of the samples are added in the order of the unmapped forms, so out_vis is
+// theirs bit for bit.  A map was checked span by span when it was made (`valid`, fold_map_kernel);
+// one that is not valid, or is another length's or layout's, is refused by every workgroup alike.
+// Its head bits are believed: wrong ones give wrong sums, at indices that every store still checks
+// against the capacity.
+template <int P, bool PLANNED, bool MAPPED>
 __global__ __launch_bounds__(FOLD_THREADS) void fold_compact_kernel(
     const int16_t *__restrict__ uv, const int16_t *__restrict__ w_plane,
     const float2 *__restrict__ vis, int64_t num_vis, int64_t tiles_per_span, int spans,
     const uint32_t *__restrict__ counts, int64_t capacity, kimg_fold_header *__restrict__ header,
     int2 *__restrict__ out_uv, int16_t *__restrict__ out_w, float2 *__restrict__ out_vis,
-    const kimg_fold_plan_data *__restrict__ plan, uint32_t *__restrict__ recount)
+    const kimg_fold_plan_data *__restrict__ plan, uint32_t *__restrict__ recount,
+    const kimg_fold_map_data *__restrict__ map)
 {
+    static_assert(!(PLANNED && MAPPED), "a map holds its plan's counts, checked when it was made");
     __shared__ unsigned long long s_red[FOLD_WAVES];
     __shared__ fold_elem<P> s_tot[2][FOLD_WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -304,6 +353,10 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_compact_kernel(
     if (PLANNED)
         plan_ok = plan->magic == KIMG_FOLD_PLAN_MAGIC && plan->spans == (uint32_t) spans
                   && plan->num_vis == num_vis && plan->tiles_per_span == tiles_per_span;
+    if (MAPPED)
+        plan_ok = map->magic == KIMG_FOLD_MAP_MAGIC && map->valid == 1u
+                  && map->spans == (uint32_t) spans && map->num_vis == num_vis
+                  && map->tiles_per_span == tiles_per_span;
     // the records before this span, and all of them: every workgroup reads the same counts and
     // takes the same decision
     unsigned long long before = 0, all = 0;
@@ -314,14 +367,21 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_compact_kernel(
     }
     const int64_t offset = (int64_t) fold_block_sum(before, s_red);
     const int64_t H = (int64_t) fold_block_sum(all, s_red);
-    const bool use = plan_ok && 2 * H <= num_vis && H <= capacity;
+    bool use = plan_ok && 2 * H <= num_vis && H <= capacity;
+    if (MAPPED)                     // (the sum its maker wrote: where the map's w_plane begins)
+        use = use && map->count == H;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         if (!PLANNED || !use)       // (a plan's verdict comes with the last ticket)
             header->use_folded = use ? 1u : 0u;
         header->spans = (uint32_t) spans;
         header->count = H;
-        header->uv = reinterpret_cast<const int16_t *>(out_uv);
-        header->w_plane = out_w;
+        if (MAPPED) {
+            header->uv = reinterpret_cast<const int16_t *>(fold_map_uv(map, num_vis));
+            header->w_plane = fold_map_w(map, num_vis, H);
+        } else {
+            header->uv = reinterpret_cast<const int16_t *>(out_uv);
+            header->w_plane = out_w;
+        }
         header->vis = out_vis;
         header->capacity = capacity;
     }
@@ -331,15 +391,19 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_compact_kernel(
     const int64_t span_start = (int64_t) blockIdx.x * tiles_per_span * FOLD_TILE;
     int64_t span_end = span_start + tiles_per_span * FOLD_TILE;
     span_end = span_end < num_vis ? span_end : num_vis;
-    // a tile's loads are issued before the tile before it is worked on (one polarization: with more
-    // the second set of registers would cost a wave per SIMD)
-    constexpr bool PREFETCH = P == 1;
+    // a tile's loads are issued before the tile before it is worked on (one polarization, and two
+    // without the keys: with more the second set of registers would cost a wave per SIMD)
+    constexpr bool PREFETCH = P == 1 || (MAPPED && P == 2);
     fold_keys keys, next_keys;
     fold_samples<P> smp, next_smp;
+    const uint8_t *__restrict__ map_bits = MAPPED ? fold_map_bits(map) : nullptr;
     auto load_tile = [&](int64_t tile, fold_keys &k, fold_samples<P> &s) __attribute__((always_inline)) {
         const int64_t i0 = tile + (int64_t) threadIdx.x * FOLD_RECORDS;
         if (tile < span_end && i0 < num_vis) {
-            fold_load_keys(uv, w_plane, i0, num_vis, span_start, k);
+            if (MAPPED)
+                k.heads = map_bits[i0 / FOLD_RECORDS];
+            else
+                fold_load_keys(uv, w_plane, i0, num_vis, span_start, k);
             fold_load_samples<P>(vis, i0, num_vis, s);
         }
     };
@@ -358,7 +422,8 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_compact_kernel(
             load_tile(tile + FOLD_TILE, next_keys, next_smp);
         else
             load_tile(tile, keys, smp);
-        const unsigned heads = i0 < num_vis ? fold_heads(keys, i0, num_vis, span_start) : 0u;
+        const unsigned heads = i0 >= num_vis ? 0u
+            : MAPPED ? keys.heads : fold_heads(keys, i0, num_vis, span_start);
         // this thread's element: its heads and the sum since its last head
         fold_elem<P> e;
         e.cnt = __builtin_popcount(heads);
@@ -422,7 +487,7 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_compact_kernel(
 #pragma unroll
                     for (int p = 0; p < P; p++)
                         out_vis[(r - 1) * P + p] = acc[p];
-                if (r < capacity) {
+                if (!MAPPED && r < capacity) {
                     out_uv[r] = keys.uv[j];
                     out_w[r] = (int16_t) keys.wp[j];
                 }
@@ -460,6 +525,107 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_compact_kernel(
     }
 }
 
+// Fills a fold map from a stream and its plan: the span layout, offsets and ticket of the planned
+// compaction, without the samples.  Every thread leaves its fold_heads, every head its coordinates
+// at the index the compaction gives it -- checked against `heads_room`, the records the buffer
+// holds, whatever the plan says.  `valid` becomes 1 only when the plan was this layout's, its H fits
+// the buffer and every span counted what the plan gave it: a stale plan makes a map that no call
+// will use.  (map->ticket zeroed ahead of the launch.)
+__global__ __launch_bounds__(FOLD_THREADS) void fold_map_kernel(
+    const int16_t *__restrict__ uv, const int16_t *__restrict__ w_plane, int64_t num_vis,
+    int64_t tiles_per_span, int spans, const kimg_fold_plan_data *__restrict__ plan,
+    int64_t heads_room, kimg_fold_map_data *__restrict__ map)
+{
+    __shared__ unsigned long long s_red[FOLD_WAVES];
+    __shared__ int s_cnt[2][FOLD_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+
+    const bool plan_ok = plan->magic == KIMG_FOLD_PLAN_MAGIC && plan->spans == (uint32_t) spans
+                         && plan->num_vis == num_vis && plan->tiles_per_span == tiles_per_span;
+    unsigned long long before = 0, all = 0;
+    for (int i = threadIdx.x; i < spans; i += FOLD_THREADS) {
+        const unsigned c = plan->counts[i];
+        all += c;
+        before += i < (int) blockIdx.x ? c : 0u;
+    }
+    const int64_t offset = (int64_t) fold_block_sum(before, s_red);
+    const int64_t H = (int64_t) fold_block_sum(all, s_red);
+    const bool ok = plan_ok && H <= heads_room;
+    if (blockIdx.x == 0) {
+        for (int i = threadIdx.x; i < KIMG_FOLD_MAX_SPANS; i += FOLD_THREADS)
+            map->counts[i] = i < spans ? plan->counts[i] : 0u;
+        if (threadIdx.x == 0) {
+            map->magic = KIMG_FOLD_MAP_MAGIC;
+            map->spans = (uint32_t) spans;
+            map->num_vis = num_vis;
+            map->tiles_per_span = tiles_per_span;
+            map->count = H;
+            map->heads = heads_room;
+            map->reserved = 0;
+            if (!ok)                // (else the last ticket's)
+                map->valid = 0;
+        }
+    }
+    if (!ok)
+        return;
+
+    uint8_t *__restrict__ bits = const_cast<uint8_t *>(fold_map_bits(map));
+    int2 *__restrict__ out_uv = const_cast<int2 *>(fold_map_uv(map, num_vis));
+    int16_t *__restrict__ out_w = const_cast<int16_t *>(fold_map_w(map, num_vis, H));
+    const int64_t span_start = (int64_t) blockIdx.x * tiles_per_span * FOLD_TILE;
+    int64_t span_end = span_start + tiles_per_span * FOLD_TILE;
+    span_end = span_end < num_vis ? span_end : num_vis;
+    int64_t run_base = offset;      // output index of the next tile's first head
+    int parity = 0;
+    for (int64_t tile = span_start; tile < span_end; tile += FOLD_TILE, parity ^= 1) {
+        const int64_t i0 = tile + (int64_t) threadIdx.x * FOLD_RECORDS;
+        fold_keys keys;
+        unsigned heads = 0;
+        if (i0 < num_vis) {
+            fold_load_keys(uv, w_plane, i0, num_vis, span_start, keys);
+            heads = fold_heads(keys, i0, num_vis, span_start);
+            bits[i0 / FOLD_RECORDS] = (uint8_t) heads;
+        }
+        // heads before this thread in its tile: a scan over the wave, the waves' totals through LDS
+        const int cnt = __builtin_popcount(heads);
+        int inc = cnt;
+#pragma unroll
+        for (int d = 1; d < WAVE; d *= 2) {
+            const int o = __shfl_up(inc, d, WAVE);
+            if (lane >= d)
+                inc += o;
+        }
+        if (lane == WAVE - 1)
+            s_cnt[parity][wave] = inc;
+        __syncthreads();        // (one per tile: s_cnt alternates between two copies)
+        int prefix = 0, whole = 0;
+#pragma unroll
+        for (int w = 0; w < FOLD_WAVES; w++) {
+            prefix += w < wave ? s_cnt[parity][w] : 0;
+            whole += s_cnt[parity][w];
+        }
+        int64_t r = run_base + prefix + inc - cnt;
+#pragma unroll
+        for (int j = 0; j < FOLD_RECORDS; j++) {
+            if ((heads >> j) & 1u) {
+                if (r < heads_room) {
+                    out_uv[r] = keys.uv[j];
+                    out_w[r] = (int16_t) keys.wp[j];
+                }
+                r++;
+            }
+        }
+        run_base += whole;
+    }
+    if (threadIdx.x == 0) {
+        const int64_t mine = run_base - offset;
+        const unsigned add = 1u + (mine != (int64_t) plan->counts[blockIdx.x] ? 0x10000u : 0u);
+        const unsigned now = atomicAdd(&map->ticket[0], add) + add;
+        if ((now & 0xffffu) == (unsigned) spans)
+            map->valid = (now >> 16) == 0 ? 1u : 0u;
+    }
+}
+
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 } // namespace
@@ -471,27 +637,67 @@ size_t kimg_fold_workspace_bytes(int P, int64_t capacity)
 
 int kimg_fold_launch(const int16_t *uv, const int16_t *w_plane, const float2 *vis, int64_t num_vis,
                      int P, int64_t capacity, void *workspace, hipStream_t stream,
-                     const kimg_fold_plan_data *plan_data)
+                     const kimg_fold_plan_data *plan_data, const kimg_fold_map_data *map)
 {
     if (capacity < 0)
         capacity = 0;
     const fold_ws ws = fold_carve(P, capacity, workspace);
     const fold_plan plan = fold_plan_of(num_vis, P);
+    if (map != nullptr) {
+        // one launch: the samples in, the sums out
+        kimg_for_pols(P, [&](auto p) {
+            fold_compact_kernel<decltype(p)::value, false, true>
+                <<<plan.spans, FOLD_THREADS, 0, stream>>>(
+                uv, w_plane, vis, num_vis, plan.tiles_per_span, plan.spans, map->counts, capacity,
+                ws.header, ws.uv, ws.w_plane, ws.vis, nullptr, nullptr, map); });
+        return kimg_launch_status();
+    }
     if (plan_data != nullptr) {
         // the workspace's counts are free for the spans' own counts
         KIMG_HIP(hipMemsetAsync(ws.header->ticket, 0, sizeof(ws.header->ticket), stream));
         kimg_for_pols(P, [&](auto p) {
-            fold_compact_kernel<decltype(p)::value, true><<<plan.spans, FOLD_THREADS, 0, stream>>>(
+            fold_compact_kernel<decltype(p)::value, true, false>
+                <<<plan.spans, FOLD_THREADS, 0, stream>>>(
                 uv, w_plane, vis, num_vis, plan.tiles_per_span, plan.spans, plan_data->counts,
-                capacity, ws.header, ws.uv, ws.w_plane, ws.vis, plan_data, ws.counts); });
+                capacity, ws.header, ws.uv, ws.w_plane, ws.vis, plan_data, ws.counts, nullptr); });
         return kimg_launch_status();
     }
     fold_count_kernel<<<plan.spans, FOLD_THREADS, 0, stream>>>(uv, w_plane, num_vis,
                                                                plan.tiles_per_span, ws.counts);
     kimg_for_pols(P, [&](auto p) {
-        fold_compact_kernel<decltype(p)::value, false><<<plan.spans, FOLD_THREADS, 0, stream>>>(
+        fold_compact_kernel<decltype(p)::value, false, false>
+            <<<plan.spans, FOLD_THREADS, 0, stream>>>(
             uv, w_plane, vis, num_vis, plan.tiles_per_span, plan.spans, ws.counts, capacity,
-            ws.header, ws.uv, ws.w_plane, ws.vis, nullptr, nullptr); });
+            ws.header, ws.uv, ws.w_plane, ws.vis, nullptr, nullptr, nullptr); });
+    return kimg_launch_status();
+}
+
+extern "C" size_t kimg_fold_map_bytes(int64_t num_vis, int num_polarizations, int64_t heads)
+{
+    if (num_vis < 1 || num_polarizations < 1 || num_polarizations > 4 || heads < 0)
+        return 0;
+    return fold_map_bytes(num_vis, heads);
+}
+
+extern "C" int kimg_fold_map(const int16_t *uv, const int16_t *w_plane, int64_t num_vis,
+                             int num_polarizations, const void *plan, void *map,
+                             size_t map_bytes, void *stream)
+{
+    KIMG_CHECK_ARG(uv && w_plane && plan && map && num_vis >= 1);
+    if (num_polarizations < 1 || num_polarizations > 4)
+        return KIMG_EUNSUPPORTED;
+    KIMG_CHECK_ARG(aligned16(uv) && aligned16(w_plane) && aligned16(plan) && aligned16(map));
+    if (map_bytes < fold_map_bytes(num_vis, 0))
+        return KIMG_EWORKSPACE;
+    // the records the buffer has room for: whole eights of 10 bytes each
+    const int64_t heads_room = (int64_t) ((map_bytes - fold_map_bytes(num_vis, 0)) / 80) * 8;
+    kimg_fold_map_data *data = static_cast<kimg_fold_map_data *>(map);
+    const fold_plan layout = fold_plan_of(num_vis, num_polarizations);
+    hipStream_t s = (hipStream_t) stream;
+    KIMG_HIP(hipMemsetAsync(data->ticket, 0, sizeof(data->ticket), s));
+    fold_map_kernel<<<layout.spans, FOLD_THREADS, 0, s>>>(
+        uv, w_plane, num_vis, layout.tiles_per_span, layout.spans,
+        static_cast<const kimg_fold_plan_data *>(plan), heads_room, data);
     return kimg_launch_status();
 }
 
@@ -521,21 +727,39 @@ extern "C" size_t kimg_fold_runs_workspace_bytes(int num_polarizations, int64_t 
     return kimg_fold_workspace_bytes(num_polarizations, capacity);
 }
 
-extern "C" int kimg_fold_runs_planned(const int16_t *uv, const int16_t *w_plane, const void *vis,
-                                      int64_t num_vis, int num_polarizations, int64_t capacity,
-                                      void *workspace, size_t workspace_bytes, void *stream,
-                                      const void *fold_plan)
+static int fold_runs_any(const int16_t *uv, const int16_t *w_plane, const void *vis,
+                         int64_t num_vis, int num_polarizations, int64_t capacity, void *workspace,
+                         size_t workspace_bytes, void *stream, const void *plan, const void *map)
 {
     KIMG_CHECK_ARG(uv && w_plane && vis && workspace && num_vis >= 1 && capacity >= 0);
     if (num_polarizations < 1 || num_polarizations > 4)
         return KIMG_EUNSUPPORTED;
     KIMG_CHECK_ARG(aligned16(uv) && aligned16(w_plane) && aligned16(vis) && aligned16(workspace)
-                   && aligned16(fold_plan));
+                   && aligned16(plan) && aligned16(map));
     if (workspace_bytes < kimg_fold_workspace_bytes(num_polarizations, capacity))
         return KIMG_EWORKSPACE;
     return kimg_fold_launch(uv, w_plane, static_cast<const float2 *>(vis), num_vis,
                             num_polarizations, capacity, workspace, (hipStream_t) stream,
-                            static_cast<const kimg_fold_plan_data *>(fold_plan));
+                            static_cast<const kimg_fold_plan_data *>(plan),
+                            static_cast<const kimg_fold_map_data *>(map));
+}
+
+extern "C" int kimg_fold_runs_planned(const int16_t *uv, const int16_t *w_plane, const void *vis,
+                                      int64_t num_vis, int num_polarizations, int64_t capacity,
+                                      void *workspace, size_t workspace_bytes, void *stream,
+                                      const void *fold_plan)
+{
+    return fold_runs_any(uv, w_plane, vis, num_vis, num_polarizations, capacity, workspace,
+                         workspace_bytes, stream, fold_plan, nullptr);
+}
+
+extern "C" int kimg_fold_runs_mapped(const int16_t *uv, const int16_t *w_plane, const void *vis,
+                                     int64_t num_vis, int num_polarizations, int64_t capacity,
+                                     void *workspace, size_t workspace_bytes, void *stream,
+                                     const void *fold_map)
+{
+    return fold_runs_any(uv, w_plane, vis, num_vis, num_polarizations, capacity, workspace,
+                         workspace_bytes, stream, nullptr, fold_map);
 }
 
 extern "C" int kimg_fold_runs(const int16_t *uv, const int16_t *w_plane, const void *vis,

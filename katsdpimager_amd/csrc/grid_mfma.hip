@@ -1577,12 +1577,13 @@ int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
                    const int16_t *uv, const int16_t *w_plane, const void *vis, int64_t num_vis,
                    const void *convolve_kernel, int w_planes, int oversample, int kernel_width,
                    void *workspace, size_t workspace_bytes, int arith, hipStream_t stream,
-                   const void *fold_plan)
+                   const void *fold_plan, const void *fold_map)
 {
     const bool fold = !(arith & KIMG_ARITH_NO_FOLD);
     const bool prefold_never = (arith & KIMG_ARITH_NO_PREFOLD) != 0;
-    // (a fold plan is the caller's statement that the stream folds: the pre-pass at any length)
-    const bool prefold_always = (arith & KIMG_ARITH_PREFOLD) != 0 || fold_plan != nullptr;
+    // (a fold plan or map is the caller's statement that the stream folds: the pre-pass at any length)
+    const bool prefold_always = (arith & KIMG_ARITH_PREFOLD) != 0 || fold_plan != nullptr
+                                || fold_map != nullptr;
     arith &= ~(KIMG_ARITH_NO_FOLD | KIMG_ARITH_PREFOLD | KIMG_ARITH_NO_PREFOLD);
     const bool in_lds = table_in_lds(P, w_planes, oversample, kernel_width);
     if (!in_lds && (workspace == nullptr
@@ -1603,7 +1604,8 @@ int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
         void *fold_ws = static_cast<unsigned char *>(workspace) + (own_bytes - 256);
         if (const int rc = kimg_fold_launch(uv, w_plane, (const float2 *) vis, num_vis, P, num_vis / 2,
                                             fold_ws, stream,
-                                            static_cast<const kimg_fold_plan_data *>(fold_plan)))
+                                            static_cast<const kimg_fold_plan_data *>(fold_plan),
+                                            static_cast<const kimg_fold_map_data *>(fold_map)))
             return rc;
         folded = static_cast<const kimg_fold_header *>(fold_ws);
     }

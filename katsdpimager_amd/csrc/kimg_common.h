@@ -73,7 +73,7 @@ int kimg_grid_mfma(void *grid, int64_t grid_row_stride, int64_t grid_pol_stride,
                    const int16_t *uv, const int16_t *w_plane, const void *vis, int64_t num_vis,
                    const void *convolve_kernel, int w_planes, int oversample, int kernel_width,
                    void *workspace, size_t workspace_bytes, int arith, hipStream_t stream,
-                   const void *fold_plan = nullptr);
+                   const void *fold_plan = nullptr, const void *fold_map = nullptr);
 bool kimg_grid_mfma_supported(int P, int w_planes, int oversample, int kernel_width);
 size_t kimg_grid_mfma_workspace_bytes(int P, int w_planes, int oversample, int kernel_width);
 // What kimg_grid_mfma needs ON TOP of the above to run the fold pre-pass on num_vis records, and the
@@ -115,12 +115,30 @@ struct kimg_fold_plan_data {
     uint32_t reserved[8];
     uint32_t counts[KIMG_FOLD_MAX_SPANS];   // heads of runs per span
 };
+// A fold map (kimg_fold_map, include/kimg.h): what the pre-pass derives from uv and w_plane alone,
+// kept by the caller in device memory -- this block, then one byte of head bits per 8 records (a
+// thread's fold_heads; padded to 16 bytes), then the compacted uv (int2 [H], H rounded up to 8) and
+// w_plane (int16 [H]).  Trusted for results once `valid` is set, never for addresses: see
+// fold_compact_kernel.
+constexpr uint32_t KIMG_FOLD_MAP_MAGIC = 0x314d4c46u;      // "FLM1"
+struct kimg_fold_map_data {
+    uint32_t magic, spans;          // as in the plan it was made from
+    int64_t num_vis, tiles_per_span;
+    int64_t count;                  // H
+    int64_t heads;                  // records the buffer has room for
+    uint32_t valid;                 // 1: every span found the plan's count when the map was made
+    uint32_t reserved;
+    uint32_t ticket[4];             // (of the launch that fills the map, as kimg_fold_header's)
+    uint32_t counts[KIMG_FOLD_MAX_SPANS];
+};
 size_t kimg_fold_workspace_bytes(int P, int64_t capacity);
 // (16-byte aligned uv, w_plane, vis and workspace; workspace of at least the size above; `plan`: null
-// or a fold plan in device memory, which replaces the count launch)
+// or a fold plan in device memory, which replaces the count launch; `map`: null or a fold map, which
+// replaces the key loads and the compacted coordinates as well, and comes before a plan)
 int kimg_fold_launch(const int16_t *uv, const int16_t *w_plane, const float2 *vis, int64_t num_vis,
                      int P, int64_t capacity, void *workspace, hipStream_t stream,
-                     const kimg_fold_plan_data *plan = nullptr);
+                     const kimg_fold_plan_data *plan = nullptr,
+                     const kimg_fold_map_data *map = nullptr);
 // *out = the bit pattern of the largest |component| among the n floats of a kernel table (ktable.hip):
 // the fp16 hi/lo forms of the window kernels choose their table scale from it when the table is in
 // HBM.  (Hidden: a helper between two units of the library, no part of its dynamic symbol table.)

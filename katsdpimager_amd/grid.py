@@ -229,13 +229,20 @@ class FoldPlan:
     """One measurement of a (uv, w_plane, num_vis) stream for the gridder's fold pre-pass
     (``kimg_fold_plan``, include/kimg.h): ``heads`` runs among ``num_vis`` records of
     ``polarizations`` polarizations, and the device buffer ``plan`` that spares every gridding
-    call on that stream the count launch.  It says nothing about any other stream."""
+    call on that stream the count launch.  It says nothing about any other stream.
 
-    def __init__(self, plan, heads, num_vis, polarizations):
+    ``map`` (``kimg_fold_map``; None: no map) is the device buffer that also spares those calls the
+    coordinates: which records head a run, and the compacted uv and w_plane.  It lives and dies with
+    the plan.  Unlike the plan it is believed: it holds for the exact bytes of uv and w_plane it was
+    made from, so a caller that rewrites bound coordinates IN PLACE must measure again
+    (``Gridder.measure_locality``) -- rebinding them or another length drops it by itself."""
+
+    def __init__(self, plan, heads, num_vis, polarizations, map=None):
         self.plan = plan
         self.heads = heads
         self.num_vis = num_vis
         self.polarizations = polarizations
+        self.map = map
 
     @property
     def foldable(self):
@@ -245,13 +252,21 @@ class FoldPlan:
 
 def measure_fold_plan(queue, uv, w_plane, num_vis, polarizations):
     """:class:`FoldPlan` of the first ``num_vis`` records of the device arrays ``uv`` and
-    ``w_plane`` (16-byte aligned); synchronises with ``queue`` (one small read-back)."""
+    ``w_plane`` (16-byte aligned); synchronises with ``queue`` (one small read-back).  A stream
+    that folds also gets its fold map: ``num_vis / 8 + 10 heads`` bytes, one more launch."""
     plan = accel.DeviceArray(queue.context, (int(lib().kimg_fold_plan_bytes()),), np.uint8,
                              queue=queue)
     check(lib().kimg_fold_plan(uv.ptr, w_plane.ptr, num_vis, polarizations, plan.ptr, queue.handle),
           'kimg_fold_plan')
     heads = int(plan.get(queue)[24:32].view(np.int64)[0])
-    return FoldPlan(plan, heads, num_vis, polarizations)
+    fold_plan = FoldPlan(plan, heads, num_vis, polarizations)
+    if fold_plan.foldable:
+        nbytes = int(lib().kimg_fold_map_bytes(num_vis, polarizations, heads))
+        fold_plan.map = accel.DeviceArray(queue.context, (nbytes,), np.uint8, queue=queue)
+        check(lib().kimg_fold_map(uv.ptr, w_plane.ptr, num_vis, polarizations, plan.ptr,
+                                  fold_plan.map.ptr, nbytes, queue.handle), 'kimg_fold_map')
+        queue.finish()      # (the map may be used from another queue)
+    return fold_plan
 
 
 #: `auto` variant: calls smaller than this go straight to the window kernel ...
@@ -263,7 +278,7 @@ AUTO_JUMP_FRACTION = 0.05
 
 def _tuning(tuning, real_dtype=np.float32):
     tuning = tuning or {}
-    unknown = set(tuning) - {'variant', 'arith', 'fold_runs'}
+    unknown = set(tuning) - {'variant', 'arith', 'fold_runs', 'fold_map'}
     if unknown:
         raise ValueError('unknown tuning keys: {}'.format(sorted(unknown)))
     try:
@@ -279,17 +294,21 @@ def _tuning(tuning, real_dtype=np.float32):
     fold_runs = tuning.get('fold_runs', True)
     if not isinstance(fold_runs, (bool, np.bool_)):
         raise ValueError('unknown tuning value {!r} for fold_runs'.format(fold_runs))
+    if not isinstance(tuning.get('fold_map', True), (bool, np.bool_)):
+        raise ValueError('unknown tuning value {!r} for fold_map'.format(tuning['fold_map']))
     return variant, arith, bool(fold_runs)
 
 
 class GridderTemplate:
     """grid.py:549-653.  ``tuning`` may hold ``{'variant': 'auto'|'generic'|'mfma'|'binned',
-    'arith': 'fp32'|'split_fp16'|'fp32_32x32', 'fold_runs': True|False}`` (the reference's tuning dict carries its autotuned work-group
+    'arith': 'fp32'|'split_fp16'|'fp32_32x32', 'fold_runs': True|False, 'fold_map': True|False}`` (the reference's tuning dict carries its autotuned work-group
     shape; there is no autotuner here -- the kernel geometry is fixed by the MFMA tile shape).
     All are per template, passed to the C ABI on every call: nothing is read from the environment.
     ``fold_runs`` (default True): the window kernel sums the weighted samples of consecutive records
     with equal (u, v, sub_u, sub_v, w_plane) and applies one update (include/kimg.h); the float64
     gridder and the degridder have no such step and ignore the key.
+    ``fold_map`` (default True): calls on a measured stream that folds use its fold map
+    (``kimg_grid_mapped``); False keeps them on the plan alone (``kimg_grid_planned``).
 
     ``mfma`` is the window kernel on the stream as it comes; ``binned`` first sorts the visibilities
     by grid tile on the device (for streams without locality: time order, shuffled).  ``auto``
@@ -310,6 +329,7 @@ class GridderTemplate:
         self.fixed_image_parameters = fixed_image_parameters
         self.fixed_grid_parameters = fixed_grid_parameters
         self.variant, self.arith, self.fold_runs = _tuning(tuning, fixed_image_parameters.real_dtype)
+        self.fold_map = bool((tuning or {}).get('fold_map', True))
         self.kernel_pad = 0
 
     def instantiate(self, *args, **kwargs):
@@ -492,6 +512,8 @@ class Gridder(GridDegrid):
     # ---- the fold plan of the bound stream (FoldPlan) -------------------------------------------
     # It belongs to this operation and the buffers bound to it: unlike `locality_hint` it is never
     # copied to another operation, and it goes when uv or w_plane is rebound or num_vis changes.
+    # Its fold map goes with it.  Coordinates rewritten IN PLACE are the one change nothing here can
+    # see: a stale plan costs time only, a stale map gives a wrong grid, so measure_locality() again.
     # `_fold` is (FoldPlan, key); the key is checked again at every call, because slots can also be
     # bound through a compound slot of an OperationSequence, which does not come through bind().
     _fold = None
@@ -564,7 +586,9 @@ class Gridder(GridDegrid):
     def measure_locality(self):
         """:meth:`GridDegrid.measure_locality`, and where the calls on the bound stream will take
         the window kernel also its :class:`FoldPlan`: every such call then skips the count launch
-        of the fold pre-pass, or the whole pre-pass if the stream does not fold."""
+        of the fold pre-pass and, with the plan's fold map, the coordinates' share of it -- or the
+        whole pre-pass if the stream does not fold.  Call it again after rewriting the bound uv or
+        w_plane in place: the map holds for the bytes it was made from."""
         f = super().measure_locality()
         self._fold = None
         if self._fold_window_route():
@@ -582,6 +606,8 @@ class Gridder(GridDegrid):
             return 'kimg_grid', 0, ()
         if not fold_plan.foldable:
             return 'kimg_grid', GRID_ARITH_NO_PREFOLD, ()
+        if fold_plan.map is not None and getattr(self.template, 'fold_map', True):
+            return 'kimg_grid_mapped', 0, (fold_plan.map.ptr,)
         return 'kimg_grid_planned', 0, (fold_plan.plan.ptr,)
 
     def _run(self):

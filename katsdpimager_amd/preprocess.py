@@ -483,8 +483,9 @@ class VisibilityReaderDevice:
                               v['weights'], v['vis'], locality, fold_plan)
 
     def _fold_plan(self, channel, w_slice):
-        """``grid.FoldPlan`` of a stored slice, measured once (``kimg_fold_plan`` + a small
-        read-back) and kept with the slice; None for a merged slice, which has no two adjacent
+        """``grid.FoldPlan`` of a stored slice, with its fold map if the slice folds, measured once
+        (``kimg_fold_plan`` + a small read-back, ``kimg_fold_map``) and kept with the slice -- the
+        map goes where the plan goes, when the slice's records change; None for a merged slice, which has no two adjacent
         records with equal coordinates, and where there is no window kernel to use it."""
         store = self._stores[channel][w_slice]
         if store.ordered and self.collector.merge:
