@@ -11,6 +11,7 @@ store -> imaging weights, PSF, major/minor cycles -> restored image, all on one 
     python examples/image_channel.py --statwt 8             (noise that differs between baselines; see statwt_band)
     python examples/image_channel.py --rfiflag              (bursts of interference in a band of noise; see rfiflag_band)
     python examples/image_channel.py --moments              (a band with two line sources into a cube; see moments_band)
+    python examples/image_channel.py --moments --imcontsub 1:1-3,5-10  (... with a continuum source, taken out on the cube)
 
 It follows the reference's per-channel flow (frontend.py:31-83 preprocess_visibilities,
 :465-658 process_channel) with the loaders and FITS output left out: the sky is three point
@@ -507,10 +508,22 @@ def moments_band(args):
     goes into a :class:`cube.SpectralCube` with the channel's noise estimate; the other channels stay
     unfilled.  The cube lives on a queue of its own: ``put`` waits for the imager's queue and the
     imager waits for the copy.  Prints moments 0, 1 and 2 (``clip_sigma=3``, radio velocity about the
-    band centre) at the two positions next to what was injected; ``--output`` writes the cube."""
+    band centre) at the two positions next to what was injected; ``--output`` writes the cube.
+
+    With ``--imcontsub ORDER[:first-last,...]`` a continuum source of 0.4 Jy, sloping by 0.01 Jy a
+    channel, lies on source A, so every channel is imaged; moment 0 is taken twice, of the cube as
+    imaged and after ``imcontsub.ImContSub`` has fitted a polynomial of that order per pixel to the
+    channels outside the listed ranges (default 1-3,5-10, the two lines) and subtracted it in place,
+    and both are printed next to the injected line integral."""
     import synth
-    from katsdpimager_amd import accel, cube, frontend, imaging, loader, parameters, preprocess, weight
+    from katsdpimager_amd import accel, cube, frontend, imaging, imcontsub, loader, parameters, preprocess, weight
     C = 12
+    contsub = None
+    if args.imcontsub:
+        order, _, spans = args.imcontsub.partition(':')
+        ranges = [(int(a), int(b) + 1) for a, b in (span.split('-') for span in (spans or '1-3,5-10').split(','))]
+        contsub = imcontsub.ImContSubParameters(int(order), line_ranges=ranges)
+        contsub.mask(C)
     line_a = np.zeros(C)
     line_a[1:4] = [0.5, 1.0, 0.5]
     line_b = np.zeros(C)
@@ -531,6 +544,8 @@ def moments_band(args):
         n = math.sqrt(1 - l * l - m * m)
         source = np.exp(-2j * np.pi * (uvw_wl[:, 0] * l + uvw_wl[:, 1] * m + uvw_wl[:, 2] * (n - 1))) / n
         vis += source[:, None] * lines[name][None, :]
+        if contsub is not None and name == 'A':
+            vis += source[:, None] * (0.4 + 0.01 * (np.arange(C) - 5.5))[None, :]
     frequencies = _frequencies(obs, C)
     rest_frequency = float(frequencies[C // 2])
     dataset = loader.LoaderArrays(uvw, vis[:, :, None].astype(np.complex64),
@@ -546,7 +561,7 @@ def moments_band(args):
     G = args.pixels
     sc = cube.SpectralCube(ctx, cube_queue, frequencies, [0], (G, G), channel_width=frequencies[1] - frequencies[0])
     for channel in range(C):
-        if line_a[channel] == 0 and line_b[channel] == 0:
+        if contsub is None and line_a[channel] == 0 and line_b[channel] == 0:
             continue
         stats = frontend.process_channel(collector.reader(), channel, imager, image_p, grid_p, clean_p,
                                          weight_p.weight_type, args.vis_block, 1, True)
@@ -556,7 +571,15 @@ def moments_band(args):
         copied = sc.put(channel, imager.buffer('dirty'), stats['noise'], wait_for=[queue.enqueue_marker()])
         queue.enqueue_wait_for_events([copied])         # (the next channel rewrites the buffer)
     params = cube.MomentParameters((0, 1, 2), rest_frequency=rest_frequency, clip_sigma=3.0)
-    maps = cube.MomentsTemplate(ctx, params).instantiate(cube_queue, sc.shape)(sc)
+    moments = cube.MomentsTemplate(ctx, params).instantiate(cube_queue, sc.shape)
+    unsubtracted = continuum_map = None
+    if contsub is not None:
+        unsubtracted = moments(sc)[0].get(cube_queue)[0]
+        fit = imcontsub.ImContSubTemplate(ctx, contsub).instantiate(cube_queue, sc.shape)(sc)
+        continuum_map = fit['continuum'].get(cube_queue)[0]
+        print('imcontsub {}: {} of {} pixels fitted'.format(
+            contsub, int((fit['count'].get(cube_queue) >= contsub.order + 1).sum()), G * G))
+    maps = moments(sc)
     host = {key: value.get(cube_queue)[0] for key, value in maps.items()}
     velocity = sc.coordinates('velocity', rest_frequency)
     width = abs(velocity[-1] - velocity[0]) / (C - 1)
@@ -575,6 +598,11 @@ def moments_band(args):
             name, lp, mp, int(host['count'][y, x])))
         for m, unit in ((0, 'Jy/beam.km/s'), (1, 'km/s'), (2, 'km/s')):
             print('  moment {}: {:12.6f} {}, injected {:12.6f}'.format(m, got[m], unit, injected[m]))
+        if contsub is not None:
+            results['sources'][name].update(unsubtracted=float(unsubtracted[y, x]),
+                                            continuum=float(continuum_map[y, x]))
+            print('  moment 0 without the subtraction: {:12.6f}; continuum map {:.4f} Jy/beam'.format(
+                float(unsubtracted[y, x]), float(continuum_map[y, x])))
     if args.output:
         from katsdpimager_amd import io, polarization
         image_p.fixed.polarizations = [polarization.STOKES_I]
@@ -640,7 +668,13 @@ def main(argv=None):
                     help='instead of the three-source channel: image a synthetic band with two line sources '
                          'into a spectral cube on the device and print moments 0, 1 and 2 at the sources '
                          'next to what was injected; --output writes the cube')
+    ap.add_argument('--imcontsub', metavar='ORDER[:first-last,...]',
+                    help='with --moments: leave a continuum source on source A, and fit and subtract a '
+                         'polynomial of this order per pixel of the cube outside the listed channels '
+                         '(default 1-3,5-10) ahead of the moments, e.g. --imcontsub 1')
     args = ap.parse_args(argv)
+    if args.imcontsub and not args.moments:
+        ap.error('--imcontsub goes with --moments')
     if args.moments:
         return moments_band(args)
     if args.rfiflag is not None:

@@ -1407,8 +1407,7 @@ int kimg_rfi_flag(const void *vis, int64_t vis_channel_pitch, float *weights,
  *   (2^31 - 1 workgroups of 256 elements).  M = 0 is then a successful call that does nothing.
  * Asynchronous on `stream`, no allocation, capturable; equal inputs give equal bits.
  * Not done here: a common restoring beam across planes, spatial smoothing of the selection,
- *   image-plane continuum subtraction, position-velocity cuts, medians (CASA moments 3 to 7, 10,
- *   11), cubes across several GPUs. */
+ *   position-velocity cuts, medians (CASA moments 3 to 7, 10, 11), cubes across several GPUs. */
 #define KIMG_MOMENTS_MAX_CHANNELS 4096
 #define KIMG_MOMENT_0 1
 #define KIMG_MOMENT_1 2
@@ -1420,6 +1419,77 @@ int kimg_moments(const float *cube, int64_t channel_pitch, int num_channels, int
                  int first, int stop, const double *x, const float *cut, const uint8_t *filled_host,
                  double width, int select_hanning, int outputs, float *moment0, float *moment1,
                  float *moment2, float *moment8, float *moment9, int32_t *count, void *stream);
+
+/* ---- Image-plane continuum subtraction (imcontsub.hip): per element of the plane of a spectral
+ * cube, a low-order polynomial fitted across the line-free channels and subtracted from every filled
+ * channel (CASA imcontsub, MIRIAD contsub) -- the image-plane partner of kimg_uvcontsub, for a cube
+ * that already exists and for continuum anywhere in the field.  The reference has none; the semantics
+ * are this library's, and katsdpimager_amd/imcontsub.py holds them once more as numpy
+ * (imcontsub_host).
+ *
+ * cube: DEVICE float32 [C][M]: C = num_channels (1 .. KIMG_MOMENTS_MAX_CHANNELS) planes of
+ *   M = plane_elements values (for images [P][H][W], dense, M = P * H * W), channel_pitch elements
+ *   apart, channel_pitch >= M.  line: DEVICE float32 [C][M] with a pitch of its own, the result:
+ *   either exactly `cube` (the same pointer AND the same pitch: in place) or a buffer that shares no
+ *   byte with the cube's C planes (any other overlap is KIMG_EINVAL).  Elements of the padding are
+ *   neither read nor written.  Indices are 64-bit throughout.
+ * Tables, per channel: filled_host HOST uint8 [C], nonzero = the plane holds an image; fit_host HOST
+ *   uint8 [C], nonzero = a line-free channel; w DEVICE float64 [C], the weight of every channel, and
+ *   w_host HOST float64 [C], the same numbers where the call itself can read them; basis DEVICE
+ *   float64 [K][C], K = order + 1, order 0 .. KIMG_IMCONTSUB_MAX_ORDER: the value of basis function
+ *   k at channel c (continuum.legendre_basis, by channel index or by frequency).  bref0 .. bref3: the
+ *   basis functions 0 .. K - 1 at the reference position, by value (the rest is ignored).
+ *   A channel ENTERS THE FIT iff fit_host[c], filled_host[c] and 0 < w_host[c] < inf.  The call folds
+ *   the three into one bit mask; it and the filled mask travel to the kernel by value, so the host
+ *   tables may be freed on return and a captured call keeps the masks it was captured with.  w and
+ *   basis are read by the kernel (scalar loads).
+ * Per element m of the plane on its own, all in float64, nothing fused.  I = cube[c][m] is usable
+ *   iff it is finite.  Over the channels that enter the fit, in ascending c, for every usable I:
+ *       n += 1;  wb = w[c] * B[k][c];  A[k][l] += wb * B[l][c] (l <= k);  b[k] += wb * I
+ *   -- the steps of kimg_uvcontsub with one real right-hand side.  The element is FITTED iff
+ *   n >= max(K, min_samples), 1 <= min_samples <= C.  Then A a = b is solved by Cholesky without
+ *   pivoting and two triangular solves, as in kimg_uvcontsub.
+ * Outputs for a fitted element: for every filled channel c of the whole band with finite I,
+ *       line[c][m] = float32(I - model_c),  model_c = sum_k a[k] * B[k][c]
+ *   summed from 0 in ascending k; an I that is not finite is stored as it is, bit for bit.  A channel
+ *   that is not filled is neither read nor written.
+ *       continuum[m]       = float32(sum_k a[k] * bref[k])     (from 0, ascending k)
+ *       coefficients[k][m] = float32(a[k]),  planes coefficient_pitch elements apart (>= M)
+ *       count[m]           = n  (int32)
+ *       rms[m]             = float32(sqrt(R / (n - K))),  R = the sum of r * r, r = I - model_c, over the
+ *                            usable samples of the channels that enter the fit, in ascending c;
+ *                            NaN unless n > K.
+ *   For an element that is NOT fitted: every filled channel of line at m becomes the quiet NaN
+ *   0x7fc00000; continuum, coefficients and rms become NaN; count is still n.
+ *   outputs: the KIMG_IMCONTSUB_* bits of the maps that are written, at least one; the pointer of a
+ *   bit that is not set is ignored (NULL will do) and nothing is written through it.
+ * Kernel forms (the host picks): four consecutive elements per thread with 16-byte loads and stores
+ *   when cube, line, both pitches * 4, every requested map and, with coefficients,
+ *   coefficient_pitch * 4 are 16-byte aligned, for the first 4 * (M / 4) elements; one element per
+ *   thread for the tail and for everything else.  One launch per form; a voxel of a fit channel is
+ *   read twice, of any other filled channel once, and written once.  No LDS, no atomics, no workspace.
+ * Returns, before any HIP call: KIMG_EINVAL for order < 0, order > 3, C < 1 or a null host table;
+ *   then KIMG_EUNSUPPORTED for C > KIMG_MOMENTS_MAX_CHANNELS, for fewer than K channels that enter the
+ *   fit (nothing could ever be fitted) or for M beyond the grid limit (2^31 - 1 workgroups of 256
+ *   elements); then KIMG_EINVAL for a null cube, line, w or basis, M < 0, min_samples outside 1 .. C,
+ *   a pitch below M, outputs without any KIMG_IMCONTSUB_* bit or with others, a pointer that is not
+ *   aligned to its element, a requested map that is NULL, or a line that overlaps the cube without
+ *   being the cube.  M = 0 is then a successful call that does nothing.
+ * Asynchronous on `stream`, no allocation, capturable.  The order of every sum is fixed: equal inputs
+ *   give equal bits.  Agreement with the twin: the bound of kimg_uvcontsub's tests,
+ *   |dev - t| <= 2^-24 |t| + 1e-9 S against the twin's value before its one rounding.
+ * Not done here: medians or robust fits, per-pixel weights, a fit across several cubes. */
+#define KIMG_IMCONTSUB_MAX_ORDER 3
+#define KIMG_IMCONTSUB_CONTINUUM 1
+#define KIMG_IMCONTSUB_COEFFICIENTS 2
+#define KIMG_IMCONTSUB_RMS 4
+#define KIMG_IMCONTSUB_COUNT 8
+int kimg_imcontsub(const float *cube, int64_t channel_pitch, float *line, int64_t line_channel_pitch,
+                   int num_channels, int64_t plane_elements, const uint8_t *filled_host,
+                   const uint8_t *fit_host, const double *w_host, const double *w,
+                   const double *basis, int order, double bref0, double bref1, double bref2,
+                   double bref3, int min_samples, int outputs, float *continuum, float *coefficients,
+                   int64_t coefficient_pitch, float *rms, int32_t *count, void *stream);
 
 #ifdef __cplusplus
 }

@@ -143,6 +143,10 @@ PROTOTYPES = {
     # moment maps: (cube, pitch, C, M), (first, stop), (x, cut, filled_host), width, select_hanning,
     # outputs (KIMG_MOMENT_* bits), (moment0, moment1, moment2, moment8, moment9, count), stream
     'kimg_moments': (c_int, [P, L, I, L, I, I, P, P, P, D, I, I, P, P, P, P, P, P, P]),
+    # image-plane continuum subtraction: (cube, pitch, line, pitch, C, M), (filled_host, fit_host,
+    # w_host), (w, basis, order), bref0 .. bref3, min_samples, outputs (KIMG_IMCONTSUB_* bits),
+    # (continuum, coefficients, coefficient_pitch, rms, count), stream
+    'kimg_imcontsub': (c_int, [P, L, P, L, I, L, P, P, P, P, P, I, D, D, D, D, I, I, P, P, L, P, P, P]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),

@@ -15,7 +15,8 @@ LIB = os.path.join(HERE, 'libkimg.so')
 SOURCES = ['api.hip', 'grid.hip', 'grid_mfma.hip', 'grid_fold.hip', 'grid_binned.hip', 'degrid_mfma.hip', 'image.hip', 'transform.hip', 'fft.hip', 'weight.hip',
            'clean.hip', 'clean_multi.hip', 'preprocess.hip', 'ktable.hip', 'store.hip',
            'grid_f64.hip', 'mask.hip', 'clean_scales.hip', 'contsub.hip', 'phaseshift.hip',
-           'primary_beam.hip', 'spectral.hip', 'statwt.hip', 'rfiflag.hip', 'moments.hip']
+           'primary_beam.hip', 'spectral.hip', 'statwt.hip', 'rfiflag.hip', 'moments.hip',
+           'imcontsub.hip']
 
 # -ffp-contract=off: a*b+c is fused only where the source says fmaf(); the image/CLEAN
 # kernels must round exactly like the reference's numpy host path.

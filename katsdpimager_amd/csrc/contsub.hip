@@ -6,11 +6,12 @@
 // The thread layout, the fit mask and the load round are kimg_channel_block.h's.  Pass 1 walks the fit
 // channels and keeps the normal equations in registers (K (K + 1) / 2 + 2 K doubles, 18 at K = 4); the
 // basis is the same for every lane and comes through the scalar cache.  The K x K system is
-// solved in the thread.  Pass 2 walks every channel: read, subtract, store -- or, for a sample with
+// solved in the thread (kimg_cholesky.h, shared with imcontsub.hip).  Pass 2 walks every channel: read, subtract, store -- or, for a sample with
 // fewer usable channels than coefficients, a zero into each of its weights.  No LDS, no atomics on
 // data; the two counters take one atomic add per wave each.  Traffic per element: 12 bytes per fit
 // channel, 16 per channel.
 #include "kimg_channel_block.h"
+#include "kimg_cholesky.h"
 
 namespace {
 
@@ -65,40 +66,10 @@ void uvcontsub_kernel(float2 *__restrict__ vis, int64_t vis_pitch, float *__rest
     const bool fitted = m >= K;
     double ar[K], ai[K];
     if (fitted) {
-        // Cholesky A = L L^T in place, without pivoting, then L y = b and L^T a = y
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-#pragma unroll
-            for (int l = 0; l <= k; l++) {
-                double s = A[k * (k + 1) / 2 + l];
-#pragma unroll
-                for (int i = 0; i < l; i++)
-                    s -= A[k * (k + 1) / 2 + i] * A[l * (l + 1) / 2 + i];
-                A[k * (k + 1) / 2 + l] = l == k ? sqrt(s) : s / A[l * (l + 1) / 2 + l];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            double sr = br[k], si = bi[k];
-#pragma unroll
-            for (int i = 0; i < k; i++) {
-                sr -= A[k * (k + 1) / 2 + i] * ar[i];
-                si -= A[k * (k + 1) / 2 + i] * ai[i];
-            }
-            ar[k] = sr / A[k * (k + 1) / 2 + k];
-            ai[k] = si / A[k * (k + 1) / 2 + k];
-        }
-#pragma unroll
-        for (int k = K - 1; k >= 0; k--) {
-            double sr = ar[k], si = ai[k];
-#pragma unroll
-            for (int i = k + 1; i < K; i++) {
-                sr -= A[i * (i + 1) / 2 + k] * ar[i];
-                si -= A[i * (i + 1) / 2 + k] * ai[i];
-            }
-            ar[k] = sr / A[k * (k + 1) / 2 + k];
-            ai[k] = si / A[k * (k + 1) / 2 + k];
-        }
+        // Cholesky A = L L^T in place, without pivoting, then L y = b and L^T a = y for either part
+        kimg_cholesky<K>(A);
+        kimg_cholesky_solve<K>(A, br, ar);
+        kimg_cholesky_solve<K>(A, bi, ai);
     } else {
 #pragma unroll
         for (int k = 0; k < K; k++)

@@ -13,20 +13,15 @@
 // With select_hanning the three-channel window lives in registers (prev, cur and the round's loads of
 // the NEXT channels), so every voxel is still read once.  A NaN stands for "no neighbour" in that
 // window -- outside the range, not filled or not finite are one case under the replicate rule.
-#include "kimg_common.h"
+#include "kimg_cube_column.h"
 
 namespace {
 
-constexpr int MM_THREADS = 256;
+constexpr int MM_THREADS = COL_THREADS;
 constexpr int MM_UNROLL = 4;                    // channels whose loads are in flight together
 constexpr int MM_MAX_CHANNELS = KIMG_MOMENTS_MAX_CHANNELS;
 constexpr int MM_ALL = KIMG_MOMENT_0 | KIMG_MOMENT_1 | KIMG_MOMENT_2 | KIMG_MOMENT_8 | KIMG_MOMENT_9
                        | KIMG_MOMENT_COUNT;
-
-// (one word more than the channels need: mm_filled_from reads two adjacent words)
-struct mm_filled {
-    uint32_t bits[MM_MAX_CHANNELS / 32 + 1];
-};
 
 struct mm_out {
     float *m0, *m1, *m2, *m8, *m9;
@@ -38,38 +33,6 @@ struct mm_acc {
     float peak;
     int n, pc;
 };
-
-__device__ inline float mm_nan() { return __int_as_float(0x7fc00000); }
-
-// Bit u of the result: channel c + u is filled, for u = 0 .. 32 -- one read of two adjacent words per
-// round of the channel loop.  c is clamped so that the index stays in the mask whatever the caller's
-// range; channels at and past `stop` are the caller's to mask out.
-__device__ inline uint64_t mm_filled_from(const mm_filled &f, int c)
-{
-    c = min(max(c, 0), MM_MAX_CHANNELS - 1);
-    const int i = c >> 5;
-    return (((uint64_t) f.bits[i + 1] << 32) | f.bits[i]) >> (c & 31);
-}
-
-template <int V> __device__ inline void mm_load(const float *p, float (&v)[V])
-{
-    if constexpr (V == 4) {
-        const float4 t = *reinterpret_cast<const float4 *>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-        v[0] = *p;
-    }
-}
-
-template <int V, class T> __device__ inline void mm_store(T *p, const T (&v)[V])
-{
-    if constexpr (V == 4) {
-        struct alignas(16) quad { T a, b, c, d; };
-        *reinterpret_cast<quad *>(p) = quad{v[0], v[1], v[2], v[3]};
-    } else {
-        *p = v[0];
-    }
-}
 
 // One sample: I of channel c with selection value s against the cut ct; d = x[c] - x_ref
 template <bool SECOND>
@@ -94,7 +57,7 @@ template <int V, bool HANNING, bool SECOND>
 __global__ __launch_bounds__(MM_THREADS)
 void moments_kernel(const float *__restrict__ cube, int64_t pitch, int64_t groups, int first, int stop,
                     const double *__restrict__ x, const float *__restrict__ cut,
-                    const mm_filled filled, double width, mm_out out)
+                    const col_mask filled, double width, mm_out out)
 {
     const int64_t t = (int64_t) blockIdx.x * MM_THREADS + threadIdx.x;
     const bool live = t < groups;
@@ -115,16 +78,16 @@ void moments_kernel(const float *__restrict__ cube, int64_t pitch, int64_t group
         for (int c0 = first; c0 < stop; c0 += MM_UNROLL) {
             float v[MM_UNROLL][V];
             bool on[MM_UNROLL];
-            const uint64_t have = mm_filled_from(filled, c0);
+            const uint64_t have = col_bits_from(filled, c0);
 #pragma unroll
             for (int u = 0; u < MM_UNROLL; u++) {
                 const int c = c0 + u;
                 on[u] = c < stop && ((have >> u) & 1);
 #pragma unroll
                 for (int e = 0; e < V; e++)
-                    v[u][e] = mm_nan();
+                    v[u][e] = col_nan();
                 if (on[u])
-                    mm_load<V>(p + (int64_t) c * pitch, v[u]);
+                    col_load<V>(p + (int64_t) c * pitch, v[u]);
             }
 #pragma unroll
             for (int u = 0; u < MM_UNROLL; u++) {
@@ -142,20 +105,20 @@ void moments_kernel(const float *__restrict__ cube, int64_t pitch, int64_t group
         float prev[V], cur[V];
 #pragma unroll
         for (int e = 0; e < V; e++)
-            prev[e] = cur[e] = mm_nan();
-        if (mm_filled_from(filled, first) & 1)
-            mm_load<V>(p + (int64_t) first * pitch, cur);
+            prev[e] = cur[e] = col_nan();
+        if (col_bits_from(filled, first) & 1)
+            col_load<V>(p + (int64_t) first * pitch, cur);
         for (int c0 = first; c0 < stop; c0 += MM_UNROLL) {
             float next[MM_UNROLL][V];       // the channels c0 + 1 .. c0 + MM_UNROLL
-            const uint64_t have = mm_filled_from(filled, c0);
+            const uint64_t have = col_bits_from(filled, c0);
 #pragma unroll
             for (int u = 0; u < MM_UNROLL; u++) {
                 const int c = c0 + u + 1;
 #pragma unroll
                 for (int e = 0; e < V; e++)
-                    next[u][e] = mm_nan();
+                    next[u][e] = col_nan();
                 if (c < stop && ((have >> (u + 1)) & 1))
-                    mm_load<V>(p + (int64_t) c * pitch, next[u]);
+                    col_load<V>(p + (int64_t) c * pitch, next[u]);
             }
 #pragma unroll
             for (int u = 0; u < MM_UNROLL; u++) {
@@ -188,35 +151,35 @@ void moments_kernel(const float *__restrict__ cube, int64_t pitch, int64_t group
         const bool any = a.n > 0;
         const bool positive = any && a.S0 > 0.0;
         n[e] = a.n;
-        m0[e] = any ? (float) (a.S0 * width) : mm_nan();
-        m8[e] = any ? a.peak : mm_nan();
-        m9[e] = mm_nan();
+        m0[e] = any ? (float) (a.S0 * width) : col_nan();
+        m8[e] = any ? a.peak : col_nan();
+        m9[e] = col_nan();
         if (out.m9 && any)
             m9[e] = (float) x[a.pc];
-        m1[e] = m2[e] = mm_nan();
+        m1[e] = m2[e] = col_nan();
         if constexpr (SECOND) {
             const double r = a.S1 / a.S0;
             const double q = a.S2 / a.S0;
             double var = q - r * r;
             var = var < 0.0 ? 0.0 : var;
-            m1[e] = positive ? (float) (x_ref + r) : mm_nan();
-            m2[e] = positive ? (float) sqrt(var) : mm_nan();
+            m1[e] = positive ? (float) (x_ref + r) : col_nan();
+            m2[e] = positive ? (float) sqrt(var) : col_nan();
         }
     }
-    if (out.m0) mm_store<V>(out.m0 + j, m0);
-    if (out.m1) mm_store<V>(out.m1 + j, m1);
-    if (out.m2) mm_store<V>(out.m2 + j, m2);
-    if (out.m8) mm_store<V>(out.m8 + j, m8);
-    if (out.m9) mm_store<V>(out.m9 + j, m9);
-    if (out.count) mm_store<V>(out.count + j, n);
+    if (out.m0) col_store<V>(out.m0 + j, m0);
+    if (out.m1) col_store<V>(out.m1 + j, m1);
+    if (out.m2) col_store<V>(out.m2 + j, m2);
+    if (out.m8) col_store<V>(out.m8 + j, m8);
+    if (out.m9) col_store<V>(out.m9 + j, m9);
+    if (out.count) col_store<V>(out.count + j, n);
 }
 
 template <int V>
 void mm_launch(const float *cube, int64_t pitch, int64_t groups, int first, int stop, const double *x,
-               const float *cut, const mm_filled &filled, double width, bool hanning, bool second,
+               const float *cut, const col_mask &filled, double width, bool hanning, bool second,
                const mm_out &out, hipStream_t s)
 {
-    const unsigned blocks = (unsigned) kimg_divup(groups, MM_THREADS);
+    const unsigned blocks = col_blocks(groups);
     auto go = [&](auto h, auto m) {
         moments_kernel<V, decltype(h)::value, decltype(m)::value><<<blocks, MM_THREADS, 0, s>>>(
             cube, pitch, groups, first, stop, x, cut, filled, width, out);
@@ -274,26 +237,24 @@ extern "C" int kimg_moments(const float *cube, int64_t channel_pitch, int num_ch
         }
     }
     KIMG_CHECK_ARG(((uintptr_t) cube & 3) == 0 && ((uintptr_t) x & 7) == 0 && ((uintptr_t) cut & 3) == 0);
-    if (num_channels > MM_MAX_CHANNELS || plane_elements > (int64_t) 0x7fffffff * MM_THREADS)
+    if (num_channels > MM_MAX_CHANNELS || !col_plane_fits(plane_elements))
         return KIMG_EUNSUPPORTED;
     if (plane_elements == 0)
         return 0;
 
-    mm_filled filled = {};
+    col_mask filled = {};
     for (int c = 0; c < num_channels; c++)
         if (filled_host[c])
-            filled.bits[c >> 5] |= 1u << (c & 31);
+            col_set(filled, c);
     const bool second = outputs & (KIMG_MOMENT_1 | KIMG_MOMENT_2);
     const bool hanning = select_hanning != 0;
     hipStream_t s = (hipStream_t) stream;
-    // the form: four elements per thread where every address a thread forms is 16-byte aligned, one
-    // element per thread for the tail and for everything else
-    int64_t done = 0;
-    if ((alignment & 15) == 0 && plane_elements >= 4) {
-        done = plane_elements & ~(int64_t) 3;
+    // the form (kimg_cube_column.h): four elements per thread where every address a thread forms is
+    // 16-byte aligned, one element per thread for the tail and for everything else
+    const int64_t done = col_vector_elements(alignment, plane_elements);
+    if (done)
         mm_launch<4>(cube, channel_pitch, done / 4, first, stop, x, cut, filled, width, hanning, second,
                      out, s);
-    }
     if (done < plane_elements)
         mm_launch<1>(cube + done, channel_pitch, plane_elements - done, first, stop, x, cut, filled,
                      width, hanning, second, mm_offset(out, done), s);

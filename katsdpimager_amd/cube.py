@@ -29,9 +29,10 @@ over the channels c = first .. stop - 1 in ascending order, I = cube[c][m]:
   also unless S0 > 0.  The cube is never written.
 
 Not done: a common restoring beam across planes (every plane keeps its own; all planes share one
-pixel size, which is the caller's business), spatial smoothing of the selection, image-plane continuum
-subtraction, position-velocity cuts, medians (CASA moments 3 to 7, 10, 11), cubes across several GPUs
-(with channels sharded over GPUs the caller gathers planes with :meth:`SpectralCube.put`).
+pixel size, which is the caller's business), spatial smoothing of the selection, position-velocity
+cuts, medians (CASA moments 3 to 7, 10, 11), cubes across several GPUs (with channels sharded over
+GPUs the caller gathers planes with :meth:`SpectralCube.put`).  Image-plane continuum subtraction on
+the cube is :mod:`.imcontsub`.
 """
 import ctypes
 
