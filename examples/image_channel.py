@@ -12,6 +12,7 @@ store -> imaging weights, PSF, major/minor cycles -> restored image, all on one 
     python examples/image_channel.py --rfiflag              (bursts of interference in a band of noise; see rfiflag_band)
     python examples/image_channel.py --moments              (a band with two line sources into a cube; see moments_band)
     python examples/image_channel.py --moments --imcontsub 1:1-3,5-10  (... with a continuum source, taken out on the cube)
+    python examples/image_channel.py --moments --common-beam  (... every plane restored with its own beam, then all taken to one)
 
 It follows the reference's per-channel flow (frontend.py:31-83 preprocess_visibilities,
 :465-658 process_channel) with the loaders and FITS output left out: the sky is three point
@@ -514,9 +515,16 @@ def moments_band(args):
     channel, lies on source A, so every channel is imaged; moment 0 is taken twice, of the cube as
     imaged and after ``imcontsub.ImContSub`` has fitted a polynomial of that order per pixel to the
     channels outside the listed ranges (default 1-3,5-10, the two lines) and subtracted it in place,
-    and both are printed next to the injected line integral."""
+    and both are printed next to the injected line integral.
+
+    With ``--common-beam`` every channel's beam is fitted to its PSF and the plane is restored with
+    it (the model convolved with the beam, plus the residual) and ``put`` with it; the moments are
+    taken twice, of the cube as imaged and of the cube ``smooth.CubeSmooth`` has taken to the common
+    beam, and every plane's fitted beam, the common beam and moment 0 at source A without and with
+    the smoothing are printed."""
     import synth
-    from katsdpimager_amd import accel, cube, frontend, imaging, imcontsub, loader, parameters, preprocess, weight
+    from katsdpimager_amd import (accel, beam, cube, frontend, imaging, imcontsub, loader, parameters,
+                                  preprocess, smooth, weight)
     C = 12
     contsub = None
     if args.imcontsub:
@@ -560,15 +568,22 @@ def moments_band(args):
     loader.preprocess_visibilities(dataset, collector, 0, C, (np.ones((1, 1), np.complex64), None))
     G = args.pixels
     sc = cube.SpectralCube(ctx, cube_queue, frequencies, [0], (G, G), channel_width=frequencies[1] - frequencies[0])
+    restorer = None
     for channel in range(C):
         if contsub is None and line_a[channel] == 0 and line_b[channel] == 0:
             continue
         stats = frontend.process_channel(collector.reader(), channel, imager, image_p, grid_p, clean_p,
-                                         weight_p.weight_type, args.vis_block, 1, True)
+                                         weight_p.weight_type, args.vis_block, 1, True,
+                                         fit_beam=args.common_beam)
         if stats is None:
             continue
-        imager.add_model_to_dirty()
-        copied = sc.put(channel, imager.buffer('dirty'), stats['noise'], wait_for=[queue.enqueue_marker()])
+        fitted = stats.get('restoring_beam')
+        if fitted is not None:
+            restorer = beam.restore(imager, fitted, restorer)
+        else:
+            imager.add_model_to_dirty()
+        copied = sc.put(channel, imager.buffer('dirty'), stats['noise'], wait_for=[queue.enqueue_marker()],
+                        beam=fitted)
         queue.enqueue_wait_for_events([copied])         # (the next channel rewrites the buffer)
     params = cube.MomentParameters((0, 1, 2), rest_frequency=rest_frequency, clip_sigma=3.0)
     moments = cube.MomentsTemplate(ctx, params).instantiate(cube_queue, sc.shape)
@@ -579,8 +594,25 @@ def moments_band(args):
         continuum_map = fit['continuum'].get(cube_queue)[0]
         print('imcontsub {}: {} of {} pixels fitted'.format(
             contsub, int((fit['count'].get(cube_queue) >= contsub.order + 1).sum()), G * G))
+    unsmoothed = None
+    if args.common_beam:
+        y, x = G // 2 + positions['A'][1], G // 2 + positions['A'][0]
+        unsmoothed = float(moments(sc)[0].get(cube_queue)[0][y, x])
+        smoother = smooth.CubeSmoothTemplate(ctx, smooth.CommonBeamParameters()).instantiate(cube_queue, sc.shape)
+        smoothed = smoother(sc)
+        for channel in np.flatnonzero(sc.filled):
+            print('channel {:2d}: beam {!r}, kernel radius {}, flux factor {:.6f}'.format(
+                int(channel), sc.beams[channel], int(smoother.radius[channel]),
+                float(smoother.factors[channel])))
+        print('common beam {!r}'.format(smoothed.common_beam))
+        # (the noise of a smoothed plane is the caller's to set: here the input's, scaled)
+        smoothed.noise[:] = sc.noise * smoother.factors.astype(np.float32)
+        sc = smoothed
     maps = moments(sc)
     host = {key: value.get(cube_queue)[0] for key, value in maps.items()}
+    if unsmoothed is not None:
+        print('moment 0 at source A: {:12.6f} without the smoothing, {:12.6f} with it'.format(
+            unsmoothed, float(host[0][y, x])))
     velocity = sc.coordinates('velocity', rest_frequency)
     width = abs(velocity[-1] - velocity[0]) / (C - 1)
     print('{} channels of {:.1f} km/s, {} imaged; noise estimates {:.2e} to {:.2e}'.format(
@@ -672,9 +704,14 @@ def main(argv=None):
                     help='with --moments: leave a continuum source on source A, and fit and subtract a '
                          'polynomial of this order per pixel of the cube outside the listed channels '
                          '(default 1-3,5-10) ahead of the moments, e.g. --imcontsub 1')
+    ap.add_argument('--common-beam', action='store_true',
+                    help='with --moments: fit every channel\'s beam, restore the planes with theirs, take the '
+                         'cube to the common beam and print moment 0 at source A without and with the smoothing')
     args = ap.parse_args(argv)
     if args.imcontsub and not args.moments:
         ap.error('--imcontsub goes with --moments')
+    if args.common_beam and not args.moments:
+        ap.error('--common-beam goes with --moments')
     if args.moments:
         return moments_band(args)
     if args.rfiflag is not None:

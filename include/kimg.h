@@ -1406,8 +1406,8 @@ int kimg_rfi_flag(const void *vis, int64_t vis_channel_pitch, float *weights,
  *   4-byte aligned); KIMG_EUNSUPPORTED for C > KIMG_MOMENTS_MAX_CHANNELS or M beyond the grid limit
  *   (2^31 - 1 workgroups of 256 elements).  M = 0 is then a successful call that does nothing.
  * Asynchronous on `stream`, no allocation, capturable; equal inputs give equal bits.
- * Not done here: a common restoring beam across planes, spatial smoothing of the selection,
- *   position-velocity cuts, medians (CASA moments 3 to 7, 10, 11), cubes across several GPUs. */
+ * Not done here (a common restoring beam across planes is kimg_cube_smooth's): spatial smoothing of
+ *   the selection, position-velocity cuts, medians (CASA moments 3 to 7, 10, 11), cubes across several GPUs. */
 #define KIMG_MOMENTS_MAX_CHANNELS 4096
 #define KIMG_MOMENT_0 1
 #define KIMG_MOMENT_1 2
@@ -1490,6 +1490,60 @@ int kimg_imcontsub(const float *cube, int64_t channel_pitch, float *line, int64_
                    const double *basis, int order, double bref0, double bref1, double bref2,
                    double bref3, int min_samples, int outputs, float *continuum, float *coefficients,
                    int64_t coefficient_pitch, float *rms, int32_t *count, void *stream);
+
+/* ---- Cube smoothing to a common beam (cube_smooth.hip): every filled plane of a spectral cube
+ * convolved with a small kernel of its own, so that all planes end with one restoring beam (CASA
+ * imsmooth(targetres=True) / commonbeam, MIRIAD convol options=final) -- the step between imaging
+ * and the cube operators above, which assume that a pixel means the same in every channel.  The
+ * kernel that takes the beam of channel c to the common beam T is the Gaussian of covariance
+ * Sigma_T - Sigma_c: a fraction of a pixel to a few pixels over a spectral-line band, so the
+ * convolution is direct, in the image domain, not kimg_convolve_beam's.  The reference has none; the
+ * semantics are this library's, and katsdpimager_amd/smooth.py holds them once more as numpy
+ * (cube_smooth_host), with the host code that chooses the common beam (common_beam) and makes the
+ * taps (kernel_tables).
+ *
+ * cube: DEVICE float32 [C][P][H][W], read only: C = num_channels (1 .. KIMG_MOMENTS_MAX_CHANNELS)
+ *   channels channel_pitch elements apart, channel_pitch >= P * H * W; inside a channel the
+ *   P = num_polarizations planes of H = height rows of W = width pixels are dense, as in
+ *   kimg_moments.  out: DEVICE float32 of the same shape with a pitch of its own, which shares no
+ *   byte with the cube's C channels (in-place operation is not done; any overlap is KIMG_EINVAL).
+ *   Elements of the padding are neither read nor written.  Indices are 64-bit throughout.
+ * Tables, per channel: filled_host HOST uint8 [C], nonzero = the plane holds an image; radius_host
+ *   HOST int32 [C], R_c = 0 .. KIMG_CUBE_SMOOTH_MAX_RADIUS (read for filled channels only); both
+ *   travel to the kernel by value, 5 bits a channel, so they may be freed on return and a captured
+ *   call keeps the ones it was captured with.  taps DEVICE float32 [C][taps_pitch]: channel c uses
+ *   its first (2 R_c + 1)^2 entries, row-major, taps[c][(dy + R)(2R + 1) + (dx + R)], and
+ *   taps_pitch must hold them.  They are read by the kernel (scalar loads).
+ * Per filled channel c, polarization p and pixel (y, x), R = R_c, every operation in float32,
+ *   every product and every sum rounded, nothing fused, dy ascending and within it dx ascending:
+ *       acc = +0.0f
+ *       acc = acc + (taps[c][(dy + R)(2R + 1) + (dx + R)] * I[c][p][y + dy][x + dx])
+ *   where a sample outside the plane is +0.0f, multiplied and added like any other (so an infinite
+ *   tap over the border makes a NaN).  The accumulator starts as +0.0 and +0.0 + -0.0 = +0.0, so it
+ *   is never -0.0: a sample of -0.0 comes out as +0.0, in a scaled copy (R = 0) too.
+ *   Samples that are not finite take part as they are: a NaN spreads over its footprint.  A result
+ *   that is NaN is stored as 0x7fc00000, everything else as computed.  R = 0 is the same formula
+ *   with one tap: a scaled copy.  A channel that is not filled is neither read nor written.
+ * Agreement with the twin: bit for bit (IEEE products and sums in one fixed order).
+ * Kernel forms (the host picks): 16-byte loads and stores when cube, out, both pitches * 4 and
+ *   W * 4 are 16-byte aligned, one pixel per load and store for everything else.  One launch for all
+ *   channels and polarizations; a workgroup stages a tile of 64 x 64 outputs with its halo in LDS
+ *   (36880 bytes); no atomics, no workspace.
+ * Returns, before any HIP call: KIMG_EINVAL for a null cube, out, filled_host, radius_host or taps,
+ *   C, P, H or W below 1, C > KIMG_MOMENTS_MAX_CHANNELS, a pointer that is not 4-byte aligned, a
+ *   pitch below P * H * W or so long that the cube's extent in bytes leaves int64, a filled channel whose radius is outside 0 .. 16 or whose taps do not
+ *   fit taps_pitch, or an out that overlaps the cube; then KIMG_EUNSUPPORTED for P > 65535 or more
+ *   than 2^31 - 1 tiles a plane.  No filled channel is then a successful call that does nothing.
+ * Asynchronous on `stream`, no allocation, capturable; equal inputs give equal bits.
+ * Not done here: minimum-area common beams of differently shaped ellipses (smooth.common_beam
+ *   scales the largest beam), kernels beyond R = 16 (kimg_convolve_beam's work), sub-pixel kernels
+ *   sampled better than at pixel centres, the noise of the smoothed planes, in-place operation,
+ *   cubes across several GPUs. */
+#define KIMG_CUBE_SMOOTH_MAX_RADIUS 16
+int kimg_cube_smooth(const float *cube, int64_t channel_pitch, float *out, int64_t out_channel_pitch,
+                     int num_channels, int num_polarizations, int height, int width,
+                     const uint8_t *filled_host, const int32_t *radius_host, const float *taps,
+                     int64_t taps_pitch, void *stream);
 
 #ifdef __cplusplus
 }

@@ -147,6 +147,9 @@ PROTOTYPES = {
     # w_host), (w, basis, order), bref0 .. bref3, min_samples, outputs (KIMG_IMCONTSUB_* bits),
     # (continuum, coefficients, coefficient_pitch, rms, count), stream
     'kimg_imcontsub': (c_int, [P, L, P, L, I, L, P, P, P, P, P, I, D, D, D, D, I, I, P, P, L, P, P, P]),
+    # cube smoothing to a common beam: (cube, pitch, out, pitch), (C, P, H, W), (filled_host,
+    # radius_host), (taps, taps_pitch), stream
+    'kimg_cube_smooth': (c_int, [P, L, P, L, I, I, I, I, P, P, P, L, P]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),

@@ -28,11 +28,11 @@ over the channels c = first .. stop - 1 in ascending order, I = cube[c][m]:
   9 = x of the peak's channel; ``count`` = n (int32).  Every moment is NaN where n == 0, moments 1 and 2
   also unless S0 > 0.  The cube is never written.
 
-Not done: a common restoring beam across planes (every plane keeps its own; all planes share one
-pixel size, which is the caller's business), spatial smoothing of the selection, position-velocity
-cuts, medians (CASA moments 3 to 7, 10, 11), cubes across several GPUs (with channels sharded over
-GPUs the caller gathers planes with :meth:`SpectralCube.put`).  Image-plane continuum subtraction on
-the cube is :mod:`.imcontsub`.
+Not done: spatial smoothing of the selection, position-velocity cuts, medians (CASA moments 3 to 7,
+10, 11), cubes across several GPUs (with channels sharded over GPUs the caller gathers planes with
+:meth:`SpectralCube.put`).  All planes share one pixel size, which is the caller's business; every
+plane keeps its own restoring beam until :mod:`.smooth` takes the cube to a common one.  Image-plane
+continuum subtraction on the cube is :mod:`.imcontsub`.
 """
 import ctypes
 
@@ -283,7 +283,9 @@ class SpectralCube:
 
     All planes share one pixel size and one image centre; that is the caller's business -- the
     reference chooses a pixel size per band, which is what a cube needs.  Every plane keeps its own
-    restoring beam.
+    restoring beam: ``beams`` (a list, one entry per channel) holds what :meth:`put` was told of it,
+    None where nothing; ``common_beam`` is None until ``smooth.CubeSmooth`` has made a cube whose
+    planes share one, and is then that beam.
 
     ``array`` is the device array, ``filled`` (uint8 [C]) says which planes hold an image and ``noise``
     (float32 [C], NaN = none) what :meth:`put` was told of them."""
@@ -318,14 +320,17 @@ class SpectralCube:
         self.shape = (C, len(self.polarizations), height, width)
         self.filled = np.zeros(C, np.uint8)
         self.noise = np.full(C, np.nan, np.float32)
+        self.beams = [None] * C
+        self.common_beam = None
         self.array = accel.DeviceArray(context, self.shape, np.float32, queue=queue)
         check(lib().kimg_fill(self.array.ptr, int(np.prod(self.shape)), float('nan'), queue.handle),
               'kimg_fill')
 
-    def put(self, channel, image, noise=None, wait_for=None):
+    def put(self, channel, image, noise=None, wait_for=None, beam=None):
         """Copy ``image`` -- a device array [P][H][W] (an imager's buffer will do) or a host array --
         into plane ``channel``, on the cube's queue, and record the channel's ``noise``
-        (``result['noise']`` of ``process_channel``).
+        (``result['noise']`` of ``process_channel``) and restoring ``beam`` (a ``beam.Beam`` in
+        pixels, as ``beam.fit_beam`` returns it; ``smooth.CubeSmooth`` needs one for every plane).
 
         The copy is ordered after the cube queue's own work only.  An image that another queue is
         still writing needs ``wait_for``: events of that queue (``queue.enqueue_marker()``), which the
@@ -357,6 +362,7 @@ class SpectralCube:
             self.array.set_region(queue, image, np.s_[as_int], np.s_[:])
         self.filled[as_int] = 1
         self.noise[as_int] = np.nan if noise is None else noise
+        self.beams[as_int] = beam
         return queue.enqueue_marker()
 
     def get(self, queue=None):

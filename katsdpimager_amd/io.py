@@ -150,9 +150,9 @@ def write_fits_cube(cube, image_parameters, filename, frequencies, phase_centre,
     the cards of :func:`write_fits_image` with ``NAXIS4`` = the channels, ``CRVAL4`` =
     ``frequencies[0]``, ``CDELT4`` their spacing and ``CRPIX4`` = 1; ``RESTFRQ`` when
     ``rest_frequency`` is given.  A linear FREQ axis cannot describe uneven channels: ValueError if
-    the spacing varies by more than 1e-6 of itself.  One ``beam`` serves every plane (a common
-    restoring beam is the caller's to make).  Returns (the array as written, the header as a list of
-    (key, value))."""
+    the spacing varies by more than 1e-6 of itself.  One ``beam`` serves every plane
+    (``smooth.CubeSmooth`` takes a cube to a common restoring beam).  Returns (the array as written,
+    the header as a list of (key, value))."""
     cube = np.asarray(cube)
     if cube.ndim != 4:
         raise ValueError('cube must be [channel][polarization][m][l]')
