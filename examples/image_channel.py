@@ -13,6 +13,7 @@ store -> imaging weights, PSF, major/minor cycles -> restored image, all on one 
     python examples/image_channel.py --moments              (a band with two line sources into a cube; see moments_band)
     python examples/image_channel.py --moments --imcontsub 1:1-3,5-10  (... with a continuum source, taken out on the cube)
     python examples/image_channel.py --moments --common-beam  (... every plane restored with its own beam, then all taken to one)
+    python examples/image_channel.py --moments --common-beam --measure-noise  (... and the smoothed planes' noise measured)
 
 It follows the reference's per-channel flow (frontend.py:31-83 preprocess_visibilities,
 :465-658 process_channel) with the loaders and FITS output left out: the sky is three point
@@ -521,10 +522,12 @@ def moments_band(args):
     it (the model convolved with the beam, plus the residual) and ``put`` with it; the moments are
     taken twice, of the cube as imaged and of the cube ``smooth.CubeSmooth`` has taken to the common
     beam, and every plane's fitted beam, the common beam and moment 0 at source A without and with
-    the smoothing are printed."""
+    the smoothing are printed.  The smoothed planes' noise is the unsmoothed one times the flux factor, a
+    stand-in; with ``--measure-noise`` ``cube_stats.CubeStats`` measures it on the smoothed cube, both
+    are printed per channel and the measured one makes the ``clip_sigma`` cuts."""
     import synth
-    from katsdpimager_amd import (accel, beam, cube, frontend, imaging, imcontsub, loader, parameters,
-                                  preprocess, smooth, weight)
+    from katsdpimager_amd import (accel, beam, cube, cube_stats, frontend, imaging, imcontsub, loader,
+                                  parameters, preprocess, smooth, weight)
     C = 12
     contsub = None
     if args.imcontsub:
@@ -607,6 +610,17 @@ def moments_band(args):
         print('common beam {!r}'.format(smoothed.common_beam))
         # (the noise of a smoothed plane is the caller's to set: here the input's, scaled)
         smoothed.noise[:] = sc.noise * smoother.factors.astype(np.float32)
+        if args.measure_noise:
+            # ... or measured: the stand-in is the unsmoothed noise times the flux factor, and the
+            # noise of a smoothed plane is correlated and differs from it
+            stand_in = smoothed.noise.copy()
+            measure = cube_stats.CubeStatsTemplate(ctx, cube_stats.CubeStatsParameters()).instantiate(
+                cube_queue, smoothed.shape)
+            measured = measure(smoothed, update_noise=True)
+            for channel in np.flatnonzero(smoothed.filled):
+                print('channel {:2d}: noise {:.4e} as scaled, {:.4e} measured on the smoothed plane '
+                      '({} samples)'.format(int(channel), float(stand_in[channel]),
+                                            float(smoothed.noise[channel]), int(measured.count[channel, 0])))
         sc = smoothed
     maps = moments(sc)
     host = {key: value.get(cube_queue)[0] for key, value in maps.items()}
@@ -707,7 +721,13 @@ def main(argv=None):
     ap.add_argument('--common-beam', action='store_true',
                     help='with --moments: fit every channel\'s beam, restore the planes with theirs, take the '
                          'cube to the common beam and print moment 0 at source A without and with the smoothing')
+    ap.add_argument('--measure-noise', action='store_true',
+                    help='with --moments --common-beam: measure the noise of the smoothed planes '
+                         '(cube_stats.CubeStats), print it next to the scaled stand-in and use it for the '
+                         'clip_sigma moments')
     args = ap.parse_args(argv)
+    if args.measure_noise and not args.common_beam:
+        ap.error('--measure-noise goes with --moments --common-beam')
     if args.imcontsub and not args.moments:
         ap.error('--imcontsub goes with --moments')
     if args.common_beam and not args.moments:

@@ -1545,6 +1545,66 @@ int kimg_cube_smooth(const float *cube, int64_t channel_pitch, float *out, int64
                      const uint8_t *filled_host, const int32_t *radius_host, const float *taps,
                      int64_t taps_pitch, void *stream);
 
+/* ---- Cube plane statistics (cube_stats.hip): for every plane of a spectral cube a robust noise and
+ * its companion statistics, in one call (CASA imstat per channel, MIRIAD imstat / sigest) -- what
+ * measures the noise that kimg_moments' clip_sigma cut and kimg_imcontsub's noise weights read, on a
+ * cube that did not come plane by plane from the imager: a smoothed cube, a continuum-subtracted one,
+ * one filled from the host.  The reference has none; the semantics are this library's, and
+ * katsdpimager_amd/cube_stats.py holds them once more as numpy (cube_stats_host).
+ *
+ * cube: DEVICE float32 [C][P][H][W], read only, never written: C = num_channels
+ *   (1 .. KIMG_MOMENTS_MAX_CHANNELS) channels channel_pitch elements apart, channel_pitch >= P * H * W;
+ *   inside a channel the P planes of H rows of W pixels are dense, as in kimg_moments.  Elements of
+ *   the padding are not read.  filled_host: HOST uint8 [C], nonzero = the plane holds an image; it
+ *   travels by value.  Channels first .. stop - 1 are measured.
+ * Groups: G = 1 a channel with pool_polarizations (all P planes together: one number a channel, as
+ *   the imager's own estimate), else G = P.  A group's candidates are the pixels (y, x) of its
+ *   plane(s) with border <= y < H - border, border <= x < W - border (border in pixels, >= 0,
+ *   2 * border < min(H, W)) and, with a region (DEVICE uint8 [H][W], dense, shared by all planes; null
+ *   for none), region[y][x] != 0.
+ * Samples: the candidates whose value is finite; NaN of any sign and payload, +Inf and -Inf are left
+ *   out.  n is their number.
+ * Order: by key(x) = bits ^ (bits >> 31 ? 0xffffffff : 0x80000000), the monotone map of the float32
+ *   bit pattern: -0 lies below +0.  The median of a multiset v of n >= 1 float32 values is
+ *   (lo + hi) / 2 in float32 with lo = v[(n - 1) / 2] and hi = v[n / 2] in that order (kimg_noise_est's
+ *   rule, np.median of float32 data).
+ * Outputs, DEVICE [C][G] each, group c * G + g: count (uint32) = n; min and max, the samples of
+ *   smallest and largest key; median, the median of the samples; sigma, by estimator:
+ *     KIMG_CUBE_STATS_MEDIAN_ABS  median(|x|) * KIMG_CUBE_STATS_TO_RMS, one float32 product, |x| the
+ *                                 value with its sign bit cleared (the imager's kimg_noise_est);
+ *     KIMG_CUBE_STATS_MAD         median(|x - m|) * KIMG_CUBE_STATS_TO_RMS, m the group's median,
+ *                                 x - m one float32 subtraction, its sign bit cleared (it may be +Inf,
+ *                                 which is then a value like any other).
+ *   A group with n = 0, and every group of a channel that is not filled or outside the range, gets NaN
+ *   (0x7fc00000) in the four float outputs and count 0; a channel that is not filled is not read.
+ * Exactness: everything is selection; nothing is summed and nothing rounds but the operations named
+ *   above.  The results depend neither on the launch geometry nor on the kernel form, and the twin
+ *   gives the same bits, always.  On a plane without non-finite values, pooled, without a region and
+ *   with the same border in pixels, sigma under MEDIAN_ABS is kimg_noise_est's, bit for bit.
+ * Kernel: a batched byte-wise radix select over all groups, two launches a pass whatever C is;
+ *   MEDIAN_ABS reads the cube 4 times (both selects share every load), MAD 8 times.  16-byte loads
+ *   when cube, channel_pitch * 4 and W * 4 are 16-byte aligned, one element a load otherwise.
+ * scratch: DEVICE, kimg_cube_stats_scratch_bytes(C, G) bytes (0 for arguments out of range), 8-byte
+ *   aligned; the call initialises it.
+ * Returns, before any HIP call: KIMG_EINVAL for a null pointer (region excepted), C, P, H or W below
+ *   1, C > KIMG_MOMENTS_MAX_CHANNELS, a range that is empty or leaves the band, an unknown estimator,
+ *   a border below 0 or with 2 * border >= min(H, W), a misaligned pointer, a pitch below P * H * W or
+ *   so long that the cube's extent in bytes leaves int64; then KIMG_EUNSUPPORTED for a group of 2^32
+ *   elements or more (so for every group of 2^32 candidates or more) and for G > 65535.
+ * Asynchronous on `stream`, no allocation, capturable; the caller reads the 5 * C * G numbers.
+ * Not done here: iterative sigma clipping; means and rms (an ordered float64 reduction, another
+ *   contract); statistics along the channel axis per pixel (immoments' medians); the noise of a
+ *   smoothed plane derived rather than measured; cubes across several GPUs. */
+#define KIMG_CUBE_STATS_MEDIAN_ABS 0
+#define KIMG_CUBE_STATS_MAD 1
+#define KIMG_CUBE_STATS_TO_RMS 1.4826022185056031f
+size_t kimg_cube_stats_scratch_bytes(int num_channels, int groups_per_channel);
+int kimg_cube_stats(const float *cube, int64_t channel_pitch, int num_channels, int num_polarizations,
+                    int height, int width, const uint8_t *filled_host, int first, int stop,
+                    int pool_polarizations, int estimator, int border, const uint8_t *region,
+                    void *scratch, uint32_t *count, float *min, float *max, float *median,
+                    float *sigma, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,10 @@ PROTOTYPES = {
     # cube smoothing to a common beam: (cube, pitch, out, pitch), (C, P, H, W), (filled_host,
     # radius_host), (taps, taps_pitch), stream
     'kimg_cube_smooth': (c_int, [P, L, P, L, I, I, I, I, P, P, P, L, P]),
+    # cube plane statistics: (C, G); (cube, pitch), (C, P, H, W), filled_host, (first, stop),
+    # pool_polarizations, estimator, border, region, scratch, (count, min, max, median, sigma), stream
+    'kimg_cube_stats_scratch_bytes': (c_size_t, [I, I]),
+    'kimg_cube_stats': (c_int, [P, L, I, I, I, I, P, I, I, I, I, I, P, P, P, P, P, P, P, P]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),

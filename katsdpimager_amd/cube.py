@@ -32,7 +32,9 @@ Not done: spatial smoothing of the selection, position-velocity cuts, medians (C
 10, 11), cubes across several GPUs (with channels sharded over GPUs the caller gathers planes with
 :meth:`SpectralCube.put`).  All planes share one pixel size, which is the caller's business; every
 plane keeps its own restoring beam until :mod:`.smooth` takes the cube to a common one.  Image-plane
-continuum subtraction on the cube is :mod:`.imcontsub`.
+continuum subtraction on the cube is :mod:`.imcontsub`.  The noise :meth:`SpectralCube.put` records
+is what the caller was told; :mod:`.cube_stats` measures it on the cube itself, for every plane in one
+call, where nothing was told or the planes have changed since.
 """
 import ctypes
 

@@ -24,6 +24,8 @@ amount that depends on the noise's own correlation; it is not derived here.  The
 ``noise`` is the input's times the flux factor where a plane was only scaled (``R = 0``) and NaN
 elsewhere: the caller measures it again (``frontend.process_channel``'s estimate on the smoothed
 plane) or sets it before anything that needs it (``clip_sigma``, ``weighting='noise'``).
+:mod:`.cube_stats` measures it on the returned cube, all planes in one call
+(``op(smoothed, update_noise=True)``).
 
 Not done: minimum-area common beams of differently shaped ellipses (:func:`common_beam` scales the
 largest beam until it contains the others), kernels beyond ``R = 16`` (``beam.ConvolveBeam``'s
