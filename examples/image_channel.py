@@ -12,6 +12,7 @@ store -> imaging weights, PSF, major/minor cycles -> restored image, all on one 
     python examples/image_channel.py --rfiflag              (bursts of interference in a band of noise; see rfiflag_band)
     python examples/image_channel.py --moments              (a band with two line sources into a cube; see moments_band)
     python examples/image_channel.py --moments --imcontsub 1:1-3,5-10  (... with a continuum source, taken out on the cube)
+    python examples/image_channel.py --moments --median-contsub        (... taken out by the per-pixel median, told no line ranges)
     python examples/image_channel.py --moments --common-beam  (... every plane restored with its own beam, then all taken to one)
     python examples/image_channel.py --moments --common-beam --measure-noise  (... and the smoothed planes' noise measured)
 
@@ -555,7 +556,7 @@ def moments_band(args):
         n = math.sqrt(1 - l * l - m * m)
         source = np.exp(-2j * np.pi * (uvw_wl[:, 0] * l + uvw_wl[:, 1] * m + uvw_wl[:, 2] * (n - 1))) / n
         vis += source[:, None] * lines[name][None, :]
-        if contsub is not None and name == 'A':
+        if (contsub is not None or args.median_contsub) and name == 'A':
             vis += source[:, None] * (0.4 + 0.01 * (np.arange(C) - 5.5))[None, :]
     frequencies = _frequencies(obs, C)
     rest_frequency = float(frequencies[C // 2])
@@ -573,7 +574,7 @@ def moments_band(args):
     sc = cube.SpectralCube(ctx, cube_queue, frequencies, [0], (G, G), channel_width=frequencies[1] - frequencies[0])
     restorer = None
     for channel in range(C):
-        if contsub is None and line_a[channel] == 0 and line_b[channel] == 0:
+        if contsub is None and not args.median_contsub and line_a[channel] == 0 and line_b[channel] == 0:
             continue
         stats = frontend.process_channel(collector.reader(), channel, imager, image_p, grid_p, clean_p,
                                          weight_p.weight_type, args.vis_block, 1, True,
@@ -597,6 +598,26 @@ def moments_band(args):
         continuum_map = fit['continuum'].get(cube_queue)[0]
         print('imcontsub {}: {} of {} pixels fitted'.format(
             contsub, int((fit['count'].get(cube_queue) >= contsub.order + 1).sum()), G * G))
+    median_contsub = None
+    if args.median_contsub:
+        # the continuum of source A three ways: left in, taken out by a first-order fit that is told
+        # where the lines are (--imcontsub 1), and by the per-pixel median that is told nothing
+        from katsdpimager_amd import spectrum_stats
+        y, x = G // 2 + positions['A'][1], G // 2 + positions['A'][0]
+        left_in = float(moments(sc)[0].get(cube_queue)[0][y, x])
+        copies = [cube.SpectralCube(ctx, cube_queue, frequencies, [0], (G, G), channel_width=sc.channel_width)
+                  for _ in range(2)]
+        told = imcontsub.ImContSubParameters(1, line_ranges=[(1, 4), (5, 11)])
+        imcontsub.ImContSubTemplate(ctx, told).instantiate(cube_queue, sc.shape)(sc, out=copies[0])
+        median_op = spectrum_stats.SpectrumStatsTemplate(
+            ctx, spectrum_stats.SpectrumStatsParameters()).instantiate(cube_queue, sc.shape)
+        median_maps = median_op(sc, subtract=True, out=copies[1])
+        fitted = float(moments(copies[0])[0].get(cube_queue)[0][y, x])
+        sc = copies[1]
+        by_median = float(moments(sc)[0].get(cube_queue)[0][y, x])
+        median_contsub = dict(left_in=left_in, imcontsub=fitted, median=by_median,
+                              continuum=float(median_maps['median'].get(cube_queue)[0][y, x]),
+                              sigma=float(median_maps['sigma'].get(cube_queue)[0][y, x]))
     unsmoothed = None
     if args.common_beam:
         y, x = G // 2 + positions['A'][1], G // 2 + positions['A'][0]
@@ -649,6 +670,13 @@ def moments_band(args):
                                             continuum=float(continuum_map[y, x]))
             print('  moment 0 without the subtraction: {:12.6f}; continuum map {:.4f} Jy/beam'.format(
                 float(unsubtracted[y, x]), float(continuum_map[y, x])))
+    if median_contsub is not None:
+        results['median_contsub'] = median_contsub
+        print('moment 0 at source A, injected {:.6f}: {:.6f} with the continuum left in, {:.6f} after '
+              '--imcontsub 1, {:.6f} after the median subtraction (median map {:.4f} Jy/beam, sigma map '
+              '{:.2e})'.format(results['sources']['A']['injected'][0], median_contsub['left_in'],
+                               median_contsub['imcontsub'], median_contsub['median'],
+                               median_contsub['continuum'], median_contsub['sigma']))
     if args.output:
         from katsdpimager_amd import io, polarization
         image_p.fixed.polarizations = [polarization.STOKES_I]
@@ -718,6 +746,10 @@ def main(argv=None):
                     help='with --moments: leave a continuum source on source A, and fit and subtract a '
                          'polynomial of this order per pixel of the cube outside the listed channels '
                          '(default 1-3,5-10) ahead of the moments, e.g. --imcontsub 1')
+    ap.add_argument('--median-contsub', action='store_true',
+                    help='with --moments: leave the continuum source on source A and print moment 0 there '
+                         'with it left in, after --imcontsub 1 and after the per-pixel median across the '
+                         'band has been subtracted (spectrum_stats.SpectrumStats), next to the injected value')
     ap.add_argument('--common-beam', action='store_true',
                     help='with --moments: fit every channel\'s beam, restore the planes with theirs, take the '
                          'cube to the common beam and print moment 0 at source A without and with the smoothing')
@@ -730,6 +762,9 @@ def main(argv=None):
         ap.error('--measure-noise goes with --moments --common-beam')
     if args.imcontsub and not args.moments:
         ap.error('--imcontsub goes with --moments')
+    if args.median_contsub and (not args.moments or args.imcontsub or args.common_beam):
+        ap.error('--median-contsub goes with --moments, without --imcontsub (it runs both itself) '
+                 'and without --common-beam')
     if args.common_beam and not args.moments:
         ap.error('--common-beam goes with --moments')
     if args.moments:

@@ -1407,7 +1407,9 @@ int kimg_rfi_flag(const void *vis, int64_t vis_channel_pitch, float *weights,
  *   (2^31 - 1 workgroups of 256 elements).  M = 0 is then a successful call that does nothing.
  * Asynchronous on `stream`, no allocation, capturable; equal inputs give equal bits.
  * Not done here (a common restoring beam across planes is kimg_cube_smooth's): spatial smoothing of
- *   the selection, position-velocity cuts, medians (CASA moments 3 to 7, 10, 11), cubes across several GPUs. */
+ *   the selection, position-velocity cuts, cubes across several GPUs.  The median, minimum and robust
+ *   sigma along the spectrum (CASA moments 3 and 10) are kimg_spectrum_stats'; still missing are
+ *   moments 4 to 7, the coordinate of the minimum (11) and a per-pixel cut made from those maps. */
 #define KIMG_MOMENTS_MAX_CHANNELS 4096
 #define KIMG_MOMENT_0 1
 #define KIMG_MOMENT_1 2
@@ -1478,7 +1480,9 @@ int kimg_moments(const float *cube, int64_t channel_pitch, int num_channels, int
  * Asynchronous on `stream`, no allocation, capturable.  The order of every sum is fixed: equal inputs
  *   give equal bits.  Agreement with the twin: the bound of kimg_uvcontsub's tests,
  *   |dev - t| <= 2^-24 |t| + 1e-9 S against the twin's value before its one rounding.
- * Not done here: medians or robust fits, per-pixel weights, a fit across several cubes. */
+ * Not done here: robust polynomial fits and iterative clipping (the order-0 robust case, the
+ *   per-pixel median across the band, is kimg_spectrum_stats' line), per-pixel weights, a fit across
+ *   several cubes. */
 #define KIMG_IMCONTSUB_MAX_ORDER 3
 #define KIMG_IMCONTSUB_CONTINUUM 1
 #define KIMG_IMCONTSUB_COEFFICIENTS 2
@@ -1593,8 +1597,8 @@ int kimg_cube_smooth(const float *cube, int64_t channel_pitch, float *out, int64
  *   elements or more (so for every group of 2^32 candidates or more) and for G > 65535.
  * Asynchronous on `stream`, no allocation, capturable; the caller reads the 5 * C * G numbers.
  * Not done here: iterative sigma clipping; means and rms (an ordered float64 reduction, another
- *   contract); statistics along the channel axis per pixel (immoments' medians); the noise of a
- *   smoothed plane derived rather than measured; cubes across several GPUs. */
+ *   contract); the noise of a smoothed plane derived rather than measured; cubes across several
+ *   GPUs.  Statistics along the channel axis per pixel are kimg_spectrum_stats'. */
 #define KIMG_CUBE_STATS_MEDIAN_ABS 0
 #define KIMG_CUBE_STATS_MAD 1
 #define KIMG_CUBE_STATS_TO_RMS 1.4826022185056031f
@@ -1604,6 +1608,84 @@ int kimg_cube_stats(const float *cube, int64_t channel_pitch, int num_channels, 
                     int pool_polarizations, int estimator, int border, const uint8_t *region,
                     void *scratch, uint32_t *count, float *min, float *max, float *median,
                     float *sigma, void *stream);
+
+/* ---- Spectrum statistics (spectrum_stats.hip): for every element of the plane of a spectral cube the
+ * statistics of its own spectrum -- count, min, max, median and a robust sigma along the channel axis
+ * -- as maps [P][H][W], and optionally the cube with the median subtracted from every filled channel:
+ * the per-pixel noise map that source finders scale by, and the continuum estimate that needs no line
+ * ranges (CASA immoments' moment 3, MIRIAD contsub's median mode).  kimg_cube_stats selects along a
+ * plane, one number a plane; this selects along a column, one number an element.  The reference has
+ * none; the semantics are this library's, and katsdpimager_amd/spectrum_stats.py holds them once more
+ * as numpy (spectrum_stats_host).
+ *
+ * cube: DEVICE float32 [C][M]: C = num_channels (1 .. KIMG_MOMENTS_MAX_CHANNELS) planes of
+ *   M = plane_elements values, channel_pitch elements apart, channel_pitch >= M, as in kimg_moments.
+ *   Elements of the padding are neither read nor written.  Indices are 64-bit throughout.  The cube
+ *   is never written, unless `line` is the cube (below).
+ * Tables, per channel: stat_host and filled_host, HOST uint8 [C], read during the call; they travel
+ *   to the kernels by value, a bit per channel.  A channel ENTERS the statistics iff
+ *   first <= c < stop (0 <= first < stop <= C), stat_host[c] and filled_host[c].  S is the number of
+ *   entering channels; S = 0 is legal and gives n = 0 everywhere.
+ * Per element m on its own.  The samples are the finite cube[c][m] of the entering channels (NaN of
+ *   any sign or payload, +Inf and -Inf are left out), n their count.  Order is by kimg_cube_stats'
+ *   key, key(x) = bits ^ (bits >> 31 ? 0xffffffff : 0x80000000): -0 lies below +0.  With v the samples
+ *   in that order:
+ *     median  (v[(n - 1) / 2] + v[n / 2]) / 2 in float32 (kimg_cube_stats' rule; it may overflow to Inf)
+ *     min, max  the samples of smallest and largest key
+ *     sigma   KIMG_CUBE_STATS_MAD: median(|x - median|) * KIMG_CUBE_STATS_TO_RMS, x - median one
+ *             float32 subtraction with its sign bit cleared (+Inf is a value like any other; it is
+ *             never NaN); KIMG_CUBE_STATS_MEDIAN_ABS: median(|x|) times the same constant.  The
+ *             absolute values are ordered by 0x80000000 | abs bits and their median follows the rule
+ *             above; the product is one float32 product.
+ *     count   n (int32), always.
+ *   min_samples (>= 1): the four float maps hold 0x7fc00000 where n < min_samples.
+ * outputs: the KIMG_SPECTRUM_* bits of the maps [M] that are written, at least one.  The pointer of a
+ *   bit that is not set is ignored (NULL will do) and nothing is written through it; without
+ *   KIMG_SPECTRUM_SIGMA the sigma select is not run.
+ * line: NULL, or DEVICE float32 [C][M] with a pitch of its own: either exactly `cube` (the same
+ *   pointer AND the same pitch: in place) or a buffer that shares no byte with the cube's C planes.
+ *   For every filled channel c of 0 .. C - 1 -- not only the entering ones, not only the range --
+ *   line[c][m] = cube[c][m] - median[m], one float32 subtraction, where n >= min_samples, and
+ *   0x7fc00000 where not.  Channels that are not filled are neither read nor written.  The
+ *   subtraction reads the median map: a line needs KIMG_SPECTRUM_MEDIAN among the outputs.
+ * form: KIMG_SPECTRUM_FORM_RESIDENT keeps the keys of a wave's elements in LDS and reads the cube once
+ *   (S up to kimg_spectrum_stats_resident_limit()); KIMG_SPECTRUM_FORM_STREAMING is a radix select on
+ *   4-bit digits that re-reads the entering channels 9 times for the median and 9 more for sigma, for
+ *   any S; KIMG_SPECTRUM_FORM_AUTO takes the resident form for S <= 63 and the streaming form above,
+ *   where the two were measured level.  Load forms as in
+ *   kimg_moments: four elements per thread with 16-byte accesses when cube, line, their pitches * 4
+ *   and every requested map are 16-byte aligned, for the first 4 * (M / 4) elements; one element per
+ *   thread for the tail and for everything else.
+ * Agreement: everything is exact selection plus the single float32 operations named above.  Device
+ *   and twin have equal bits always, in every form, layout and launch geometry, and the two forms
+ *   have each other's bits.  (The NaN of a non-finite cube value minus the median is a NaN; its
+ *   payload is the hardware's.)
+ * Returns, before any HIP call: KIMG_EINVAL for a null cube, stat_host or filled_host; C < 1, M < 0; a
+ *   range outside 0 <= first < stop <= C; a pitch below M; an unknown estimator; min_samples < 1;
+ *   outputs without any KIMG_SPECTRUM_* bit or with others; an unknown form; a requested map that is
+ *   NULL; a pointer that is not 4-byte aligned; a line without KIMG_SPECTRUM_MEDIAN, with a pitch
+ *   below M, or one that overlaps the cube without being the cube; then KIMG_EUNSUPPORTED for
+ *   C > KIMG_MOMENTS_MAX_CHANNELS, for M beyond the grid limit (2^31 - 1 workgroups of 64 elements)
+ *   and for KIMG_SPECTRUM_FORM_RESIDENT with S above the limit.  M = 0 is then a successful call
+ *   that does nothing.
+ * Asynchronous on `stream`, no allocation, no workspace, capturable; equal inputs give equal bits.
+ * Not done here: moments 4 to 7 (absolute mean deviations and the like), the coordinate of the
+ *   minimum (moment 11), a per-pixel cut in kimg_moments made from these maps, iterative clipping,
+ *   robust polynomial fits. */
+#define KIMG_SPECTRUM_MEDIAN 1
+#define KIMG_SPECTRUM_SIGMA 2
+#define KIMG_SPECTRUM_MIN 4
+#define KIMG_SPECTRUM_MAX 8
+#define KIMG_SPECTRUM_COUNT 16
+#define KIMG_SPECTRUM_FORM_AUTO 0
+#define KIMG_SPECTRUM_FORM_RESIDENT 1
+#define KIMG_SPECTRUM_FORM_STREAMING 2
+int kimg_spectrum_stats_resident_limit(void);
+int kimg_spectrum_stats(const float *cube, int64_t channel_pitch, int num_channels,
+                        int64_t plane_elements, int first, int stop, const uint8_t *stat_host,
+                        const uint8_t *filled_host, int estimator, int min_samples, int outputs,
+                        float *median, float *sigma, float *min, float *max, int32_t *count,
+                        float *line, int64_t line_channel_pitch, int form, void *stream);
 
 #ifdef __cplusplus
 }

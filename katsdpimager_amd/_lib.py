@@ -154,6 +154,11 @@ PROTOTYPES = {
     # pool_polarizations, estimator, border, region, scratch, (count, min, max, median, sigma), stream
     'kimg_cube_stats_scratch_bytes': (c_size_t, [I, I]),
     'kimg_cube_stats': (c_int, [P, L, I, I, I, I, P, I, I, I, I, I, P, P, P, P, P, P, P, P]),
+    # spectrum statistics: (cube, pitch, C, M), (first, stop), (stat_host, filled_host), estimator,
+    # min_samples, outputs (KIMG_SPECTRUM_* bits), (median, sigma, min, max, count), (line, pitch),
+    # form, stream
+    'kimg_spectrum_stats_resident_limit': (c_int, []),
+    'kimg_spectrum_stats': (c_int, [P, L, I, L, I, I, P, P, I, I, I, P, P, P, P, P, P, L, I, P]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),

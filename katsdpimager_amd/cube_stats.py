@@ -40,8 +40,9 @@ The contract (include/kimg.h, "Cube plane statistics").
   with the same border in pixels, ``sigma`` under 'median_abs' is :class:`clean.NoiseEst`'s, by bits.
 
 Not done: iterative sigma clipping; means and rms (they need an ordered float64 reduction and are
-another contract); per-pixel statistics along the channel axis (the "medians" of ``immoments``);
-the noise of a smoothed plane derived rather than measured; cubes across several GPUs.
+another contract); the noise of a smoothed plane derived rather than measured; cubes across several
+GPUs.  Per-pixel statistics along the channel axis (the "medians" of ``immoments``) are
+:mod:`.spectrum_stats`.
 """
 import ctypes
 

@@ -16,7 +16,9 @@ usable samples is fitted and has the model subtracted from every filled channel 
 stay as they are), any other has its filled channels set to NaN.  Channels that are not filled are
 neither read nor written.
 
-Not done: medians or robust fits, per-pixel weights, a fit across several cubes.
+Not done: robust polynomial fits and iterative clipping (the order-0 robust case, the per-pixel median
+across the band that needs no line ranges, is :mod:`.spectrum_stats` with ``subtract=True``), per-pixel
+weights, a fit across several cubes.
 """
 import ctypes
 
