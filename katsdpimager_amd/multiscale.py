@@ -101,6 +101,40 @@ def crop_range(n, patch, radius):
     return max(start, 0), min(start + size, n)
 
 
+def workspace_layout(P, H, W, psf_patch, border_pixels, radii):
+    """The sections of the workspace (include/kimg.h), in floats, of a [P][H][W] image with the
+    patch ``psf_patch`` (P, h, w), a border in pixels and the scales' radii: the starts of ``coef``,
+    ``taps``, ``tile_max``, ``tile_pos``, of ``res[k]`` (k >= 1) and of ``cross[j, k]`` (with its
+    shape), ``tile_pitch`` and ``total``."""
+    K = len(radii)
+    r64 = lambda n: (n + 63) // 64 * 64     # noqa: E731
+    tiles = (-(-(H - 2 * border_pixels) // TILE), -(-(W - 2 * border_pixels) // TILE))
+    tile_pitch = r64(tiles[0] * tiles[1])
+    image = r64(P * H * W)
+    at = 64 + 64
+    lay = dict(coef=64, taps=at, tile_pitch=tile_pitch)
+    at += MAX_SCALES * _TAPS_PITCH + r64(MAX_SCALES * (MAX_SCALES + 1) // 2 * _CROSS_PITCH)
+    lay['tile_max'] = at
+    at += K * tile_pitch
+    lay['tile_pos'] = at
+    at += 2 * K * tile_pitch
+    lay['res'] = {}
+    for k in range(1, K):
+        lay['res'][k] = at
+        at += image
+    lay['cross'] = {}
+    for j in range(K):
+        for k in range(K):
+            R = radii[j] + radii[k]
+            y0, y1 = crop_range(H, psf_patch[1], R)
+            x0, x1 = crop_range(W, psf_patch[2], R)
+            lay['cross'][j, k] = (at, (P, y1 - y0, x1 - x0))
+            at += r64(P * (y1 - y0) * (x1 - x0))
+    at += 2 * image
+    lay['total'] = at
+    return lay
+
+
 # ---- the numpy twin -------------------------------------------------------------------------
 
 def _conv_axis(a, taps):
@@ -323,34 +357,8 @@ class MultiScaleClean(accel.Operation):
         raise NotImplementedError('use reset() and run_cycles()')
 
     def _make_layout(self, psf_patch):
-        """The sections of the workspace (include/kimg.h), in floats."""
         P, H, W = self.buffer('dirty').shape
-        K = len(self._radii)
-        r64 = lambda n: (n + 63) // 64 * 64     # noqa: E731
-        tile_pitch = r64(self.tiles[0] * self.tiles[1])
-        image = r64(P * H * W)
-        at = 64 + 64
-        lay = dict(coef=64, taps=at, tile_pitch=tile_pitch)
-        at += MAX_SCALES * _TAPS_PITCH + r64(MAX_SCALES * (MAX_SCALES + 1) // 2 * _CROSS_PITCH)
-        lay['tile_max'] = at
-        at += K * tile_pitch
-        lay['tile_pos'] = at
-        at += 2 * K * tile_pitch
-        lay['res'] = {}
-        for k in range(1, K):
-            lay['res'][k] = at
-            at += image
-        lay['cross'] = {}
-        for j in range(K):
-            for k in range(K):
-                R = self._radii[j] + self._radii[k]
-                y0, y1 = crop_range(H, psf_patch[1], R)
-                x0, x1 = crop_range(W, psf_patch[2], R)
-                lay['cross'][j, k] = (at, (P, y1 - y0, x1 - x0))
-                at += r64(P * (y1 - y0) * (x1 - x0))
-        at += 2 * image
-        lay['total'] = at
-        return lay
+        return workspace_layout(P, H, W, psf_patch, self.border_pixels, self._radii)
 
     def reset(self, new_psf=True):
         """The residuals of the scales k >= 1 and every tile record are rebuilt from the dirty
