@@ -15,6 +15,7 @@ store -> imaging weights, PSF, major/minor cycles -> restored image, all on one 
     python examples/image_channel.py --moments --median-contsub        (... taken out by the per-pixel median, told no line ranges)
     python examples/image_channel.py --moments --common-beam  (... every plane restored with its own beam, then all taken to one)
     python examples/image_channel.py --moments --common-beam --measure-noise  (... and the smoothed planes' noise measured)
+    python examples/image_channel.py --moments --find-sources  (... and the smooth-and-clip detection mask of the cube)
 
 It follows the reference's per-channel flow (frontend.py:31-83 preprocess_visibilities,
 :465-658 process_channel) with the loaders and FITS output left out: the sky is three point
@@ -677,6 +678,26 @@ def moments_band(args):
               '{:.2e})'.format(results['sources']['A']['injected'][0], median_contsub['left_in'],
                                median_contsub['imcontsub'], median_contsub['median'],
                                median_contsub['continuum'], median_contsub['sigma']))
+    if args.find_sources:
+        # moment 0 at the first line source three ways: everything finite, the per-voxel 3 sigma clip
+        # (above), and through the smooth-and-clip mask, which measures every smoothed copy's noise itself
+        from katsdpimager_amd import detect
+        name = next(iter(positions))
+        y, x = G // 2 + positions[name][1], G // 2 + positions[name][0]
+        finder = detect.SmoothClipTemplate(ctx, detect.SmoothClipParameters()).instantiate(cube_queue, sc.shape)
+        found = finder(sc)
+        voxels = int(found.get(cube_queue).sum())
+        plain = cube.MomentsTemplate(ctx, cube.MomentParameters((0,), rest_frequency=rest_frequency)).instantiate(
+            cube_queue, sc.shape)
+        unclipped = float(plain(sc)[0].get(cube_queue)[0][y, x])
+        through = float(plain(found.apply(sc))[0].get(cube_queue)[0][y, x])
+        results['find_sources'] = dict(voxels=voxels, unclipped=unclipped, through_mask=through,
+                                       clipped=results['sources'][name]['moments'][0])
+        print('smooth-and-clip at {} sigma: {} of {} voxels detected'.format(
+            finder.params.threshold, voxels, int(np.prod(sc.shape))))
+        print('moment 0 at source {}, injected {:.6f}: {:.6f} unclipped, {:.6f} with clip_sigma=3, '
+              '{:.6f} through the mask'.format(name, results['sources'][name]['injected'][0], unclipped,
+                                               results['sources'][name]['moments'][0], through))
     if args.output:
         from katsdpimager_amd import io, polarization
         image_p.fixed.polarizations = [polarization.STOKES_I]
@@ -753,6 +774,10 @@ def main(argv=None):
     ap.add_argument('--common-beam', action='store_true',
                     help='with --moments: fit every channel\'s beam, restore the planes with theirs, take the '
                          'cube to the common beam and print moment 0 at source A without and with the smoothing')
+    ap.add_argument('--find-sources', action='store_true',
+                    help='with --moments: build the smooth-and-clip detection mask of the cube '
+                         '(detect.SmoothClip) and print the number of detected voxels and moment 0 at the '
+                         'first line source unclipped, with clip_sigma=3 and through the mask')
     ap.add_argument('--measure-noise', action='store_true',
                     help='with --moments --common-beam: measure the noise of the smoothed planes '
                          '(cube_stats.CubeStats), print it next to the scaled stand-in and use it for the '
@@ -762,6 +787,8 @@ def main(argv=None):
         ap.error('--measure-noise goes with --moments --common-beam')
     if args.imcontsub and not args.moments:
         ap.error('--imcontsub goes with --moments')
+    if args.find_sources and not args.moments:
+        ap.error('--find-sources goes with --moments')
     if args.median_contsub and (not args.moments or args.imcontsub or args.common_beam):
         ap.error('--median-contsub goes with --moments, without --imcontsub (it runs both itself) '
                  'and without --common-beam')

@@ -1406,8 +1406,10 @@ int kimg_rfi_flag(const void *vis, int64_t vis_channel_pitch, float *weights,
  *   4-byte aligned); KIMG_EUNSUPPORTED for C > KIMG_MOMENTS_MAX_CHANNELS or M beyond the grid limit
  *   (2^31 - 1 workgroups of 256 elements).  M = 0 is then a successful call that does nothing.
  * Asynchronous on `stream`, no allocation, capturable; equal inputs give equal bits.
- * Not done here (a common restoring beam across planes is kimg_cube_smooth's): spatial smoothing of
- *   the selection, position-velocity cuts, cubes across several GPUs.  The median, minimum and robust
+ * Not done here (a common restoring beam across planes is kimg_cube_smooth's; a selection smoothed
+ *   in space and along the spectrum is the detection mask's, "Detection mask" below, which reaches
+ *   this call through kimg_cube_mask_apply): position-velocity cuts, cubes across several GPUs.  The
+ *   median, minimum and robust
  *   sigma along the spectrum (CASA moments 3 and 10) are kimg_spectrum_stats'; still missing are
  *   moments 4 to 7, the coordinate of the minimum (11) and a per-pixel cut made from those maps. */
 #define KIMG_MOMENTS_MAX_CHANNELS 4096
@@ -1686,6 +1688,101 @@ int kimg_spectrum_stats(const float *cube, int64_t channel_pitch, int num_channe
                         const uint8_t *filled_host, int estimator, int min_samples, int outputs,
                         float *median, float *sigma, float *min, float *max, int32_t *count,
                         float *line, int64_t line_channel_pitch, int form, void *stream);
+
+/* ---- Detection mask (cube_detect.hip): the pieces of a smooth-and-clip source finder on a spectral
+ * cube (SoFiA's S+C finder, the masks built by hand around CASA immoments, tclean's auto-multithresh
+ * on cubes): the cube is smoothed with a set of spatial and spectral kernels, each smoothed copy is
+ * thresholded at a multiple of its own measured noise, and the union is the detection mask.  The
+ * spatial smoothing is kimg_cube_smooth's and the noise kimg_cube_stats'; here are the spectral
+ * boxcar, the restoring of blanks, the threshold into the mask, the pruning of short runs and the
+ * mask applied to a cube, which is how kimg_moments honours it (NaN is "not usable" there already).
+ * The reference has none; the semantics are this library's, and katsdpimager_amd/detect.py holds them
+ * once more as numpy (boxcar_host, reblank_host, threshold_host, prune_host, apply_host) together with
+ * the finder's order of calls (smooth_clip_host).
+ *
+ * Shared by the five entries.  A cube is DEVICE float32 [C][M]: C = num_channels (1 ..
+ *   KIMG_MOMENTS_MAX_CHANNELS) planes of M = plane_elements values (for images [P][H][W], dense,
+ *   M = P * H * W), a channel pitch in elements apart, pitch >= M, as in kimg_moments; every cube of a
+ *   call has a pitch of its own.  The mask is DEVICE uint8 [C][M], mask_pitch in bytes >= M: 0 = not
+ *   detected, 1 = detected; the kernels write only 0 or 1 and read any nonzero value as set.
+ *   filled_host: HOST uint8 [C], nonzero = the plane holds an image; it is read during the call and
+ *   travels by value, a bit per channel.  Padding is neither read nor written.  Indices are 64-bit.
+ *   "Not finite" is NaN of any sign or payload, +Inf and -Inf.
+ * Load forms, as in kimg_moments: four elements per thread with 16-byte float accesses where every
+ *   float base and pitch * 4 of the call is 16-byte aligned, for the first 4 * (M / 4) elements, one
+ *   element per thread for the tail and for everything else; with them the mask's four bytes are one
+ *   4-byte load where the mask's base and pitch are 4-byte aligned and four byte loads where not.
+ *   Bytes of the mask are STORED one by one, only where the contract names them.  kimg_cube_reblank
+ *   and kimg_cube_threshold store single elements, so only their loads have the 16-byte form, and
+ *   kimg_cube_mask_prune's four-wide form needs the mask's 4-byte alignment alone.
+ * Returns, before any HIP call: KIMG_EINVAL for a null pointer (kimg_cube_boxcar's mask excepted), C < 1,
+ *   M < 0 (kimg_cube_threshold: P, H or W below 1), a float pointer that is not 4-byte aligned, a
+ *   pitch below M, and what an entry lists below; KIMG_EUNSUPPORTED for C > KIMG_MOMENTS_MAX_CHANNELS
+ *   or M beyond the grid limit (2^31 - 1 workgroups of 256 elements; kimg_cube_boxcar: of 64).  M = 0
+ *   is then a successful call that does nothing.
+ * Asynchronous on `stream`, no allocation, no workspace, capturable; equal inputs give equal bits.
+ * Agreement with the twins: bit for bit, NaN in the same places.  Everything is exact selection, one
+ *   named float32 operation, or a float64 sum in a stated order in a build that fuses nothing.
+ *
+ * kimg_cube_boxcar: the spectral boxcar with replacement.  width = w = 2 h + 1, odd, 1 ..
+ *   KIMG_BOXCAR_MAX_WIDTH.  Per element m on its own: for a channel c', z[c'] = cube[c'][m] iff
+ *   0 <= c' < C, filled[c'], the value is finite and (mask is NULL or mask[c'][m] == 0); else +0.0f.
+ *   For every filled c, in float64, nothing fused, c' ascending from c - h to c + h:
+ *       acc = 0.0;  acc = acc + (double) z[c']
+ *   and out[c][m] = (float) (acc / (double) w): always divided by w, which is zero padding at the ends
+ *   of the band.  With blank != 0, out[c][m] = 0x7fc00000 where cube[c][m] itself is not finite.
+ *   Channels that are not filled are not written.  out shares no byte with the cube (KIMG_EINVAL; in
+ *   place is not done).  width = 1 is the copy with non-finite and already-detected voxels made 0.
+ *   The sum is a direct one: a running add-and-subtract window does not have its bits and is not
+ *   what this is.  Also KIMG_EINVAL: an even width, one outside 1 .. 31.
+ *   Kernel: a workgroup of one wave keeps the last w + 6 channels of its elements in LDS (8 .. 64
+ *   rows of 1 KiB at four elements per thread); every voxel is read from memory once whatever w is.
+ * kimg_cube_reblank: for every filled c, work[c][m] = 0x7fc00000 where cube[c][m] is not finite;
+ *   nothing else is written.  After the spatial smoothing of a boxcar's result (whose blanks were
+ *   made 0), it keeps blanked voxels out of the noise and the threshold.  work shares no byte with
+ *   the cube (KIMG_EINVAL).
+ * kimg_cube_threshold: sigma is DEVICE float32 [C][groups], what kimg_cube_stats wrote; groups is 1
+ *   (pooled) or P.  Per filled c and element m of polarization p: g = groups == 1 ? 0 : p,
+ *   cut = threshold * sigma[c * groups + g] (one float32 product), s = work[c][m].  The voxel is
+ *   detected iff s is finite and, in a float32 compare, s > cut (KIMG_DETECT_POSITIVE), -s > cut
+ *   (KIMG_DETECT_NEGATIVE) or fabsf(s) > cut (KIMG_DETECT_BOTH); a NaN cut detects nothing.  A detected
+ *   voxel sets mask[c][m] = 1; nothing else of the mask is written and nothing is ever cleared.  The
+ *   host does not read sigma.  Also KIMG_EINVAL: groups other than 1 and P, a threshold that is not a
+ *   finite number above 0, an unknown polarity, a sigma that is not 4-byte aligned.
+ * kimg_cube_mask_prune: per element m, every maximal run of consecutive channels with a nonzero mask
+ *   that is shorter than min_channels (1 .. C) is cleared to 0, and a nonzero byte of a run that stays
+ *   becomes 1.  All C channels are walked: a channel that is not filled is one whose mask is 0.  With
+ *   min_channels = 1 nothing is cleared, and a mask of 0 and 1 is left as it is.  Also KIMG_EINVAL:
+ *   min_channels outside 1 .. C.
+ * kimg_cube_mask_apply: for every filled c, line[c][m] = cube[c][m] where
+ *   (mask[c][m] != 0) != (invert != 0), else 0x7fc00000.  line is either exactly `cube` (the same
+ *   pointer AND the same pitch: in place) or shares no byte with it (kimg_spectrum_stats' rule;
+ *   KIMG_EINVAL).  Channels that are not filled are neither read nor written.
+ *
+ * Not done here: linking the mask into sources and a source catalogue; reliability from negative
+ *   detections; mask dilation; a running-window boxcar; the noise of a smoothed cube derived rather
+ *   than measured; spatial kernels beyond radius 16; kimg_moments reading the mask itself; cubes
+ *   across several GPUs. */
+#define KIMG_BOXCAR_MAX_WIDTH 31
+#define KIMG_DETECT_POSITIVE 0
+#define KIMG_DETECT_NEGATIVE 1
+#define KIMG_DETECT_BOTH 2
+int kimg_cube_boxcar(const float *cube, int64_t channel_pitch, const uint8_t *mask, int64_t mask_pitch,
+                     float *out, int64_t out_channel_pitch, int num_channels, int64_t plane_elements,
+                     const uint8_t *filled_host, int width, int blank, void *stream);
+int kimg_cube_reblank(float *work, int64_t work_channel_pitch, const float *cube,
+                      int64_t channel_pitch, int num_channels, int64_t plane_elements,
+                      const uint8_t *filled_host, void *stream);
+int kimg_cube_threshold(const float *work, int64_t work_channel_pitch, uint8_t *mask,
+                        int64_t mask_pitch, int num_channels, int num_polarizations, int height,
+                        int width, const uint8_t *filled_host, const float *sigma, int groups,
+                        float threshold, int polarity, void *stream);
+int kimg_cube_mask_prune(uint8_t *mask, int64_t mask_pitch, int num_channels, int64_t plane_elements,
+                         int min_channels, void *stream);
+int kimg_cube_mask_apply(const float *cube, int64_t channel_pitch, const uint8_t *mask,
+                         int64_t mask_pitch, float *line, int64_t line_channel_pitch,
+                         int num_channels, int64_t plane_elements, const uint8_t *filled_host,
+                         int invert, void *stream);
 
 #ifdef __cplusplus
 }

@@ -159,6 +159,16 @@ PROTOTYPES = {
     # form, stream
     'kimg_spectrum_stats_resident_limit': (c_int, []),
     'kimg_spectrum_stats': (c_int, [P, L, I, L, I, I, P, P, I, I, I, P, P, P, P, P, P, L, I, P]),
+    # detection mask: boxcar (cube, pitch, mask_or_null, mask_pitch, out, pitch, C, M, filled_host, width,
+    # blank, stream); reblank (work, pitch, cube, pitch, C, M, filled_host, stream); threshold (work,
+    # pitch, mask, mask_pitch, C, P, H, W, filled_host, sigma, groups, threshold, polarity, stream);
+    # prune (mask, mask_pitch, C, M, min_channels, stream); apply (cube, pitch, mask, mask_pitch, line,
+    # pitch, C, M, filled_host, invert, stream)
+    'kimg_cube_boxcar': (c_int, [P, L, P, L, P, L, I, L, P, I, I, P]),
+    'kimg_cube_reblank': (c_int, [P, L, P, L, I, L, P, P]),
+    'kimg_cube_threshold': (c_int, [P, L, P, L, I, I, I, I, P, P, I, F, I, P]),
+    'kimg_cube_mask_prune': (c_int, [P, L, I, L, I, P]),
+    'kimg_cube_mask_apply': (c_int, [P, L, P, L, P, L, I, L, P, I, P]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),

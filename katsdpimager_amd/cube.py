@@ -28,8 +28,10 @@ over the channels c = first .. stop - 1 in ascending order, I = cube[c][m]:
   9 = x of the peak's channel; ``count`` = n (int32).  Every moment is NaN where n == 0, moments 1 and 2
   also unless S0 > 0.  The cube is never written.
 
-Not done: spatial smoothing of the selection, position-velocity cuts, cubes across several GPUs (with
-channels sharded over GPUs the caller gathers planes with :meth:`SpectralCube.put`).  The median,
+Not done: position-velocity cuts, cubes across several GPUs (with channels sharded over GPUs the
+caller gathers planes with :meth:`SpectralCube.put`).  A selection smoothed in space and along the
+spectrum is :mod:`.detect`'s smooth-and-clip mask, which :meth:`detect.MaskCube.apply` hands to
+:class:`Moments` as NaN.  The median,
 minimum and robust sigma along the spectrum (CASA moments 3 and 10) are :mod:`.spectrum_stats`'; still
 missing are moments 4 to 7, the coordinate of the minimum (11) and a per-pixel cut made from those maps.  All planes share one pixel size, which is the caller's business; every
 plane keeps its own restoring beam until :mod:`.smooth` takes the cube to a common one.  Image-plane
