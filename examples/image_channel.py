@@ -15,7 +15,7 @@ store -> imaging weights, PSF, major/minor cycles -> restored image, all on one 
     python examples/image_channel.py --moments --median-contsub        (... taken out by the per-pixel median, told no line ranges)
     python examples/image_channel.py --moments --common-beam  (... every plane restored with its own beam, then all taken to one)
     python examples/image_channel.py --moments --common-beam --measure-noise  (... and the smoothed planes' noise measured)
-    python examples/image_channel.py --moments --find-sources  (... and the smooth-and-clip detection mask of the cube)
+    python examples/image_channel.py --moments --find-sources  (... and the smooth-and-clip detection mask of the cube, linked into a catalogue)
 
 It follows the reference's per-channel flow (frontend.py:31-83 preprocess_visibilities,
 :465-658 process_channel) with the loaders and FITS output left out: the sky is three point
@@ -698,6 +698,24 @@ def moments_band(args):
         print('moment 0 at source {}, injected {:.6f}: {:.6f} unclipped, {:.6f} with clip_sigma=3, '
               '{:.6f} through the mask'.format(name, results['sources'][name]['injected'][0], unclipped,
                                                results['sources'][name]['moments'][0], through))
+        # the mask linked into sources: the catalogue, and moment 0 of the first source through its own mask
+        from katsdpimager_amd import link
+        linker = link.LinkTemplate(ctx, link.LinkParameters(radius_xy=1.5, min_voxels=3)).instantiate(
+            cube_queue, sc.shape)
+        labels, catalogue = linker(found, sc)
+        results['find_sources']['catalogue'] = [
+            {field: row[field].tolist() for field in catalogue.dtype.names} for row in catalogue]
+        print('{} sources of at least 3 voxels:'.format(len(catalogue)))
+        for row in catalogue:
+            print('  {:3d}: {:5d} voxels, peak {:.6f} at (c, y, x) = ({}, {}, {}), sum {:.6f}, centroid '
+                  '({:.2f}, {:.2f}, {:.2f}), {:.6f} MHz'.format(
+                      row['id'], row['voxels'], row['peak'], row['peak_c'], row['peak_y'], row['peak_x'],
+                      row['sum'], *row['centroid'], row['frequency'] / 1e6))
+        if len(catalogue):
+            own = plain(labels.mask(source=1).apply(sc))[0].get(cube_queue)[0]
+            results['find_sources']['first_source_moment0'] = float(np.nansum(own))
+            print('moment 0 of source 1 through its own mask: {} pixels, {:.6f} in all'.format(
+                int(np.isfinite(own).sum()), float(np.nansum(own))))
     if args.output:
         from katsdpimager_amd import io, polarization
         image_p.fixed.polarizations = [polarization.STOKES_I]
@@ -777,7 +795,8 @@ def main(argv=None):
     ap.add_argument('--find-sources', action='store_true',
                     help='with --moments: build the smooth-and-clip detection mask of the cube '
                          '(detect.SmoothClip) and print the number of detected voxels and moment 0 at the '
-                         'first line source unclipped, with clip_sigma=3 and through the mask')
+                         'first line source unclipped, with clip_sigma=3 and through the mask; then link the mask '
+                         'into sources (link.Link) and print the catalogue and moment 0 of the first source')
     ap.add_argument('--measure-noise', action='store_true',
                     help='with --moments --common-beam: measure the noise of the smoothed planes '
                          '(cube_stats.CubeStats), print it next to the scaled stand-in and use it for the '

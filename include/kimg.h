@@ -1759,10 +1759,10 @@ int kimg_spectrum_stats(const float *cube, int64_t channel_pitch, int num_channe
  *   pointer AND the same pitch: in place) or shares no byte with it (kimg_spectrum_stats' rule;
  *   KIMG_EINVAL).  Channels that are not filled are neither read nor written.
  *
- * Not done here: linking the mask into sources and a source catalogue; reliability from negative
- *   detections; mask dilation; a running-window boxcar; the noise of a smoothed cube derived rather
- *   than measured; spatial kernels beyond radius 16; kimg_moments reading the mask itself; cubes
- *   across several GPUs. */
+ * Not done here (linking the mask into sources and a catalogue is "Source linking" below):
+ *   reliability from negative detections; mask dilation; a running-window boxcar; the noise of a
+ *   smoothed cube derived rather than measured; spatial kernels beyond radius 16; kimg_moments reading
+ *   the mask itself; cubes across several GPUs. */
 #define KIMG_BOXCAR_MAX_WIDTH 31
 #define KIMG_DETECT_POSITIVE 0
 #define KIMG_DETECT_NEGATIVE 1
@@ -1783,6 +1783,99 @@ int kimg_cube_mask_apply(const float *cube, int64_t channel_pitch, const uint8_t
                          int64_t mask_pitch, float *line, int64_t line_channel_pitch,
                          int num_channels, int64_t plane_elements, const uint8_t *filled_host,
                          int invert, void *stream);
+
+/* ---- Source linking (cube_link.hip): the detection mask linked into sources -- which voxels belong
+ * together, how many sources there are, where each one is and how bright -- measured into a catalogue,
+ * filtered by size, and handed back as a mask (SoFiA's linker and parameteriser, the seeds of CASA's
+ * imfit, the region list that immoments takes per source).  The reference has none; the semantics are
+ * this library's, and katsdpimager_amd/link.py holds them once more as numpy (link_host, measure_host,
+ * filter_host, label_mask_host).
+ *
+ * Shared by the entries.  The mask is DEVICE uint8 [C][M] with mask_pitch in bytes, the labels DEVICE
+ *   int32 [C][M] with a pitch of their own in elements, the cube DEVICE float32 [C][M] with its own
+ *   pitch; every pitch >= M; M = P * H * W, dense, as in kimg_cube_threshold.  filled_host: HOST uint8
+ *   [C], read during the call, travels by value.  A voxel is SET iff its channel is filled and its
+ *   mask byte is nonzero; unfilled channels of the mask and of the cube are not read.  d(c, m) =
+ *   c * M + m is the DENSE INDEX of a voxel; it knows no pitch, and nothing in a result depends on a
+ *   pitch, an offset or the launch geometry.  Padding is neither read nor written.
+ * Neighbours: two set voxels (c, p, y, x) and (c', p', y', x') iff p == p', |c - c'| <= reach_z
+ *   (0 .. 3) and (x - x')^2 + (y - y')^2 <= reach_xy_sq (0 .. 9).  The channel distance counts
+ *   channels, filled or not.  Polarization is never a linking axis.  A source is a connected
+ *   component of this relation.
+ *
+ * kimg_cube_link: labels[c][m] = 0 for a voxel that is not set (in every channel, filled or not: the
+ *   whole label cube is written), else the number of its source, 1 .. N0, sources numbered in
+ *   ascending order of their smallest dense index; counts[0] = N0 (counts: DEVICE int32 [2]).  For
+ *   reach_xy_sq in {1, 2} and reach_z <= 1 this is scipy.ndimage.label on [C][P][H][W] with a
+ *   structure that is empty along P.  Integers only: the same bits on every run.
+ *   Kernel: a lock-free union-find in the label cube (the smaller dense index is the root, atomicMin,
+ *   relaxed agent-scope loads), six launches: init, merge, flatten with a count of roots per
+ *   workgroup, a scan of those counts, the roots numbered, every voxel relabelled.
+ *   scratch: DEVICE, kimg_cube_link_scratch_bytes(C, M) bytes (0 for arguments out of range), 4-byte
+ *   aligned; the call initialises it.
+ * kimg_catalogue: a HOST struct of DEVICE arrays [capacity] each, read during the call; row s - 1 is
+ *   source s.  work: kimg_cube_catalogue_work_bytes(capacity) bytes, 8-byte aligned, the calls' own.
+ * kimg_cube_measure: for every source s <= min(counts[0], capacity), over the voxels of filled
+ *   channels with labels[c][m] == s: first = the smallest dense index; voxels = their number; finite =
+ *   the number whose cube value is finite; the inclusive bounding box c0, c1, y0, y1, x0, x1.  Over
+ *   the finite ones: peak = the largest value in kimg_cube_stats' order (key(x) of the bit pattern, -0
+ *   below +0) and peak_index its dense index, the smallest on ties; trough and trough_index likewise
+ *   for the smallest value; NaN (0x7fc00000) and -1 where finite == 0.  sum = sum f, sum_c = sum f * c,
+ *   sum_y = sum f * y, sum_x = sum f * x: float64, nothing fused, one product per term, c, y, x exact
+ *   doubles, 0 where finite == 0.  Rows beyond counts[0] and sources beyond capacity are not written.
+ *   The integer and peak fields are exact.  The ORDER of the four sums is not part of the contract
+ *   (they are float64 atomic adds of per-thread partial sums): on values whose sums are exact in
+ *   every order they equal the twin's, otherwise each differs from the exactly rounded sum by at
+ *   most n * 2^-53 * sum |term|, n = finite.
+ *   Kernel: a thread owns four consecutive elements of the plane for the whole channel loop and keeps
+ *   the partial sums, counts, box and keys of the current run of equal labels in registers; it issues
+ *   its atomics when the label changes or the walk ends.  Peaks are a 64-bit atomicMax on (value key,
+ *   inverted dense index), decoded by a last small launch.
+ * kimg_cube_link_filter: with N0 = counts[0] <= capacity, a source is kept iff voxels >= min_voxels,
+ *   x1 - x0 + 1 >= min_size_xy, y1 - y0 + 1 >= min_size_xy and c1 - c0 + 1 >= min_size_z.  Kept
+ *   sources are renumbered 1 .. N in their old order, their rows compacted to the front (rows N ..
+ *   N0 - 1 keep what they held), every label rewritten (dropped sources become 0), counts[1] = N.
+ *   With all three minima at 1 nothing changes.  With N0 > capacity nothing is changed at all and
+ *   counts[1] = N0.  Takes (C, M); no mask, no cube, no filled.
+ * kimg_cube_label_mask: mask[c][m] = 1 where labels[c][m] != 0 (source == 0) or labels[c][m] ==
+ *   source (source > 0), else 0, in every channel: the whole mask is written.
+ *
+ * Returns, before any HIP call: KIMG_EINVAL for a null pointer, C < 1, P, H or W below 1 (M < 0 where
+ *   an entry takes M), a pitch below M, a labels, cube, counts or scratch pointer that is not 4-byte
+ *   aligned, a reach out of range, capacity < 1, a catalogue with a null or misaligned array (4 bytes;
+ *   the sums and work 8), a minimum below 1, a source below 0; then KIMG_EUNSUPPORTED for
+ *   C > KIMG_MOMENTS_MAX_CHANNELS or C * M > 2^31 - 2 (labels are int32).  M = 0 is then a successful
+ *   call that does nothing to cubes.
+ * Asynchronous on `stream`, no allocation, capturable; the host reads nothing.
+ * Not done here: reliability from negative detections; mask dilation; per-source spectra and moment
+ *   maps beyond kimg_cube_label_mask's mask of one source; fluxes in Jy (the beam area and the channel
+ *   width are the caller's); uncertainties; sources across polarizations; cubes across several GPUs;
+ *   bit-reproducible sums (a store-and-sum pass, another contract). */
+typedef struct kimg_catalogue {
+    int32_t *first, *voxels, *finite, *c0, *c1, *y0, *y1, *x0, *x1;
+    float *peak;
+    int32_t *peak_index;
+    float *trough;
+    int32_t *trough_index;
+    double *sum, *sum_c, *sum_y, *sum_x;
+    void *work;
+} kimg_catalogue;
+size_t kimg_cube_link_scratch_bytes(int num_channels, int64_t plane_elements);
+size_t kimg_cube_catalogue_work_bytes(int capacity);
+int kimg_cube_link(const uint8_t *mask, int64_t mask_pitch, int32_t *labels, int64_t label_pitch,
+                   int num_channels, int num_polarizations, int height, int width,
+                   const uint8_t *filled_host, int reach_xy_sq, int reach_z, void *scratch,
+                   int32_t *counts, void *stream);
+int kimg_cube_measure(const int32_t *labels, int64_t label_pitch, const float *cube,
+                      int64_t channel_pitch, int num_channels, int num_polarizations, int height,
+                      int width, const uint8_t *filled_host, const kimg_catalogue *catalogue,
+                      int capacity, const int32_t *counts, void *stream);
+int kimg_cube_link_filter(int32_t *labels, int64_t label_pitch, int num_channels,
+                          int64_t plane_elements, const kimg_catalogue *catalogue, int capacity,
+                          int min_voxels, int min_size_xy, int min_size_z, int32_t *counts,
+                          void *stream);
+int kimg_cube_label_mask(const int32_t *labels, int64_t label_pitch, uint8_t *mask, int64_t mask_pitch,
+                         int num_channels, int64_t plane_elements, int source, void *stream);
 
 #ifdef __cplusplus
 }

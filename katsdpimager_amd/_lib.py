@@ -169,6 +169,18 @@ PROTOTYPES = {
     'kimg_cube_threshold': (c_int, [P, L, P, L, I, I, I, I, P, P, I, F, I, P]),
     'kimg_cube_mask_prune': (c_int, [P, L, I, L, I, P]),
     'kimg_cube_mask_apply': (c_int, [P, L, P, L, P, L, I, L, P, I, P]),
+    # source linking: scratch bytes (C, M); catalogue work bytes (capacity); link (mask, mask_pitch,
+    # labels, label_pitch, C, P, H, W, filled_host, reach_xy_sq, reach_z, scratch, counts, stream);
+    # measure (labels, label_pitch, cube, pitch, C, P, H, W, filled_host, kimg_catalogue *, capacity,
+    # counts, stream); filter (labels, label_pitch, C, M, kimg_catalogue *, capacity, min_voxels,
+    # min_size_xy, min_size_z, counts, stream); label mask (labels, label_pitch, mask, mask_pitch, C, M,
+    # source, stream)
+    'kimg_cube_link_scratch_bytes': (c_size_t, [I, L]),
+    'kimg_cube_catalogue_work_bytes': (c_size_t, [I]),
+    'kimg_cube_link': (c_int, [P, L, P, L, I, I, I, I, P, I, I, P, P, P]),
+    'kimg_cube_measure': (c_int, [P, L, P, L, I, I, I, I, P, P, I, P, P]),
+    'kimg_cube_link_filter': (c_int, [P, L, I, L, P, I, I, I, I, P, P]),
+    'kimg_cube_label_mask': (c_int, [P, L, P, L, I, L, I, P]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
@@ -201,6 +213,13 @@ class UVTaper(ctypes.Structure):
     _fields_ = [('quad_uu', c_double), ('quad_uv', c_double), ('quad_vv', c_double),
                 ('min_uv', c_double), ('max_uv', c_double),
                 ('inner_tukey', c_double), ('outer_tukey', c_double)]
+
+
+class Catalogue(ctypes.Structure):
+    """``kimg_catalogue`` of include/kimg.h (the tables of kimg_cube_measure and kimg_cube_link_filter)."""
+    _fields_ = [(name, c_void_p) for name in (
+        'first', 'voxels', 'finite', 'c0', 'c1', 'y0', 'y1', 'x0', 'x1', 'peak', 'peak_index', 'trough',
+        'trough_index', 'sum', 'sum_c', 'sum_y', 'sum_x', 'work')]
 
 
 class KimgLibraryError(RuntimeError):

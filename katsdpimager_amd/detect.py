@@ -42,8 +42,8 @@ border, pooling and the region; (4) ``threshold`` into the mask.  Then ``prune``
 
 Why this order and these rules is DESIGN.md 5.30.
 
-Not done: linking the mask into sources and a source catalogue; reliability from negative detections;
-mask dilation; a running-window boxcar; the noise of a smoothed cube derived rather than measured;
+Not done (linking the mask into sources and a catalogue is :mod:`.link`'s): reliability from negative
+detections; mask dilation; a running-window boxcar; the noise of a smoothed cube derived rather than measured;
 spatial kernels beyond radius 16; ``kimg_moments`` reading the mask itself; cubes across several GPUs.
 """
 import ctypes
