@@ -9,6 +9,8 @@ workgroups a group in the 16-byte form and 25 otherwise, so more than one workgr
 than one slot for every C of the tests (C = 70 pooled: 3 slots)."""
 import numpy as np
 
+from helpers import SENTINELS
+
 EINVAL = -10001
 EUNSUPPORTED = -10002
 QUIET_NAN = 0x7fc00000
@@ -245,6 +247,59 @@ def independent(cube, filled, first, stop, estimator, border, pool, region):
                 spread = np.abs(x) if estimator == 'median_abs' else np.abs((x - m).astype(np.float32))
                 out['sigma'][c, g] = np.float32(_middle(spread)[0] * constant)
     return out, exact
+
+
+# ---- the device runs (nothing of the package is imported until one is made) --------------------------
+
+#: (pad of the channel pitch, offset of the view into the buffer), in floats
+LAYOUTS = ((0, 0), (3, 0), (4, 0), (0, 1))
+SENTINEL = SENTINELS[np.dtype(np.float32)]
+
+
+def form(plane, pad, offset):
+    """What kimg_cube_stats picks for a cube in a 16-byte aligned buffer."""
+    M = int(np.prod(plane))
+    return 'vector' if offset % 4 == 0 and (M + pad) % 4 == 0 and plane[2] % 4 == 0 else 'scalar'
+
+
+class PaddedCube:
+    """[C][P][H][W] inside a flat device buffer of sentinels: `offset` floats in, channel pitch
+    P * H * W + pad."""
+
+    def __init__(self, ctx, q, inner, pad, offset):
+        from katsdpimager_amd import accel
+        shape = inner.shape
+        C, M = shape[0], int(np.prod(shape[1:]))
+        pitch = M + pad
+        self.host = np.full(offset + C * pitch, SENTINEL, np.float32)
+        self.host[offset:].reshape(C, pitch)[:, :M] = inner.reshape(C, M)
+        self.whole = accel.DeviceArray(ctx, self.host.shape, np.float32)
+        self.whole.set(q, self.host)
+        view = self.whole.tensor[offset:].view(C, pitch)[:, :M].unflatten(1, shape[1:])
+        self.array = accel.DeviceArray(ctx, shape, np.float32, tensor=view)
+
+    def assert_unchanged(self, q):
+        assert np.array_equal(self.whole.get(q).view(np.uint32), self.host.view(np.uint32)), \
+            'the cube or its padding changed'
+
+
+def check(ctx, q, cube, filled, keywords, region, forms, where, layouts=LAYOUTS, device_region=False):
+    """One case on the layouts against the twin; returns the twin's result."""
+    from katsdpimager_amd import accel, cube_stats
+    params = cube_stats.CubeStatsParameters(**keywords)
+    twin = cube_stats.cube_stats_host(cube, filled, params, region)
+    op = cube_stats.CubeStatsTemplate(ctx, params).instantiate(q, cube.shape)
+    if device_region and region is not None:
+        on_device = accel.DeviceArray(ctx, region.shape, np.uint8)
+        on_device.set(q, region)
+        region = on_device
+    for pad, offset in layouts:
+        source = PaddedCube(ctx, q, cube, pad, offset)
+        forms.add(form(cube.shape[1:], pad, offset))
+        got = op(source.array, filled=filled, region=region)
+        source.assert_unchanged(q)
+        assert_same(got, twin, where + (pad, offset))
+    return twin
 
 
 def assert_same(result, want, where=None):

@@ -7,6 +7,8 @@ import math
 
 import numpy as np
 
+from helpers import SENTINELS
+
 EINVAL = -10001
 EUNSUPPORTED = -10002
 POLARITIES = ('positive', 'negative', 'both')
@@ -267,6 +269,61 @@ def assert_faint_source(single, full):
     near = (np.abs(c - c0) <= 5) & (np.abs(y - y0) <= 8) & (np.abs(x - x0) <= 8)
     assert near.all(), 'detections away from the source: {}'.format(
         list(zip(c[~near].tolist(), y[~near].tolist(), x[~near].tolist()))[:4])
+
+
+# ---- the device buffers (nothing of the package is imported until one is made) -------------------------
+
+FLOAT_LAYOUTS = ((0, 0), (3, 0), (4, 0), (0, 1))
+MASK_LAYOUTS = ((0, 0), (1, 0), (4, 0), (0, 1), (3, 0))
+FLOAT_SENTINEL = SENTINELS[np.dtype(np.float32)]
+MASK_SENTINEL = np.uint8(0xa5)           # (nonzero: a read of the padding is a set voxel)
+
+
+def float_form(M, pad, offset):
+    if offset % 4 or (M + pad) % 4 or M < 4:
+        return 'scalar'
+    return 'vector' if M % 4 == 0 else 'vector+tail'
+
+
+def mask_form(M, pad, offset):
+    return 'bytes' if offset % 4 or (M + pad) % 4 else 'word'
+
+
+class Padded:
+    """[C][M] of float32 or uint8 inside a flat device buffer of sentinels: `offset` elements in,
+    channel pitch M + pad.  `inner` None: sentinels throughout (a target)."""
+
+    def __init__(self, ctx, q, C, M, inner, pad, offset, dtype=np.float32):
+        from katsdpimager_amd import accel
+        self.C, self.M, self.pitch, self.offset = C, M, M + pad, offset
+        self.dtype = np.dtype(dtype)
+        sentinel = FLOAT_SENTINEL if self.dtype == np.float32 else MASK_SENTINEL
+        self.host = np.full(offset + C * self.pitch, sentinel, self.dtype)
+        if inner is not None:
+            self.rows(self.host)[:, :M] = inner.reshape(C, M)
+        self.whole = accel.DeviceArray(ctx, self.host.shape, self.dtype)
+        self.whole.set(q, self.host)
+        self.ptr = self.whole.ptr + offset * self.dtype.itemsize
+
+    def rows(self, flat):
+        return flat[self.offset:].reshape(self.C, self.pitch)
+
+    def assert_holds(self, q, want, channels, where):
+        """The buffer holds `want` [C][M] in `channels` (a bool [C]; None: all) and what it held before
+        everywhere else; returns nothing."""
+        now = self.whole.get(q)
+        expect = self.host.copy()
+        on = np.ones(self.C, bool) if channels is None else np.asarray(channels) != 0
+        self.rows(expect)[on, :self.M] = want.reshape(self.C, self.M)[on]
+        assert_same_bits(now, expect, where)
+
+    def assert_unchanged(self, q, where):
+        assert np.array_equal(self.whole.get(q).view(np.uint8), self.host.view(np.uint8)), \
+            (where, 'an input or its padding changed')
+
+
+def host_ptr(array):
+    return array.ctypes.data_as(ctypes.c_void_p)
 
 
 # ---- the ABI's argument errors ---------------------------------------------------------------------

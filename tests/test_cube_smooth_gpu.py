@@ -10,100 +10,20 @@ payload, the padding, the unfilled channels of ``out`` and the source cube, byte
 
 Layouts: every plane inside a buffer of sentinels with the channel pitch padded by 0, 3 and 4 floats
 and once more starting 1 float into the buffer; the second buffer's pitch is 4 floats longer.
-_form says which kernel form each gets."""
-import ctypes
-
+cube_smooth_cases.form says which kernel form each gets."""
 import numpy as np
 import pytest
 
 import cube_smooth_cases as cases
-from helpers import context_queue, SENTINELS
+from helpers import context_queue
 
 pytestmark = pytest.mark.gpu
 
 #: the last three are there for the 16-byte form (W a multiple of 4): one with four polarizations, and
 #: the last is two tiles by three
 PLANES = ((1, 1, 1), (1, 3, 5), (2, 7, 9), (1, 5, 257), (3, 33, 65), (4, 8, 12), (1, 70, 132))
-#: (pad of the channel pitch, offset of the view into the buffer), in floats
-LAYOUTS = ((0, 0), (3, 0), (4, 0), (0, 1))
-OUT_PAD = 4
-SENTINEL = SENTINELS[np.dtype(np.float32)]
-
-
-def _form(plane, pad, offset):
-    """What kimg_cube_smooth picks for cubes in 16-byte aligned buffers: 'vector' (16-byte loads and
-    stores) when the base, both pitches and W are multiples of 4 floats, else 'scalar'.  (OUT_PAD
-    keeps the second buffer's alignment the first's.)"""
-    M = int(np.prod(plane))
-    return 'vector' if offset % 4 == 0 and (M + pad) % 4 == 0 and plane[2] % 4 == 0 else 'scalar'
-
-
-class _PaddedCube:
-    """[C][P][H][W] inside a flat device buffer of sentinels: `offset` floats in, channel pitch
-    P * H * W + pad.  ``inner`` None: sentinels inside as well."""
-
-    def __init__(self, ctx, q, shape, inner, pad, offset):
-        from katsdpimager_amd import accel
-        C = shape[0]
-        self.shape = tuple(shape)
-        self.M = int(np.prod(shape[1:]))
-        self.pitch = self.M + pad
-        self.host = np.full(offset + C * self.pitch, SENTINEL, np.float32)
-        self.inside = np.zeros(self.host.shape, bool)
-        self.inside[offset:].reshape(C, self.pitch)[:, :self.M] = True
-        if inner is not None:
-            self.host[self.inside] = inner.reshape(-1)
-        self.whole = accel.DeviceArray(ctx, self.host.shape, np.float32)
-        self.whole.set(q, self.host)
-        view = self.whole.tensor[offset:].view(C, self.pitch)[:, :self.M].unflatten(1, shape[1:])
-        self.array = accel.DeviceArray(ctx, shape, np.float32, tensor=view)
-
-    def get(self, q):
-        """The cube; the padding must be what it was, byte for byte."""
-        out = self.whole.get(q)
-        assert np.array_equal(out.view(np.uint32)[~self.inside], self.host.view(np.uint32)[~self.inside]), \
-            'the padding changed'
-        return out[self.inside].reshape(self.shape)
-
-    def assert_unchanged(self, q):
-        assert np.array_equal(self.whole.get(q).view(np.uint32), self.host.view(np.uint32)), \
-            'the cube or its padding changed'
-
-
-def _smooth(lib, q, source, target, filled, radius, taps_device, taps_pitch):
-    from katsdpimager_amd._lib import check
-    C, P, H, W = source.shape
-    check(lib.kimg_cube_smooth(
-        source.array.ptr, source.pitch, target.array.ptr, target.pitch, C, P, H, W,
-        filled.ctypes.data_as(ctypes.c_void_p), radius.ctypes.data_as(ctypes.c_void_p),
-        taps_device.ptr, taps_pitch, q.handle), 'kimg_cube_smooth')
-
-
-def _run_layouts(ctx, q, cube, filled, radius, taps, forms, where):
-    """One cube on every layout against the float64 convolution and the twin; returns how many
-    values were finite and checked against the bound."""
-    from katsdpimager_amd import accel, smooth, _lib
-    sentinels = np.full(cube.shape, SENTINEL, np.float32)
-    twin = smooth.cube_smooth_host(cube, filled, radius, taps, out=sentinels)
-    taps_device = accel.DeviceArray(ctx, taps.shape, np.float32)
-    taps_device.set(q, taps)
-    checked = 0
-    for pad, offset in LAYOUTS:
-        source = _PaddedCube(ctx, q, cube.shape, cube, pad, offset)
-        target = _PaddedCube(ctx, q, cube.shape, None, pad + OUT_PAD, offset)
-        forms.add(_form(cube.shape[1:], pad, offset))
-        _smooth(_lib.lib(), q, source, target, filled, radius, taps_device, taps.shape[1])
-        got = target.get(q)
-        source.assert_unchanged(q)
-        at = where + (pad, offset)
-        checked += cases.assert_within_bound(got, cube, filled, radius, taps, at)
-        on = filled != 0
-        assert np.array_equal(np.isnan(got[on]), np.isnan(twin[on])), at
-        assert (cases.bits(got[on])[np.isnan(got[on])] == cases.QUIET_NAN).all(), at
-        assert (got[~on] == SENTINEL).all(), at
-        different = cases.bits(got) != cases.bits(twin)
-        assert not different.any(), (at, int(different.sum()), np.argwhere(different)[:4].tolist())
-    return checked
+#: (the layouts, the padded cube and the run over the layouts are shared with test_cube_band_gpu.py)
+_run_layouts = cases.run_layouts
 
 
 @pytest.mark.parametrize('C', [1, 2, 5])

@@ -8,64 +8,18 @@ Layouts: the channel pitch padded by 0, 3 and 4 floats, and once more starting 1
 buffer.  With buffers that are 16-byte aligned, pads 0 and 4 at offset 0 get the 16-byte loads when W
 and P * H * W are multiples of 4 floats; pad 3 (unless P * H * W + 3 is a multiple of 4, which it is for
 none of the planes with W a multiple of 4) and offset 1 get one element a load, and so does every
-plane whose W is no multiple of 4.  _form says which."""
+plane whose W is no multiple of 4.  cube_stats_cases.form says which."""
 import numpy as np
 import pytest
 
 import cube_stats_cases as cases
-from helpers import context_queue, SENTINELS
+from helpers import context_queue
 
 pytestmark = pytest.mark.gpu
 
-#: (pad of the channel pitch, offset of the view into the buffer), in floats
-LAYOUTS = ((0, 0), (3, 0), (4, 0), (0, 1))
-SENTINEL = SENTINELS[np.dtype(np.float32)]
-
-
-def _form(plane, pad, offset):
-    """What kimg_cube_stats picks for a cube in a 16-byte aligned buffer."""
-    M = int(np.prod(plane))
-    return 'vector' if offset % 4 == 0 and (M + pad) % 4 == 0 and plane[2] % 4 == 0 else 'scalar'
-
-
-class _PaddedCube:
-    """[C][P][H][W] inside a flat device buffer of sentinels: `offset` floats in, channel pitch
-    P * H * W + pad."""
-
-    def __init__(self, ctx, q, inner, pad, offset):
-        from katsdpimager_amd import accel
-        shape = inner.shape
-        C, M = shape[0], int(np.prod(shape[1:]))
-        pitch = M + pad
-        self.host = np.full(offset + C * pitch, SENTINEL, np.float32)
-        self.host[offset:].reshape(C, pitch)[:, :M] = inner.reshape(C, M)
-        self.whole = accel.DeviceArray(ctx, self.host.shape, np.float32)
-        self.whole.set(q, self.host)
-        view = self.whole.tensor[offset:].view(C, pitch)[:, :M].unflatten(1, shape[1:])
-        self.array = accel.DeviceArray(ctx, shape, np.float32, tensor=view)
-
-    def assert_unchanged(self, q):
-        assert np.array_equal(self.whole.get(q).view(np.uint32), self.host.view(np.uint32)), \
-            'the cube or its padding changed'
-
-
-def _check(ctx, q, cube, filled, keywords, region, forms, where, layouts=LAYOUTS, device_region=False):
-    """One case on the layouts against the twin; returns the twin's result."""
-    from katsdpimager_amd import accel, cube_stats
-    params = cube_stats.CubeStatsParameters(**keywords)
-    twin = cube_stats.cube_stats_host(cube, filled, params, region)
-    op = cube_stats.CubeStatsTemplate(ctx, params).instantiate(q, cube.shape)
-    if device_region and region is not None:
-        on_device = accel.DeviceArray(ctx, region.shape, np.uint8)
-        on_device.set(q, region)
-        region = on_device
-    for pad, offset in layouts:
-        source = _PaddedCube(ctx, q, cube, pad, offset)
-        forms.add(_form(cube.shape[1:], pad, offset))
-        got = op(source.array, filled=filled, region=region)
-        source.assert_unchanged(q)
-        cases.assert_same(got, twin, where + (pad, offset))
-    return twin
+#: (the layouts, the padded cube and the run over the layouts are shared with test_cube_band_gpu.py)
+_PaddedCube = cases.PaddedCube
+_check = cases.check
 
 
 @pytest.mark.parametrize('C', [1, 5, 70])

@@ -16,63 +16,19 @@ import numpy as np
 import pytest
 
 import detect_cases as cases
-from helpers import context_queue, SENTINELS
+from helpers import context_queue
 
 pytestmark = pytest.mark.gpu
 
 CHANNELS = (1, 2, 3, 8, 9, 33, 65)
 PLANES = ((1, 1, 1), (1, 3, 5), (2, 7, 9), (4, 16, 16), (1, 5, 257), (3, 33, 65))
-FLOAT_LAYOUTS = ((0, 0), (3, 0), (4, 0), (0, 1))
-MASK_LAYOUTS = ((0, 0), (1, 0), (4, 0), (0, 1), (3, 0))
-FLOAT_SENTINEL = SENTINELS[np.dtype(np.float32)]
-MASK_SENTINEL = np.uint8(0xa5)           # (nonzero: a read of the padding is a set voxel)
-
-
-def _float_form(M, pad, offset):
-    if offset % 4 or (M + pad) % 4 or M < 4:
-        return 'scalar'
-    return 'vector' if M % 4 == 0 else 'vector+tail'
-
-
-def _mask_form(M, pad, offset):
-    return 'bytes' if offset % 4 or (M + pad) % 4 else 'word'
-
-
-class _Padded:
-    """[C][M] of float32 or uint8 inside a flat device buffer of sentinels: `offset` elements in,
-    channel pitch M + pad.  `inner` None: sentinels throughout (a target)."""
-
-    def __init__(self, ctx, q, C, M, inner, pad, offset, dtype=np.float32):
-        from katsdpimager_amd import accel
-        self.C, self.M, self.pitch, self.offset = C, M, M + pad, offset
-        self.dtype = np.dtype(dtype)
-        sentinel = FLOAT_SENTINEL if self.dtype == np.float32 else MASK_SENTINEL
-        self.host = np.full(offset + C * self.pitch, sentinel, self.dtype)
-        if inner is not None:
-            self.rows(self.host)[:, :M] = inner.reshape(C, M)
-        self.whole = accel.DeviceArray(ctx, self.host.shape, self.dtype)
-        self.whole.set(q, self.host)
-        self.ptr = self.whole.ptr + offset * self.dtype.itemsize
-
-    def rows(self, flat):
-        return flat[self.offset:].reshape(self.C, self.pitch)
-
-    def assert_holds(self, q, want, channels, where):
-        """The buffer holds `want` [C][M] in `channels` (a bool [C]; None: all) and what it held before
-        everywhere else; returns nothing."""
-        now = self.whole.get(q)
-        expect = self.host.copy()
-        on = np.ones(self.C, bool) if channels is None else np.asarray(channels) != 0
-        self.rows(expect)[on, :self.M] = want.reshape(self.C, self.M)[on]
-        cases.assert_same_bits(now, expect, where)
-
-    def assert_unchanged(self, q, where):
-        assert np.array_equal(self.whole.get(q).view(np.uint8), self.host.view(np.uint8)), \
-            (where, 'an input or its padding changed')
-
-
-def _host_ptr(array):
-    return array.ctypes.data_as(ctypes.c_void_p)
+#: (the layouts and the padded buffers are shared with test_cube_band_gpu.py)
+FLOAT_LAYOUTS = cases.FLOAT_LAYOUTS
+MASK_LAYOUTS = cases.MASK_LAYOUTS
+_float_form = cases.float_form
+_mask_form = cases.mask_form
+_Padded = cases.Padded
+_host_ptr = cases.host_ptr
 
 
 @pytest.mark.parametrize('C', CHANNELS)

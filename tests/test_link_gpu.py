@@ -8,207 +8,26 @@ padded by 0, 1, 4 and 3 bytes and once more starting 1 byte in; the label pitch 
 labels and once more starting 1 label in.  A workgroup of the dense launches holds 1024 elements of one
 channel, so every case with C > 1 spans several, and (1, 5, 257) and (3, 33, 65) do so in one channel."""
 import ctypes
-import math
 
 import numpy as np
 import pytest
 
 import link_cases as cases
-from helpers import context_queue, SENTINELS
+from helpers import context_queue
 
 pytestmark = pytest.mark.gpu
 
 CHANNELS = (1, 2, 3, 9, 33)
 PLANES = ((1, 1, 1), (1, 3, 5), (2, 7, 9), (1, 5, 257), (3, 33, 65))
-FLOAT_LAYOUTS = ((0, 0), (3, 0), (4, 0), (0, 1))
-MASK_LAYOUTS = ((0, 0), (1, 0), (4, 0), (3, 0), (0, 1))
-LABEL_LAYOUTS = ((0, 0), (1, 0), (4, 0), (0, 1))
 DENSITIES = (0.01, 0.1, 0.45)
-SENTINEL = {np.dtype(np.float32): SENTINELS[np.dtype(np.float32)], np.dtype(np.uint8): np.uint8(0xa5),
-            np.dtype(np.int32): SENTINELS[np.dtype(np.int32)], np.dtype(np.float64): SENTINELS[np.dtype(np.float64)]}
-
-
-class _Padded:
-    """[C][M] inside a flat device buffer of sentinels: `offset` elements in, channel pitch M + pad.
-    `inner` None: sentinels throughout (a target)."""
-
-    def __init__(self, ctx, q, C, M, inner, pad, offset, dtype):
-        from katsdpimager_amd import accel
-        self.C, self.M, self.pitch, self.offset = C, M, M + pad, offset
-        self.dtype = np.dtype(dtype)
-        self.host = np.full(offset + C * self.pitch, SENTINEL[self.dtype], self.dtype)
-        if inner is not None:
-            self.rows(self.host)[:, :M] = inner.reshape(C, M)
-        self.whole = accel.DeviceArray(ctx, self.host.shape, self.dtype)
-        self.whole.set(q, self.host)
-        self.ptr = self.whole.ptr + offset * self.dtype.itemsize
-
-    def rows(self, flat):
-        return flat[self.offset:].reshape(self.C, self.pitch)
-
-    def assert_holds(self, q, want, where):
-        """The buffer holds `want` [C][M] and what it held before everywhere else."""
-        expect = self.host.copy()
-        self.rows(expect)[:, :self.M] = want.reshape(self.C, self.M)
-        cases.assert_same_bits(self.whole.get(q), expect, where)
-
-    def assert_unchanged(self, q, where):
-        assert np.array_equal(self.whole.get(q).view(np.uint8), self.host.view(np.uint8)), \
-            (where, 'an input or its padding changed')
-
-
-class _Tables:
-    """The device arrays of a kimg_catalogue with `rows` rows each, full of sentinels, and counts."""
-
-    def __init__(self, ctx, q, rows):
-        from katsdpimager_amd import accel, link, _lib
-        self.rows = rows
-        self.arrays = {}
-        for name in link.TABLE_DTYPE.names:
-            dtype = link.TABLE_DTYPE[name]
-            array = accel.DeviceArray(ctx, (rows,), dtype)
-            array.set(q, np.full(rows, SENTINEL[dtype], dtype))
-            self.arrays[name] = array
-        self.work = accel.DeviceArray(ctx, (3 * rows,), np.int64)
-        self.counts = accel.DeviceArray(ctx, (2,), np.int32)
-        self.counts.set(q, np.full(2, SENTINEL[np.dtype(np.int32)], np.int32))
-        self.struct = _lib.Catalogue(work=self.work.ptr, **{n: a.ptr for n, a in self.arrays.items()})
-
-    def get(self, q):
-        from katsdpimager_amd import link
-        table = np.zeros(self.rows, link.TABLE_DTYPE)
-        for name, array in self.arrays.items():
-            table[name] = array.get(q)
-        return table
-
-    def assert_untouched(self, table, start, where):
-        for name in table.dtype.names:
-            dtype = table.dtype[name]
-            want = np.full(len(table) - start, SENTINEL[dtype], dtype)
-            cases.assert_same_bits(np.ascontiguousarray(table[name][start:]), want, (where, name, 'rows beyond'))
-
-
-def _host_ptr(array):
-    return array.ctypes.data_as(ctypes.c_void_p)
-
-
-def _scratch(ctx, C, M):
-    from katsdpimager_amd import accel, _lib
-    return accel.DeviceArray(ctx, (_lib.lib().kimg_cube_link_scratch_bytes(C, M) // 4,), np.int32)
-
-
-def _fsum_rows(labels, cube, filled, rows):
-    """Per source and sum: (math.fsum of the terms in float64, math.fsum of their magnitudes)."""
-    C, P, H, W = labels.shape
-    member = (labels > 0) & (np.asarray(filled).reshape(-1, 1, 1, 1) != 0) & np.isfinite(cube)
-    d = np.flatnonzero(member.reshape(-1))
-    s = labels.reshape(-1)[d] - 1
-    order = np.argsort(s, kind='stable')
-    d, s = d[order], s[order]
-    f = cube.reshape(-1)[d].astype(np.float64)
-    c = (d // (P * H * W)).astype(np.float64)
-    y = (d % (H * W) // W).astype(np.float64)
-    x = (d % W).astype(np.float64)
-    cuts = np.searchsorted(s, np.arange(rows + 1))
-    out = []
-    for k in range(rows):
-        a, b = cuts[k], cuts[k + 1]
-        out.append([(math.fsum(t), math.fsum(np.abs(t))) for t in (f[a:b], f[a:b] * c[a:b], f[a:b] * y[a:b], f[a:b] * x[a:b])])
-    return out
-
-
-def _assert_measured(got, want, labels, cube, filled, exact, where):
-    """Integer fields and peaks by bits; sums equal (`exact`) or within the bound of the fsum."""
-    for name in cases.INT_FIELDS + ('peak', 'trough'):
-        cases.assert_same_bits(np.ascontiguousarray(got[name]), np.ascontiguousarray(want[name]), (where, name))
-    if exact:
-        for name in cases.SUM_FIELDS:
-            cases.assert_same_bits(np.ascontiguousarray(got[name]), np.ascontiguousarray(want[name]), (where, name))
-        return
-    sums = _fsum_rows(labels, cube, filled, len(want))
-    for s in range(len(want)):
-        for k, name in enumerate(cases.SUM_FIELDS):
-            exact_sum, magnitude = sums[s][k]
-            bound = int(want['finite'][s]) * 2.0 ** -53 * magnitude
-            assert abs(float(got[name][s]) - exact_sum) <= bound, (where, s, name, got[name][s], exact_sum, bound)
-
-
-def _run_case(ctx, q, mask, cube, filled, reach, minima, layouts, extra_rows=3, capacity=None):
-    """link, measure, filter and label_mask of one case in every layout of `layouts` against the
-    twins; the labels of all layouts are the same.  Returns N0."""
-    from katsdpimager_amd import link, _lib
-    lib = _lib.lib()
-    s = q.handle
-    C, P, H, W = mask.shape
-    M = P * H * W
-    want_labels, N0 = link.link_host(mask, filled, *reach)
-    rows = N0 if capacity is None else min(N0, capacity)
-    want_table = link.measure_host(want_labels, cube, filled, N0, capacity)
-    exact = bool(np.all(cube[np.isfinite(cube)] == np.round(cube[np.isfinite(cube)])))
-    if capacity is None:
-        want_filtered, want_kept = link.filter_host(want_labels, want_table, *minima)
-        t = want_table
-        keep = ((t['voxels'] >= minima[0]) & (t['x1'] - t['x0'] + 1 >= minima[1])
-                & (t['y1'] - t['y0'] + 1 >= minima[1]) & (t['c1'] - t['c0'] + 1 >= minima[2]))
-        assert keep.sum() == len(want_kept)
-    first = None
-    for (fpad, foff), (mpad, moff), (lpad, loff) in layouts:
-        at = (mask.shape, reach, (fpad, foff), (mpad, moff), (lpad, loff))
-        the_mask = _Padded(ctx, q, C, M, mask, mpad, moff, np.uint8)
-        the_cube = _Padded(ctx, q, C, M, cube, fpad, foff, np.float32)
-        labels = _Padded(ctx, q, C, M, None, lpad, loff, np.int32)
-        scratch = _scratch(ctx, C, M)
-        tables = _Tables(ctx, q, rows + extra_rows)
-        room = rows + extra_rows if capacity is None else capacity
-        _lib.check(lib.kimg_cube_link(the_mask.ptr, the_mask.pitch, labels.ptr, labels.pitch, C, P, H, W,
-                                      _host_ptr(filled), reach[0], reach[1], scratch.ptr, tables.counts.ptr, s),
-                   'link')
-        labels.assert_holds(q, want_labels, at + ('labels',))
-        assert tables.counts.get(q)[0] == N0, at
-        got_labels = labels.whole.get(q)
-        if first is None:
-            first = labels.rows(got_labels)[:, :M].copy()
-        assert np.array_equal(labels.rows(got_labels)[:, :M], first), at + ('labels differ between layouts',)
-
-        _lib.check(lib.kimg_cube_measure(labels.ptr, labels.pitch, the_cube.ptr, the_cube.pitch, C, P, H, W,
-                                         _host_ptr(filled), ctypes.byref(tables.struct), room,
-                                         tables.counts.ptr, s), 'measure')
-        got = tables.get(q)
-        tables.assert_untouched(got, rows, at)
-        _assert_measured(got[:rows], want_table, want_labels, cube, filled, exact, at)
-        labels.assert_holds(q, want_labels, at + ('labels after measure',))
-
-        if capacity is None:
-            _lib.check(lib.kimg_cube_link_filter(labels.ptr, labels.pitch, C, M, ctypes.byref(tables.struct),
-                                                 room, *minima, tables.counts.ptr, s), 'filter')
-            labels.assert_holds(q, want_filtered, at + ('filtered labels', minima))
-            after = tables.get(q)
-            N = len(want_kept)
-            assert list(tables.counts.get(q)) == [N0, N], at
-            cases.assert_same_bits(after[:N], got[:rows][keep], at + ('rows after the filter',))
-            cases.assert_same_bits(after[N:], got[N:], at + ('rows behind the kept ones',))
-            final = want_filtered
-        else:
-            # more sources than rows: the filter changes nothing
-            _lib.check(lib.kimg_cube_link_filter(labels.ptr, labels.pitch, C, M, ctypes.byref(tables.struct),
-                                                 room, 2, 1, 1, tables.counts.ptr, s), 'filter')
-            labels.assert_holds(q, want_labels, at + ('labels after a filter without rows',))
-            assert list(tables.counts.get(q)) == [N0, N0], at
-            cases.assert_same_bits(tables.get(q), got, at + ('rows after a filter without rows',))
-            final = want_labels
-
-        for source in (0, max(1, int(final.max()) // 2)):
-            out = _Padded(ctx, q, C, M, None, mpad, moff, np.uint8)
-            _lib.check(lib.kimg_cube_label_mask(labels.ptr, labels.pitch, out.ptr, out.pitch, C, M, source, s),
-                       'label_mask')
-            out.assert_holds(q, link.label_mask_host(final, source), at + ('label_mask', source))
-        the_mask.assert_unchanged(q, at)
-        the_cube.assert_unchanged(q, at)
-    return N0
-
-
-def _layouts(count=5):
-    return [(FLOAT_LAYOUTS[k % 4], MASK_LAYOUTS[k % 5], LABEL_LAYOUTS[k % 4]) for k in range(count)]
+#: (the layouts, the padded buffers, the catalogue's tables and the run of one case against the twins
+#: are shared with test_cube_band_gpu.py)
+_Padded = cases.Padded
+_host_ptr = cases.host_ptr
+_scratch = cases.scratch
+_fsum_rows = cases.fsum_rows
+_run_case = cases.run_case
+_layouts = cases.layouts
 
 
 @pytest.mark.parametrize('C', CHANNELS)
