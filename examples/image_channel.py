@@ -15,7 +15,7 @@ store -> imaging weights, PSF, major/minor cycles -> restored image, all on one 
     python examples/image_channel.py --moments --median-contsub        (... taken out by the per-pixel median, told no line ranges)
     python examples/image_channel.py --moments --common-beam  (... every plane restored with its own beam, then all taken to one)
     python examples/image_channel.py --moments --common-beam --measure-noise  (... and the smoothed planes' noise measured)
-    python examples/image_channel.py --moments --find-sources  (... and the smooth-and-clip detection mask of the cube, linked into a catalogue)
+    python examples/image_channel.py --moments --find-sources  (... and the smooth-and-clip detection mask of the cube, linked into a catalogue and parameterised: flux, peak, centroid, w50)
 
 It follows the reference's per-channel flow (frontend.py:31-83 preprocess_visibilities,
 :465-658 process_channel) with the loaders and FITS output left out: the sky is three point
@@ -716,6 +716,31 @@ def moments_band(args):
             results['find_sources']['first_source_moment0'] = float(np.nansum(own))
             print('moment 0 of source 1 through its own mask: {} pixels, {:.6f} in all'.format(
                 int(np.isfinite(own).sum()), float(np.nansum(own))))
+            # every source's spectrum in one more pass, and what a parameteriser makes of it: in Jy
+            # where the planes carry their beams (--common-beam), else in sums of pixel values
+            from katsdpimager_amd import sources
+            with_beams = sc.common_beam is not None or all(
+                sc.beams[c] is not None for c in np.flatnonzero(sc.filled))
+            source_params = sources.SourceParameters(rest_frequency=rest_frequency,
+                                                     units='beam' if with_beams else 'pixel')
+            parameteriser = sources.SourcesTemplate(ctx, source_params).instantiate(cube_queue, sc.shape)
+            spectra, source_lines = parameteriser(labels, sc, catalogue)
+            first = source_lines[0]
+            unit = 'Jy' if with_beams else 'Jy/beam.pixel'
+            results['find_sources'].update(
+                flux_unit=unit + '.km/s', first_source_flux=float(first['flux']),
+                first_source_flux_err=float(first['flux_err']), first_source_peak=float(first['peak']),
+                first_source_centroid=float(first['centroid']), first_source_w50=float(first['w50']),
+                first_source_w20=float(first['w20']),
+                first_source_spectrum=[t.tolist() for t in spectra.spectrum(1)])
+            line = lines[name]
+            print('source 1 from its spectrum ({} channels): flux {:.6f} +- {:.6f} {}.km/s, peak {:.6f} {} in '
+                  'channel {}, centroid {:.3f} km/s, w50 {:.3f} km/s, w20 {:.3f} km/s; the line injected at '
+                  'source {} has its centroid at {:.3f} km/s and {:.3f} km/s above half its peak'.format(
+                      int(first['channels']), first['flux'], first['flux_err'], unit, first['peak'], unit,
+                      int(first['peak_channel']), first['centroid'], first['w50'], first['w20'], name,
+                      results['sources'][name]['injected'][1],
+                      float(np.ptp(velocity[line >= 0.5 * line.max()]))))
     if args.output:
         from katsdpimager_amd import io, polarization
         image_p.fixed.polarizations = [polarization.STOKES_I]

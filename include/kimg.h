@@ -1847,10 +1847,10 @@ int kimg_cube_mask_apply(const float *cube, int64_t channel_pitch, const uint8_t
  *   C > KIMG_MOMENTS_MAX_CHANNELS or C * M > 2^31 - 2 (labels are int32).  M = 0 is then a successful
  *   call that does nothing to cubes.
  * Asynchronous on `stream`, no allocation, capturable; the host reads nothing.
- * Not done here: reliability from negative detections; mask dilation; per-source spectra and moment
- *   maps beyond kimg_cube_label_mask's mask of one source; fluxes in Jy (the beam area and the channel
- *   width are the caller's); uncertainties; sources across polarizations; cubes across several GPUs;
- *   bit-reproducible sums (a store-and-sum pass, another contract). */
+ * Not done here (per-source spectra, fluxes in Jy and their errors are "Source spectra and line
+ *   parameters" below): reliability from negative detections; mask dilation; per-source moment
+ *   maps beyond kimg_cube_label_mask's mask of one source; sources across polarizations; cubes across
+ *   several GPUs; bit-reproducible sums (a store-and-sum pass, another contract). */
 typedef struct kimg_catalogue {
     int32_t *first, *voxels, *finite, *c0, *c1, *y0, *y1, *x0, *x1;
     float *peak;
@@ -1876,6 +1876,96 @@ int kimg_cube_link_filter(int32_t *labels, int64_t label_pitch, int num_channels
                           void *stream);
 int kimg_cube_label_mask(const int32_t *labels, int64_t label_pitch, uint8_t *mask, int64_t mask_pitch,
                          int num_channels, int64_t plane_elements, int source, void *stream);
+
+/* ---- Source spectra and line parameters (cube_sources.hip): what a source finder ends with (SoFiA's
+ * parameteriser) -- the integrated spectrum of every linked source, and from it the flux with its
+ * error, the peak flux density, the centroid and the line widths w50 and w20.  The reference has none;
+ * the semantics are this library's, and katsdpimager_amd/sources.py holds them once more as numpy
+ * (source_spectra_host, source_lines_host).
+ *
+ * The ragged layout, shared by the two entries.  num_sources = N: sources 1 .. N.  c0: DEVICE int32
+ *   [N], the first channel of each source's range.  offsets: DEVICE int32 [N + 1].  Source s owns the
+ *   entries offsets[s-1] .. offsets[s] - 1 of every table, one per channel c0[s-1] + k.  total =
+ *   offsets[N] <= 2^31 - 2 is the length of every table.  (The ranges are the caller's: the
+ *   catalogue's c0 .. c1 of kimg_cube_measure, or wider.)  c0 and offsets are DEVICE data that the host
+ *   cannot check, so the kernels do: see below.
+ *
+ * kimg_cube_source_spectra: labels, label_pitch, cube, channel_pitch, C = num_channels, M =
+ *   plane_elements, filled_host, the dense index, the pitches and "unfilled channels are not read,
+ *   padding is neither read nor written" are those of "Source linking" above.  sum: DEVICE float64
+ *   [total]; voxels, finite: DEVICE int32 [total].  The call first zeroes all `total` entries of the
+ *   three tables.  Then, for every source s and channel c of its range, over the voxels of channel c
+ *   (filled) with labels[c][m] == s: voxels = their number, finite = the number whose cube value is
+ *   finite, sum = the float64 sum of the finite values.  Entries of unfilled channels inside a range
+ *   therefore read 0.  A voxel whose label is <= 0 or > N, or whose channel lies outside its row's
+ *   [c0, c0 + offsets[s] - offsets[s-1]), is skipped; an entry is written only at an index inside
+ *   both its row and [0, total), so that wrong c0 or offsets give wrong numbers, never a write outside
+ *   the tables.  The two counts are exact.  The ORDER of the sum is not part of the contract (float64
+ *   atomic adds of partial sums, as kimg_cube_measure's): on values whose sums are exact in every
+ *   order it equals the twin's (which sums in ascending dense index), otherwise it differs from the
+ *   exactly rounded sum by at most n * 2^-53 * sum |term|, n = finite.
+ *   Kernel: one read of labels and cube, 16-byte loads where base and pitch allow; within a wave the
+ *   lanes that hold the same label in consecutive lanes combine their sums and counts by shuffles
+ *   before one lane issues the atomics.
+ *   Returns, before any HIP call: KIMG_EINVAL for a null pointer, a pointer that is not 4-byte (sum:
+ *   8-byte) aligned, N < 0, total < 0, C < 1, M < 0, a pitch below M; then KIMG_EUNSUPPORTED for
+ *   C > KIMG_MOMENTS_MAX_CHANNELS, C * M > 2^31 - 2 or total > 2^31 - 2.  N = 0 or M = 0 is then a
+ *   successful call that writes nothing.  Asynchronous on `stream`, no allocation, capturable; the host
+ *   reads nothing.
+ *
+ * kimg_source_lines: N, c0, offsets, total as above; sum, finite: the tables of
+ *   kimg_cube_source_spectra (read only).  C = num_channels.  unit_host, width_host, coord_host,
+ *   variance_host: HOST float64 [C], read during the call: the entry copies them on `stream` into
+ *   channel_tables, DEVICE float64 [4 * C], 8-byte aligned, the caller's space (so the call is
+ *   asynchronous but, for these copies, not capturable).  unit[c] turns a sum of pixel values into a
+ *   flux density (1 / beam area in pixels for Jy/beam), width[c] is the channel's width on the axis
+ *   of coord[c], variance[c] the variance that ONE finite voxel of channel c adds to the flux.
+ *   lines: a HOST struct of DEVICE arrays [N] each, row s - 1 is source s.
+ *   One thread per source; everything float64, in ascending channel order, nothing fused, one product
+ *   per term.  With n = offsets[s] - offsets[s-1], k = 0 .. n - 1, c = c0[s-1] + k, d_k = sum_k *
+ *   unit[c], x_k = coord[c]:
+ *     flux:     F = 0; F = F + d_k * width[c].
+ *     flux_err: V = 0; V = V + (double) finite_k * variance[c]; flux_err = sqrt(V).
+ *     peak, peak_channel: over the entries with finite_k > 0 in ascending k, the first d_k, replaced
+ *               only by a d_k > peak (the lowest channel wins a tie); peak_channel = c0 + k of it.  NaN
+ *               and -1 without such an entry.
+ *     centroid: S0 = 0, S1 = 0; S0 = S0 + d_k; S1 = S1 + d_k * x_k; centroid = S1 / S0, NaN where
+ *               S0 == 0.
+ *     w50, w20 (SoFiA's rule), only where peak > 0, NaN otherwise: L = 0.5 * peak (0.2 * peak).  k =
+ *               the first entry from the low end with d_k >= L; lo = x_0 if k == 0, else
+ *               x_{k-1} + (((L - d_{k-1}) / (d_k - d_{k-1})) * (x_k - x_{k-1})).  k = the first entry
+ *               from the high end with d_k >= L; hi = x_{n-1} if k == n - 1, else
+ *               x_{k+1} + (((L - d_{k+1}) / (d_k - d_{k+1})) * (x_k - x_{k+1})).  w = |hi - lo|.  The
+ *               edges are outputs too: w50_lo, w50_hi, w20_lo, w20_hi.
+ *     channels = n.
+ *   Every NaN that is written is 0x7ff8000000000000.  The float64 divide and sqrt of this build are
+ *   correctly rounded, so given the same spectra the device has the twin's bits.  A row whose range
+ *   leaves 0 .. C or whose entries leave 0 .. total is treated as one with n = 0 (flux 0, error 0,
+ *   the rest NaN / -1): nothing outside the tables is read.
+ *   Returns, before any HIP call: KIMG_EINVAL for a null pointer, a misaligned one (4 bytes; 8 for
+ *   float64), a lines struct with a null or misaligned array, N < 0, total < 0, C < 1; then
+ *   KIMG_EUNSUPPORTED for C > KIMG_MOMENTS_MAX_CHANNELS or total > 2^31 - 2.  N = 0 is then a
+ *   successful call that copies and writes nothing.
+ *
+ * Not done here: reliability from negative detections; mask dilation; per-source moment maps;
+ *   bit-reproducible sums (a store-and-sum pass, another contract); sources across polarizations;
+ *   Gaussian or busy-function fits to the spectra; cubes across several GPUs. */
+typedef struct kimg_source_line_table {
+    double *flux, *flux_err, *peak;
+    int32_t *peak_channel;
+    double *centroid, *w50, *w20, *w50_lo, *w50_hi, *w20_lo, *w20_hi;
+    int32_t *channels;
+} kimg_source_line_table;
+int kimg_cube_source_spectra(const int32_t *labels, int64_t label_pitch, const float *cube,
+                             int64_t channel_pitch, int num_channels, int64_t plane_elements,
+                             const uint8_t *filled_host, int num_sources, const int32_t *c0,
+                             const int32_t *offsets, int64_t total, double *sum, int32_t *voxels,
+                             int32_t *finite, void *stream);
+int kimg_source_lines(int num_sources, const int32_t *c0, const int32_t *offsets, int64_t total,
+                      const double *sum, const int32_t *finite, int num_channels,
+                      const double *unit_host, const double *width_host, const double *coord_host,
+                      const double *variance_host, double *channel_tables,
+                      const kimg_source_line_table *lines, void *stream);
 
 #ifdef __cplusplus
 }

@@ -181,6 +181,11 @@ PROTOTYPES = {
     'kimg_cube_measure': (c_int, [P, L, P, L, I, I, I, I, P, P, I, P, P]),
     'kimg_cube_link_filter': (c_int, [P, L, I, L, P, I, I, I, I, P, P]),
     'kimg_cube_label_mask': (c_int, [P, L, P, L, I, L, I, P]),
+    # source spectra and lines: spectra (labels, label_pitch, cube, pitch, C, M, filled_host, N, c0,
+    # offsets, total, sum, voxels, finite, stream); lines (N, c0, offsets, total, sum, finite, C, unit_host,
+    # width_host, coord_host, variance_host, channel_tables, kimg_source_line_table *, stream)
+    'kimg_cube_source_spectra': (c_int, [P, L, P, L, I, L, P, I, P, P, L, P, P, P, P]),
+    'kimg_source_lines': (c_int, [I, P, P, L, P, P, I, P, P, P, P, P, P, P]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
@@ -220,6 +225,13 @@ class Catalogue(ctypes.Structure):
     _fields_ = [(name, c_void_p) for name in (
         'first', 'voxels', 'finite', 'c0', 'c1', 'y0', 'y1', 'x0', 'x1', 'peak', 'peak_index', 'trough',
         'trough_index', 'sum', 'sum_c', 'sum_y', 'sum_x', 'work')]
+
+
+class SourceLineTable(ctypes.Structure):
+    """``kimg_source_line_table`` of include/kimg.h (the rows of kimg_source_lines)."""
+    _fields_ = [(name, c_void_p) for name in (
+        'flux', 'flux_err', 'peak', 'peak_channel', 'centroid', 'w50', 'w20', 'w50_lo', 'w50_hi', 'w20_lo',
+        'w20_hi', 'channels')]
 
 
 class KimgLibraryError(RuntimeError):

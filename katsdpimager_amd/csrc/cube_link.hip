@@ -17,13 +17,13 @@
 // chain of labels always ends in a root (L[d] == d + 1), and nothing waits for another workgroup.
 // Inside the merge launch every read of L is a relaxed agent-scope atomic load: a value read may be
 // old, but it was once true, and an old parent still leads to the root.
-#include "kimg_cube_column.h"
+//
+// The launch geometry, the label load, the filled bits and the host's range checks are
+// kimg_cube_labels.h's, shared with cube_sources.hip.
+#include "kimg_cube_labels.h"
 
 namespace {
 
-constexpr int LK_THREADS = 256;
-constexpr int LK_V = 4;
-constexpr int LK_CHUNK = LK_THREADS * LK_V;
 constexpr int LK_SCAN_THREADS = 1024;
 
 // What every dense launch knows of the cubes
@@ -32,11 +32,6 @@ struct lk_shape {
     int C, P, H, W;
     int mask_wide, label_wide;      // one access for a thread's four mask bytes / four labels
 };
-
-__device__ inline bool lk_filled(const col_mask &filled, int c)
-{
-    return (filled.bits[c >> 5] >> (c & 31)) & 1;
-}
 
 // The workgroup's channel and the thread's first element and number of elements (<= 0: none)
 __device__ inline void lk_place(const lk_shape &g, int &c, int64_t &j, int &n)
@@ -56,18 +51,6 @@ __device__ inline uint32_t lk_mask_load(const uint8_t *p, int n, int wide)
     for (int e = 0; e < n; e++)
         t |= (uint32_t) p[e] << (8 * e);
     return t;
-}
-
-__device__ inline void lk_label_load(const int32_t *p, int n, int wide, int32_t (&v)[LK_V])
-{
-    if (wide && n == LK_V) {
-        const int4 t = *reinterpret_cast<const int4 *>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < LK_V; e++)
-            v[e] = e < n ? p[e] : 0;
-    }
 }
 
 // Where the label of dense index d lies
@@ -588,25 +571,6 @@ void lk_label_mask_kernel(const int32_t *__restrict__ labels, uint8_t *__restric
 }
 
 // ---- host -------------------------------------------------------------------------------------------
-
-col_mask lk_filled_mask(const uint8_t *filled_host, int num_channels)
-{
-    col_mask filled = {};
-    for (int c = 0; c < num_channels; c++)
-        if (filled_host[c])
-            col_set(filled, c);
-    return filled;
-}
-
-bool lk_aligned(const void *p, uintptr_t to) { return ((uintptr_t) p & (to - 1)) == 0; }
-
-// C * M fits the labels
-bool lk_fits(int num_channels, int64_t plane_elements)
-{
-    return num_channels <= COL_MAX_CHANNELS && plane_elements <= ((int64_t) INT32_MAX - 1) / num_channels;
-}
-
-int64_t lk_blocks_per_channel(int64_t plane_elements) { return (plane_elements + LK_CHUNK - 1) / LK_CHUNK; }
 
 lk_shape lk_shape_of(int C, int P, int H, int W, int64_t M, const void *mask, int64_t mask_pitch,
                      const void *labels, int64_t label_pitch)

@@ -36,10 +36,11 @@ the plane (SoFiA's default), 1.5 is 8-connectivity, 2 and 3 bridge gaps.
 
 Why these rules, and what the kernels cost, is DESIGN.md 5.31.
 
-Not done: reliability from negative detections; mask dilation; per-source spectra and moment maps
-beyond ``labels.mask(source=)``; fluxes in Jy (the beam area and channel width are the caller's, from
-``cube.beams``); uncertainties; sources across polarizations; cubes across several GPUs;
-bit-reproducible sums.
+Per-source spectra, fluxes in Jy with their errors and line widths are :mod:`.sources`'.
+
+Not done: reliability from negative detections; mask dilation; per-source moment maps beyond
+``labels.mask(source=)``; sources across polarizations; cubes across several GPUs; bit-reproducible
+sums.
 """
 import ctypes
 import math
