@@ -4,8 +4,9 @@ spectral-line user reads (CASA ``immoments``, MIRIAD ``moment``): integrated int
 intensity-weighted coordinate (1, the velocity field), dispersion (2), peak (8) and coordinate of the
 peak (9), each over the samples above a noise cut.
 
-:class:`SpectralCube` is the container: ``frontend.process_channel`` leaves a channel's images in the
-imager's buffers, :meth:`SpectralCube.put` copies one into its plane and records the channel's noise.
+:class:`SpectralCube` is the container (it lives in :mod:`.cube_operator`, with what the cube
+operators share, and is exported from here): ``frontend.process_channel`` leaves a channel's images in
+the imager's buffers, :meth:`SpectralCube.put` copies one into its plane and records the channel's noise.
 :class:`MomentsTemplate` / :class:`Moments` is the operator (csrc/moments.hip, ``kimg_moments``);
 :func:`moments_host` is the same contract as numpy and the executable specification the device
 matches bit for bit.
@@ -45,32 +46,15 @@ import numpy as np
 
 from . import accel
 from ._lib import lib, check
-from .channel_block import integer
+from .channel_block import OperatorTemplate
+# (the container and its helpers live with what the cube operators share; their old home exports them)
+from .cube_operator import (  # noqa: F401
+    AXES as _AXES, MAX_CHANNELS, SPEED_OF_LIGHT_KMS, CubeOperator, MapArray, SpectralCube,
+    _rest_frequency, channel_pitch, channel_range, host_cube, host_filled, is_bool, mark_ready,
+    range_in_band, velocities)
 
-#: KIMG_MOMENTS_MAX_CHANNELS
-MAX_CHANNELS = 4096
 #: KIMG_MOMENT_* of include/kimg.h
 MOMENT_BITS = {0: 1, 1: 2, 2: 4, 8: 8, 9: 16, 'count': 32}
-#: km/s
-SPEED_OF_LIGHT_KMS = 299792.458
-
-_AXES = ('velocity', 'frequency')
-
-
-def _rest_frequency(value):
-    try:
-        value = float(value)
-    except (TypeError, ValueError):
-        raise ValueError('rest_frequency must be a number') from None
-    if not 0.0 < value < np.inf:                    # (false for NaN)
-        raise ValueError('rest_frequency must be finite and above 0')
-    return value
-
-
-def velocities(frequencies, rest_frequency):
-    """The radio convention ``c (1 - f / f0)`` in km/s, float64."""
-    f0 = _rest_frequency(rest_frequency)
-    return (1.0 - np.asarray(frequencies, np.float64) / f0) * SPEED_OF_LIGHT_KMS
 
 
 def moment_bunit(moment, bunit='Jy/beam', axis='velocity'):
@@ -103,7 +87,7 @@ class MomentParameters:
         if not moments:
             raise ValueError('no moments asked for')
         for m in moments:
-            if isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)) \
+            if is_bool(m) or not isinstance(m, (int, np.integer)) \
                     or int(m) not in (0, 1, 2, 8, 9):
                 raise ValueError('moments must come from 0, 1, 2, 8, 9, not {!r}'.format(m))
         moments = tuple(int(m) for m in moments)
@@ -114,20 +98,12 @@ class MomentParameters:
             raise ValueError("axis must be 'velocity' or 'frequency'")
         self.axis = axis
         self.rest_frequency = None if rest_frequency is None else _rest_frequency(rest_frequency)
-        self.channels = None
-        if channels is not None:
-            try:
-                first, stop = channels
-            except (TypeError, ValueError):
-                raise ValueError('channels must be (first, stop)') from None
-            first = integer(first, 'first channel', 0, MAX_CHANNELS - 1)
-            stop = integer(stop, 'stop channel', first + 1, MAX_CHANNELS)
-            self.channels = (first, stop)
+        self.channels = None if channels is None else channel_range(channels, 'channels')
         if clip_sigma is not None and cut is not None:
             raise ValueError('at most one of clip_sigma and cut may be given')
         self.clip_sigma = None if clip_sigma is None else self._number(clip_sigma, 'clip_sigma')
         self.cut = None if cut is None else self._number(cut, 'cut')
-        if not isinstance(select_hanning, (bool, np.bool_)):
+        if not is_bool(select_hanning):
             raise ValueError('select_hanning must be a bool')
         self.select_hanning = bool(select_hanning)
 
@@ -143,14 +119,7 @@ class MomentParameters:
 
     def range(self, num_channels):
         """(first, stop) within a band of ``num_channels`` channels."""
-        num_channels = int(num_channels)
-        if not 1 <= num_channels <= MAX_CHANNELS:
-            raise ValueError('1 to {} channels'.format(MAX_CHANNELS))
-        if self.channels is None:
-            return 0, num_channels
-        if self.channels[1] > num_channels:
-            raise ValueError('channels {} beyond the {} of the cube'.format(self.channels, num_channels))
-        return self.channels
+        return range_in_band(self.channels, num_channels)
 
     def cut_table(self, num_channels, noise=None, filled=None):
         """float32 [C]: the cut of every channel.  ``clip_sigma`` needs ``noise`` (float32 [C], NaN =
@@ -202,11 +171,10 @@ def range_width(x, first, stop, channel_width=None):
 def _tables(num_channels, coordinates, cut, filled):
     x = np.ascontiguousarray(coordinates, np.float64)
     cut = np.ascontiguousarray(cut, np.float32)
-    filled = np.ascontiguousarray(np.asarray(filled) != 0, np.uint8)
-    for name, table in (('coordinates', x), ('cut', cut), ('filled', filled)):
+    for name, table in (('coordinates', x), ('cut', cut)):
         if table.shape != (num_channels,):
             raise ValueError('{} must have one entry per channel'.format(name))
-    return x, cut, filled
+    return x, cut, host_filled(filled, num_channels).view(np.uint8)
 
 
 def moments_host(cube, coordinates, cut, filled, params, channel_width=None):
@@ -214,11 +182,7 @@ def moments_host(cube, coordinates, cut, filled, params, channel_width=None):
     ascending channel order.  ``cube`` float32 [C][...plane]; ``coordinates`` float64 [C] (x);
     ``cut`` float32 [C]; ``filled`` [C]; ``channel_width`` on the axis of x, for a range of one
     channel.  Returns ``{moment: float32 [...plane]}`` for ``params.moments`` plus ``'count'`` (int32)."""
-    cube = np.asarray(cube)
-    if cube.dtype != np.float32:
-        raise TypeError('cube must be float32')
-    if cube.ndim < 2:
-        raise ValueError('cube must be [channel][...plane]')
+    cube = host_cube(cube)
     C = cube.shape[0]
     plane = cube.shape[1:]
     x, cut, filled = _tables(C, coordinates, cut, filled)
@@ -277,150 +241,7 @@ def moments_host(cube, coordinates, cut, filled, params, channel_width=None):
     return out
 
 
-class SpectralCube:
-    """The images of ``len(frequencies)`` channels in ONE device allocation, float32
-    [channel][polarization][m][l], NaN until a plane is :meth:`put`.
-
-    ``frequencies``: float64 [C], Hz, strictly monotonic (ValueError otherwise).  ``polarizations``:
-    the list of polarization ids of every plane (``image_parameters.fixed.polarizations``), or their
-    number.  ``shape`` = (height, width) of a plane.  ``channel_width`` (Hz): needed only for moments
-    over a single channel.
-
-    All planes share one pixel size and one image centre; that is the caller's business -- the
-    reference chooses a pixel size per band, which is what a cube needs.  Every plane keeps its own
-    restoring beam: ``beams`` (a list, one entry per channel) holds what :meth:`put` was told of it,
-    None where nothing; ``common_beam`` is None until ``smooth.CubeSmooth`` has made a cube whose
-    planes share one, and is then that beam.
-
-    ``array`` is the device array, ``filled`` (uint8 [C]) says which planes hold an image and ``noise``
-    (float32 [C], NaN = none) what :meth:`put` was told of them."""
-
-    def __init__(self, context, queue, frequencies, polarizations, shape, channel_width=None):
-        frequencies = np.array(frequencies, np.float64)
-        if frequencies.ndim != 1 or not 1 <= len(frequencies) <= MAX_CHANNELS:
-            raise ValueError('frequencies must be [channel], 1 to {} of them'.format(MAX_CHANNELS))
-        if not np.all(np.isfinite(frequencies)):
-            raise ValueError('frequencies must be finite')
-        steps = np.diff(frequencies)
-        if len(steps) and not (np.all(steps > 0) or np.all(steps < 0)):
-            raise ValueError('frequencies must be strictly monotonic')
-        if isinstance(polarizations, (int, np.integer)):
-            polarizations = list(range(int(polarizations)))
-        self.polarizations = list(polarizations)
-        try:
-            height, width = (int(s) for s in shape)
-        except (TypeError, ValueError):
-            raise ValueError('shape must be (height, width)') from None
-        if not self.polarizations or height < 1 or width < 1:
-            raise ValueError('an empty plane')
-        if channel_width is not None:
-            channel_width = float(channel_width)
-            if channel_width != channel_width or channel_width == 0.0:
-                raise ValueError('channel_width must be a number other than 0')
-        self.context = context
-        self.command_queue = queue
-        self.frequencies = frequencies
-        self.channel_width = channel_width
-        C = len(frequencies)
-        self.shape = (C, len(self.polarizations), height, width)
-        self.filled = np.zeros(C, np.uint8)
-        self.noise = np.full(C, np.nan, np.float32)
-        self.beams = [None] * C
-        self.common_beam = None
-        self.array = accel.DeviceArray(context, self.shape, np.float32, queue=queue)
-        check(lib().kimg_fill(self.array.ptr, int(np.prod(self.shape)), float('nan'), queue.handle),
-              'kimg_fill')
-
-    def put(self, channel, image, noise=None, wait_for=None, beam=None):
-        """Copy ``image`` -- a device array [P][H][W] (an imager's buffer will do) or a host array --
-        into plane ``channel``, on the cube's queue, and record the channel's ``noise``
-        (``result['noise']`` of ``process_channel``) and restoring ``beam`` (a ``beam.Beam`` in
-        pixels, as ``beam.fit_beam`` returns it; ``smooth.CubeSmooth`` needs one for every plane).
-
-        The copy is ordered after the cube queue's own work only.  An image that another queue is
-        still writing needs ``wait_for``: events of that queue (``queue.enqueue_marker()``), which the
-        cube's queue waits for on the device before it copies.  ``process_channel`` itself waits for
-        the imager before it returns; what is enqueued after it (``add_model_to_dirty``) does not.
-        Returns an event of the cube's queue that fires when the copy is done: the image's queue
-        waits for it (``enqueue_wait_for_events``) before it writes the buffer again."""
-        try:
-            as_int = int(channel)
-        except (TypeError, ValueError):
-            raise TypeError('channel must be an integer') from None
-        if as_int != channel or not 0 <= as_int < self.shape[0]:
-            raise ValueError('no channel {!r} in a cube of {}'.format(channel, self.shape[0]))
-        device = isinstance(image, accel.DeviceArray)
-        if not device:
-            image = np.asarray(image)
-        if image.dtype != np.float32:
-            raise TypeError('image must be float32, not {}'.format(image.dtype))
-        if tuple(image.shape) != self.shape[1:]:
-            raise ValueError('image of shape {} for planes of {}'.format(tuple(image.shape), self.shape[1:]))
-        if noise is not None:
-            noise = np.float32(noise)
-        queue = self.command_queue
-        if wait_for:
-            queue.enqueue_wait_for_events(wait_for)
-        if device:
-            image.copy_region(queue, self.array, np.s_[:], np.s_[as_int])
-        else:
-            self.array.set_region(queue, image, np.s_[as_int], np.s_[:])
-        self.filled[as_int] = 1
-        self.noise[as_int] = np.nan if noise is None else noise
-        self.beams[as_int] = beam
-        return queue.enqueue_marker()
-
-    def get(self, queue=None):
-        """The cube as a host array (waits for the queue)."""
-        return self.array.get(self.command_queue if queue is None else queue)
-
-    def coordinates(self, axis='frequency', rest_frequency=None):
-        """float64 [C]: the frequencies (Hz), or with 'velocity' the radio velocities
-        ``c (1 - f / rest_frequency)`` in km/s."""
-        if axis == 'frequency':
-            return self.frequencies.copy()
-        if axis == 'velocity':
-            if rest_frequency is None:
-                raise ValueError('the velocity axis needs a rest frequency')
-            return velocities(self.frequencies, rest_frequency)
-        raise ValueError("axis must be 'velocity' or 'frequency'")
-
-    def axis_channel_width(self, axis='frequency', rest_frequency=None):
-        """``channel_width`` on the axis (Hz or km/s, absolute), or None."""
-        if self.channel_width is None:
-            return None
-        if axis == 'frequency':
-            return abs(self.channel_width)
-        return abs(self.channel_width) / _rest_frequency(rest_frequency) * SPEED_OF_LIGHT_KMS
-
-
-class MapArray(accel.DeviceArray):
-    """A map of one :class:`Moments` call.  ``ready`` fires when the call has written it, and
-    :meth:`get` makes its queue wait for that on the device first, so a read on ANY queue sees the
-    finished map; kernels of other queues that take the raw pointer wait for ``ready`` themselves
-    (``queue.enqueue_wait_for_events([map.ready])``)."""
-
-    ready = None
-
-    def get(self, command_queue, ary=None):
-        if self.ready is not None:
-            command_queue.enqueue_wait_for_events([self.ready])
-        return super().get(command_queue, ary)
-
-
-class MomentsTemplate:
-    def __init__(self, context, params, tuning=None):
-        if not isinstance(params, MomentParameters):
-            raise TypeError('params must be MomentParameters')
-        lib()
-        self.context = context
-        self.params = params
-
-    def instantiate(self, *args, **kwargs):
-        return Moments(self, *args, **kwargs)
-
-
-class Moments:
+class Moments(CubeOperator):
     """``kimg_moments`` for cubes of shape ``cube_shape`` = (C, P, H, W).  ``op(cube)`` takes a
     :class:`SpectralCube` and returns ``{moment: MapArray float32 [P][H][W]}`` for the moments of
     the parameters plus ``'count'`` (int32 [P][H][W], the samples that entered); maps that were not
@@ -434,63 +255,32 @@ class Moments:
     refused here).  ``channel_width``, on the axis of x, serves a range of one channel."""
 
     def __init__(self, template, command_queue, cube_shape):
-        self.template = template
-        self.params = template.params
-        self.command_queue = command_queue
-        try:
-            self.cube_shape = tuple(int(s) for s in cube_shape)
-        except (TypeError, ValueError):
-            raise ValueError('cube_shape must be (C, P, H, W)') from None
-        if len(self.cube_shape) != 4 or min(self.cube_shape) < 1:
-            raise ValueError('cube_shape must be (C, P, H, W)')
+        super().__init__(template, command_queue, cube_shape)
         self.range = self.params.range(self.cube_shape[0])
         self._tables = None
-
-    @staticmethod
-    def _channel_pitch(array):
-        C, P, H, W = array.shape
-        strides = array.tensor.stride()
-        dense = (W, H * W, P * H * W)
-        if (W > 1 and strides[3] != 1) or (H > 1 and strides[2] != W) or (P > 1 and strides[1] != H * W):
-            raise ValueError('the [polarization][m][l] plane must be dense')
-        if C == 1:
-            return dense[2]
-        if strides[0] < dense[2]:
-            raise ValueError('channels overlap')
-        return int(strides[0])
 
     def __call__(self, cube, coordinates=None, cut=None, filled=None, channel_width=None):
         params = self.params
         C = self.cube_shape[0]
         first, stop = self.range
-        from_cube = isinstance(cube, SpectralCube)
-        array = cube.array if from_cube else cube
-        if not isinstance(array, accel.DeviceArray):
-            raise TypeError('cube must be a SpectralCube or a DeviceArray')
-        if array.dtype != np.float32:
-            raise TypeError('cube must be float32')
-        if tuple(array.shape) != self.cube_shape:
-            raise ValueError('the operator was made for cubes of {}, this one is {}'.format(
-                self.cube_shape, tuple(array.shape)))
-        if from_cube:
-            if coordinates is not None or cut is not None or filled is not None \
-                    or channel_width is not None:
-                raise ValueError('a SpectralCube brings its own coordinates, cut and filled')
+        array = self._array(cube, 'cube')
+        filled = self._own_filled(cube, filled, coordinates=coordinates, cut=cut,
+                                  channel_width=channel_width)
+        if isinstance(cube, SpectralCube):
             coordinates = cube.coordinates(params.axis, params.rest_frequency)
-            filled = cube.filled
             cut = params.cut_table(C, cube.noise, filled)
             if stop - first == 1:
                 channel_width = cube.axis_channel_width(params.axis, params.rest_frequency)
         else:
-            if coordinates is None or filled is None:
-                raise ValueError('a plain array needs coordinates and filled')
+            if coordinates is None:
+                raise ValueError('a plain array needs coordinates')
             if cut is None:
                 cut = params.cut_table(C)
             elif np.ndim(cut) == 0:
                 cut = np.full(C, MomentParameters._number(cut, 'cut'), np.float32)
         x, cut, filled = _tables(C, coordinates, cut, filled)
         width = range_width(x, first, stop, channel_width)
-        pitch = self._channel_pitch(array)
+        pitch = channel_pitch(array)
         queue = self.command_queue
         context = queue.context
         # one upload: x, then cut
@@ -510,7 +300,11 @@ class Moments:
             array.ptr, pitch, C, int(np.prod(plane)), first, stop, self._tables.ptr,
             self._tables.ptr + 8 * C, filled.ctypes.data_as(ctypes.c_void_p), width,
             int(params.select_hanning), outputs, *pointers, queue.handle), 'kimg_moments')
-        ready = queue.enqueue_marker()
-        for array in out.values():
-            array.ready = ready
+        mark_ready(queue, out.values())
         return out
+
+
+class MomentsTemplate(OperatorTemplate):
+    params_type = MomentParameters
+    operator = Moments
+

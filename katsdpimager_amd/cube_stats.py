@@ -51,7 +51,8 @@ import numpy as np
 from . import accel
 from ._lib import lib, check
 from .channel_block import integer
-from .cube import MAX_CHANNELS, Moments, SpectralCube
+from .cube_operator import (CubeOperator, CubeTemplate, SpectralCube, channel_pitch, channel_range,
+                            host_cube, host_filled, host_plane_mask, is_bool, range_in_band)
 
 #: KIMG_CUBE_STATS_MEDIAN_ABS, KIMG_CUBE_STATS_MAD
 ESTIMATORS = {'median_abs': 0, 'mad': 1}
@@ -70,34 +71,17 @@ class CubeStatsParameters:
         if not isinstance(estimator, str) or estimator not in ESTIMATORS:
             raise ValueError("estimator must be 'median_abs' or 'mad'")
         self.estimator = estimator
-        if isinstance(border, (bool, np.bool_)):
+        if is_bool(border):
             raise ValueError('border must be an integer, not a bool')
         self.border = integer(border, 'border', 0, 2 ** 30)
-        if not isinstance(pool_polarizations, (bool, np.bool_)):
+        if not is_bool(pool_polarizations):
             raise ValueError('pool_polarizations must be a bool')
         self.pool_polarizations = bool(pool_polarizations)
-        self.channels = None
-        if channels is not None:
-            try:
-                first, stop = channels
-            except (TypeError, ValueError):
-                raise ValueError('channels must be (first, stop)') from None
-            if isinstance(first, (bool, np.bool_)) or isinstance(stop, (bool, np.bool_)):
-                raise ValueError('channels must be integers, not bools')
-            first = integer(first, 'first channel', 0, MAX_CHANNELS - 1)
-            stop = integer(stop, 'stop channel', first + 1, MAX_CHANNELS)
-            self.channels = (first, stop)
+        self.channels = None if channels is None else channel_range(channels, 'channels')
 
     def range(self, num_channels):
         """(first, stop) within a band of ``num_channels`` channels."""
-        num_channels = int(num_channels)
-        if not 1 <= num_channels <= MAX_CHANNELS:
-            raise ValueError('1 to {} channels'.format(MAX_CHANNELS))
-        if self.channels is None:
-            return 0, num_channels
-        if self.channels[1] > num_channels:
-            raise ValueError('channels {} beyond the {} of the cube'.format(self.channels, num_channels))
-        return self.channels
+        return range_in_band(self.channels, num_channels)
 
     def groups(self, num_polarizations):
         """G: groups per channel."""
@@ -152,30 +136,15 @@ def _sorted(values):
     return values_of(np.sort(keys(values)))
 
 
-def _region(region, height, width):
-    region = np.asarray(region)
-    if region.dtype != np.uint8 and region.dtype != np.bool_:
-        raise TypeError('region must be uint8 or bool')
-    if region.shape != (height, width):
-        raise ValueError('region of shape {} for planes of {}'.format(region.shape, (height, width)))
-    return region != 0
-
-
 def cube_stats_host(cube, filled, params, region=None):
     """The contract of ``kimg_cube_stats`` (include/kimg.h) in numpy: per group the finite candidates
     sorted by integer key and indexed.  ``cube`` float32 [C][P][H][W]; ``filled`` [C]; ``region``
     None or uint8/bool [H][W].  Returns a :class:`CubeStatsResult`."""
     if not isinstance(params, CubeStatsParameters):
         raise TypeError('params must be CubeStatsParameters')
-    cube = np.asarray(cube)
-    if cube.dtype != np.float32:
-        raise TypeError('cube must be float32')
-    if cube.ndim != 4:
-        raise ValueError('cube must be [channel][polarization][y][x]')
+    cube = host_cube(cube, ndim=4)
     C, P, H, W = cube.shape
-    filled = np.asarray(filled) != 0
-    if filled.shape != (C,):
-        raise ValueError('filled must have one entry per channel')
+    filled = host_filled(filled, C)
     first, stop = params.range(C)
     params.check_plane(H, W)
     G = params.groups(P)
@@ -185,7 +154,7 @@ def cube_stats_host(cube, filled, params, region=None):
     candidate = np.zeros((H, W), bool)
     candidate[b:H - b, b:W - b] = True
     if region is not None:
-        candidate &= _region(region, H, W)
+        candidate &= host_plane_mask(region, (H, W), 'region')
     count = np.zeros((C, G), np.uint32)
     out = {name: np.full((C, G), np.nan, np.float32) for name in _FIELDS[1:]}
     for c in range(first, stop):
@@ -222,19 +191,28 @@ def record_noise(the_cube, result, params):
             the_cube.noise[c] = result.sigma[c, 0]
 
 
-class CubeStatsTemplate:
-    def __init__(self, context, params):
-        if not isinstance(params, CubeStatsParameters):
-            raise TypeError('params must be CubeStatsParameters')
-        lib()
-        self.context = context
-        self.params = params
-
-    def instantiate(self, *args, **kwargs):
-        return CubeStats(self, *args, **kwargs)
+def stats_buffers(queue, num_channels, groups):
+    """``(scratch, out)`` of :func:`enqueue_cube_stats` for C channels of G groups: the library's
+    scratch and the five tables, uint32 [5][C][G]."""
+    words = lib().kimg_cube_stats_scratch_bytes(num_channels, groups) // 4
+    return (accel.DeviceArray(queue.context, (words,), np.uint32, queue=queue),
+            accel.DeviceArray(queue.context, (5, num_channels, groups), np.uint32, queue=queue))
 
 
-class CubeStats:
+def enqueue_cube_stats(queue, array_ptr, pitch, shape, filled, first, stop, params, region_ptr,
+                       scratch, out):
+    """One ``kimg_cube_stats`` on ``queue``: the cube of ``shape`` = (C, P, H, W) at ``array_ptr``
+    with the channel ``pitch``, ``filled`` the host uint8 [C], ``params`` the
+    :class:`CubeStatsParameters`; ``out[k]`` takes field k of ``_FIELDS``."""
+    C, P, H, W = shape
+    step = 4 * C * params.groups(P)
+    check(lib().kimg_cube_stats(
+        array_ptr, pitch, C, P, H, W, filled.ctypes.data_as(ctypes.c_void_p), first, stop,
+        int(params.pool_polarizations), ESTIMATORS[params.estimator], params.border, region_ptr,
+        scratch.ptr, *(out.ptr + k * step for k in range(5)), queue.handle), 'kimg_cube_stats')
+
+
+class CubeStats(CubeOperator):
     """``kimg_cube_stats`` for cubes of shape ``cube_shape`` = (C, P, H, W).  ``op(the_cube,
     region=None, update_noise=False)`` takes a :class:`cube.SpectralCube` and returns a
     :class:`CubeStatsResult`; ``update_noise=True`` (pooled only) writes ``sigma[:, 0]`` into
@@ -247,89 +225,42 @@ class CubeStats:
     with the one read of the ``5 * C * G`` numbers, so it waits for the queue."""
 
     def __init__(self, template, command_queue, cube_shape):
-        self.template = template
-        self.params = template.params
-        self.command_queue = command_queue
-        try:
-            self.cube_shape = tuple(int(s) for s in cube_shape)
-        except (TypeError, ValueError):
-            raise ValueError('cube_shape must be (C, P, H, W)') from None
-        if len(self.cube_shape) != 4 or min(self.cube_shape) < 1 or self.cube_shape[0] > MAX_CHANNELS:
-            raise ValueError('cube_shape must be (C, P, H, W), at most {} channels'.format(MAX_CHANNELS))
+        super().__init__(template, command_queue, cube_shape, band=True)
         C, P, H, W = self.cube_shape
         self.range = self.params.range(C)
         self.params.check_plane(H, W)
         self.groups = self.params.groups(P)
         if (P if self.groups == 1 else 1) * H * W >= 2 ** 32:
             raise ValueError('a group of 2^32 elements or more')
-        self._scratch = self._out = self._region = None
-
-    def _device_region(self, region):
-        queue = self.command_queue
-        H, W = self.cube_shape[2:]
-        if isinstance(region, accel.DeviceArray):
-            if region.dtype != np.uint8 and region.dtype != np.bool_:
-                raise TypeError('region must be uint8 or bool')
-            if tuple(region.shape) != (H, W):
-                raise ValueError('region of shape {} for planes of {}'.format(tuple(region.shape), (H, W)))
-            if W > 1 and region.tensor.stride()[1] != 1 or H > 1 and region.tensor.stride()[0] != W:
-                raise ValueError('region must be dense')
-            region.used_on(queue)
-            return region
-        host = np.ascontiguousarray(_region(region, H, W), np.uint8)
-        if self._region is None:
-            self._region = accel.DeviceArray(queue.context, (H, W), np.uint8, queue=queue)
-        self._region.set(queue, host)
-        return self._region
+        self._scratch = self._out = None
 
     def __call__(self, cube, filled=None, region=None, update_noise=False):
         params = self.params
-        C, P, H, W = self.cube_shape
-        G = self.groups
         queue = self.command_queue
-        from_cube = isinstance(cube, SpectralCube)
-        array = cube.array if from_cube else cube
-        if not isinstance(array, accel.DeviceArray):
-            raise TypeError('cube must be a SpectralCube or a DeviceArray')
-        if array.dtype != np.float32:
-            raise TypeError('cube must be float32')
-        if tuple(array.shape) != self.cube_shape:
-            raise ValueError('the operator was made for cubes of {}, this one is {}'.format(
-                self.cube_shape, tuple(array.shape)))
-        if not isinstance(update_noise, (bool, np.bool_)):
+        array = self._array(cube, 'cube')
+        if not is_bool(update_noise):
             raise ValueError('update_noise must be a bool')
-        if from_cube:
-            if filled is not None:
-                raise ValueError('a SpectralCube brings its own filled')
-            filled = cube.filled
-        else:
-            if filled is None:
-                raise ValueError('a plain array needs filled')
-            if update_noise:
-                raise ValueError('update_noise needs a SpectralCube')
+        filled = self._own_filled(cube, filled)
+        if update_noise and not isinstance(cube, SpectralCube):
+            raise ValueError('update_noise needs a SpectralCube')
         if update_noise and not params.pool_polarizations:
             raise ValueError('update_noise needs pool_polarizations: a cube records one noise a channel')
-        filled = np.ascontiguousarray(np.asarray(filled) != 0, np.uint8)
-        if filled.shape != (C,):
-            raise ValueError('filled must have one entry per channel')
-        pitch = Moments._channel_pitch(array)
+        filled = self._filled(filled)
+        pitch = channel_pitch(array)
         region_ptr = None if region is None else self._device_region(region).ptr
         if self._scratch is None:
-            context = queue.context
-            words = lib().kimg_cube_stats_scratch_bytes(C, G) // 4
-            self._scratch = accel.DeviceArray(context, (words,), np.uint32, queue=queue)
-            self._out = accel.DeviceArray(context, (5, C, G), np.uint32, queue=queue)
-        first, stop = self.range
+            self._scratch, self._out = stats_buffers(queue, self.cube_shape[0], self.groups)
         array.used_on(queue)
-        out = self._out.ptr
-        step = 4 * C * G
-        check(lib().kimg_cube_stats(
-            array.ptr, pitch, C, P, H, W, filled.ctypes.data_as(ctypes.c_void_p), first, stop,
-            int(params.pool_polarizations), ESTIMATORS[params.estimator], params.border, region_ptr,
-            self._scratch.ptr, out, out + step, out + 2 * step, out + 3 * step, out + 4 * step,
-            queue.handle), 'kimg_cube_stats')
+        enqueue_cube_stats(queue, array.ptr, pitch, self.cube_shape, filled, *self.range, params,
+                           region_ptr, self._scratch, self._out)
         words = self._out.get(queue)
         result = CubeStatsResult(words[0].copy(), *(words[i].view(np.float32).copy() for i in range(1, 5)))
         if update_noise:
             record_noise(cube, result, params)
         return result
+
+
+class CubeStatsTemplate(CubeTemplate):
+    params_type = CubeStatsParameters
+    operator = CubeStats
+

@@ -54,8 +54,10 @@ import numpy as np
 from . import accel
 from ._lib import lib, check
 from .channel_block import integer
-from .cube import MAX_CHANNELS, Moments, SpectralCube
-from .cube_stats import ESTIMATORS, CubeStatsParameters, cube_stats_host
+from .cube_operator import (MAX_CHANNELS, CubeOperator, CubeTemplate, ReadyArray, SpectralCube, band_size,
+                            blank_stale_planes, carry_over, channel_pitch, check_out_cube, host_cube,
+                            host_filled, host_plane_mask, is_bool, wait_ready)
+from .cube_stats import CubeStatsParameters, cube_stats_host, enqueue_cube_stats, stats_buffers
 from .smooth import MAX_RADIUS, _truncate, cube_smooth_host
 
 #: KIMG_BOXCAR_MAX_WIDTH
@@ -66,39 +68,8 @@ POLARITIES = {'positive': 0, 'negative': 1, 'both': 2}
 _QUIET = np.array([0x7fc00000], np.uint32).view(np.float32)[0]
 
 
-def _is_bool(value):
-    return isinstance(value, (bool, np.bool_))
-
-
-def _cube(cube, what='cube'):
-    cube = np.asarray(cube)
-    if cube.dtype != np.float32:
-        raise TypeError('{} must be float32'.format(what))
-    if cube.ndim < 2:
-        raise ValueError('{} must be [channel][...plane]'.format(what))
-    if not 1 <= cube.shape[0] <= MAX_CHANNELS:
-        raise ValueError('1 to {} channels'.format(MAX_CHANNELS))
-    return cube
-
-
-def _filled(filled, num_channels):
-    filled = np.asarray(filled) != 0
-    if filled.shape != (num_channels,):
-        raise ValueError('filled must have one entry per channel')
-    return filled
-
-
-def _mask(mask, shape):
-    mask = np.asarray(mask)
-    if mask.dtype != np.uint8 and mask.dtype != np.bool_:
-        raise TypeError('mask must be uint8 or bool')
-    if mask.shape != tuple(shape):
-        raise ValueError('mask of shape {} for a cube of {}'.format(mask.shape, tuple(shape)))
-    return mask != 0
-
-
 def _width(width):
-    if _is_bool(width):
+    if is_bool(width):
         raise ValueError('a width must be an integer, not a bool')
     width = integer(width, 'a spectral width', 1, MAX_WIDTH)
     if width % 2 == 0:
@@ -109,14 +80,14 @@ def _width(width):
 def boxcar_host(cube, filled, width, mask=None, blank=False, out=None):
     """The contract of ``kimg_cube_boxcar`` in numpy.  Returns a new array whose unfilled channels are
     ``out``'s (NaN without one)."""
-    cube = _cube(cube)
+    cube = host_cube(cube, band=True)
     C = cube.shape[0]
-    filled = _filled(filled, C)
+    filled = host_filled(filled, C)
     width = _width(width)
     h = width // 2
     usable = np.isfinite(cube) & filled.reshape((C,) + (1,) * (cube.ndim - 1))
     if mask is not None:
-        usable &= ~_mask(mask, cube.shape)
+        usable &= ~host_plane_mask(mask, cube.shape, 'mask')
     z = np.where(usable, cube, np.float32(0)).astype(np.float64)
     result = np.full(cube.shape, np.nan, np.float32) if out is None else np.array(out, np.float32)
     if result.shape != cube.shape:
@@ -136,11 +107,11 @@ def boxcar_host(cube, filled, width, mask=None, blank=False, out=None):
 def reblank_host(work, cube, filled):
     """The contract of ``kimg_cube_reblank`` in numpy: a copy of ``work`` with NaN where a filled
     channel of ``cube`` is not finite."""
-    cube = _cube(cube)
-    work = _cube(work, 'work')
+    cube = host_cube(cube, band=True)
+    work = host_cube(work, 'work', band=True)
     if work.shape != cube.shape:
         raise ValueError('work has another shape')
-    filled = _filled(filled, cube.shape[0])
+    filled = host_filled(filled, cube.shape[0])
     result = work.copy()
     for c in np.flatnonzero(filled):
         result[c] = np.where(np.isfinite(cube[c]), work[c], _QUIET)
@@ -162,11 +133,11 @@ def _threshold(value):
 def threshold_host(work, mask, filled, sigma, threshold, polarity='positive'):
     """The contract of ``kimg_cube_threshold`` in numpy.  ``work`` float32 [C][P][H][W]; ``sigma``
     float32 [C][G], G = 1 or P.  Returns a new mask: ``mask`` with the detections set to 1."""
-    work = _cube(work, 'work')
+    work = host_cube(work, 'work', band=True)
     if work.ndim != 4:
         raise ValueError('work must be [channel][polarization][y][x]')
     C, P = work.shape[:2]
-    filled = _filled(filled, C)
+    filled = host_filled(filled, C)
     mask = np.asarray(mask)
     if mask.dtype != np.uint8 or mask.shape != work.shape:
         raise ValueError('mask must be uint8 of the shape of work')
@@ -198,7 +169,7 @@ def prune_host(mask, min_channels):
     if mask.dtype != np.uint8 or mask.ndim < 2:
         raise ValueError('mask must be uint8 [channel][...plane]')
     C = mask.shape[0]
-    if _is_bool(min_channels):
+    if is_bool(min_channels):
         raise ValueError('min_channels must be an integer, not a bool')
     min_channels = integer(min_channels, 'min_channels', 1, C)
     on = mask != 0
@@ -216,9 +187,9 @@ def prune_host(mask, min_channels):
 def apply_host(cube, mask, filled, invert=False, out=None):
     """The contract of ``kimg_cube_mask_apply`` in numpy.  Returns a new array whose unfilled channels
     are ``out``'s (the cube's own without one, as in place)."""
-    cube = _cube(cube)
-    filled = _filled(filled, cube.shape[0])
-    keep = _mask(mask, cube.shape) != bool(invert)
+    cube = host_cube(cube, band=True)
+    filled = host_filled(filled, cube.shape[0])
+    keep = host_plane_mask(mask, cube.shape, 'mask') != bool(invert)
     result = cube.copy() if out is None else np.array(out, np.float32)
     if result.shape != cube.shape:
         raise ValueError('out has another shape')
@@ -281,7 +252,7 @@ class SmoothClipParameters:
         if not spatial_fwhm or not spectral_widths:
             raise ValueError('no smoothing kernel asked for')
         for fwhm in spatial_fwhm:
-            if _is_bool(fwhm):
+            if is_bool(fwhm):
                 raise ValueError('a spatial FWHM must be a number, not a bool')
             gaussian_taps(fwhm, self.truncate)
         self.spatial_fwhm = tuple(float(fwhm) for fwhm in spatial_fwhm)
@@ -296,18 +267,17 @@ class SmoothClipParameters:
         self.estimator = self.stats.estimator
         self.border = self.stats.border
         self.pool_polarizations = self.stats.pool_polarizations
-        if not _is_bool(replace):
+        if not is_bool(replace):
             raise ValueError('replace must be a bool')
         self.replace = bool(replace)
-        if _is_bool(min_channels):
+        if is_bool(min_channels):
             raise ValueError('min_channels must be an integer, not a bool')
         self.min_channels = integer(min_channels, 'min_channels', 1, MAX_CHANNELS)
 
     def check_shape(self, shape):
         """ValueError unless cubes of ``shape`` = (C, P, H, W) can be searched."""
         C, P, H, W = shape
-        if not 1 <= C <= MAX_CHANNELS:
-            raise ValueError('1 to {} channels'.format(MAX_CHANNELS))
+        band_size(C)
         if self.min_channels > C:
             raise ValueError('min_channels {} in a cube of {} channels'.format(self.min_channels, C))
         self.stats.check_plane(H, W)
@@ -330,11 +300,11 @@ def smooth_clip_host(cube, filled, params, region=None):
     (not where voxels may be detected).  Returns the mask, uint8 [C][P][H][W]."""
     if not isinstance(params, SmoothClipParameters):
         raise TypeError('params must be SmoothClipParameters')
-    cube = _cube(cube)
+    cube = host_cube(cube, band=True)
     if cube.ndim != 4:
         raise ValueError('cube must be [channel][polarization][y][x]')
     C = cube.shape[0]
-    filled = _filled(filled, C)
+    filled = host_filled(filled, C)
     params.check_shape(cube.shape)
     mask = np.zeros(cube.shape, np.uint8)
     for fwhm in params.spatial_fwhm:
@@ -352,19 +322,9 @@ def smooth_clip_host(cube, filled, params, region=None):
     return mask
 
 
-class MaskCube(accel.DeviceArray):
-    """A detection mask, device uint8 [C][P][H][W]: 0 = not detected, 1 = detected.  ``ready`` fires
-    when the call that made it has written it, and :meth:`get` makes its queue wait for that on the
-    device first, as :class:`cube.MapArray`.  ``filled`` (uint8 [C]) is what the finder was told."""
-
-    ready = None
-    filled = None
-    command_queue = None
-
-    def get(self, command_queue, ary=None):
-        if self.ready is not None:
-            command_queue.enqueue_wait_for_events([self.ready])
-        return super().get(command_queue, ary)
+class MaskCube(ReadyArray):
+    """A detection mask, device uint8 [C][P][H][W]: 0 = not detected, 1 = detected; a
+    :class:`cube_operator.ReadyArray`, whose ``filled`` (uint8 [C]) is what the finder was told."""
 
     def apply(self, cube, out=None, invert=False):
         """``kimg_cube_mask_apply``: the :class:`cube.SpectralCube` ``cube`` with NaN where the mask is
@@ -377,55 +337,31 @@ class MaskCube(accel.DeviceArray):
             raise TypeError('cube must be a SpectralCube')
         if tuple(cube.shape) != self.shape:
             raise ValueError('a mask of {} for a cube of {}'.format(self.shape, tuple(cube.shape)))
-        if not _is_bool(invert):
+        if not is_bool(invert):
             raise ValueError('invert must be a bool')
-        if out is not None and out is not cube:
-            if not isinstance(out, SpectralCube):
-                raise TypeError('out must be a SpectralCube')
-            if tuple(out.shape) != self.shape or not np.array_equal(out.frequencies, cube.frequencies):
-                raise ValueError('out has another shape or other frequencies')
+        check_out_cube(cube, out, 'masked cube', same=('shape', 'frequencies'))
         queue = self.command_queue
         if out is None:
-            out = SpectralCube(queue.context, queue, cube.frequencies, cube.polarizations,
-                               cube.shape[2:], cube.channel_width)
+            out = SpectralCube.like(cube, queue)
         filled = np.ascontiguousarray(cube.filled != 0, np.uint8)
-        if self.ready is not None:
-            queue.enqueue_wait_for_events([self.ready])
+        wait_ready(queue, self)
         cube.array.used_on(queue)
         out.array.used_on(queue)
         self.used_on(queue)
         C = self.shape[0]
         M = int(np.prod(self.shape[1:]))
+        out_pitch = channel_pitch(out.array)
         if out is not cube:
-            # (planes out held that the cube does not: back to what an unfilled plane holds)
-            for c in np.flatnonzero((out.filled != 0) & (filled == 0)):
-                check(lib().kimg_fill(out.array.ptr + 4 * int(c) * Moments._channel_pitch(out.array),
-                                      M, float('nan'), queue.handle), 'kimg_fill')
+            blank_stale_planes(queue, out.array, out_pitch,
+                               np.flatnonzero((out.filled != 0) & (filled == 0)), M)
         check(lib().kimg_cube_mask_apply(
-            cube.array.ptr, Moments._channel_pitch(cube.array), self.ptr, M, out.array.ptr,
-            Moments._channel_pitch(out.array), C, M, filled.ctypes.data_as(ctypes.c_void_p),
-            int(invert), queue.handle), 'kimg_cube_mask_apply')
-        if out is not cube:
-            out.filled[:] = cube.filled
-            out.noise[:] = cube.noise
-            out.beams = list(cube.beams)
-            out.common_beam = cube.common_beam
+            cube.array.ptr, channel_pitch(cube.array), self.ptr, M, out.array.ptr, out_pitch, C, M,
+            filled.ctypes.data_as(ctypes.c_void_p), int(invert), queue.handle), 'kimg_cube_mask_apply')
+        carry_over(cube, out, beams=True)
         return out
 
 
-class SmoothClipTemplate:
-    def __init__(self, context, params):
-        if not isinstance(params, SmoothClipParameters):
-            raise TypeError('params must be SmoothClipParameters')
-        lib()
-        self.context = context
-        self.params = params
-
-    def instantiate(self, *args, **kwargs):
-        return SmoothClip(self, *args, **kwargs)
-
-
-class SmoothClip:
+class SmoothClip(CubeOperator):
     """The smooth-and-clip finder for cubes of shape ``cube_shape`` = (C, P, H, W).  ``op(the_cube,
     region=None)`` takes a :class:`cube.SpectralCube` and returns a :class:`MaskCube`;
     ``op(array, filled=..., region=None)`` takes a plain :class:`accel.DeviceArray` [C][P][H][W] whose
@@ -439,25 +375,16 @@ class SmoothClip:
     ``command_queue`` and never waits for the device.  The cube is never written."""
 
     def __init__(self, template, command_queue, cube_shape):
-        self.template = template
-        self.params = params = template.params
-        self.command_queue = queue = command_queue
-        try:
-            self.cube_shape = tuple(int(s) for s in cube_shape)
-        except (TypeError, ValueError):
-            raise ValueError('cube_shape must be (C, P, H, W)') from None
-        if len(self.cube_shape) != 4 or min(self.cube_shape) < 1:
-            raise ValueError('cube_shape must be (C, P, H, W)')
+        super().__init__(template, command_queue, cube_shape)
+        params = self.params
+        queue = command_queue
         params.check_shape(self.cube_shape)
         C, P, H, W = self.cube_shape
         context = queue.context
         self.groups = params.stats.groups(P)
         self._work = [accel.DeviceArray(context, self.cube_shape, np.float32, queue=queue)
                       for _ in range(2 if any(f > 0 for f in params.spatial_fwhm) else 1)]
-        words = lib().kimg_cube_stats_scratch_bytes(C, self.groups) // 4
-        self._scratch = accel.DeviceArray(context, (words,), np.uint32, queue=queue)
-        self._stats = accel.DeviceArray(context, (5, C, self.groups), np.uint32, queue=queue)
-        self._region = None
+        self._scratch, self._stats = stats_buffers(queue, C, self.groups)
         # per FWHM above 0: (radius int32 [C], taps on the device [C][(2 R + 1)^2], the same row for
         # every channel: kimg_cube_smooth has a kernel per channel)
         self._taps = {}
@@ -468,62 +395,21 @@ class SmoothClip:
                 table.set(queue, np.tile(taps, (C, 1)))
                 self._taps[fwhm] = (np.full(C, radius, np.int32), table)
 
-    def _device_region(self, region):
-        queue = self.command_queue
-        H, W = self.cube_shape[2:]
-        if isinstance(region, accel.DeviceArray):
-            if region.dtype != np.uint8 and region.dtype != np.bool_:
-                raise TypeError('region must be uint8 or bool')
-            if tuple(region.shape) != (H, W):
-                raise ValueError('region of shape {} for planes of {}'.format(tuple(region.shape), (H, W)))
-            if W > 1 and region.tensor.stride()[1] != 1 or H > 1 and region.tensor.stride()[0] != W:
-                raise ValueError('region must be dense')
-            region.used_on(queue)
-            return region
-        region = np.asarray(region)
-        if region.dtype != np.uint8 and region.dtype != np.bool_:
-            raise TypeError('region must be uint8 or bool')
-        if region.shape != (H, W):
-            raise ValueError('region of shape {} for planes of {}'.format(region.shape, (H, W)))
-        if self._region is None:
-            self._region = accel.DeviceArray(queue.context, (H, W), np.uint8, queue=queue)
-        self._region.set(queue, np.ascontiguousarray(region != 0, np.uint8))
-        return self._region
-
     def __call__(self, cube, filled=None, region=None):
         params = self.params
         C, P, H, W = self.cube_shape
         M = P * H * W
         queue = self.command_queue
-        from_cube = isinstance(cube, SpectralCube)
-        array = cube.array if from_cube else cube
-        if not isinstance(array, accel.DeviceArray):
-            raise TypeError('cube must be a SpectralCube or a DeviceArray')
-        if array.dtype != np.float32:
-            raise TypeError('cube must be float32')
-        if tuple(array.shape) != self.cube_shape:
-            raise ValueError('the operator was made for cubes of {}, this one is {}'.format(
-                self.cube_shape, tuple(array.shape)))
-        if from_cube:
-            if filled is not None:
-                raise ValueError('a SpectralCube brings its own filled')
-            filled = cube.filled
-        elif filled is None:
-            raise ValueError('a plain array needs filled')
-        filled = np.ascontiguousarray(np.asarray(filled) != 0, np.uint8)
-        if filled.shape != (C,):
-            raise ValueError('filled must have one entry per channel')
-        pitch = Moments._channel_pitch(array)
+        array = self._array(cube, 'cube')
+        filled = self._filled(self._own_filled(cube, filled))
+        pitch = channel_pitch(array)
         region_ptr = None if region is None else self._device_region(region).ptr
-        mask = MaskCube(queue.context, self.cube_shape, np.uint8, queue=queue)
-        mask.command_queue = queue
-        mask.filled = filled.copy()
+        mask = MaskCube.of_cube(queue, self.cube_shape, np.uint8, filled)
         mask.zero(queue)
         array.used_on(queue)
         handle = queue.handle
         filled_ptr = filled.ctypes.data_as(ctypes.c_void_p)
-        stats = self._stats.ptr
-        step = 4 * C * self.groups
+        sigma_ptr = self._stats.ptr + 4 * 4 * C * self.groups      # (the fifth table)
         A = self._work[0]
         for fwhm in params.spatial_fwhm:
             for width in params.spectral_widths:
@@ -540,16 +426,18 @@ class SmoothClip:
                         'kimg_cube_smooth')
                     check(lib().kimg_cube_reblank(work.ptr, M, array.ptr, pitch, C, M, filled_ptr,
                                                   handle), 'kimg_cube_reblank')
-                check(lib().kimg_cube_stats(
-                    work.ptr, M, C, P, H, W, filled_ptr, 0, C, int(params.pool_polarizations),
-                    ESTIMATORS[params.estimator], params.border, region_ptr, self._scratch.ptr,
-                    stats, stats + step, stats + 2 * step, stats + 3 * step, stats + 4 * step,
-                    handle), 'kimg_cube_stats')
+                enqueue_cube_stats(queue, work.ptr, M, self.cube_shape, filled, 0, C, params.stats,
+                                   region_ptr, self._scratch, self._stats)
                 check(lib().kimg_cube_threshold(
-                    work.ptr, M, mask.ptr, M, C, P, H, W, filled_ptr, stats + 4 * step, self.groups,
+                    work.ptr, M, mask.ptr, M, C, P, H, W, filled_ptr, sigma_ptr, self.groups,
                     params.threshold, POLARITIES[params.polarity], handle), 'kimg_cube_threshold')
         if params.min_channels > 1:
             check(lib().kimg_cube_mask_prune(mask.ptr, M, C, M, params.min_channels, handle),
                   'kimg_cube_mask_prune')
         mask.ready = queue.enqueue_marker()
         return mask
+
+
+class SmoothClipTemplate(CubeTemplate):
+    params_type = SmoothClipParameters
+    operator = SmoothClip

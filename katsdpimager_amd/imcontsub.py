@@ -26,9 +26,10 @@ import numpy as np
 
 from . import accel
 from ._lib import lib, check
-from .channel_block import ChannelSelection, integer
+from .channel_block import ChannelSelection, OperatorTemplate, integer
 from .continuum import MAX_ORDER, legendre_basis
-from .cube import MAX_CHANNELS, MapArray, Moments, SpectralCube
+from .cube_operator import (MAX_CHANNELS, CubeOperator, MapArray, SpectralCube, band_size, carry_over,
+                            channel_pitch, check_out_cube, host_cube, host_filled, mark_ready)
 
 #: KIMG_IMCONTSUB_* of include/kimg.h
 OUTPUT_BITS = {'continuum': 1, 'coefficients': 2, 'rms': 4, 'count': 8}
@@ -79,9 +80,7 @@ class ImContSubParameters:
 
     def mask(self, num_channels):
         """The selection over ``num_channels`` channels, uint8 (1 = line-free)."""
-        num_channels = int(num_channels)
-        if not 1 <= num_channels <= MAX_CHANNELS:
-            raise ValueError('1 to {} channels'.format(MAX_CHANNELS))
+        num_channels = band_size(num_channels)
         if self.min_samples is not None and self.min_samples > num_channels:
             raise ValueError('min_samples {} for {} channels'.format(self.min_samples, num_channels))
         return self._selection.mask(num_channels)
@@ -121,9 +120,7 @@ class ImContSubParameters:
         bref float64 [K], min_samples)``.  ValueError when fewer than ``order + 1`` channels enter."""
         C = int(num_channels)
         selection = self.mask(C)
-        filled = np.ascontiguousarray(np.asarray(filled) != 0, np.uint8)
-        if filled.shape != (C,):
-            raise ValueError('filled must have one entry per channel')
+        filled = host_filled(filled, C).view(np.uint8)
         B = self.basis(C, frequencies)
         asked = selection & filled
         w = self.weights(C, asked, noise)
@@ -146,22 +143,13 @@ class ImContSubParameters:
         return text + ')'
 
 
-def _check_cube(cube):
-    cube = np.asarray(cube)
-    if cube.dtype != np.float32:
-        raise TypeError('cube must be float32')
-    if cube.ndim < 2:
-        raise ValueError('cube must be [channel][...plane]')
-    return cube
-
-
 def imcontsub_host_double(cube, filled, params, frequencies=None, noise=None):
     """The contract up to its last step: ``(line, maps)`` with every value in float64 BEFORE the one
     rounding to float32.  ``line`` [C][...plane]: the residual of fitted elements, NaN in the filled
     channels of the others, the input's own value where that is not finite or the channel not filled.
     ``maps``: ``'continuum'``, ``'coefficients'`` [K][...plane], ``'rms'`` (float64, NaN where the
     contract says so), ``'count'`` (int32) and ``'fitted'`` (bool)."""
-    cube = _check_cube(cube)
+    cube = host_cube(cube)
     C = cube.shape[0]
     plane = cube.shape[1:]
     filled, fit, w, B, bref, min_samples = params.tables(C, filled, frequencies, noise)
@@ -232,7 +220,7 @@ def imcontsub_host(cube, filled, params, frequencies=None, noise=None):
     to float32.  ``cube`` float32 [C][...plane], ``filled`` [C]; ``frequencies`` (float64 [C]) for
     ``axis='frequency'``, ``noise`` (float32 [C]) for ``weighting='noise'``.  Returns a new array and
     the maps: ``(line, {'continuum', 'coefficients', 'rms', 'count'})``."""
-    cube = _check_cube(cube)
+    cube = host_cube(cube)
     line, maps = imcontsub_host_double(cube, filled, params, frequencies, noise)
     with np.errstate(all='ignore'):
         rounded = line.astype(np.float32)
@@ -247,19 +235,7 @@ def imcontsub_host(cube, filled, params, frequencies=None, noise=None):
     return rounded, out
 
 
-class ImContSubTemplate:
-    def __init__(self, context, params, tuning=None):
-        if not isinstance(params, ImContSubParameters):
-            raise TypeError('params must be ImContSubParameters')
-        lib()
-        self.context = context
-        self.params = params
-
-    def instantiate(self, *args, **kwargs):
-        return ImContSub(self, *args, **kwargs)
-
-
-class ImContSub:
+class ImContSub(CubeOperator):
     """``kimg_imcontsub`` for cubes of shape ``cube_shape`` = (C, P, H, W).  ``op(cube)`` takes a
     :class:`cube.SpectralCube` and works in place; ``op(cube, out=other)`` writes the line cube into
     another SpectralCube of the same shape and frequencies and leaves the source alone -- ``other``'s
@@ -274,15 +250,7 @@ class ImContSub:
     array itself (or None: in place) or share no memory with it."""
 
     def __init__(self, template, command_queue, cube_shape, outputs=DEFAULT_OUTPUTS):
-        self.template = template
-        self.params = template.params
-        self.command_queue = command_queue
-        try:
-            self.cube_shape = tuple(int(s) for s in cube_shape)
-        except (TypeError, ValueError):
-            raise ValueError('cube_shape must be (C, P, H, W)') from None
-        if len(self.cube_shape) != 4 or min(self.cube_shape) < 1:
-            raise ValueError('cube_shape must be (C, P, H, W)')
+        super().__init__(template, command_queue, cube_shape)
         self.params.mask(self.cube_shape[0])
         try:
             outputs = tuple(outputs)
@@ -294,40 +262,19 @@ class ImContSub:
         self.outputs = outputs
         self._tables = None
 
-    def _array(self, cube, what):
-        array = cube.array if isinstance(cube, SpectralCube) else cube
-        if not isinstance(array, accel.DeviceArray):
-            raise TypeError('{} must be a SpectralCube or a DeviceArray'.format(what))
-        if array.dtype != np.float32:
-            raise TypeError('{} must be float32'.format(what))
-        if tuple(array.shape) != self.cube_shape:
-            raise ValueError('the operator was made for cubes of {}, this one is {}'.format(
-                self.cube_shape, tuple(array.shape)))
-        return array
-
     def __call__(self, cube, filled=None, frequencies=None, noise=None, out=None):
         params = self.params
         C = self.cube_shape[0]
         K = params.order + 1
-        from_cube = isinstance(cube, SpectralCube)
         array = self._array(cube, 'cube')
-        if from_cube:
-            if filled is not None or frequencies is not None or noise is not None:
-                raise ValueError('a SpectralCube brings its own filled, frequencies and noise')
-            filled, frequencies, noise = cube.filled, cube.frequencies, cube.noise
-            if out is not None and out is not cube:
-                if not isinstance(out, SpectralCube):
-                    raise TypeError('the line cube of a SpectralCube is a SpectralCube')
-                if not np.array_equal(out.frequencies, cube.frequencies):
-                    raise ValueError('out has other frequencies')
-        elif filled is None:
-            raise ValueError('a plain array needs filled')
-        elif isinstance(out, SpectralCube):
-            raise TypeError('the line cube of a plain array is a plain array')
+        filled = self._own_filled(cube, filled, frequencies=frequencies, noise=noise)
+        if isinstance(cube, SpectralCube):
+            frequencies, noise = cube.frequencies, cube.noise
+        check_out_cube(cube, out, 'line cube')
         target = array if out is None else self._array(out, 'out')
         filled, fit, w, B, bref, min_samples = params.tables(C, filled, frequencies, noise)
-        pitch = Moments._channel_pitch(array)
-        target_pitch = Moments._channel_pitch(target)
+        pitch = channel_pitch(array)
+        target_pitch = channel_pitch(target)
         queue = self.command_queue
         context = queue.context
         # one upload: w, then the basis
@@ -356,10 +303,11 @@ class ImContSub:
             params.order, *reference, min_samples, bits, pointer['continuum'],
             pointer['coefficients'], M, pointer['rms'], pointer['count'], queue.handle),
             'kimg_imcontsub')
-        ready = queue.enqueue_marker()
-        for m in maps.values():
-            m.ready = ready
-        if from_cube and out is not None and out is not cube:
-            out.filled[:] = cube.filled
-            out.noise[:] = cube.noise
+        mark_ready(queue, maps.values())
+        carry_over(cube, out)
         return maps
+
+
+class ImContSubTemplate(OperatorTemplate):
+    params_type = ImContSubParameters
+    operator = ImContSub

@@ -50,7 +50,8 @@ import numpy as np
 from . import accel
 from ._lib import lib, check, Catalogue
 from .channel_block import integer
-from .cube import MAX_CHANNELS, Moments, SpectralCube
+from .cube_operator import (CubeOperator, CubeTemplate, ReadyArray, SpectralCube, band_size, channel_pitch,
+                            host_filled, is_bool, wait_ready)
 from .detect import MaskCube
 
 MAX_REACH_XY_SQ = 9
@@ -86,12 +87,8 @@ class TooManySources(RuntimeError):
         self.labels = labels
 
 
-def _is_bool(value):
-    return isinstance(value, (bool, np.bool_))
-
-
 def _reach(reach_xy_sq, reach_z):
-    if _is_bool(reach_xy_sq) or _is_bool(reach_z):
+    if is_bool(reach_xy_sq) or is_bool(reach_z):
         raise ValueError('a reach must be an integer, not a bool')
     return (integer(reach_xy_sq, 'reach_xy_sq', 0, MAX_REACH_XY_SQ),
             integer(reach_z, 'reach_z', 0, MAX_REACH_Z))
@@ -103,14 +100,10 @@ def _set_voxels(mask, filled):
         raise TypeError('mask must be uint8 or bool')
     if mask.ndim != 4:
         raise ValueError('mask must be [channel][polarization][y][x]')
-    if not 1 <= mask.shape[0] <= MAX_CHANNELS:
-        raise ValueError('1 to {} channels'.format(MAX_CHANNELS))
+    band_size(mask.shape[0])
     if mask.size > 2 ** 31 - 2:
         raise ValueError('more than 2^31 - 2 voxels')
-    filled = np.asarray(filled) != 0
-    if filled.shape != (mask.shape[0],):
-        raise ValueError('filled must have one entry per channel')
-    return (mask != 0) & filled.reshape(-1, 1, 1, 1)
+    return (mask != 0) & host_filled(filled, mask.shape[0]).reshape(-1, 1, 1, 1)
 
 
 def neighbour_offsets(reach_xy_sq, reach_z):
@@ -187,10 +180,7 @@ def measure_host(labels, cube, filled, num_sources=None, capacity=None):
     if cube.dtype != np.float32 or cube.shape != labels.shape:
         raise ValueError('cube must be float32 of the shape of labels')
     C, P, H, W = labels.shape
-    filled = np.asarray(filled) != 0
-    if filled.shape != (C,):
-        raise ValueError('filled must have one entry per channel')
-    member = (labels > 0) & filled.reshape(-1, 1, 1, 1)
+    member = (labels > 0) & host_filled(filled, C).reshape(-1, 1, 1, 1)
     if num_sources is None:
         num_sources = int(labels[member].max()) if member.any() else 0
     rows = num_sources if capacity is None else min(num_sources, capacity)
@@ -229,7 +219,7 @@ def measure_host(labels, cube, filled, num_sources=None, capacity=None):
 
 
 def _minimum(value, name):
-    if _is_bool(value):
+    if is_bool(value):
         raise ValueError('{} must be an integer, not a bool'.format(name))
     return integer(value, name, 1, 2 ** 31 - 1)
 
@@ -256,7 +246,7 @@ def filter_host(labels, table, min_voxels=1, min_size_xy=1, min_size_z=1):
 def label_mask_host(labels, source=0):
     """The contract of ``kimg_cube_label_mask`` in numpy: uint8 of the labels' shape."""
     labels = _labels(labels)
-    if _is_bool(source):
+    if is_bool(source):
         raise ValueError('source must be an integer, not a bool')
     source = integer(source, 'source', 0, 2 ** 31 - 1)
     return (labels == source if source else labels != 0).astype(np.uint8)
@@ -302,7 +292,7 @@ class LinkParameters:
 
     def __init__(self, radius_xy=1, radius_z=1, min_voxels=1, min_size_xy=1, min_size_z=1,
                  max_sources=65536):
-        if _is_bool(radius_xy):
+        if is_bool(radius_xy):
             raise ValueError('radius_xy must be a number, not a bool')
         try:
             radius_xy = float(radius_xy)
@@ -310,7 +300,7 @@ class LinkParameters:
             raise ValueError('radius_xy must be a number') from None
         if not 0.0 <= radius_xy <= 3.0:                 # (false for NaN)
             raise ValueError('radius_xy must be 0 to 3')
-        if _is_bool(radius_z):
+        if is_bool(radius_z):
             raise ValueError('radius_z must be an integer, not a bool')
         self.radius_xy = radius_xy
         self.radius_z = integer(radius_z, 'radius_z', 0, MAX_REACH_Z)
@@ -318,7 +308,7 @@ class LinkParameters:
         self.min_voxels = _minimum(min_voxels, 'min_voxels')
         self.min_size_xy = _minimum(min_size_xy, 'min_size_xy')
         self.min_size_z = _minimum(min_size_z, 'min_size_z')
-        if _is_bool(max_sources):
+        if is_bool(max_sources):
             raise ValueError('max_sources must be an integer, not a bool')
         self.max_sources = integer(max_sources, 'max_sources', 1, 2 ** 24)
 
@@ -333,54 +323,28 @@ class LinkParameters:
                     self.max_sources)
 
 
-class LabelCube(accel.DeviceArray):
-    """Source labels, device int32 [C][P][H][W]: 0 = no source, s = source s of the catalogue.
-    ``ready`` fires when the call that made it has written it, and :meth:`get` makes its queue wait
-    for that on the device first, as :class:`detect.MaskCube`.  ``filled`` (uint8 [C]) is what the
-    linker was told."""
-
-    ready = None
-    filled = None
-    command_queue = None
-
-    def get(self, command_queue, ary=None):
-        if self.ready is not None:
-            command_queue.enqueue_wait_for_events([self.ready])
-        return super().get(command_queue, ary)
+class LabelCube(ReadyArray):
+    """Source labels, device int32 [C][P][H][W]: 0 = no source, s = source s of the catalogue; a
+    :class:`cube_operator.ReadyArray`, whose ``filled`` (uint8 [C]) is what the linker was told."""
 
     def mask(self, source=0):
         """``kimg_cube_label_mask``: the :class:`detect.MaskCube` of every source (``source`` 0) or of
         source ``source`` alone, on the labels' queue."""
-        if _is_bool(source):
+        if is_bool(source):
             raise ValueError('source must be an integer, not a bool')
         source = integer(source, 'source', 0, 2 ** 31 - 1)
         queue = self.command_queue
-        if self.ready is not None:
-            queue.enqueue_wait_for_events([self.ready])
+        wait_ready(queue, self)
         self.used_on(queue)
-        mask = MaskCube(queue.context, self.shape, np.uint8, queue=queue)
-        mask.command_queue = queue
-        mask.filled = self.filled.copy()
-        M = int(np.prod(self.shape[1:]))
+        mask = MaskCube.of_cube(queue, self.shape, np.uint8, self.filled)
+        M =int(np.prod(self.shape[1:]))
         check(lib().kimg_cube_label_mask(self.ptr, M, mask.ptr, M, self.shape[0], M, source,
                                          queue.handle), 'kimg_cube_label_mask')
         mask.ready = queue.enqueue_marker()
         return mask
 
 
-class LinkTemplate:
-    def __init__(self, context, params):
-        if not isinstance(params, LinkParameters):
-            raise TypeError('params must be LinkParameters')
-        lib()
-        self.context = context
-        self.params = params
-
-    def instantiate(self, *args, **kwargs):
-        return Link(self, *args, **kwargs)
-
-
-class Link:
+class Link(CubeOperator):
     """The linker for cubes of shape ``cube_shape`` = (C, P, H, W).  ``op(mask, the_cube)`` takes a
     :class:`detect.MaskCube` and a :class:`cube.SpectralCube`; ``op(mask, array, filled=...,
     frequencies=None)`` takes plain :class:`accel.DeviceArray` s (uint8 and float32) whose [P][H][W]
@@ -392,18 +356,10 @@ class Link:
     and waits for the device once, at the end, when it reads the tables and the two counts."""
 
     def __init__(self, template, command_queue, cube_shape):
-        self.template = template
-        self.params = params = template.params
-        self.command_queue = queue = command_queue
-        try:
-            self.cube_shape = tuple(int(s) for s in cube_shape)
-        except (TypeError, ValueError):
-            raise ValueError('cube_shape must be (C, P, H, W)') from None
-        if len(self.cube_shape) != 4 or min(self.cube_shape) < 1:
-            raise ValueError('cube_shape must be (C, P, H, W)')
+        super().__init__(template, command_queue, cube_shape, band=True)
+        params = self.params
+        queue = command_queue
         C, P, H, W = self.cube_shape
-        if C > MAX_CHANNELS:
-            raise ValueError('1 to {} channels'.format(MAX_CHANNELS))
         if C * P * H * W > 2 ** 31 - 2:
             raise ValueError('more than 2^31 - 2 voxels: labels are int32')
         context = queue.context
@@ -430,38 +386,18 @@ class Link:
         C, P, H, W = self.cube_shape
         M = P * H * W
         queue = self.command_queue
-        from_cube = isinstance(cube, SpectralCube)
-        array = cube.array if from_cube else cube
-        if not isinstance(array, accel.DeviceArray) or not isinstance(mask, accel.DeviceArray):
-            raise TypeError('mask and cube must be device arrays (MaskCube, SpectralCube)')
-        if array.dtype != np.float32:
-            raise TypeError('cube must be float32')
-        if mask.dtype != np.uint8:
-            raise TypeError('mask must be uint8')
-        if tuple(array.shape) != self.cube_shape or tuple(mask.shape) != self.cube_shape:
-            raise ValueError('the operator was made for cubes of {}, these are {} and {}'.format(
-                self.cube_shape, tuple(mask.shape), tuple(array.shape)))
-        if from_cube:
-            if filled is not None or frequencies is not None:
-                raise ValueError('a SpectralCube brings its own filled and frequencies')
-            filled = cube.filled
+        mask, array = self._arrays((mask, 'mask', np.uint8), (cube, 'cube', np.float32))
+        filled = self._filled(self._own_filled(cube, filled, frequencies=frequencies))
+        if isinstance(cube, SpectralCube):
             frequencies = cube.frequencies
-        elif filled is None:
-            raise ValueError('a plain array needs filled')
-        filled = np.ascontiguousarray(np.asarray(filled) != 0, np.uint8)
-        if filled.shape != (C,):
-            raise ValueError('filled must have one entry per channel')
         if frequencies is not None and np.shape(frequencies) != (C,):
             raise ValueError('frequencies must have one entry per channel')
-        pitch = Moments._channel_pitch(array)
-        mask_pitch = Moments._channel_pitch(mask)
-        if getattr(mask, 'ready', None) is not None:
-            queue.enqueue_wait_for_events([mask.ready])
+        pitch = channel_pitch(array)
+        mask_pitch = channel_pitch(mask)
+        self._wait_ready(mask)
         mask.used_on(queue)
         array.used_on(queue)
-        labels = LabelCube(queue.context, self.cube_shape, np.int32, queue=queue)
-        labels.command_queue = queue
-        labels.filled = filled.copy()
+        labels = LabelCube.of_cube(queue, self.cube_shape, np.int32, filled)
         handle = queue.handle
         filled_ptr = filled.ctypes.data_as(ctypes.c_void_p)
         counts = self._tables.ptr
@@ -487,3 +423,8 @@ class Link:
             dtype = TABLE_DTYPE[name]
             table[name] = raw[at:at + dtype.itemsize * N].view(dtype)
         return labels, catalogue_host(table, self.cube_shape, frequencies)
+
+
+class LinkTemplate(CubeTemplate):
+    params_type = LinkParameters
+    operator = Link

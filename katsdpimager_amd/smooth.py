@@ -40,7 +40,9 @@ import numpy as np
 from . import accel
 from ._lib import lib, check
 from .beam import Beam, beam_covariance_sqrt
-from .cube import MAX_CHANNELS, Moments, SpectralCube
+from .cube_operator import (  # noqa: F401  (MAX_CHANNELS: the limit band_size holds this module to)
+    MAX_CHANNELS, CubeOperator, CubeTemplate, SpectralCube, band_size, blank_stale_planes, channel_pitch,
+    check_out_cube, host_cube)
 
 #: KIMG_CUBE_SMOOTH_MAX_RADIUS
 MAX_RADIUS = 16
@@ -137,8 +139,7 @@ def _kernels(beams, target, filled, truncate, units):
     if not isinstance(target, Beam):
         raise TypeError('target must be a Beam')
     beams, filled = _filled_beams(beams, filled)
-    if not 1 <= len(beams) <= MAX_CHANNELS:
-        raise ValueError('1 to {} channels'.format(MAX_CHANNELS))
+    band_size(len(beams))
     sigma_t = beam_covariance(target)
     det_t = _det(sigma_t)
     out = {}
@@ -223,11 +224,7 @@ def cube_smooth_host(cube, filled, radius, taps, out=None):
     ascending and within it dx ascending, ``acc = acc + (tap * shifted plane)`` in float32 from
     +0.0, every product and sum rounded; a NaN result is stored as 0x7fc00000.  Returns a new array
     whose unfilled channels are ``out``'s (NaN without one)."""
-    cube = np.asarray(cube)
-    if cube.dtype != np.float32:
-        raise TypeError('cube must be float32')
-    if cube.ndim != 4:
-        raise ValueError('cube must be [channel][polarization][y][x]')
+    cube = host_cube(cube, ndim=4)
     C, P, H, W = cube.shape
     filled, radius, taps = _check_tables(C, filled, radius, taps)
     result = np.full(cube.shape, np.nan, np.float32) if out is None else np.array(out, np.float32)
@@ -269,19 +266,7 @@ class CommonBeamParameters:
             self.target, self.truncate, self.units)
 
 
-class CubeSmoothTemplate:
-    def __init__(self, context, params):
-        if not isinstance(params, CommonBeamParameters):
-            raise TypeError('params must be CommonBeamParameters')
-        lib()
-        self.context = context
-        self.params = params
-
-    def instantiate(self, *args, **kwargs):
-        return CubeSmooth(self, *args, **kwargs)
-
-
-class CubeSmooth:
+class CubeSmooth(CubeOperator):
     """``kimg_cube_smooth`` for cubes of shape ``cube_shape`` = (C, P, H, W).  ``op(cube)`` takes a
     :class:`cube.SpectralCube` whose planes were :meth:`~cube.SpectralCube.put` with their beams and
     returns a second SpectralCube, allocated unless ``out=`` gives one (same shape, frequencies,
@@ -300,28 +285,9 @@ class CubeSmooth:
     After a call ``target``, ``radius`` (int32 [C]) and ``factors`` (float64 [C]) say what it did."""
 
     def __init__(self, template, command_queue, cube_shape):
-        self.template = template
-        self.params = template.params
-        self.command_queue = command_queue
-        try:
-            self.cube_shape = tuple(int(s) for s in cube_shape)
-        except (TypeError, ValueError):
-            raise ValueError('cube_shape must be (C, P, H, W)') from None
-        if len(self.cube_shape) != 4 or min(self.cube_shape) < 1 or self.cube_shape[0] > MAX_CHANNELS:
-            raise ValueError('cube_shape must be (C, P, H, W), at most {} channels'.format(MAX_CHANNELS))
+        super().__init__(template, command_queue, cube_shape, band=True)
         self.target = self.radius = self.factors = None
         self._taps = None
-
-    def _array(self, cube, what):
-        array = cube.array if isinstance(cube, SpectralCube) else cube
-        if not isinstance(array, accel.DeviceArray):
-            raise TypeError('{} must be a SpectralCube or a DeviceArray'.format(what))
-        if array.dtype != np.float32:
-            raise TypeError('{} must be float32'.format(what))
-        if tuple(array.shape) != self.cube_shape:
-            raise ValueError('the operator was made for cubes of {}, this one is {}'.format(
-                self.cube_shape, tuple(array.shape)))
-        return array
 
     def __call__(self, cube, out=None, beams=None, filled=None):
         params = self.params
@@ -330,25 +296,14 @@ class CubeSmooth:
         context = queue.context
         from_cube = isinstance(cube, SpectralCube)
         array = self._array(cube, 'cube')
+        filled = self._own_filled(cube, filled, beams=beams)
         if from_cube:
-            if beams is not None or filled is not None:
-                raise ValueError('a SpectralCube brings its own beams and filled')
-            beams, filled = cube.beams, cube.filled
+            beams = cube.beams
             if out is cube:
                 raise ValueError('the smoothed cube cannot be the cube itself')
-            if out is not None:
-                if not isinstance(out, SpectralCube):
-                    raise TypeError('the smoothed cube of a SpectralCube is a SpectralCube')
-                if not np.array_equal(out.frequencies, cube.frequencies):
-                    raise ValueError('out has other frequencies')
-                if out.polarizations != cube.polarizations:
-                    raise ValueError('out has other polarizations')
-                if out.channel_width != cube.channel_width:
-                    raise ValueError('out has another channel width')
-        elif beams is None or filled is None:
-            raise ValueError('a plain array needs beams and filled')
-        elif isinstance(out, SpectralCube):
-            raise TypeError('the smoothed cube of a plain array is a plain array')
+        elif beams is None:
+            raise ValueError('a plain array needs beams')
+        check_out_cube(cube, out, 'smoothed cube', same=('frequencies', 'polarizations', 'channel_width'))
         if out is not None:
             destination = self._array(out, 'out')
         beams, on = _filled_beams(beams, filled)
@@ -363,21 +318,17 @@ class CubeSmooth:
         # everything that can be refused has been: allocate
         if out is None:
             if from_cube:
-                out = SpectralCube(context, queue, cube.frequencies, cube.polarizations,
-                                   cube.shape[2:], cube.channel_width)
+                out = SpectralCube.like(cube, queue)
                 destination = out.array
             else:
                 out = destination = accel.DeviceArray(context, self.cube_shape, np.float32, queue=queue)
                 check(lib().kimg_fill(out.ptr, int(np.prod(self.cube_shape)), float('nan'),
                                       queue.handle), 'kimg_fill')
-        pitch = Moments._channel_pitch(array)
-        out_pitch = Moments._channel_pitch(destination)
+        pitch = channel_pitch(array)
+        out_pitch = channel_pitch(destination)
         if from_cube:
-            # (planes out held that the source does not: back to what an unfilled plane holds)
-            M = int(np.prod(self.cube_shape[1:]))
-            for c in np.flatnonzero((out.filled != 0) & ~on):
-                check(lib().kimg_fill(destination.ptr + 4 * int(c) * out_pitch, M, float('nan'),
-                                      queue.handle), 'kimg_fill')
+            blank_stale_planes(queue, destination, out_pitch, np.flatnonzero((out.filled != 0) & ~on),
+                               int(np.prod(self.cube_shape[1:])))
         if self._taps is None:
             self._taps = accel.DeviceArray(context, taps.shape, np.float32, queue=queue)
         self._taps.set(queue, taps)
@@ -395,3 +346,8 @@ class CubeSmooth:
             out.beams = [target if f else None for f in on]
             out.common_beam = target
         return out
+
+
+class CubeSmoothTemplate(CubeTemplate):
+    params_type = CommonBeamParameters
+    operator = CubeSmooth

@@ -50,8 +50,9 @@ import numpy as np
 
 from . import accel, smooth
 from ._lib import lib, check, SourceLineTable
-from .cube import MAX_CHANNELS, Moments, SpectralCube, _AXES, _rest_frequency
-from .link import _is_bool, _labels
+from .cube_operator import (AXES, MAX_CHANNELS, CubeOperator, CubeTemplate, SpectralCube, _rest_frequency,
+                            channel_pitch, host_filled, is_bool, velocities)
+from .link import _labels
 
 MAX_TOTAL = 2 ** 31 - 2
 _UNITS = ('beam', 'pixel')
@@ -101,10 +102,7 @@ def source_spectra_host(labels, cube, filled, c0, offsets):
     cube = np.asarray(cube)
     if cube.dtype != np.float32 or cube.shape != labels.shape:
         raise ValueError('cube must be float32 of the shape of labels')
-    C = labels.shape[0]
-    filled = np.asarray(filled) != 0
-    if filled.shape != (C,):
-        raise ValueError('filled must have one entry per channel')
+    filled = host_filled(filled, labels.shape[0])
     c0, offsets = _layout(c0, offsets)
     N = len(c0)
     total = int(offsets[-1])
@@ -207,10 +205,10 @@ def source_lines_host(c0, offsets, total_sum, finite, tables):
 
 
 def _axis(axis, rest_frequency, units):
-    if axis not in _AXES:
+    if axis not in AXES:
         raise ValueError("axis must be 'velocity' or 'frequency'")
     if rest_frequency is not None:
-        if _is_bool(rest_frequency):
+        if is_bool(rest_frequency):
             raise ValueError('rest_frequency must be a number, not a bool')
         rest_frequency = _rest_frequency(rest_frequency)
     if units not in _UNITS:
@@ -310,7 +308,7 @@ class SourceSpectra:
 
     def spectrum(self, source, command_queue=None):
         """``(channels, sum, voxels, finite)`` of source ``source`` (1 to N)."""
-        if _is_bool(source) or not isinstance(source, (int, np.integer)) or not 1 <= source <= len(self):
+        if is_bool(source) or not isinstance(source, (int, np.integer)) or not 1 <= source <= len(self):
             raise ValueError('source must be 1 to {}'.format(len(self)))
         queue = self._queue if command_queue is None else command_queue
         a, b = int(self.offsets[source - 1]), int(self.offsets[source])
@@ -318,19 +316,7 @@ class SourceSpectra:
         return (channels,) + tuple(t[a:b].copy() for t in self.get(queue))
 
 
-class SourcesTemplate:
-    def __init__(self, context, params):
-        if not isinstance(params, SourceParameters):
-            raise TypeError('params must be SourceParameters')
-        lib()
-        self.context = context
-        self.params = params
-
-    def instantiate(self, *args, **kwargs):
-        return Sources(self, *args, **kwargs)
-
-
-class Sources:
+class Sources(CubeOperator):
     """The parameteriser for cubes of shape ``cube_shape`` = (C, P, H, W).  ``op(labels, the_cube,
     catalogue)`` takes a :class:`link.LabelCube`, a :class:`cube.SpectralCube` and the catalogue of
     :class:`link.Link` (its ``id``, ``c0`` and ``c1`` are read); ``op(labels, array, catalogue,
@@ -345,18 +331,8 @@ class Sources:
     results without a launch."""
 
     def __init__(self, template, command_queue, cube_shape):
-        self.template = template
-        self.params = template.params
-        self.command_queue = command_queue
-        try:
-            self.cube_shape = tuple(int(s) for s in cube_shape)
-        except (TypeError, ValueError):
-            raise ValueError('cube_shape must be (C, P, H, W)') from None
-        if len(self.cube_shape) != 4 or min(self.cube_shape) < 1:
-            raise ValueError('cube_shape must be (C, P, H, W)')
+        super().__init__(template, command_queue, cube_shape, band=True)
         C, P, H, W = self.cube_shape
-        if C > MAX_CHANNELS:
-            raise ValueError('1 to {} channels'.format(MAX_CHANNELS))
         if C * P * H * W > 2 ** 31 - 2:
             raise ValueError('more than 2^31 - 2 voxels: labels are int32')
         self._channel_tables = accel.DeviceArray(command_queue.context, (4 * C,), np.float64,
@@ -372,7 +348,6 @@ class Sources:
             raise ValueError('a cube of one channel needs tables: its channel width is not known')
         coord = frequencies.copy()
         if params.axis == 'velocity':
-            from .cube import velocities
             coord = velocities(frequencies, params.rest_frequency)
         width = np.empty(C, np.float64)
         width[1:-1] = np.abs(coord[2:] - coord[:-2]) / 2.0
@@ -385,33 +360,17 @@ class Sources:
         C, P, H, W = self.cube_shape
         M = P * H * W
         queue = self.command_queue
-        from_cube = isinstance(cube, SpectralCube)
-        array = cube.array if from_cube else cube
-        if not isinstance(array, accel.DeviceArray) or not isinstance(labels, accel.DeviceArray):
-            raise TypeError('labels and cube must be device arrays (LabelCube, SpectralCube)')
-        if array.dtype != np.float32:
-            raise TypeError('cube must be float32')
-        if labels.dtype != np.int32:
-            raise TypeError('labels must be int32')
-        if tuple(array.shape) != self.cube_shape or tuple(labels.shape) != self.cube_shape:
-            raise ValueError('the operator was made for cubes of {}, these are {} and {}'.format(
-                self.cube_shape, tuple(labels.shape), tuple(array.shape)))
-        if from_cube:
-            if filled is not None or frequencies is not None or tables is not None:
-                raise ValueError('a SpectralCube brings its own filled, frequencies and tables')
-            filled = cube.filled
+        labels, array = self._arrays((labels, 'labels', np.int32), (cube, 'cube', np.float32))
+        filled = self._own_filled(cube, filled, frequencies=frequencies, tables=tables)
+        if isinstance(cube, SpectralCube):
             tables = line_tables(cube, params.axis, params.rest_frequency, params.units)
         else:
-            if filled is None:
-                raise ValueError('a plain array needs filled')
             if (tables is None) == (frequencies is None):
                 raise ValueError('a plain array needs either tables or frequencies')
             if tables is None:
                 tables = self._tables_from_frequencies(frequencies)
         tables = _channel_tables(tables, C)
-        filled = np.ascontiguousarray(np.asarray(filled) != 0, np.uint8)
-        if filled.shape != (C,):
-            raise ValueError('filled must have one entry per channel')
+        filled = self._filled(filled)
         catalogue = np.asarray(catalogue)
         if catalogue.ndim != 1 or catalogue.dtype.names is None \
                 or not {'c0', 'c1'} <= set(catalogue.dtype.names):
@@ -427,10 +386,9 @@ class Sources:
             empty = SourceSpectra(c0, offsets, (None, None, None), None)
             empty._queue = queue
             return empty, lines
-        pitch = Moments._channel_pitch(array)
-        label_pitch = Moments._channel_pitch(labels)
-        if getattr(labels, 'ready', None) is not None:
-            queue.enqueue_wait_for_events([labels.ready])
+        pitch = channel_pitch(array)
+        label_pitch = channel_pitch(labels)
+        self._wait_ready(labels)
         labels.used_on(queue)
         array.used_on(queue)
         context = queue.context
@@ -469,3 +427,8 @@ class Sources:
         spectra._queue = queue
         spectra._layout = layout
         return spectra, lines
+
+
+class SourcesTemplate(CubeTemplate):
+    params_type = SourceParameters
+    operator = Sources

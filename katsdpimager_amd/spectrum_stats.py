@@ -39,10 +39,10 @@ import ctypes
 
 import numpy as np
 
-from . import accel
 from ._lib import lib, check
-from .channel_block import integer
-from .cube import MAX_CHANNELS, MapArray, Moments, SpectralCube
+from .channel_block import OperatorTemplate, integer
+from .cube_operator import (CubeOperator, MapArray, carry_over, channel_pitch, channel_range,
+                            check_out_cube, host_cube, host_filled, is_bool, mark_ready, range_in_band)
 from .cube_stats import ESTIMATORS, TO_RMS, keys, values_of
 
 #: KIMG_SPECTRUM_* of include/kimg.h
@@ -52,22 +52,6 @@ DEFAULT_OUTPUTS = ('median', 'sigma', 'count')
 FORMS = {'auto': 0, 'resident': 1, 'streaming': 2}
 
 _NONE = np.uint64(1) << np.uint64(32)       # above every key: what is not a sample
-
-
-def _is_bool(value):
-    return isinstance(value, (bool, np.bool_))
-
-
-def _channel_range(pair, what):
-    try:
-        first, stop = pair
-    except (TypeError, ValueError):
-        raise ValueError('{} must be (first, stop)'.format(what)) from None
-    if _is_bool(first) or _is_bool(stop):
-        raise ValueError('{} must be integers, not bools'.format(what))
-    first = integer(first, 'the first channel of ' + what, 0, MAX_CHANNELS - 1)
-    stop = integer(stop, 'the stop channel of ' + what, first + 1, MAX_CHANNELS)
-    return first, stop
 
 
 class SpectrumStatsParameters:
@@ -82,15 +66,15 @@ class SpectrumStatsParameters:
         if not isinstance(estimator, str) or estimator not in ESTIMATORS:
             raise ValueError("estimator must be 'median_abs' or 'mad'")
         self.estimator = estimator
-        self.channels = None if channels is None else _channel_range(channels, 'channels')
+        self.channels = None if channels is None else channel_range(channels, 'channels')
         self.exclude_ranges = None
         if exclude_ranges is not None:
             try:
                 ranges = list(exclude_ranges)
             except TypeError:
                 raise ValueError('exclude_ranges must be a list of (first, stop)') from None
-            self.exclude_ranges = [_channel_range(r, 'an excluded range') for r in ranges]
-        if _is_bool(min_samples):
+            self.exclude_ranges = [channel_range(r, 'an excluded range') for r in ranges]
+        if is_bool(min_samples):
             raise ValueError('min_samples must be an integer, not a bool')
         self.min_samples = integer(min_samples, 'min_samples', 1, 2 ** 31 - 1)
         if isinstance(outputs, str):
@@ -106,14 +90,7 @@ class SpectrumStatsParameters:
 
     def range(self, num_channels):
         """(first, stop) within a band of ``num_channels`` channels."""
-        num_channels = int(num_channels)
-        if not 1 <= num_channels <= MAX_CHANNELS:
-            raise ValueError('1 to {} channels'.format(MAX_CHANNELS))
-        if self.channels is None:
-            return 0, num_channels
-        if self.channels[1] > num_channels:
-            raise ValueError('channels {} beyond the {} of the cube'.format(self.channels, num_channels))
-        return self.channels
+        return range_in_band(self.channels, num_channels)
 
     def stat(self, num_channels):
         """uint8 [C]: 1 where ``exclude_ranges`` lets a channel in (the range and ``filled`` come on
@@ -130,9 +107,7 @@ class SpectrumStatsParameters:
     def entering(self, num_channels, filled):
         """bool [C]: the channels that enter the statistics."""
         first, stop = self.range(num_channels)
-        filled = np.asarray(filled) != 0
-        if filled.shape != (num_channels,):
-            raise ValueError('filled must have one entry per channel')
+        filled = host_filled(filled, num_channels)
         enter = (self.stat(num_channels) != 0) & filled
         enter[:first] = False
         enter[stop:] = False
@@ -169,11 +144,7 @@ def spectrum_stats_host(cube, filled, params, subtract=False):
     that are not filled."""
     if not isinstance(params, SpectrumStatsParameters):
         raise TypeError('params must be SpectrumStatsParameters')
-    cube = np.asarray(cube)
-    if cube.dtype != np.float32:
-        raise TypeError('cube must be float32')
-    if cube.ndim < 2:
-        raise ValueError('cube must be [channel][...plane]')
+    cube = host_cube(cube)
     C = cube.shape[0]
     plane = cube.shape[1:]
     enter = params.entering(C, filled)
@@ -213,32 +184,12 @@ def spectrum_stats_host(cube, filled, params, subtract=False):
     return maps, line
 
 
-class SpectrumStatsTemplate:
-    """``tuning``: None or ``{'form': 'auto' | 'resident' | 'streaming'}`` -- the kernel form
-    (csrc/spectrum_stats.hip); 'resident' takes at most :func:`resident_limit` entering channels."""
-
-    def __init__(self, context, params, tuning=None):
-        if not isinstance(params, SpectrumStatsParameters):
-            raise TypeError('params must be SpectrumStatsParameters')
-        tuning = dict(tuning or {})
-        form = tuning.pop('form', 'auto')
-        if tuning or form not in FORMS:
-            raise ValueError("tuning must be {'form': 'auto', 'resident' or 'streaming'}")
-        lib()
-        self.context = context
-        self.params = params
-        self.form = form
-
-    def instantiate(self, *args, **kwargs):
-        return SpectrumStats(self, *args, **kwargs)
-
-
 def resident_limit():
     """The largest number of entering channels the resident form takes."""
     return int(lib().kimg_spectrum_stats_resident_limit())
 
 
-class SpectrumStats:
+class SpectrumStats(CubeOperator):
     """``kimg_spectrum_stats`` for cubes of shape ``cube_shape`` = (C, P, H, W).  ``op(the_cube,
     subtract=False, out=None)`` takes a :class:`cube.SpectralCube` and returns ``{name: MapArray
     [P][H][W]}`` for the parameters' ``outputs`` ('count' int32, the others float32); maps that were
@@ -252,59 +203,26 @@ class SpectrumStats:
     it."""
 
     def __init__(self, template, command_queue, cube_shape):
-        self.template = template
-        self.params = template.params
-        self.command_queue = command_queue
-        try:
-            self.cube_shape = tuple(int(s) for s in cube_shape)
-        except (TypeError, ValueError):
-            raise ValueError('cube_shape must be (C, P, H, W)') from None
-        if len(self.cube_shape) != 4 or min(self.cube_shape) < 1:
-            raise ValueError('cube_shape must be (C, P, H, W)')
+        super().__init__(template, command_queue, cube_shape)
         self.range = self.params.range(self.cube_shape[0])
         self._stat = self.params.stat(self.cube_shape[0])
-
-    def _array(self, cube, what):
-        array = cube.array if isinstance(cube, SpectralCube) else cube
-        if not isinstance(array, accel.DeviceArray):
-            raise TypeError('{} must be a SpectralCube or a DeviceArray'.format(what))
-        if array.dtype != np.float32:
-            raise TypeError('{} must be float32'.format(what))
-        if tuple(array.shape) != self.cube_shape:
-            raise ValueError('the operator was made for cubes of {}, this one is {}'.format(
-                self.cube_shape, tuple(array.shape)))
-        return array
 
     def __call__(self, cube, filled=None, subtract=False, out=None):
         params = self.params
         C = self.cube_shape[0]
-        if not _is_bool(subtract):
+        if not is_bool(subtract):
             raise ValueError('subtract must be a bool')
         if out is not None and not subtract:
             raise ValueError('out is where subtract=True writes; it was not asked for')
-        from_cube = isinstance(cube, SpectralCube)
         array = self._array(cube, 'cube')
-        if from_cube:
-            if filled is not None:
-                raise ValueError('a SpectralCube brings its own filled')
-            filled = cube.filled
-            if out is not None and out is not cube:
-                if not isinstance(out, SpectralCube):
-                    raise TypeError('the line cube of a SpectralCube is a SpectralCube')
-                if not np.array_equal(out.frequencies, cube.frequencies):
-                    raise ValueError('out has other frequencies')
-        elif filled is None:
-            raise ValueError('a plain array needs filled')
-        elif isinstance(out, SpectralCube):
-            raise TypeError('the line cube of a plain array is a plain array')
-        filled = np.ascontiguousarray(np.asarray(filled) != 0, np.uint8)
-        if filled.shape != (C,):
-            raise ValueError('filled must have one entry per channel')
-        pitch = Moments._channel_pitch(array)
+        filled = self._own_filled(cube, filled)
+        check_out_cube(cube, out, 'line cube')
+        filled = self._filled(filled)
+        pitch = channel_pitch(array)
         target = target_pitch = None
         if subtract:
             target = array if out is None else self._array(out, 'out')
-            target_pitch = Moments._channel_pitch(target)
+            target_pitch = channel_pitch(target)
         queue = self.command_queue
         context = queue.context
         plane = self.cube_shape[1:]
@@ -329,10 +247,21 @@ class SpectrumStats:
             ESTIMATORS[params.estimator], params.min_samples, bits, *pointers,
             None if target is None else target.ptr, 0 if target is None else target_pitch,
             FORMS[self.template.form], queue.handle), 'kimg_spectrum_stats')
-        ready = queue.enqueue_marker()
-        for m in maps.values():
-            m.ready = ready
-        if from_cube and out is not None and out is not cube:
-            out.filled[:] = cube.filled
-            out.noise[:] = cube.noise
+        mark_ready(queue, maps.values())
+        carry_over(cube, out)
         return {name: maps[name] for name in params.outputs}
+
+
+class SpectrumStatsTemplate(OperatorTemplate):
+    """``tuning``: None or ``{'form': 'auto' | 'resident' | 'streaming'}`` -- the kernel form
+    (csrc/spectrum_stats.hip); 'resident' takes at most :func:`resident_limit` entering channels."""
+
+    params_type = SpectrumStatsParameters
+    operator = SpectrumStats
+
+    def __init__(self, context, params, tuning=None):
+        super().__init__(context, params)
+        tuning = dict(tuning or {})
+        self.form = tuning.pop('form', 'auto')
+        if tuning or self.form not in FORMS:
+            raise ValueError("tuning must be {'form': 'auto', 'resident' or 'streaming'}")
