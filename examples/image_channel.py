@@ -15,7 +15,7 @@ store -> imaging weights, PSF, major/minor cycles -> restored image, all on one 
     python examples/image_channel.py --moments --median-contsub        (... taken out by the per-pixel median, told no line ranges)
     python examples/image_channel.py --moments --common-beam  (... every plane restored with its own beam, then all taken to one)
     python examples/image_channel.py --moments --common-beam --measure-noise  (... and the smoothed planes' noise measured)
-    python examples/image_channel.py --moments --find-sources  (... and the smooth-and-clip detection mask of the cube, linked into a catalogue and parameterised: flux, peak, centroid, w50)
+    python examples/image_channel.py --moments --find-sources  (... and the smooth-and-clip detection mask of the cube, linked into a catalogue and parameterised: flux, peak, centroid, w50; and every source's own moment maps)
 
 It follows the reference's per-channel flow (frontend.py:31-83 preprocess_visibilities,
 :465-658 process_channel) with the loaders and FITS output left out: the sky is three point
@@ -741,6 +741,29 @@ def moments_band(args):
                       int(first['peak_channel']), first['centroid'], first['w50'], first['w20'], name,
                       results['sources'][name]['injected'][1],
                       float(np.ptp(velocity[line >= 0.5 * line.max()]))))
+            # the moment maps of every source inside its own box in one pass, and at the peak pixel of
+            # source 1 the same two numbers by the three passes of labels.mask(source=1): they are equal
+            from katsdpimager_amd import source_maps
+            mapper = source_maps.SourceMapsTemplate(ctx, source_maps.SourceMapParameters(
+                (0, 1), rest_frequency=rest_frequency)).instantiate(cube_queue, sc.shape)
+            own_maps = mapper(labels, sc, catalogue)
+            row = catalogue[0]
+            box = own_maps.map(1, cube_queue)
+            at = (int(row['peak_y'] - row['y0']), int(row['peak_x'] - row['x0']))
+            ranged = cube.MomentsTemplate(ctx, cube.MomentParameters(
+                (0, 1), rest_frequency=rest_frequency, channels=(int(row['c0']), int(row['c1']) + 1))).instantiate(
+                    cube_queue, sc.shape)
+            three = ranged(labels.mask(source=1).apply(sc))
+            through_mask = tuple(float(three[m].get(cube_queue)[0][row['peak_y'], row['peak_x']]) for m in (0, 1))
+            from_map = tuple(float(box[m][at]) for m in (0, 1))
+            results['find_sources'].update(first_source_map_shape=box[0].shape, first_source_map=from_map,
+                                           first_source_through_mask=through_mask,
+                                           source_map_entries=own_maps.total)
+            print('source 1 at its peak pixel, from its own {} x {} map (one pass for all {} sources, {} '
+                  'entries): moment 0 {:.6f}, moment 1 {:.6f} km/s; through labels.mask(source=1) over its '
+                  'channels (three passes): {:.6f}, {:.6f} km/s'.format(
+                      box[0].shape[0], box[0].shape[1], len(catalogue), own_maps.total, *from_map,
+                      *through_mask))
     if args.output:
         from katsdpimager_amd import io, polarization
         image_p.fixed.polarizations = [polarization.STOKES_I]

@@ -1848,8 +1848,8 @@ int kimg_cube_mask_apply(const float *cube, int64_t channel_pitch, const uint8_t
  *   call that does nothing to cubes.
  * Asynchronous on `stream`, no allocation, capturable; the host reads nothing.
  * Not done here (per-source spectra, fluxes in Jy and their errors are "Source spectra and line
- *   parameters" below): reliability from negative detections; mask dilation; per-source moment
- *   maps beyond kimg_cube_label_mask's mask of one source; sources across polarizations; cubes across
+ *   parameters" below, the moment maps of every source "Per-source moment maps"): reliability from
+ *   negative detections; mask dilation; sources across polarizations; cubes across
  *   several GPUs; bit-reproducible sums (a store-and-sum pass, another contract). */
 typedef struct kimg_catalogue {
     int32_t *first, *voxels, *finite, *c0, *c1, *y0, *y1, *x0, *x1;
@@ -1947,8 +1947,9 @@ int kimg_cube_label_mask(const int32_t *labels, int64_t label_pitch, uint8_t *ma
  *   KIMG_EUNSUPPORTED for C > KIMG_MOMENTS_MAX_CHANNELS or total > 2^31 - 2.  N = 0 is then a
  *   successful call that copies and writes nothing.
  *
- * Not done here: reliability from negative detections; mask dilation; per-source moment maps;
- *   bit-reproducible sums (a store-and-sum pass, another contract); sources across polarizations;
+ * Not done here (per-source moment maps, whose sums are bit-reproducible, are "Per-source moment maps"
+ *   below): reliability from negative detections; mask dilation; bit-reproducible sums of the spectra
+ *   (a store-and-sum pass, another contract); sources across polarizations;
  *   Gaussian or busy-function fits to the spectra; cubes across several GPUs. */
 typedef struct kimg_source_line_table {
     double *flux, *flux_err, *peak;
@@ -1966,6 +1967,77 @@ int kimg_source_lines(int num_sources, const int32_t *c0, const int32_t *offsets
                       const double *unit_host, const double *width_host, const double *coord_host,
                       const double *variance_host, double *channel_tables,
                       const kimg_source_line_table *lines, void *stream);
+
+/* ---- Per-source moment maps (cube_source_maps.hip): the moment maps of EVERY linked source inside its
+ * own bounding box, in one pass over labels and cube -- what SoFiA writes next to its catalogue and
+ * what immoments gives per region.  The reference has none; the semantics are this library's, and
+ * katsdpimager_amd/source_maps.py holds them once more as numpy (source_maps_host).
+ *
+ * Inputs.  labels: DEVICE int32 [C][P][H][W], label_pitch elements from channel to channel; cube:
+ *   DEVICE float32 of the same shape with a pitch of its own; both pitches >= P * H * W, the [P][H][W]
+ *   plane dense, padding neither read nor written; neither array is ever written.  filled_host: HOST
+ *   uint8 [C], read during the call, travels to the kernel by value, a bit per channel.  x: DEVICE
+ *   float64 [C], the coordinate of every channel.  rows: DEVICE kimg_source_map_row [N], row s - 1 is
+ *   source s (1 .. N = num_sources): offset, pol, the box's corner y0, x0 and its extent h, w, the
+ *   channel range c0 .. c1 (inclusive), and x_ref and width of "Moment maps" for that range, made by
+ *   the host: x_ref = x[(c0 + c1 + 1) / 2], width = |x[c1] - x[c0]| / (c1 - c0), or the channel width
+ *   for c0 == c1.  Rows come in ascending offset.
+ * The ragged layout.  Source s owns h_s * w_s entries of every table from offset_s on; the entry of
+ *   its pixel (y, x) is offset_s + (y - y0_s) * w_s + (x - x0_s).  total <= 2^31 - 2 is the length of
+ *   every table; for the rows the host makes, total = offset_N + h_N * w_N.  Boxes of different sources
+ *   may overlap in the plane: their entries do not.
+ * Which voxels enter.  Voxel (c, p, y, x) with label s enters entry (s, y, x) iff 1 <= s <= N,
+ *   filled[c], p == pol_s, 0 <= y - y0_s < h_s, 0 <= x - x0_s < w_s, c0_s <= c <= c1_s, offset_s >= 0
+ *   and the entry's index is < total.  Every other voxel is skipped.  The rows are DEVICE data that the
+ *   host cannot check, so the kernels do: an index is formed only from a row whose box holds the pixel,
+ *   and is checked against total, so that wrong rows give wrong numbers, never an access outside the
+ *   tables.  Unfilled channels are not read; the cube is read only where a wave of 64 lanes (256
+ *   consecutive plane elements, or 64 in the one-element form) holds a label.
+ * Arithmetic.  Per entry, over the voxels that enter in ascending channel order, exactly the sample
+ *   rule of "Moment maps" without a cut: only a finite I counts; n += 1; d = x[c] - x_ref_s; S0 += I;
+ *   t = I * d; S1 += t; S2 += t * d, float64, nothing fused; the peak (float32, starting at -inf) is
+ *   replaced, with its channel, only if I > peak.
+ * kimg_cube_source_maps gathers these sums into the state table in `workspace` (8-byte aligned, at
+ *   least kimg_cube_source_maps_workspace_bytes(total) = 36 * total bytes, zeroed by the call with a
+ *   hipMemsetAsync): a column walk, one thread per pixel (four consecutive plane elements per thread
+ *   with 16-byte label and cube loads where labels, cube and both pitches * 4 are 16-byte aligned, for
+ *   the first 4 * (M / 4) elements; one element per thread for the tail and everything else).  A
+ *   thread keeps the sums of the source at its pixel in registers and exchanges them with the state
+ *   table, by plain stores and loads, only where the label at the pixel changes to another source's.  No
+ *   atomics, so equal inputs give equal bits.
+ * kimg_source_maps_finish turns the state into the tables that `outputs` (KIMG_MOMENT_* bits, as in
+ *   kimg_moments; the pointer of a bit that is not set is ignored) asks for, float32 [total] each and
+ *   count int32 [total], one thread per entry, its source found by binary search in the offsets.  The
+ *   formulas are kimg_moments': S0 * width_s; x_ref_s + S1 / S0; sqrt(max(0, S2 / S0 - r * r)); the
+ *   peak; x of the peak's channel; NaN where n == 0, moments 1 and 2 also unless S0 > 0.  An entry that
+ *   no voxel entered -- a box pixel the source never touches, or an index inside no row's box -- reads
+ *   NaN and count 0.  All `total` entries of every requested table are written, and nothing else.
+ * Agreement.  Entry (s, y, x) equals, bit for bit and moment 2 included, what kimg_moments gives at
+ *   (pol_s, y, x) over first = c0_s, stop = c1_s + 1 with cut -inf on the cube with every voxel not
+ *   labelled s set to NaN: both units compile the same expressions (csrc/kimg_moment_math.h).
+ * Returns, before any HIP call: KIMG_EINVAL for a null or misaligned pointer (4 bytes; 8 for x, rows
+ *   and the workspace), C, P, H or W below 1, N < 0, total < 0, a pitch below P * H * W, outputs without
+ *   any KIMG_MOMENT_* bit or with others, or a requested output that is NULL; then KIMG_EUNSUPPORTED for
+ *   C > KIMG_MOMENTS_MAX_CHANNELS, C * P * H * W > 2^31 - 2 or total > 2^31 - 2; then KIMG_EWORKSPACE for
+ *   a short workspace.  N = 0 or total = 0 is then a successful call that does nothing.  Asynchronous on
+ *   `stream`, no allocation; the host reads nothing.
+ * Not done here: pasting the maps back into one plane; a noise cut or Hanning selection per source;
+ *   sources across polarizations; cubes across several GPUs. */
+typedef struct kimg_source_map_row {
+    int32_t offset, pol, y0, x0, h, w, c0, c1;
+    double x_ref, width;
+} kimg_source_map_row;
+size_t kimg_cube_source_maps_workspace_bytes(int64_t total);
+int kimg_cube_source_maps(const int32_t *labels, int64_t label_pitch, const float *cube,
+                          int64_t channel_pitch, int num_channels, int num_polarizations, int height,
+                          int width, const uint8_t *filled_host, const double *x, int num_sources,
+                          const kimg_source_map_row *rows, int64_t total, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int kimg_source_maps_finish(int num_sources, const kimg_source_map_row *rows, int64_t total,
+                            const void *workspace, size_t workspace_bytes, const double *x,
+                            int num_channels, int outputs, float *moment0, float *moment1,
+                            float *moment2, float *moment8, float *moment9, int32_t *count,
+                            void *stream);
 
 #ifdef __cplusplus
 }

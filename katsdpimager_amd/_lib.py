@@ -186,6 +186,12 @@ PROTOTYPES = {
     # width_host, coord_host, variance_host, channel_tables, kimg_source_line_table *, stream)
     'kimg_cube_source_spectra': (c_int, [P, L, P, L, I, L, P, I, P, P, L, P, P, P, P]),
     'kimg_source_lines': (c_int, [I, P, P, L, P, P, I, P, P, P, P, P, P, P]),
+    # per-source moment maps: workspace bytes (total); maps (labels, label_pitch, cube, pitch, C, P, H, W,
+    # filled_host, x, N, rows, total, workspace, workspace_bytes, stream); finish (N, rows, total, workspace,
+    # workspace_bytes, x, C, outputs, moment0, moment1, moment2, moment8, moment9, count, stream)
+    'kimg_cube_source_maps_workspace_bytes': (c_size_t, [L]),
+    'kimg_cube_source_maps': (c_int, [P, L, P, L, I, I, I, I, P, P, I, P, L, P, c_size_t, P]),
+    'kimg_source_maps_finish': (c_int, [I, P, L, P, c_size_t, P, I, I, P, P, P, P, P, P, P]),
     # float64 path
     'kimg_grid_f64': (c_int, [P, L, L, I, I, P, L, L, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),
     'kimg_degrid_f64': (c_int, [P, L, L, I, I, P, P, P, P, L, P, I, I, I, P, c_size_t, I, P]),

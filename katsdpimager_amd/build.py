@@ -17,7 +17,7 @@ SOURCES = ['api.hip', 'grid.hip', 'grid_mfma.hip', 'grid_fold.hip', 'grid_binned
            'grid_f64.hip', 'mask.hip', 'clean_scales.hip', 'contsub.hip', 'phaseshift.hip',
            'primary_beam.hip', 'spectral.hip', 'statwt.hip', 'rfiflag.hip', 'moments.hip',
            'imcontsub.hip', 'cube_smooth.hip', 'cube_stats.hip', 'spectrum_stats.hip',
-           'cube_detect.hip', 'cube_link.hip', 'cube_sources.hip']
+           'cube_detect.hip', 'cube_link.hip', 'cube_sources.hip', 'cube_source_maps.hip']
 
 # -ffp-contract=off: a*b+c is fused only where the source says fmaf(); the image/CLEAN
 # kernels must round exactly like the reference's numpy host path.

@@ -14,6 +14,7 @@
 // the NEXT channels), so every voxel is still read once.  A NaN stands for "no neighbour" in that
 // window -- outside the range, not filled or not finite are one case under the replicate rule.
 #include "kimg_cube_column.h"
+#include "kimg_moment_math.h"
 
 namespace {
 
@@ -27,30 +28,6 @@ struct mm_out {
     float *m0, *m1, *m2, *m8, *m9;
     int32_t *count;
 };
-
-struct mm_acc {
-    double S0, S1, S2;
-    float peak;
-    int n, pc;
-};
-
-// One sample: I of channel c with selection value s against the cut ct; d = x[c] - x_ref
-template <bool SECOND>
-__device__ inline void mm_add(mm_acc &a, float I, double s, double ct, double d, int c)
-{
-    const bool enter = isfinite(I) && s > ct;
-    const double Id = (double) I;
-    a.n += enter ? 1 : 0;
-    a.S0 = enter ? a.S0 + Id : a.S0;
-    if constexpr (SECOND) {
-        const double t = Id * d;
-        a.S1 = enter ? a.S1 + t : a.S1;
-        a.S2 = enter ? a.S2 + t * d : a.S2;
-    }
-    const bool higher = enter && I > a.peak;
-    a.peak = higher ? I : a.peak;
-    a.pc = higher ? c : a.pc;
-}
 
 // `groups` threads have work: thread t owns the elements t * V .. t * V + V - 1
 template <int V, bool HANNING, bool SECOND>
@@ -147,24 +124,15 @@ void moments_kernel(const float *__restrict__ cube, int64_t pitch, int64_t group
     int32_t n[V];
 #pragma unroll
     for (int e = 0; e < V; e++) {
-        const mm_acc &a = acc[e];
-        const bool any = a.n > 0;
-        const bool positive = any && a.S0 > 0.0;
-        n[e] = a.n;
-        m0[e] = any ? (float) (a.S0 * width) : col_nan();
-        m8[e] = any ? a.peak : col_nan();
+        const mm_values v = mm_finish<SECOND>(acc[e], width, x_ref);
+        n[e] = acc[e].n;
+        m0[e] = v.m0;
+        m1[e] = v.m1;
+        m2[e] = v.m2;
+        m8[e] = v.m8;
         m9[e] = col_nan();
-        if (out.m9 && any)
-            m9[e] = (float) x[a.pc];
-        m1[e] = m2[e] = col_nan();
-        if constexpr (SECOND) {
-            const double r = a.S1 / a.S0;
-            const double q = a.S2 / a.S0;
-            double var = q - r * r;
-            var = var < 0.0 ? 0.0 : var;
-            m1[e] = positive ? (float) (x_ref + r) : col_nan();
-            m2[e] = positive ? (float) sqrt(var) : col_nan();
-        }
+        if (out.m9 && v.any)
+            m9[e] = (float) x[acc[e].pc];
     }
     if (out.m0) col_store<V>(out.m0 + j, m0);
     if (out.m1) col_store<V>(out.m1 + j, m1);

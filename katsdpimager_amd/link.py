@@ -36,11 +36,11 @@ the plane (SoFiA's default), 1.5 is 8-connectivity, 2 and 3 bridge gaps.
 
 Why these rules, and what the kernels cost, is DESIGN.md 5.31.
 
-Per-source spectra, fluxes in Jy with their errors and line widths are :mod:`.sources`'.
+Per-source spectra, fluxes in Jy with their errors and line widths are :mod:`.sources`'; the moment maps
+of every source inside its own box are :mod:`.source_maps`'.
 
-Not done: reliability from negative detections; mask dilation; per-source moment maps beyond
-``labels.mask(source=)``; sources across polarizations; cubes across several GPUs; bit-reproducible
-sums.
+Not done: reliability from negative detections; mask dilation; sources across polarizations; cubes
+across several GPUs; bit-reproducible sums.
 """
 import ctypes
 import math

@@ -39,9 +39,12 @@ width on the axis.  ``variance[c] = Omega * (noise[c] * unit[c] * width[c])^2`` 
 to the variance of the flux: pixels within a beam are correlated, so n of them carry the noise of
 ``n / Omega`` independent ones, each ``Omega`` pixels' worth.
 
-Not done: reliability from negative detections; mask dilation; per-source moment maps; bit-reproducible
-sums; sources across polarizations; Gaussian or busy-function fits to the spectra; cubes across several
-GPUs.  Why these rules, and what the kernels cost, is DESIGN.md 5.32.
+The moment maps of every source inside its own box, whose sums are bit-reproducible, are
+:mod:`.source_maps`'.
+
+Not done: reliability from negative detections; mask dilation; bit-reproducible sums of the spectra;
+sources across polarizations; Gaussian or busy-function fits to the spectra; cubes across several GPUs.
+Why these rules, and what the kernels cost, is DESIGN.md 5.32.
 """
 import ctypes
 import math
